@@ -11,10 +11,21 @@ sequences (weak scaling: the sequence count per GPU is fixed as N grows; no per-
 collective).  Inputs for every timed frame are generated on the GPU and resident in HBM before
 the timed region.
 
-Roofline: the last `len(STAGES)` warm-up steps time each pipeline stage once (HIP events around
-that stage's launch, `Engine.probe`); the slowest stage is the dominant kernel and is probed on
-every timed step.  Its algorithmic bytes per launch (DESIGN.md §4 per-stage model, priced with
-the engine's own per-frame unit counts) over its measured average launch time is `achieved`.
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure
+needs: it stages the frames, runs the untimed steps, times the N steps and prints one JSON line
+(`value` frames/s, `ms_per_step`, ...; `roofline` and `cpu_baseline` are null).  `--dump-outputs
+DIR` also writes what the last timed step returned to its caller (`DIR/out_rows.npy`,
+`DIR/out_counts.npy`); the inputs are seeded, so two builds run with the same arguments can be
+compared output for output.  Everything else the benchmark measures is behind `--full`:
+
+Roofline (`--full`): the last `len(STAGES)` warm-up steps time each pipeline stage once (HIP
+events around that stage's launch, `Engine.probe`); the slowest stage is the dominant kernel and
+is probed on every timed step.  Its algorithmic bytes per launch (DESIGN.md §4 per-stage model,
+priced with the engine's own per-frame unit counts) over its measured average launch time is
+`achieved`.  One more probe step per stage follows the timed steps.  A plain run takes the same
+untimed steps without the probes, so both modes time the same frames.
+
+CPU baseline (`--full`, one GPU, unless `--no-cpu-baseline`): the C oracle on the host's cores.
 
 Single process: `python bench.py`.  Multi-GPU: `python bench.py --gpus N` starts N child ranks
 itself (one per GPU, `launch_ranks`), or `torch.distributed.run --nproc-per-node N bench.py
@@ -319,8 +330,10 @@ def run_dropin(args):
         tr.update(d, img, e) if F else tr.update(d, img)
     t0 = time.perf_counter()
     for d, e, _ in frames[args.warmup:]:
-        tr.update(d, img, e) if F else tr.update(d, img)
+        res = tr.update(d, img, e) if F else tr.update(d, img)
     wall = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out_rows": np.asarray(res)})
     mean_d = float(np.mean([f[0].shape[0] for f in frames[args.warmup:]]))
     ref = REFERENCE_CPU_FPS.get(args.config)
     line = {
@@ -342,6 +355,55 @@ def run_dropin(args):
                       f"(BASELINE.md §2)"},
     }
     print(json.dumps(line), flush=True)
+
+
+def roofline_of(config, kind, F, dominant, dom_ms, units):
+    """The roofline record of the dominant stage: its algorithmic bytes (StrongSort's gallery
+    distance: flops) per launch over `dom_ms`, its measured time per step."""
+    if kind == "ocsort":
+        per_launch = (units["tracks"] * OCS_TRACK_BYTES + units["dets"] * 24 +
+                      units["outputs"] * 64)
+    elif kind == "boosttrack":
+        per_launch = boost_stage_bytes(dominant, units, F)
+    elif kind == "strongsort":
+        per_launch = ss_stage_bytes(dominant, units, F)
+    else:
+        per_launch = stage_bytes(dominant, units, F)
+    achieved = per_launch / (dom_ms * 1e-3) / 1e9
+    traffic = load_traffic(config, dominant)
+    roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic}
+    if kind == "strongsort" and dominant == "nn":
+        # the gallery distance is fp64 matrix-core work: 2 x sample rows x detections x F
+        # per launch against the measured dense fp64 MFMA rate
+        flops = 2.0 * units["rows"] * (units["dets"] / max(units["seqs"], 1)) * F
+        tf = flops / (dom_ms * 1e-3) / 1e12
+        roof = {"bound": "mfma", "achieved": round(tf, 2), "peak": F64_MFMA_PEAK_TFS,
+                "unit": "TFLOP/s", "frac": round(tf / F64_MFMA_PEAK_TFS, 4),
+                "peak_measured": F64_MFMA_MEASURED_TFS,
+                "frac_of_measured": round(tf / F64_MFMA_MEASURED_TFS, 4),
+                "traffic": traffic, "algorithmic_flops_per_launch": int(flops)}
+    return {**roof, "kernel": dominant, "kernel_ms": round(dom_ms, 4),
+            "algorithmic_bytes_per_launch": int(per_launch)}
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # all files of one --dump-outputs together
+
+
+def dump_outputs(dest, arrays, suffix=""):
+    """Write each array as `dest/<name><suffix>.npy` in float64 (what the engine writes; counts
+    are exact in it).  Past DUMP_MAX_BYTES in all, every array keeps a fixed, seeded sample of its
+    rows in their order, the same rows in every run."""
+    dest = Path(dest)
+    dest.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    # (256 bytes per file set aside for the .npy header)
+    over = sum(a.nbytes for a in arrays.values()) / (DUMP_MAX_BYTES - 256 * len(arrays))
+    for name, a in arrays.items():
+        if over > 1.0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] / over))
+            a = a[np.sort(np.random.default_rng(20240).choice(a.shape[0], keep, replace=False))]
+        np.save(dest / f"{name}{suffix}.npy", a)
 
 
 def free_port():
@@ -397,7 +459,14 @@ def main():
                     help="BoT-SORT/ByteTrack engine track slots per sequence")
     ap.add_argument("--det-cap", type=int, default=256,
                     help="BoT-SORT/ByteTrack engine detection slots per sequence")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-stage "
+                         "probes and the roofline of the dominant kernel, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (the packed "
+                         "output rows and the per-sequence row counts) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--with-d2h", action="store_true",
                     help="deliver every frame's output rows to pinned host memory inside the "
                          "timed region (a side-stream copy per frame, overlapped with the next "
@@ -422,6 +491,8 @@ def main():
     if args.cpu_worker:
         print(json.dumps(cpu_worker(json.loads(args.cpu_worker))), flush=True)
         return
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.dropin:
         return run_dropin(args)
     if args.gpus < 1:
@@ -479,39 +550,74 @@ def main():
     # W warm-up steps (at least start_frame - 1 - probes: the first timed frame), then one
     # untimed probe step per pipeline stage, then the K timed steps.  The stages are probed on
     # the last 2 x stages untimed steps (warm-up ones included), each twice, the larger kept: one
-    # event pair beside a concurrent side stream can read short
+    # event pair beside a concurrent side stream can read short.  The probes are --full's; a
+    # plain run takes the same untimed steps without them, so both modes time the same frames
+    full = args.full
     n_probe = len(stages)
     warmup = max(args.warmup, args.start_frame - 1 - n_probe)
     t_first = warmup + n_probe
-    n_pr = min(2 * n_probe, t_first)
+    n_pr = min(2 * n_probe, t_first) if full else 0
     total = t_first + args.steps
     # after the timed steps, one more probe step per stage: the stages at the timed frames' state
     # (StrongSort's galleries, for one, are still filling during the early probes)
-    n_frames = total + n_probe
+    n_frames = total + (n_probe if full else 0)
     if c5 and n_frames > src.n_frames_max:
         raise SystemExit("boosttrack_mot8: warmup + probes + steps exceed the shortest "
                          "sequence (600 frames)")
-    frames = [src.frame(t) for t in range(1, n_frames + 1)]  # resident in HBM before timing
-    n_rows = [int(f[1][-1].item()) for f in frames]  # detections per frame (host, pre-timing)
-    max_n = max(n_rows)
+    # The frames of a run are resident in HBM before they are timed.  A run of more frames than
+    # fit in half the free device memory stages them a batch at a time: the clock stops, with the
+    # device idle, while the next batch is generated, so generation is never timed.
+    frames, off_h = {}, {}  # frame index -> (dets, det_off, embs) in HBM; -> det_off on the host
+    staged = 0
+
+    def stage(upto):
+        nonlocal staged
+        for k in range(staged, upto):
+            frames[k] = src.frame(k + 1)
+            off_h[k] = frames[k][1].cpu().numpy()
+        staged = max(staged, upto)
+
+    stage(1)
+    frame_bytes = sum(x.numel() * x.element_size() for x in frames[0] if x is not None)
+    batch = max(2, torch.cuda.mem_get_info(dev)[0] // 2 // max(frame_bytes, 1))
+    stage(min(n_frames, max(batch, t_first + 1)))
     width = 10 if kind == "strongsort" else 8
-    out = torch.empty((max_n, width), dtype=torch.float64, device=dev)
-    cnt = torch.empty(S, dtype=torch.int32, device=dev)
     # --with-d2h: a ring of output buffers, each frame's rows (and per-sequence counts) copied to
     # pinned host memory on a side stream while the next frame computes; a buffer is rewritten
     # only after its copy completed (event), so no frame's rows are lost or torn
     RING = 3
-    d2h = None
-    if args.with_d2h:
-        d2h = dict(
-            outs=[torch.empty((max_n, width), dtype=torch.float64, device=dev)
-                  for _ in range(RING)],
-            cnts=[torch.empty(S, dtype=torch.int32, device=dev) for _ in range(RING)],
-            host=[torch.empty((max_n, width), dtype=torch.float64, pin_memory=True)
-                  for _ in range(RING)],
-            hcnt=[torch.empty(S, dtype=torch.int32, pin_memory=True) for _ in range(RING)],
-            side=torch.cuda.Stream(device=dev),
-            done=[None] * RING, bytes=0)
+    max_n, out, cnt, d2h = 0, None, None, None
+
+    def alloc_outputs():
+        """Output buffers for the largest staged frame (kept when they are large enough)."""
+        nonlocal max_n, out, cnt, d2h
+        need = max(int(off_h[k][-1]) for k in frames)
+        if need <= max_n:
+            return
+        max_n = need
+        out = torch.empty((max_n, width), dtype=torch.float64, device=dev)
+        cnt = torch.empty(S, dtype=torch.int32, device=dev)
+        if args.with_d2h:
+            d2h = dict(
+                outs=[torch.empty((max_n, width), dtype=torch.float64, device=dev)
+                      for _ in range(RING)],
+                cnts=[torch.empty(S, dtype=torch.int32, device=dev) for _ in range(RING)],
+                host=[torch.empty((max_n, width), dtype=torch.float64, pin_memory=True)
+                      for _ in range(RING)],
+                hcnt=[torch.empty(S, dtype=torch.int32, pin_memory=True) for _ in range(RING)],
+                side=d2h["side"] if d2h else torch.cuda.Stream(device=dev),
+                done=[None] * RING, bytes=d2h["bytes"] if d2h else 0)
+
+    def next_batch(k):
+        """Frames before k have run: drop them and stage the next batch (device idle, untimed)."""
+        torch.cuda.synchronize()
+        for j in [j for j in frames if j < k]:
+            del frames[j]
+        stage(min(n_frames, k + batch))
+        alloc_outputs()
+        torch.cuda.synchronize()
+
+    alloc_outputs()
     stream = torch.cuda.current_stream()
     torch.cuda.synchronize()
 
@@ -553,7 +659,7 @@ def main():
         ev.record(stream)
         side = d2h["side"]
         side.wait_event(ev)
-        n = n_rows[k]
+        n = int(off_h[k][-1])
         with torch.cuda.stream(side):
             d2h["host"][slot][:n].copy_(out[:n], non_blocking=True)
             d2h["hcnt"][slot].copy_(cnt, non_blocking=True)
@@ -562,7 +668,8 @@ def main():
         d2h["done"][slot] = done
         d2h["bytes"] += n * width * 8 + S * 4
 
-    # warm-up, then the probe steps: each times one stage to find the dominant kernel
+    # warm-up, then the probe steps: each times one stage to find the dominant kernel (--full;
+    # a plain run takes them as further warm-up steps)
     stage_ms = {}
     for k in range(t_first):
         j = k - (t_first - n_pr)
@@ -590,49 +697,68 @@ def main():
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
-    # two event records per step around the dominant stage's launch (OCSort: its one kernel)
-    eng.probe(True if ocs else dominant)
+    # --full: two event records per step around the dominant stage's launch (OCSort: its one
+    # kernel)
+    if full:
+        eng.probe(True if ocs else dominant)
     if d2h is not None:
         d2h["bytes"] = 0
-    t0 = time.perf_counter()
-    for k in range(t_first, total):
-        step(k)
-    torch.cuda.synchronize()  # (every stream of the device: the side-stream copies included)
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    wall = time.perf_counter() - t0
+    wall, k = 0.0, t_first
+    while k < total:
+        if k >= staged:
+            next_batch(k)
+        end = min(total, staged)
+        t0 = time.perf_counter()
+        for j in range(k, end):
+            step(j)
+        torch.cuda.synchronize()  # (every stream of the device: the side-stream copies included)
+        if end == total:
+            if dist:
+                dist.barrier()
+            torch.cuda.synchronize()
+        wall += time.perf_counter() - t0
+        k = end
     d2h_bytes = d2h["bytes"] if d2h is not None else 0
-    dom_ms, dom_n = eng.probe_read()
-    eng.probe(False if ocs else None)
-    dom_ms /= args.steps  # per step: the dominant stage's launches over all chunks
     if eng.status() != 0:
         raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
-    units = eng.frame_stats()  # last timed frame, all sequences of this rank
-    if ocs:
-        units["dets"] = int(frames[total - 1][1][-1].item())
+    dom_ms, units = 0.0, None
+    if full:
+        dom_ms, dom_n = eng.probe_read()
+        eng.probe(False if ocs else None)
+        dom_ms /= args.steps  # per step: the dominant stage's launches over all chunks
+        units = eng.frame_stats()  # last timed frame, all sequences of this rank
+    if full and ocs:
+        units["dets"] = int(off_h[total - 1][-1])
     emb_bytes = 8 if bst or sss else 4
-    if sss:
+    if full and sss:
         units["seqs"] = S
         # distinct gallery samples compared per queried track at the last timed frame
         units["rows_per_queried_track"] = round(units["rows"] / max(units["queried"], 1), 2)
         # LSAPs solved (all frames of this rank): certified unique / unique up to rejected pairs
         # / ties re-solved in scipy's order / cascade stages restarted
         units["lsap_all_frames"] = eng.lsap_stats()
-    if kind in ("bytetrack", "botsort"):
+    if full and kind in ("bytetrack", "botsort"):
         # associations whose optimum was tied, re-solved in lapx's JV order, summed
         # over all frames of this rank
         units["lap_ties_all_frames"] = eng.lap_ties()
 
     # per-sequence records of this rank's shard: [global seq id, frames timed, dets timed,
     # rows of the last frame, checksum of the last frame, rank wall s, dominant-stage ms]
-    off_h = [frames[k][1].cpu().numpy() for k in range(t_first, total)]
-    dets_seq = np.sum([np.diff(o) for o in off_h], 0)
-    last_off, cnt_h, out_h = off_h[-1], cnt.cpu().numpy(), out.cpu().numpy()
-    # untimed, after the timed region and its outputs: one probe step per stage at the timed
-    # frames' state (StrongSort's galleries, for one, are still filling during the early probes)
+    dets_seq = np.sum([np.diff(off_h[k]) for k in range(t_first, total)], 0)
+    last_off, cnt_h, out_h = off_h[total - 1], cnt.cpu().numpy(), out.cpu().numpy()
+    # what the last timed step handed its caller: each sequence's output rows, packed in sequence
+    # order, and the per-sequence row counts
+    rows = [out_h[last_off[i]: last_off[i] + cnt_h[i]] for i in range(S)]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out_rows": np.concatenate(rows, 0), "out_counts": cnt_h},
+                     "" if world == 1 else f"_rank{rank}")
+    # --full, untimed, after the timed region and its outputs: one probe step per stage at the
+    # timed frames' state (StrongSort's galleries, for one, are still filling during the early
+    # probes)
     stage_ms_late = {}
-    for j in range(n_probe):
+    for j in range(n_probe if full else 0):
+        if total + j >= staged:
+            next_batch(total + j)
         eng.probe(stages[j])
         step(total + j)
         stage_ms_late[stages[j]] = eng.probe_read()[0]
@@ -640,8 +766,7 @@ def main():
     torch.cuda.synchronize()
     recs = np.zeros((S, 7))
     for i, g in enumerate(c5_mine if c5 else shard_sequences(S * world, world, rank)):
-        rows_i = out_h[last_off[i]: last_off[i] + cnt_h[i]]
-        recs[i] = [g, args.steps, dets_seq[i], cnt_h[i], output_checksum(rows_i), wall, dom_ms]
+        recs[i] = [g, args.steps, dets_seq[i], cnt_h[i], output_checksum(rows[i]), wall, dom_ms]
     # RCCL over xGMI only to gather these KB-scale records once, never per frame
     allrec = gather_records(recs, dist, dev if backend == "nccl" else "cpu")
     t_max = float(allrec[:, 5].max())
@@ -651,29 +776,14 @@ def main():
         n_all = C5_TOTAL if c5 else S * world
         assert np.array_equal(np.sort(allrec[:, 0]), np.arange(n_all)), "shard gather"
         mean_d = float(allrec[:, 2].sum() / allrec[:, 1].sum())
-        if ocs:
-            per_launch = (units["tracks"] * OCS_TRACK_BYTES + units["dets"] * 24 +
-                          units["outputs"] * 64)
-        elif bst:
-            per_launch = boost_stage_bytes(dominant, units, F)
-        elif sss:
-            per_launch = ss_stage_bytes(dominant, units, F)
-        else:
-            per_launch = stage_bytes(dominant, units, F)
-        achieved = per_launch / (dom_ms * 1e-3) / 1e9
-        traffic = load_traffic(args.config, dominant)
-        roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic}
-        if sss and dominant == "nn":
-            # the gallery distance is fp64 matrix-core work: 2 x sample rows x detections x F
-            # per launch against the measured dense fp64 MFMA rate
-            flops = 2.0 * units["rows"] * (units["dets"] / max(units["seqs"], 1)) * F
-            tf = flops / (dom_ms * 1e-3) / 1e12
-            roof = {"bound": "mfma", "achieved": round(tf, 2), "peak": F64_MFMA_PEAK_TFS,
-                    "unit": "TFLOP/s", "frac": round(tf / F64_MFMA_PEAK_TFS, 4),
-                    "peak_measured": F64_MFMA_MEASURED_TFS,
-                    "frac_of_measured": round(tf / F64_MFMA_MEASURED_TFS, 4),
-                    "traffic": traffic, "algorithmic_flops_per_launch": int(flops)}
+        roofline = None
+        if full:
+            roofline = {**roofline_of(args.config, kind, F, dominant, dom_ms, units),
+                        "probe_steps": n_pr, "launches_per_step": len(bounds),
+                        "units_last_frame": units,
+                        "stage_ms_probe": {k: round(v, 4) for k, v in stage_ms.items()},
+                        "stage_ms_after_timed": {k: round(v, 4)
+                                                 for k, v in stage_ms_late.items()}}
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": warmup,
@@ -707,17 +817,10 @@ def main():
                            "bytes_per_step": round(d2h_bytes / args.steps),
                            "GB_s": round(d2h_bytes / t_max / 1e9, 2)}} if d2h is not None else
                           {})},
-            "roofline": {**roof, "kernel": dominant,
-                         "kernel_ms": round(dom_ms, 4), "probe_steps": n_pr,
-                         "launches_per_step": len(bounds),
-                         "algorithmic_bytes_per_launch": int(per_launch),
-                         "units_last_frame": units,
-                         "stage_ms_probe": {k: round(v, 4) for k, v in stage_ms.items()},
-                         "stage_ms_after_timed": {k: round(v, 4)
-                                                  for k, v in stage_ms_late.items()}},
+            "roofline": roofline,
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.config, kind, n_obj, F, params,
                                                 args.cpu_seconds)
         print(json.dumps(line), flush=True)

@@ -8,7 +8,7 @@ for r in $(seq 1 "$R"); do
   for v in "$@"; do
     lib=boxmot_amd/lib/libbxassoc.so
     [ "$v" != base ] && lib=boxmot_amd/lib/libbxassoc_$v.so
-    BX_LIB_PATH=$lib timeout -k 10 150 python bench.py --config "$CFG" --no-cpu-baseline \
+    BX_LIB_PATH=$lib timeout -k 10 150 python bench.py --full --config "$CFG" --no-cpu-baseline \
       > "gpurun_out/ab/${CFG}_${v}_$r.json" 2>/dev/null
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], sys.argv[3], d['value'], d['ms_per_step'], {k: round(v, 4) for k, v in d['roofline']['stage_ms_probe'].items()})" \
       "gpurun_out/ab/${CFG}_${v}_$r.json" "$v" "$r"

@@ -13,7 +13,7 @@ for r in $(seq 1 "$R"); do
       [ -z "$p" ] && continue
       if [ "${p%%=*}" = lib ]; then lib=boxmot_amd/lib/libbxassoc_${p#*=}.so; else envs+=("$p"); fi
     done
-    env "${envs[@]}" BX_LIB_PATH=$lib timeout -k 10 150 python bench.py --config "$CFG" --no-cpu-baseline \
+    env "${envs[@]}" BX_LIB_PATH=$lib timeout -k 10 150 python bench.py --full --config "$CFG" --no-cpu-baseline \
       > "gpurun_out/ab/${CFG}_${name}_$r.json" 2>/dev/null || { echo "$name $r FAILED"; exit 1; }
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], sys.argv[3], d['value'], d['ms_per_step'], {k: round(v, 4) for k, v in d['roofline']['stage_ms_probe'].items()})" \
       "gpurun_out/ab/${CFG}_${name}_$r.json" "$name" "$r"

@@ -4,7 +4,7 @@
 set -euo pipefail
 CFG=$1; shift
 for v in "$@"; do
-  BX_LIB_PATH=boxmot_amd/lib/libbxassoc_$v.so timeout -k 10 150 python bench.py --config $CFG \
+  BX_LIB_PATH=boxmot_amd/lib/libbxassoc_$v.so timeout -k 10 150 python bench.py --full --config $CFG \
     --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/${CFG}_$v.json 2> gpurun_out/${CFG}_$v.err
 done
 mkdir -p gpurun_out/tl

@@ -58,7 +58,7 @@ def main(tag, config, dest=None, timed_n=50):
     out = {"tag": tag, "config": config, "stages": {}}
     md = [f"# rocprofv3 summary — {tag} / {config}", "",
           f"Commands: `bash tools/trace_only.sh {tag} {config}` (rocprofv3 --kernel-trace "
-          f"--stats, bench.py --steps 50 --warmup 10) and `bash tools/pmc_passes.sh {tag} "
+          f"--stats, bench.py --full --steps 50 --warmup 10) and `bash tools/pmc_passes.sh {tag} "
           f"{config}` (separate --pmc passes: SQ group, FETCH_SIZE, WRITE_SIZE, misc).", "",
           "## Engine kernels (rocprofv3 --stats)", "",
           "| stage | kernel | calls | avg us (all) | avg us (timed 50) | FETCH x2 + WRITE "
