@@ -20,6 +20,7 @@ HEADER = REPO / "include" / "bxassoc.h"
 HEADER_OCS = REPO / "include" / "bxocsort.h"
 HEADER_BOOST = REPO / "include" / "bxboost.h"
 HEADER_SS = REPO / "include" / "bxstrongsort.h"
+HEADER_DEEPOC = REPO / "include" / "bxdeepocsort.h"
 HEADER_IO = REPO / "include" / "bxio.h"
 
 HIPCC_FLAGS = [
@@ -31,7 +32,7 @@ HIPCC_FLAGS = [
     "-mllvm", "-amdgpu-mfma-vgpr-form=1",
 ]
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
-           "bx_strongsort.hip", "bx_io.cpp"]
+           "bx_strongsort.hip", "bx_deepocsort.hip", "bx_io.cpp"]
 
 
 class NativeUnavailable(RuntimeError):
@@ -162,6 +163,18 @@ class BxBoostConfig(C.Structure):
     ]
 
 
+class BxDeepocConfig(C.Structure):
+    _fields_ = [
+        ("n_seq", C.c_int32), ("track_cap", C.c_int32), ("det_cap", C.c_int32),
+        ("emb_dim", C.c_int32), ("det_thresh", C.c_double), ("iou_threshold", C.c_double),
+        ("inertia", C.c_double), ("q_xy_scaling", C.c_double), ("q_s_scaling", C.c_double),
+        ("w_association_emb", C.c_double), ("alpha_fixed_emb", C.c_double),
+        ("aw_param", C.c_double), ("max_age", C.c_int32), ("min_hits", C.c_int32),
+        ("delta_t", C.c_int32), ("embedding_off", C.c_int32), ("aw_off", C.c_int32),
+        ("asso_kind", C.c_int32), ("frame_w", C.c_double), ("frame_h", C.c_double),
+    ]
+
+
 class BxSsConfig(C.Structure):
     _fields_ = [
         ("n_seq", C.c_int32), ("track_cap", C.c_int32), ("det_cap", C.c_int32),
@@ -205,6 +218,11 @@ EXPORTS = [
     "bx_kf_xysr_update", "bx_kf_boost_initiate", "bx_kf_boost_predict", "bx_kf_boost_update",
     "bx_kf_boost_mh_dist", "bx_ss_track_attrs_host", "bx_ss_track_attrs_set_host",
     "bx_ss_last_feature_host", "bx_ss_last_feature_set_host",
+    "bx_deepoc_create", "bx_deepoc_destroy", "bx_deepoc_reset", "bx_deepoc_step",
+    "bx_deepoc_update_host", "bx_deepoc_copy_state", "bx_deepoc_status",
+    "bx_deepoc_counters_host", "bx_deepoc_set_id_count", "bx_deepoc_set_frame_size",
+    "bx_deepoc_tracks_host", "bx_deepoc_state_set_host", "bx_deepoc_frame_stats_host",
+    "bx_deepoc_probe", "bx_deepoc_probe_read", "bx_deepoc_embcost",
 ]
 
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -320,6 +338,22 @@ _SIGS = {
     "bx_ss_track_attrs_set_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
     "bx_ss_last_feature_host": ([_vp, C.c_int, C.c_int, _vp, _vp], C.c_int),
     "bx_ss_last_feature_set_host": ([_vp, C.c_int, C.c_int, _vp, _vp, C.c_int], C.c_int),
+    "bx_deepoc_create": ([C.POINTER(BxDeepocConfig), C.POINTER(C.c_void_p)], C.c_int),
+    "bx_deepoc_destroy": ([_vp], C.c_int),
+    "bx_deepoc_reset": ([_vp, C.c_int, C.c_int, _vp], C.c_int),
+    "bx_deepoc_step": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_deepoc_update_host": ([_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _ip, _vp], C.c_int),
+    "bx_deepoc_copy_state": ([_vp, _vp], C.c_int),
+    "bx_deepoc_status": ([_vp, _ip], C.c_int),
+    "bx_deepoc_counters_host": ([_vp, C.c_int, _ip, _ip, _ip], C.c_int),
+    "bx_deepoc_set_id_count": ([_vp, C.c_int, C.c_int, _vp], C.c_int),
+    "bx_deepoc_set_frame_size": ([_vp, C.c_int, C.c_double, C.c_double, _vp], C.c_int),
+    "bx_deepoc_tracks_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _ip], C.c_int),
+    "bx_deepoc_state_set_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_deepoc_frame_stats_host": ([_vp, C.c_int, C.c_int, C.POINTER(C.c_int64)], C.c_int),
+    "bx_deepoc_probe": ([_vp, C.c_int], C.c_int),
+    "bx_deepoc_probe_read": ([_vp, _dp, _ip], C.c_int),
+    "bx_deepoc_embcost": ([C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
 }
 
 _lib = None

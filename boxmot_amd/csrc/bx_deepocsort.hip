@@ -1,0 +1,1149 @@
+// bx_deepocsort.hip — the DeepOCSort per-frame update on MI355X.
+//
+// Reference: boxmot/trackers/deepocsort/deepocsort.py:265-498 (DeepOcSort.update), its
+// KalmanBoxTracker (deepocsort.py:51-235: OCSort's, plus apply_affine_correction and the
+// embedding moving average) over the XYSR Kalman filter with observation-centric re-update
+// (motion/kalman_filters/aabb/xysr_kf.py:48-291, apply_affine_correction :111-135),
+// enhanced_associate with the appearance term (utils/association.py:377-556),
+// compute_aw_max_metric (:320-374) and the legacy lapx linear_assignment (:105-114), with the
+// patches P1-P5 of SURVEY.md Appendix A as in bx_ocsort.hip.
+//
+// Per frame, three launches on the caller's stream:
+//   deepoc_embcost_kernel  dets_embs @ trk_embs.T for every detection x pre-frame track of every
+//                          sequence: the fp64 MFMA tile of bx_embtile.h (shared with BoostTrack)
+//   deepoc_frame_kernel    one wave64 workgroup per sequence, grown from ocsort_frame_kernel on
+//                          the device code of bx_ocs_device.h: CMC affine correction, predict,
+//                          first association (IoU + direction consistency + appearance), updates,
+//                          OCR round, births, outputs, deaths; emits embedding records
+//   deepoc_feature_kernel  wave per record: emb = a*emb + (1-a)*det, emb /= ||emb|| (wave-order
+//                          norm, as boost_feature_kernel), or the newborn's copy of its row
+// The library builds with -ffp-contract=off; every expression keeps numpy's operation order.
+#include <float.h>
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/bxdeepocsort.h"
+#include "bx_device.h"
+
+using namespace bx;
+
+int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
+hipError_t bx_lds_attr(const void* kern, size_t bytes);  // bx_engine.hip (never lowers a limit)
+
+namespace {
+
+#include "bx_ocs_device.h"
+#include "bx_embtile.h"
+
+// OCSort's device record (o.min_conf unused, o.use_byte 0) plus the appearance state.  Per
+// sequence, seqst[SO_IDS] starts at 1 (KalmanBoxTracker.count = 1, deepocsort.py:305).
+struct DocDev {
+  OcsDev o;
+  int F;               // embedding width (0 with embedding_off)
+  int x_off;           // bytes of LDS the shared carve takes (DocLds follows)
+  int emb_off, aw_off;
+  double w_emb, alpha_fixed, aw_param;
+  double* emb;         // [S][T][F] track embeddings by slot
+  double* ec;          // [S][D][T] emb cost by (detection of the frame, pre-frame list position)
+  double* em;          // [S][D*T] the masked emb cost of the first association, [nh][nt]
+  int* rec;            // [S][D] per detection of the frame: the slot its embedding goes to, or -1
+  double* rec_a;       // [S][D] EMA weight alpha, < 0: newborn copy
+};
+
+// LDS past the shared carve: pre-frame list position of each kept track, AW weights and flags
+struct DocLds {
+  int* pp;      // [T]
+  double* rw;   // [D]
+  double* cw;   // [T]
+  int *ra, *ca; // [D], [T]
+};
+
+__host__ __device__ inline size_t doc_i8(size_t n) { return ((n * 4 + 7) / 8) * 8; }
+size_t doc_lds_extra(int D, int T) {
+  return doc_i8(T) + (size_t)D * 8 + (size_t)T * 8 + doc_i8(D) + doc_i8(T);
+}
+__device__ void doc_carve(const OcsDev& g, char* base, DocLds& X) {
+  size_t o = 0;
+  X.pp = (int*)(base + o);
+  o += doc_i8(g.T);
+  X.rw = (double*)(base + o);
+  o += (size_t)g.D * 8;
+  X.cw = (double*)(base + o);
+  o += (size_t)g.T * 8;
+  X.ra = (int*)(base + o);
+  o += doc_i8(g.D);
+  X.ca = (int*)(base + o);
+}
+
+// m @ p + t of the two corner points of a box (deepocsort.py:196-198)
+__device__ __forceinline__ void warp_box(const double* w, double* b) {
+  const double x1 = (w[0] * b[0] + w[1] * b[1]) + w[2], y1 = (w[3] * b[0] + w[4] * b[1]) + w[5];
+  const double x2 = (w[0] * b[2] + w[1] * b[3]) + w[2], y2 = (w[3] * b[2] + w[4] * b[3]) + w[5];
+  b[0] = x1;
+  b[1] = y1;
+  b[2] = x2;
+  b[3] = y2;
+}
+
+// P[i0:i0+2, i0:i0+2] = m @ P[..] @ m.T, left to right (xysr_kf.py:122-123)
+__device__ __forceinline__ void warp_cov(const double* w, double* P, int i0) {
+  const double p00 = P[i0 * 7 + i0], p01 = P[i0 * 7 + i0 + 1];
+  const double p10 = P[(i0 + 1) * 7 + i0], p11 = P[(i0 + 1) * 7 + i0 + 1];
+  const double a00 = w[0] * p00 + w[1] * p10, a01 = w[0] * p01 + w[1] * p11;
+  const double a10 = w[3] * p00 + w[4] * p10, a11 = w[3] * p01 + w[4] * p11;
+  P[i0 * 7 + i0] = a00 * w[0] + a01 * w[1];
+  P[i0 * 7 + i0 + 1] = a00 * w[3] + a01 * w[4];
+  P[(i0 + 1) * 7 + i0] = a10 * w[0] + a11 * w[1];
+  P[(i0 + 1) * 7 + i0 + 1] = a10 * w[3] + a11 * w[4];
+}
+
+// KalmanFilterXYSR.apply_affine_correction on one (x, P) (xysr_kf.py:119-123)
+__device__ __forceinline__ void warp_state(const double* w, double* x, double* P) {
+  const double x0 = (w[0] * x[0] + w[1] * x[1]) + w[2], x1 = (w[3] * x[0] + w[4] * x[1]) + w[5];
+  const double v0 = w[0] * x[4] + w[1] * x[5], v1 = w[3] * x[4] + w[4] * x[5];
+  x[0] = x0;
+  x[1] = x1;
+  x[4] = v0;
+  x[5] = v1;
+  warp_cov(w, P, 0);
+  warp_cov(w, P, 4);
+}
+
+// KalmanBoxTracker.apply_affine_correction (deepocsort.py:191-208) of one track, by one lane.
+// last_observation and observations[its age] are ONE array in the reference (update stores the
+// same `bbox` object in both), so a write through either name shows through the other: the
+// newest observation is warped once as last_observation (only if its sum is > 0) and once more
+// when the loop over ages age-delta_t..age reaches its key.  Here the two are separate copies,
+// kept equal.
+__device__ void doc_affine(const OcsDev& g, OcsTrk& t, const double* w) {
+  double lo[4] = {t.last_obs[0], t.last_obs[1], t.last_obs[2], t.last_obs[3]};
+  if (sum5(t.last_obs) > 0) warp_box(w, lo);
+  for (int dt = g.delta_t; dt >= 0; dt--) {
+    const int want = t.age - dt;
+    if (want < 0 || t.obs_age[want & (OBS_KEEP - 1)] != want) continue;
+    if (want == t.last_age)
+      warp_box(w, lo);
+    else
+      warp_box(w, t.obs_box[want & (OBS_KEEP - 1)]);
+  }
+  if (t.last_age >= 0) {
+    for (int q = 0; q < 4; q++) t.last_obs[q] = t.obs_box[t.last_age & (OBS_KEEP - 1)][q] = lo[q];
+  }
+  warp_state(w, t.x, t.P);
+  // the frozen snapshot (attr_saved) of a track that is not observed; its last_measurement is
+  // warped too in the reference but never read again
+  if (!t.observed && t.has_saved) warp_state(w, t.sx, t.sP);
+}
+
+__global__ void __launch_bounds__(256)
+    deepoc_embcost_kernel(DocDev g, int seq0, const int* __restrict__ det_off,
+                          const double* __restrict__ embs) {
+  __shared__ double lds[2 * EC_STAGE];
+  const int b = blockIdx.x, seq = seq0 + b;
+  const int T = g.o.T;
+  const int r0 = det_off[b];
+  int nd = det_off[b + 1] - r0;
+  if (nd > g.o.D) nd = g.o.D;
+  const int nt = g.o.seqst[(size_t)seq * SQO + SO_NTR];
+  const int d0 = (int)blockIdx.y / ec_tiles_t(T) * EC_BM;
+  const int t0 = (int)blockIdx.y % ec_tiles_t(T) * EC_BN;
+  if (d0 >= nd || t0 >= nt) return;  // workgroup-uniform
+  const int F = g.F;
+  const int* order = g.o.order + (size_t)seq * T;
+  const double* temb = g.emb + (size_t)seq * T * F;
+  const int tid = threadIdx.x;
+  const int ar = ec_arow(tid), br = ec_brow(tid);
+  const bool a_ok = d0 + ar < nd, b_ok = t0 + br < nt;
+  const double* ap = embs + (size_t)(r0 + (a_ok ? d0 + ar : 0)) * F + ec_ak(tid);
+  const double* bp = temb + (size_t)(b_ok ? order[t0 + br] : 0) * F + ec_bk(tid);
+  d4 acc[2];
+  ec_tile(lds, F, a_ok, ap, b_ok, bp, acc);
+  ec_tile_store(acc, d0, t0, nd, nt, g.ec + (size_t)seq * g.o.D * T, T);
+}
+
+// the op: the same tile on plain arrays, grid (1, tiles of nd x nt)
+__global__ void __launch_bounds__(256)
+    deepoc_embcost_op_kernel(int nd, int nt, int F, const double* __restrict__ A,
+                             const double* __restrict__ B, double* __restrict__ out) {
+  __shared__ double lds[2 * EC_STAGE];
+  const int d0 = (int)blockIdx.x / ec_tiles_t(nt) * EC_BM;
+  const int t0 = (int)blockIdx.x % ec_tiles_t(nt) * EC_BN;
+  if (d0 >= nd || t0 >= nt) return;
+  const int tid = threadIdx.x;
+  const int ar = ec_arow(tid), br = ec_brow(tid);
+  const bool a_ok = d0 + ar < nd, b_ok = t0 + br < nt;
+  const double* ap = A + (size_t)(a_ok ? d0 + ar : 0) * F + ec_ak(tid);
+  const double* bp = B + (size_t)(b_ok ? t0 + br : 0) * F + ec_bk(tid);
+  d4 acc[2];
+  ec_tile(lds, F, a_ok, ap, b_ok, bp, acc);
+  ec_tile_store(acc, d0, t0, nd, nt, out, nt);
+}
+
+__global__ void __launch_bounds__(OW)
+    deepoc_frame_kernel(DocDev gd, int seq0, const float* __restrict__ dets,
+                        const int* __restrict__ det_off, const double* __restrict__ warps,
+                        double* __restrict__ out, int* __restrict__ out_count) {
+  extern __shared__ __align__(16) char lds_raw[];
+  const OcsDev& g = gd.o;
+  OcsLds L;
+  DocLds X;
+  carve(g, lds_raw, L);
+  doc_carve(g, lds_raw + gd.x_off, X);
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x, seq = seq0 + b;
+  L.jv.dc = nullptr;
+  const int r0 = det_off[b];
+  int n = det_off[b + 1] - r0;
+  if (n > g.D) {  // the host checks det_cap; a device-side overflow is latched, never run past
+    if (threadIdx.x == 0) atomicExch(g.status, (int)BX_ERR_CAPACITY);
+    n = g.D;
+  }
+  int* sq = g.seqst + (size_t)seq * SQO;
+  OcsTrk* trk = g.trk + (size_t)seq * g.T;
+  int* order = g.order + (size_t)seq * g.T;
+  double* tb = g.tb + (size_t)seq * g.T * TB;
+  double* cost = g.cost_g ? g.cost_g + (size_t)seq * g.D * g.T : nullptr;
+  const bool use_emb = !gd.emb_off;
+  const double* ec = use_emb ? gd.ec + (size_t)seq * g.D * g.T : nullptr;
+  double* em = use_emb ? gd.em + (size_t)seq * g.D * g.T : nullptr;
+  int* rec = gd.rec + (size_t)seq * g.D;
+  double* rec_a = gd.rec_a + (size_t)seq * g.D;
+  const int frame = sq[SO_FRAME] + 1;
+  const int id0 = sq[SO_IDS];
+  const int nt0 = sq[SO_NTR];
+  const double thr = g.asso_threshold;
+  const int ak = g.asso_kind;
+  const double fw = g.fsz[2 * seq], fh = g.fsz[2 * seq + 1];
+
+  // detections (setup_decorator's float32 rounding is the input format); deepocsort.py:339
+  for (int q = lane; q < n * 6; q += OW) L.dd[q] = (double)dets[(size_t)r0 * 6 + q];
+  for (int p = lane; p < nt0; p += OW) L.lst2[p] = order[p];
+  if (use_emb)
+    for (int i = lane; i < n; i += OW) rec[i] = -1;
+  __syncthreads();
+  const int nh = wave_compact(
+      n, [&](int i) { return L.dd[6 * i + 4] > g.det_thresh; }, [&](int i, int p) { L.hi[p] = i; });
+
+  // embedding record of detection row i (deepocsort.py:357-360, :415, :446): the track slot and
+  // alpha = af + (1 - af) * (1 - trust), trust = (conf - det_thresh) / (1 - det_thresh)
+  auto emit = [&](int i, int slot, bool born) {
+    if (!use_emb) return;
+    const double trust = (L.dd[6 * i + 4] - g.det_thresh) / (1 - g.det_thresh);
+    const double af = gd.alpha_fixed;
+    rec_a[i] = born ? -1.0 : af + (1 - af) * (1 - trust);
+    rec[i] = slot;
+  };
+
+  // ---- CMC affine correction of every track (deepocsort.py:352-355), a lane per track -------
+  if (warps) {
+    double w[6];
+    for (int q = 0; q < 6; q++) w[q] = warps[(size_t)b * 6 + q];
+    for (int p = lane; p < nt0; p += OW) doc_affine(g, trk[L.lst2[p]], w);
+    __syncthreads();
+  }
+
+  const int oct = lane >> 3, r8 = lane & 7, rr8 = r8 < 7 ? r8 : 6;
+
+  // predict every track (an octet per track); tracks whose prediction has a NaN leave the list
+  // (deepocsort.py:367-382).  tb row per kept track: box[4], k-previous obs[5], last_obs[5],
+  // vel[2]; pp = its pre-frame list position (the column of ec)
+  int nt = 0;
+  for (int c = 0; c < nt0; c += 8) {
+    const int p = c + oct;
+    bool keep = false;
+    int slot = -1;
+    double v0 = 0.0, v1 = 0.0;  // this lane's two tb entries: [r8] and [8 + r8]
+    if (p < nt0) {
+      slot = L.lst2[p];
+      OcsTrk& t = trk[slot];
+      KfRow k;
+      row_load(t.x, t.P, rr8, k);
+      if ((osh(k.x, 6) + osh(k.x, 2)) <= 0 && rr8 == 6) k.x *= 0.0;
+      kfo_predict(g, rr8, k);
+      row_store(t.x, t.P, r8, k);
+      const int age = t.age + 1;
+      if (r8 == 0) {
+        t.age = age;
+        if (t.tsu > 0) t.hit_streak = 0;
+        t.tsu++;
+      }
+      double xs[4], bx[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) xs[q] = osh(k.x, q);
+      x_to_bbox(xs, bx);
+      keep = !(isnan(bx[0]) || isnan(bx[1]) || isnan(bx[2]) || isnan(bx[3]));
+      // k_previous_obs (deepocsort.py:17-25) with the post-predict age
+      int qq = -1;
+      const int last_age = t.last_age;
+      if (last_age >= 0) {
+        qq = obs_first(t, age - g.delta_t, g.delta_t);
+        if (qq < 0) qq = last_age & (OBS_KEEP - 1);  // observations[max(keys)]
+      }
+      auto val = [&](int e) -> double {
+        if (e < 4) return e == 0 ? bx[0] : e == 1 ? bx[1] : e == 2 ? bx[2] : bx[3];
+        if (e < 9) return qq < 0 ? -1.0 : t.obs_box[qq][e - 4];
+        if (e < 14) return t.last_obs[e - 9];
+        return t.has_vel ? t.vel[e - 14] : 0.0;
+      };
+      v0 = val(r8);
+      v1 = val(8 + r8);
+    }
+    const unsigned long long m = __ballot(keep && r8 == 0);
+    if (keep) {
+      const int q = nt + __popcll(m & ((1ull << (lane & ~7)) - 1ull));
+      if (r8 == 0) {
+        L.lst[q] = slot;
+        X.pp[q] = p;
+      }
+      double* row = tb + (size_t)q * TB;
+      row[r8] = v0;
+      row[8 + r8] = v1;
+    }
+    nt += __popcll(m);
+  }
+  __syncthreads();
+
+  // ---- first association: associate(dets over det_thresh, predicted tracks, emb cost) -------
+  int nm = 0, nud = 0, nut = 0;
+  if (nt == 0) {
+    for (int k = lane; k < nh; k += OW) L.ud[k] = k;
+    nud = nh;
+  } else {
+    int nmi = 0;
+    if (nh > 0) {
+      // pass 1 (lane per track, dets broadcast from LDS): IoU > threshold counts for the
+      // one-to-one test, as OCSort
+      for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = 0;
+      __syncthreads();
+      for (int c = 0; c < nt; c += OW) {
+        const int ti = c + lane;
+        if (ti < nt) {
+          const double* bq = tb + (size_t)ti * TB;
+          const double b0 = bq[0], b1 = bq[1], b2 = bq[2], b3 = bq[3];
+          const double at = (b2 - b0) * (b3 - b1);
+          int cc = 0;
+          for (int d = 0; d < nh; d++) {
+            const double* a = L.dd + 6 * L.hi[d];
+            const double xx1 = fmax(a[0], b0), yy1 = fmax(a[1], b1);
+            const double xx2 = fmin(a[2], b2), yy2 = fmin(a[3], b3);
+            const double w = fmax(0.0, xx2 - xx1), h = fmax(0.0, yy2 - yy1);
+            const double wh = w * h;
+            if (wh > 0.0 || thr < 0.0 || ak != ASSO_IOU) {
+              const double o = ak == ASSO_IOU ? wh / ((a[2] - a[0]) * (a[3] - a[1]) + at - wh)
+                                              : asso_pair(ak, a, bq, fw, fh);
+              if (o > thr) {
+                atomicAdd(&L.rowcnt[d], 1);
+                L.rowcol[d] = ti;
+                cc++;
+              }
+            }
+          }
+          L.colcnt[ti] = cc;
+        }
+      }
+      __syncthreads();
+      int mr = 0, mcx = 0;
+      for (int k = lane; k < nh; k += OW) mr = max(mr, L.rowcnt[k]);
+      for (int k = lane; k < nt; k += OW) mcx = max(mcx, L.colcnt[k]);
+      for (int o = 32; o >= 1; o >>= 1) {
+        mr = max(mr, __shfl_xor(mr, o));
+        mcx = max(mcx, __shfl_xor(mcx, o));
+      }
+      if (mr == 1 && mcx == 1) {  // one-to-one: np.stack(np.where(iou > thr), 1), row-major
+        nmi = wave_compact(
+            nh, [&](int d) { return L.rowcnt[d] == 1; },
+            [&](int d, int p) {
+              L.mi[2 * p] = d;
+              L.mi[2 * p + 1] = L.rowcol[d];
+            });
+      } else {
+        // the appearance term (association.py:464-473): emb = ec.copy(); emb[iou <= 0] = 0,
+        // then the adaptive weights of its rows and columns, or the fixed weight
+        if (use_emb) {
+          for (int c = 0; c < nt; c += OW) {
+            const int ti = c + lane;
+            if (ti < nt) {
+              const double* r = tb + (size_t)ti * TB;
+              const int col = X.pp[ti];
+              for (int d = 0; d < nh; d++) {
+                const double o = asso_pair(ak, L.dd + 6 * L.hi[d], r, fw, fh);
+                em[d * nt + ti] = o <= 0 ? 0.0 : ec[(size_t)L.hi[d] * g.T + col];
+              }
+            }
+          }
+          __syncthreads();
+          if (!gd.aw_off) {
+            for (int d = lane; d < nh; d += OW) {
+              bool ap;
+              X.rw[d] = aw_weight(em + (size_t)d * nt, nt, 1, gd.aw_param, &ap);
+              X.ra[d] = ap;
+            }
+            for (int ti = lane; ti < nt; ti += OW) {
+              bool ap;
+              X.cw[ti] = aw_weight(em + ti, nh, nt, gd.aw_param, &ap);
+              X.ca[ti] = ap;
+            }
+            __syncthreads();
+          }
+        }
+        // the full cost -((IoU + direction consistency) + appearance) and P4's legacy
+        // linear_assignment of it
+        double* C = (nh * nt <= g.cost_lds) ? L.cost : cost;
+        for (int c = 0; c < nt; c += OW) {
+          const int ti = c + lane;
+          if (ti < nt) {
+            const double* r = tb + (size_t)ti * TB;
+            const double* p = r + 4;
+            const double cx2 = (p[0] + p[2]) / 2.0, cy2 = (p[1] + p[3]) / 2.0;
+            const double vy = r[14], vx = r[15];
+            const double valid = p[4] < 0 ? 0.0 : 1.0;
+            for (int d = 0; d < nh; d++) {
+              const double* a = L.dd + 6 * L.hi[d];
+              const double o = asso_pair(ak, a, r, fw, fh);
+              // speed_direction_batch (association.py:10-20) against the k-previous obs
+              const double cx1 = (a[0] + a[2]) / 2.0, cy1 = (a[1] + a[3]) / 2.0;
+              double dx = cx1 - cx2, dy = cy1 - cy2;
+              const double norm = sqrt(dx * dx + dy * dy) + 1e-6;
+              dx = dx / norm;
+              dy = dy / norm;
+              double cth = vx * dx + vy * dy;
+              cth = cth < -1 ? -1 : (cth > 1 ? 1 : cth);
+              double ang = ocs_acos(cth);
+              ang = (3.14159265358979323846 / 2.0 - fabs(ang)) / 3.14159265358979323846;
+              const double mc = (valid * ang) * g.inertia;
+              double total = o + mc;
+              if (use_emb) {
+                const double e = em[d * nt + ti];
+                if (gd.aw_off) {
+                  total += e * gd.w_emb;
+                } else {  // compute_aw_max_metric: ((w * row) * col) * emb
+                  double w = gd.w_emb;
+                  if (X.ra[d]) w *= X.rw[d];
+                  if (X.ca[ti]) w *= X.cw[ti];
+                  total += w * e;
+                }
+              }
+              C[d * nt + ti] = -total;
+            }
+          }
+        }
+        __syncthreads();
+        nmi = ocs_lap(C, nh, nt, L.jv, L.mi);
+      }
+    }
+    // P3: unmatched = absent from the candidate pairs, ascending; then the IoU validation with
+    // rejected pairs appended in pair order (P5)
+    for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = L.colcnt[k] = 0;
+    __syncthreads();
+    for (int q = lane; q < nmi; q += OW) {
+      L.rowcnt[L.mi[2 * q]] = 1;
+      L.colcnt[L.mi[2 * q + 1]] = 1;
+    }
+    __syncthreads();
+    nud = wave_compact(nh, [&](int d) { return L.rowcnt[d] == 0; }, [&](int d, int p) { L.ud[p] = d; });
+    nut = wave_compact(nt, [&](int t) { return L.colcnt[t] == 0; }, [&](int t, int p) { L.ut[p] = t; });
+    for (int c = 0; c < nmi; c += OW) {
+      const int q = c + lane;
+      bool ok = false, rej = false;
+      int d = 0, ti = 0;
+      if (q < nmi) {
+        d = L.mi[2 * q];
+        ti = L.mi[2 * q + 1];
+        ok = asso_pair(ak, L.dd + 6 * L.hi[d], tb + (size_t)ti * TB, fw, fh) >= thr;
+        rej = !ok;
+      }
+      const unsigned long long mo = __ballot(ok), mr = __ballot(rej);
+      const unsigned long long below = (1ull << lane) - 1ull;
+      if (ok) {
+        const int p = nm + __popcll(mo & below);
+        L.mm[2 * p] = d;
+        L.mm[2 * p + 1] = ti;
+      }
+      if (rej) {
+        const int p = __popcll(mr & below);
+        L.ud[nud + p] = d;
+        L.ut[nut + p] = ti;
+      }
+      nm += __popcll(mo);
+      nud += __popcll(mr);
+      nut += __popcll(mr);
+    }
+    __syncthreads();
+  }
+  for (int c = 0; c < nm; c += 8) {
+    const int q = c + oct;
+    if (q < nm) {
+      const int i = L.hi[L.mm[2 * q]], slot = L.lst[L.mm[2 * q + 1]];
+      const double* r = L.dd + 6 * i;
+      ocs_update_det(g, trk[slot], r8, r, r[5], i);
+      if (r8 == 0) emit(i, slot, false);
+    }
+  }
+  __syncthreads();
+
+  // ---- OCR round on the last observations (deepocsort.py:420-456) ---------------------------
+  if (nud > 0 && nut > 0) {
+    double mx = -INF;
+    for (int c = 0; c < nut; c += OW) {
+      const int k = c + lane;
+      if (k < nut) {
+        const double* bq = tb + (size_t)L.ut[k] * TB + 9;
+        for (int d = 0; d < nud; d++)
+          mx = fmax(mx, asso_pair(ak, L.dd + 6 * L.hi[L.ud[d]], bq, fw, fh));
+      }
+    }
+    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+    if (mx > thr) {
+      double* C = (nud * nut <= g.cost_lds) ? L.cost : cost;
+      for (int c = 0; c < nut; c += OW) {
+        const int k = c + lane;
+        if (k < nut) {
+          const double* bq = tb + (size_t)L.ut[k] * TB + 9;
+          for (int d = 0; d < nud; d++)
+            C[d * nut + k] = -asso_pair(ak, L.dd + 6 * L.hi[L.ud[d]], bq, fw, fh);
+        }
+      }
+      __syncthreads();
+      const int np_ = ocs_lap(C, nud, nut, L.jv, L.mi);
+      for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = L.fl[k] = 0;
+      __syncthreads();
+      for (int c = 0; c < np_; c += 8) {
+        const int q = c + oct;
+        if (q < np_) {
+          const int a = L.mi[2 * q], k = L.mi[2 * q + 1];
+          if (!(-C[a * nut + k] < thr)) {
+            const int di = L.ud[a], ti = L.ut[k];
+            const int i = L.hi[di], slot = L.lst[ti];
+            const double* r = L.dd + 6 * i;
+            ocs_update_det(g, trk[slot], r8, r, r[5], i);
+            if (r8 == 0) {
+              emit(i, slot, false);
+              L.rowcnt[di] = 2;
+              L.fl[ti] = 2;
+            }
+          }
+        }
+      }
+      __syncthreads();
+      for (int k = lane; k < nud; k += OW)
+        if (L.rowcnt[L.ud[k]] == 0) L.rowcnt[L.ud[k]] = 1;
+      for (int k = lane; k < nut; k += OW)
+        if (L.fl[L.ut[k]] == 0) L.fl[L.ut[k]] = 1;
+      __syncthreads();
+      // np.setdiff1d: ascending, unique
+      nud = wave_compact(nh, [&](int d) { return L.rowcnt[d] == 1; }, [&](int d, int p) { L.ud[p] = d; });
+      nut = wave_compact(nt, [&](int t) { return L.fl[t] == 1; }, [&](int t, int p) { L.ut[p] = t; });
+    }
+  }
+  for (int c = 0; c < nut; c += 8) {
+    const int k = c + oct;
+    if (k < nut) ocs_update_none(g, trk[L.lst[L.ut[k]]], r8);
+  }
+
+  // ---- new tracks for the unmatched detections (free slots ascending) -----------------------
+  for (int s2 = lane; s2 < g.T; s2 += OW) L.fl[s2] = 0;
+  __syncthreads();
+  for (int p = lane; p < nt; p += OW) L.fl[L.lst[p]] = 1;
+  __syncthreads();
+  const int nfree = wave_compact(g.T, [&](int s2) { return L.fl[s2] == 0; }, [&](int s2, int p) { L.lst2[p] = s2; });
+  int nnew = nud;
+  if (nnew > nfree) {
+    if (lane == 0) atomicExch(g.status, (int)BX_ERR_TRACK_OVERFLOW);
+    nnew = nfree;
+  }
+  for (int c = 0; c < nnew; c += 8) {
+    const int k = c + oct;
+    if (k < nnew) {
+      const int slot = L.lst2[k];
+      const int i = L.hi[L.ud[k]];
+      const double* r = L.dd + 6 * i;
+      OcsTrk& t = trk[slot];
+      const double w = r[2] - r[0], h = r[3] - r[1];
+      const double z[4] = {r[0] + w / 2.0, r[1] + h / 2.0, w * h, w / (h + 1e-6)};
+      if (r8 < 7) {
+        t.x[r8] = r8 == 0 ? z[0] : r8 == 1 ? z[1] : r8 == 2 ? z[2] : r8 == 3 ? z[3] : 0.0;
+        const double pd = r8 < 4 ? 10.0 : 10000.0;
+#pragma unroll
+        for (int j = 0; j < 7; j++) t.P[r8 * 7 + j] = j == r8 ? pd : 0.0;
+      }
+      if (r8 == 0) {
+        t.observed = 0;
+        t.has_saved = 0;
+        t.hvalid = 0;
+        t.htail = 0;
+        t.id = id0 + k;
+        t.conf = r[4];
+        t.cls = r[5];
+        t.det_ind = i;
+        for (int q = 0; q < 5; q++) t.last_obs[q] = -1.0;
+        t.last_age = -1;
+        for (int q = 0; q < OBS_KEEP; q++) t.obs_age[q] = -1;
+        t.has_vel = 0;
+        t.vel[0] = t.vel[1] = 0.0;
+        t.tsu = t.hits = t.hit_streak = t.age = 0;
+        L.lst[nt + k] = slot;
+        emit(i, slot, true);  // emb = the detection's raw row (deepocsort.py:466)
+      }
+    }
+  }
+  __syncthreads();
+  const int ntr = nt + nnew;
+
+  // ---- outputs in reversed list order, then deletion of the dead (deepocsort.py:473-495) ----
+  double* orow = out + (size_t)r0 * 8;
+  const int nout = wave_compact(
+      ntr,
+      [&](int k) {
+        const OcsTrk& t = trk[L.lst[ntr - 1 - k]];
+        return t.tsu < 1 && (t.hit_streak >= g.min_hits || frame <= g.min_hits);
+      },
+      [&](int k, int p) {
+        const OcsTrk& t = trk[L.lst[ntr - 1 - k]];
+        double d[4];
+        if (sum5(t.last_obs) < 0) {
+          x_to_bbox(t.x, d);
+        } else {
+          for (int q = 0; q < 4; q++) d[q] = t.last_obs[q];
+        }
+        if (p < n) {
+          double* o = orow + (size_t)p * 8;
+          o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3];
+          o[4] = (double)t.id;  // no +1 (deepocsort.py:489): the counter starts at 1
+          o[5] = t.conf;
+          o[6] = t.cls;
+          o[7] = (double)t.det_ind;
+        }
+      });
+  const int nkeep = wave_compact(
+      ntr, [&](int k) { return trk[L.lst[k]].tsu <= g.max_age; },
+      [&](int k, int p) { order[p] = L.lst[k]; });
+  if (lane == 0) {
+    out_count[b] = nout < n ? nout : n;
+    sq[SO_FRAME] = frame;
+    sq[SO_IDS] = id0 + nnew;
+    sq[SO_NTR] = nkeep;
+    sq[SO_NOUT] = nout;
+  }
+}
+
+// update_emb (deepocsort.py:184-186) / the newborn's emb = its detection's row; wave per
+// detection of the frame, 4 per workgroup.  The norm is summed in boost_feature_kernel's order:
+// lane-strided partial sums, then a butterfly over the wave.
+__global__ void __launch_bounds__(256)
+    deepoc_feature_kernel(DocDev g, int seq0, const int* __restrict__ det_off,
+                          const double* __restrict__ embs) {
+  const int b = blockIdx.y, seq = seq0 + b;
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int r0 = det_off[b];
+  int n = det_off[b + 1] - r0;
+  if (n > g.o.D) n = g.o.D;
+  if (k >= n) return;  // whole waves leave together
+  const int slot = g.rec[(size_t)seq * g.o.D + k];
+  if (slot < 0) return;
+  const double alpha = g.rec_a[(size_t)seq * g.o.D + k];
+  const int F = g.F;
+  double* e = g.emb + ((size_t)seq * g.o.T + slot) * F;
+  const double* x = embs + (size_t)(r0 + k) * F;
+  if (alpha < 0.0) {
+    for (int q = lane; q < F; q += 64) e[q] = x[q];
+    return;
+  }
+  const double om = 1 - alpha;
+  double s = 0.0;
+  for (int q = lane; q < F; q += 64) {
+    const double v = alpha * e[q] + om * x[q];
+    e[q] = v;
+    s += v * v;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+  const double nrm = sqrt(s);
+  for (int q = lane; q < F; q += 64) e[q] = e[q] / nrm;
+}
+
+__global__ void deepoc_reset_kernel(DocDev g, int seq0, int nseq) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < nseq * SQO) g.o.seqst[(size_t)seq0 * SQO + k] = (k % SQO == SO_IDS) ? 1 : 0;
+}
+
+}  // namespace
+
+struct bx_deepoc {
+  DocDev dev;
+  bx_deepoc_config cfg;
+  void* arena = nullptr;
+  size_t lds = 0;
+  // host-path staging and pinned mirrors for update_host
+  float* h_dets = nullptr;
+  double* h_embs = nullptr;
+  double* h_warp = nullptr;
+  int* h_off = nullptr;
+  double* h_out = nullptr;
+  int* h_cnt = nullptr;
+  float* p_dets = nullptr;
+  double* p_embs = nullptr;
+  double* p_warp = nullptr;
+  double* p_out = nullptr;
+  int* p_cnt = nullptr;
+  int* p_sq = nullptr;
+  int cache_seq = -1;
+  // timing probe
+  int probe_stage = -1;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+  int ev_used = 0;
+};
+
+#define DCHK(x)                                                                    \
+  do {                                                                             \
+    hipError_t _e = (x);                                                           \
+    if (_e != hipSuccess)                                                          \
+      return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
+  } while (0)
+
+static int probe_begin(bx_deepoc* e, int stage, hipStream_t st) {
+  if (e->probe_stage != stage) return BX_OK;
+  if (e->ev_used == (int)e->ev.size()) {
+    hipEvent_t a, b;
+    DCHK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
+    DCHK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
+    e->ev.push_back({a, b});
+  }
+  DCHK(hipEventRecord(e->ev[e->ev_used].first, st));
+  return BX_OK;
+}
+
+static int probe_end(bx_deepoc* e, int stage, hipStream_t st) {
+  if (e->probe_stage != stage) return BX_OK;
+  DCHK(hipEventRecord(e->ev[e->ev_used++].second, st));
+  return BX_OK;
+}
+
+static int launch(bx_deepoc* e, int seq0, int nseq, const float* dets, const int* off,
+                  const double* embs, const double* warps, double* out, int* cnt, hipStream_t st) {
+  const DocDev& d = e->dev;
+  const bool emb = !d.emb_off;
+  int rc;
+  if (emb && !embs) return bx_record_error(BX_ERR_SHAPE, "DeepOCSort needs embeddings unless embedding_off");
+  if (emb) {
+    if ((rc = probe_begin(e, 0, st))) return rc;
+    hipLaunchKernelGGL(deepoc_embcost_kernel, dim3(nseq, ec_tiles(d.o.D, d.o.T)), dim3(256), 0, st,
+                       d, seq0, off, embs);
+    DCHK(hipGetLastError());
+    if ((rc = probe_end(e, 0, st))) return rc;
+  }
+  if ((rc = probe_begin(e, 1, st))) return rc;
+  hipLaunchKernelGGL(deepoc_frame_kernel, dim3(nseq), dim3(OW), e->lds, st, d, seq0, dets, off,
+                     warps, out, cnt);
+  DCHK(hipGetLastError());
+  if ((rc = probe_end(e, 1, st))) return rc;
+  if (emb) {
+    if ((rc = probe_begin(e, 2, st))) return rc;
+    hipLaunchKernelGGL(deepoc_feature_kernel, dim3((d.o.D + 3) / 4, nseq), dim3(256), 0, st, d,
+                       seq0, off, embs);
+    DCHK(hipGetLastError());
+    if ((rc = probe_end(e, 2, st))) return rc;
+  }
+  return BX_OK;
+}
+
+extern "C" {
+
+int bx_deepoc_create(const bx_deepoc_config* c, bx_deepoc** out) {
+  if (!c || !out) return bx_record_error(BX_ERR_INVALID, "null argument");
+  if (c->n_seq <= 0 || c->track_cap <= 0 || c->det_cap <= 0 || c->track_cap > 512 ||
+      c->det_cap > 512)
+    return bx_record_error(BX_ERR_INVALID, "n_seq/track_cap/det_cap out of range");
+  if (c->delta_t < 1 || c->delta_t > OBS_KEEP - 1)
+    return bx_record_error(BX_ERR_INVALID, "delta_t must be in [1, 7]");
+  if (!c->embedding_off && c->emb_dim <= 0)
+    return bx_record_error(BX_ERR_INVALID, "emb_dim must be positive unless embedding_off");
+  if (c->asso_kind < ASSO_IOU || c->asso_kind > ASSO_CENTROID)
+    return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0)
+    return bx_record_error(BX_ERR_NO_DEVICE, "no HIP device visible");
+  bx_deepoc* e = new bx_deepoc();
+  e->cfg = *c;
+  // everything that can fail runs in `fill`: a failure frees what was allocated so far
+  auto fill = [&]() -> int {
+    DocDev& dd = e->dev;
+    OcsDev& d = dd.o;
+    d.S = c->n_seq;
+    d.T = c->track_cap;
+    d.D = c->det_cap;
+    d.N = d.T > d.D ? d.T : d.D;
+    d.min_conf = 0.0;
+    d.det_thresh = c->det_thresh;
+    d.asso_threshold = c->iou_threshold;
+    d.inertia = c->inertia;
+    d.q_xy = 1.0 * c->q_xy_scaling;
+    d.q_s = 1.0 * c->q_s_scaling;
+    d.max_age = c->max_age;
+    d.min_hits = c->min_hits;
+    d.delta_t = c->delta_t;
+    d.use_byte = 0;
+    d.asso_kind = c->asso_kind;
+    // basetracker.py:59-62: max_obs = 50, or max_age + 5 when max_age >= 50
+    d.max_obs = c->max_age >= 50 ? c->max_age + 5 : 50;
+    dd.emb_off = c->embedding_off != 0;
+    dd.aw_off = c->aw_off != 0;
+    dd.F = dd.emb_off ? 0 : c->emb_dim;
+    dd.w_emb = c->w_association_emb;
+    dd.alpha_fixed = c->alpha_fixed_emb;
+    dd.aw_param = c->aw_param;
+    // LDS: the fixed part plus as much cost matrix as keeps ~4 workgroups per CU resident
+    const size_t extra = doc_lds_extra(d.D, d.T);
+    const size_t fixed = lds_bytes(d.D, d.T, d.N, 0) + extra;
+    long budget = 40 * 1024 - (long)fixed;
+    int cl = budget > 0 ? (int)(budget / 8) : 0;
+    if (cl > d.D * d.T) cl = d.D * d.T;
+    if (cl < 64) cl = 64;
+    d.cost_lds = cl;
+    dd.x_off = (int)lds_bytes(d.D, d.T, d.N, cl);
+    e->lds = (size_t)dd.x_off + extra;
+    if (e->lds > 160 * 1024) {
+      return bx_record_error(BX_ERR_INVALID, "track_cap/det_cap too large for one workgroup's LDS");
+    }
+    const bool need_g = (long)d.D * d.T > cl;
+    const size_t S = d.S, T = d.T, D = d.D, F = dd.F;
+    size_t off = 0;
+    auto carve_b = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_trk = carve_b(S * T * sizeof(OcsTrk));
+    const size_t o_sq = carve_b(S * SQO * sizeof(int));
+    const size_t o_ord = carve_b(S * T * sizeof(int));
+    const size_t o_tb = carve_b(S * T * TB * sizeof(double));
+    const size_t o_cg = need_g ? carve_b(S * D * T * sizeof(double)) : 0;
+    const size_t o_st = carve_b(sizeof(int) * 4);
+    const size_t o_fsz = carve_b(S * 2 * sizeof(double));
+    const size_t o_emb = carve_b(S * T * (F ? F : 1) * sizeof(double));
+    const size_t o_ec = carve_b(F ? S * D * T * sizeof(double) : 8);
+    const size_t o_em = carve_b(F ? S * D * T * sizeof(double) : 8);
+    const size_t o_rec = carve_b(S * D * sizeof(int));
+    const size_t o_ra = carve_b(S * D * sizeof(double));
+    if (hipMalloc(&e->arena, off) != hipSuccess) {
+      return bx_record_error(BX_ERR_HIP, "hipMalloc of the DeepOCSort arena failed");
+    }
+    DCHK(hipMemset(e->arena, 0, off));
+    char* base = (char*)e->arena;
+    d.trk = (OcsTrk*)(base + o_trk);
+    d.seqst = (int*)(base + o_sq);
+    d.order = (int*)(base + o_ord);
+    d.tb = (double*)(base + o_tb);
+    d.cost_g = need_g ? (double*)(base + o_cg) : nullptr;
+    d.status = (int*)(base + o_st);
+    d.fsz = (double*)(base + o_fsz);
+    d.dbg = nullptr;
+    dd.emb = (double*)(base + o_emb);
+    dd.ec = (double*)(base + o_ec);
+    dd.em = (double*)(base + o_em);
+    dd.rec = (int*)(base + o_rec);
+    dd.rec_a = (double*)(base + o_ra);
+    {
+      std::vector<double> f(2 * S);
+      for (size_t k = 0; k < S; k++) {
+        f[2 * k] = c->frame_w;
+        f[2 * k + 1] = c->frame_h;
+      }
+      DCHK(hipMemcpy(d.fsz, f.data(), sizeof(double) * 2 * S, hipMemcpyHostToDevice));
+      std::vector<int> sq(S * SQO, 0);
+      for (size_t k = 0; k < S; k++) sq[k * SQO + SO_IDS] = 1;
+      DCHK(hipMemcpy(d.seqst, sq.data(), sizeof(int) * sq.size(), hipMemcpyHostToDevice));
+    }
+    DCHK(bx_lds_attr((const void*)deepoc_frame_kernel, e->lds));
+    DCHK(hipMalloc(&e->h_dets, sizeof(float) * 6 * D));
+    DCHK(hipMalloc(&e->h_embs, sizeof(double) * D * (F ? F : 1)));
+    DCHK(hipMalloc(&e->h_warp, sizeof(double) * 6));
+    DCHK(hipMalloc(&e->h_off, sizeof(int) * 2));
+    DCHK(hipMalloc(&e->h_out, sizeof(double) * 8 * D));
+    DCHK(hipMalloc(&e->h_cnt, sizeof(int)));
+    DCHK(hipHostMalloc(&e->p_dets, sizeof(float) * 6 * D));
+    DCHK(hipHostMalloc(&e->p_embs, sizeof(double) * D * (F ? F : 1)));
+    DCHK(hipHostMalloc(&e->p_warp, sizeof(double) * 6));
+    DCHK(hipHostMalloc(&e->p_out, sizeof(double) * 8 * D));
+    DCHK(hipHostMalloc(&e->p_cnt, sizeof(int) * 4));
+    DCHK(hipHostMalloc(&e->p_sq, sizeof(int) * SQO));
+    return BX_OK;
+  };
+  const int rc = fill();
+  if (rc) {
+    bx_deepoc_destroy(e);
+    return rc;
+  }
+  *out = e;
+  return BX_OK;
+}
+
+int bx_deepoc_copy_state(bx_deepoc* dst, bx_deepoc* src) {
+  if (!dst || !src) return bx_record_error(BX_ERR_INVALID, "null engine");
+  const OcsDev &a = src->dev.o, &b = dst->dev.o;
+  if (a.S != b.S || b.T < a.T || b.D < a.D || src->dev.F != dst->dev.F)
+    return bx_record_error(BX_ERR_INVALID, "bx_deepoc_copy_state: destination must have the "
+                                           "source's sequences and embedding width and at least "
+                                           "its capacities");
+  DCHK(hipDeviceSynchronize());
+  const size_t S = a.S, Ta = a.T, Tb = b.T, F = src->dev.F;
+  DCHK(hipMemcpy2D(b.trk, Tb * sizeof(OcsTrk), a.trk, Ta * sizeof(OcsTrk), Ta * sizeof(OcsTrk), S,
+                   hipMemcpyDeviceToDevice));
+  DCHK(hipMemcpy2D(b.order, Tb * sizeof(int), a.order, Ta * sizeof(int), Ta * sizeof(int), S,
+                   hipMemcpyDeviceToDevice));
+  if (F)
+    DCHK(hipMemcpy2D(dst->dev.emb, Tb * F * sizeof(double), src->dev.emb, Ta * F * sizeof(double),
+                     Ta * F * sizeof(double), S, hipMemcpyDeviceToDevice));
+  DCHK(hipMemcpy(b.seqst, a.seqst, S * SQO * sizeof(int), hipMemcpyDeviceToDevice));
+  DCHK(hipMemcpy(b.fsz, a.fsz, S * 2 * sizeof(double), hipMemcpyDeviceToDevice));
+  DCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
+  dst->cache_seq = -1;
+  DCHK(hipDeviceSynchronize());
+  return BX_OK;
+}
+
+int bx_deepoc_destroy(bx_deepoc* e) {
+  if (!e) return BX_OK;
+  for (auto& p : e->ev) {
+    (void)hipEventDestroy(p.first);
+    (void)hipEventDestroy(p.second);
+  }
+  (void)hipFree(e->arena);
+  (void)hipFree(e->h_dets);
+  (void)hipFree(e->h_embs);
+  (void)hipFree(e->h_warp);
+  (void)hipFree(e->h_off);
+  (void)hipFree(e->h_out);
+  (void)hipFree(e->h_cnt);
+  (void)hipHostFree(e->p_dets);
+  (void)hipHostFree(e->p_embs);
+  (void)hipHostFree(e->p_warp);
+  (void)hipHostFree(e->p_out);
+  (void)hipHostFree(e->p_cnt);
+  (void)hipHostFree(e->p_sq);
+  delete e;
+  return BX_OK;
+}
+
+int bx_deepoc_reset(bx_deepoc* e, int seq0, int nseq, void* stream) {
+  if (!e || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.o.S)
+    return bx_record_error(BX_ERR_INVALID, "bad sequence range");
+  if (!nseq) return BX_OK;
+  e->cache_seq = -1;
+  hipLaunchKernelGGL(deepoc_reset_kernel, dim3((nseq * SQO + 255) / 256), dim3(256), 0,
+                     (hipStream_t)stream, e->dev, seq0, nseq);
+  DCHK(hipGetLastError());
+  return BX_OK;
+}
+
+int bx_deepoc_step(bx_deepoc* e, int seq0, int nseq, const float* dets, const int32_t* det_off,
+                   const double* embs, const double* warps, double* out, int32_t* out_count,
+                   void* stream) {
+  if (!e || seq0 < 0 || nseq <= 0 || seq0 + nseq > e->dev.o.S || !det_off || !out || !out_count)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_step");
+  e->cache_seq = -1;
+  return launch(e, seq0, nseq, dets, det_off, embs, warps, out, out_count, (hipStream_t)stream);
+}
+
+int bx_deepoc_update_host(bx_deepoc* e, int seq, const float* dets, int n, const double* embs,
+                          const double* warp, double* out, int* n_out, void* stream) {
+  if (!e || seq < 0 || seq >= e->dev.o.S || n < 0 || (n && (!dets || !out)) || !n_out)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_update_host");
+  if (n > e->dev.o.D) return bx_record_error(BX_ERR_CAPACITY, "detections exceed det_cap");
+  const size_t F = e->dev.F;
+  if (n && F && !embs)
+    return bx_record_error(BX_ERR_SHAPE, "DeepOCSort needs embeddings unless embedding_off");
+  hipStream_t st = (hipStream_t)stream;
+  if (n) {
+    memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
+    DCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
+    if (F) {
+      memcpy(e->p_embs, embs, sizeof(double) * F * n);
+      DCHK(hipMemcpyAsync(e->h_embs, e->p_embs, sizeof(double) * F * n, hipMemcpyHostToDevice, st));
+    }
+  }
+  if (warp) {
+    memcpy(e->p_warp, warp, sizeof(double) * 6);
+    DCHK(hipMemcpyAsync(e->h_warp, e->p_warp, sizeof(double) * 6, hipMemcpyHostToDevice, st));
+  }
+  e->p_cnt[2] = 0;
+  e->p_cnt[3] = n;
+  DCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
+  e->cache_seq = -1;
+  int rc = launch(e, seq, 1, e->h_dets, e->h_off, e->h_embs, warp ? e->h_warp : nullptr, e->h_out,
+                  e->h_cnt, st);
+  if (rc) return rc;
+  DCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+  DCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (n) DCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
+  DCHK(hipMemcpyAsync(e->p_sq, e->dev.o.seqst + (size_t)seq * SQO, sizeof(int) * SQO,
+                      hipMemcpyDeviceToHost, st));
+  DCHK(hipStreamSynchronize(st));
+  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
+  e->cache_seq = seq;
+  if (cnt) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
+  *n_out = cnt;
+  if (status == BX_ERR_CAPACITY)
+    return bx_record_error(BX_ERR_CAPACITY, "a sequence's detections exceeded det_cap on the device");
+  if (status)
+    return bx_record_error(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
+  return BX_OK;
+}
+
+int bx_deepoc_status(bx_deepoc* e, int* status) {
+  if (!e || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
+  DCHK(hipMemcpy(status, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost));
+  return BX_OK;
+}
+
+int bx_deepoc_counters_host(bx_deepoc* e, int seq, int* frame_count, int* id_count,
+                            int* n_tracks) {
+  if (!e || seq < 0 || seq >= e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
+  int s[SQO];
+  if (seq == e->cache_seq) {
+    memcpy(s, e->p_sq, sizeof(s));
+  } else {
+    DCHK(hipDeviceSynchronize());
+    DCHK(hipMemcpy(s, e->dev.o.seqst + (size_t)seq * SQO, sizeof(s), hipMemcpyDeviceToHost));
+  }
+  if (frame_count) *frame_count = s[SO_FRAME];
+  if (id_count) *id_count = s[SO_IDS];
+  if (n_tracks) *n_tracks = s[SO_NTR];
+  return BX_OK;
+}
+
+int bx_deepoc_set_id_count(bx_deepoc* e, int seq, int id_count, void* stream) {
+  if (!e || seq < 0 || seq >= e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
+  e->cache_seq = -1;
+  DCHK(hipMemcpyAsync(e->dev.o.seqst + (size_t)seq * SQO + SO_IDS, &id_count, sizeof(int),
+                      hipMemcpyHostToDevice, (hipStream_t)stream));
+  DCHK(hipStreamSynchronize((hipStream_t)stream));
+  return BX_OK;
+}
+
+int bx_deepoc_set_frame_size(bx_deepoc* e, int seq, double w, double h, void* stream) {
+  if (!e || seq < 0 || seq >= e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
+  const double f[2] = {w, h};
+  DCHK(hipMemcpyAsync(e->dev.o.fsz + 2 * (size_t)seq, f, sizeof(f), hipMemcpyHostToDevice,
+                      (hipStream_t)stream));
+  DCHK(hipStreamSynchronize((hipStream_t)stream));
+  return BX_OK;
+}
+
+// the list order of a sequence, on the host
+static int list_order(bx_deepoc* e, int seq, std::vector<int>& ord) {
+  DCHK(hipDeviceSynchronize());
+  int s[SQO];
+  DCHK(hipMemcpy(s, e->dev.o.seqst + (size_t)seq * SQO, sizeof(s), hipMemcpyDeviceToHost));
+  ord.resize(s[SO_NTR]);
+  if (s[SO_NTR])
+    DCHK(hipMemcpy(ord.data(), e->dev.o.order + (size_t)seq * e->dev.o.T, sizeof(int) * s[SO_NTR],
+                   hipMemcpyDeviceToHost));
+  return BX_OK;
+}
+
+int bx_deepoc_tracks_host(bx_deepoc* e, int seq, int cap, int32_t* ids, double* x, double* p,
+                          double* emb, int* n) {
+  if (!e || seq < 0 || seq >= e->dev.o.S || cap < 0 || !n)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_tracks_host");
+  std::vector<int> ord;
+  int rc = list_order(e, seq, ord);
+  if (rc) return rc;
+  const int nt = (int)ord.size();
+  const size_t F = e->dev.F, T = e->dev.o.T;
+  for (int k = 0; k < nt && k < cap; k++) {
+    OcsTrk t;
+    DCHK(hipMemcpy(&t, e->dev.o.trk + (size_t)seq * T + ord[k], sizeof(OcsTrk),
+                   hipMemcpyDeviceToHost));
+    if (ids) ids[k] = t.id;
+    if (x) memcpy(x + 7 * k, t.x, sizeof(t.x));
+    if (p) memcpy(p + 49 * k, t.P, sizeof(t.P));
+    if (emb && F)
+      DCHK(hipMemcpy(emb + F * k, e->dev.emb + ((size_t)seq * T + ord[k]) * F, sizeof(double) * F,
+                     hipMemcpyDeviceToHost));
+  }
+  *n = nt;
+  return BX_OK;
+}
+
+int bx_deepoc_state_set_host(bx_deepoc* e, int seq, int n, const int32_t* ids, const double* x,
+                             const double* p, const double* emb) {
+  if (!e || seq < 0 || seq >= e->dev.o.S || n < 0 || (n && !ids))
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_state_set_host");
+  std::vector<int> ord;
+  int rc = list_order(e, seq, ord);
+  if (rc) return rc;
+  const int nt = (int)ord.size();
+  const size_t F = e->dev.F, T = e->dev.o.T;
+  for (int j = 0; j < n; j++) {
+    OcsTrk* dt = nullptr;
+    OcsTrk t;
+    int slot = -1;
+    for (int k = 0; k < nt && !dt; k++) {
+      OcsTrk* cand = e->dev.o.trk + (size_t)seq * T + ord[k];
+      DCHK(hipMemcpy(&t, cand, sizeof(OcsTrk), hipMemcpyDeviceToHost));
+      if (t.id == ids[j]) dt = cand, slot = ord[k];
+    }
+    if (!dt) return bx_record_error(BX_ERR_INVALID, "state_set: no live track with that id");
+    if (x) memcpy(t.x, x + 7 * j, sizeof(t.x));
+    if (p) memcpy(t.P, p + 49 * j, sizeof(t.P));
+    DCHK(hipMemcpy(dt, &t, sizeof(OcsTrk), hipMemcpyHostToDevice));
+    if (emb && F)
+      DCHK(hipMemcpy(e->dev.emb + ((size_t)seq * T + slot) * F, emb + F * j, sizeof(double) * F,
+                     hipMemcpyHostToDevice));
+  }
+  return BX_OK;
+}
+
+int bx_deepoc_frame_stats_host(bx_deepoc* e, int seq0, int nseq, int64_t* sums) {
+  if (!e || !sums || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.o.S)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_frame_stats_host");
+  std::vector<int> s((size_t)nseq * SQO);
+  DCHK(hipDeviceSynchronize());
+  if (nseq)
+    DCHK(hipMemcpy(s.data(), e->dev.o.seqst + (size_t)seq0 * SQO, sizeof(int) * s.size(),
+                   hipMemcpyDeviceToHost));
+  int64_t t = 0, o = 0, f = 0;
+  for (int k = 0; k < nseq; k++) {
+    t += s[(size_t)k * SQO + SO_NTR];
+    o += s[(size_t)k * SQO + SO_NOUT];
+    f = s[(size_t)k * SQO + SO_FRAME] > f ? s[(size_t)k * SQO + SO_FRAME] : f;
+  }
+  sums[0] = t;
+  sums[1] = o;
+  sums[2] = f;
+  return BX_OK;
+}
+
+int bx_deepoc_probe(bx_deepoc* e, int stage) {
+  if (!e || stage < -1 || stage > 2) return bx_record_error(BX_ERR_INVALID, "bad probe stage");
+  e->probe_stage = stage;
+  e->ev_used = 0;
+  return BX_OK;
+}
+
+int bx_deepoc_probe_read(bx_deepoc* e, double* total_ms, int* count) {
+  if (!e || !total_ms || !count) return bx_record_error(BX_ERR_INVALID, "null argument");
+  double s = 0.0;
+  for (int k = 0; k < e->ev_used; k++) {
+    DCHK(hipEventSynchronize(e->ev[k].second));
+    float ms = 0.f;
+    DCHK(hipEventElapsedTime(&ms, e->ev[k].first, e->ev[k].second));
+    s += ms;
+  }
+  *total_ms = s;
+  *count = e->ev_used;
+  e->ev_used = 0;
+  return BX_OK;
+}
+
+int bx_deepoc_embcost(int nd, int nt, int F, const double* dets_embs, const double* trk_embs,
+                      double* out, void* stream) {
+  if (nd < 0 || nt < 0 || F <= 0 || ((nd && nt) && (!dets_embs || !trk_embs || !out)))
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_embcost");
+  if (!nd || !nt) return BX_OK;
+  hipLaunchKernelGGL(deepoc_embcost_op_kernel, dim3(ec_tiles(nd, nt)), dim3(256), 0,
+                     (hipStream_t)stream, nd, nt, F, dets_embs, trk_embs, out);
+  DCHK(hipGetLastError());
+  return BX_OK;
+}
+
+}  // extern "C"

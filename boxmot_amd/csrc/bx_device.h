@@ -121,6 +121,30 @@ __device__ inline double bx_atan(double x) {
   return hx < 0 ? -r : r;
 }
 
+// compute_aw_max_metric's weight of one row or column (utils/association.py:320-374): v[k *
+// stride], k < n; *apply says whether the line has the two positive entries the weight needs.
+// Shared by the op (bx_ops.hip aw_kernel) and DeepOCSort's first association.
+__device__ inline double aw_weight(const double* v, int n, int stride, double bottom, bool* apply) {
+  double m1 = -INFINITY, m2 = -INFINITY;
+  int cnt = 0;
+  for (int k = 0; k < n; k++) {
+    const double c = v[(size_t)k * stride];
+    if (!(c > 0)) continue;
+    cnt++;
+    if (c > m1) {
+      m2 = m1;
+      m1 = c;
+    } else if (c > m2) {
+      m2 = c;
+    }
+  }
+  *apply = cnt >= 2;
+  if (cnt < 2) return 1.0;
+  if (m1 == 0) return 0.0;
+  const double ex = m2 / m1 - bottom;
+  return 1 - (ex > 0 ? ex : 0.0) / (1 - bottom);
+}
+
 // AssociationFunction registry (utils/iou.py:79-346), numpy's operation order per mode.
 // kind: 0 iou, 1 hmiou, 2 giou, 3 diou, 4 ciou, 5 centroid (frame size w, h).
 enum { ASSO_IOU = 0, ASSO_HMIOU = 1, ASSO_GIOU = 2, ASSO_DIOU = 3, ASSO_CIOU = 4,

@@ -45,26 +45,6 @@ __global__ void pairwise_kernel(int kind, const double* a, int na, int lda, cons
 // compute_aw_max_metric (utils/association.py:320-374): one workgroup; thread per row, then per
 // column, for the weights (LDS), then the grid of products in ((w * rw) * cw) * emb order
 constexpr int AW_MAX = 4096;
-__device__ double aw_weight(const double* v, int n, int stride, double bottom, bool* apply) {
-  double m1 = -INFINITY, m2 = -INFINITY;
-  int cnt = 0;
-  for (int k = 0; k < n; k++) {
-    const double c = v[(size_t)k * stride];
-    if (!(c > 0)) continue;
-    cnt++;
-    if (c > m1) {
-      m2 = m1;
-      m1 = c;
-    } else if (c > m2) {
-      m2 = c;
-    }
-  }
-  *apply = cnt >= 2;
-  if (cnt < 2) return 1.0;
-  if (m1 == 0) return 0.0;
-  const double ex = m2 / m1 - bottom;
-  return 1 - (ex > 0 ? ex : 0.0) / (1 - bottom);
-}
 __global__ void __launch_bounds__(1024) aw_kernel(const double* emb, int nr, int nc, double w0,
                                                   double bottom, double* out) {
   __shared__ double rw[AW_MAX], cw[AW_MAX];

@@ -478,6 +478,185 @@ class OcsortEngine:
 
 
 @dataclass
+class DeepOcsortParams:
+    """DeepOcSort constructor parameters (deepocsort.py:265-287 names and defaults)."""
+
+    det_thresh: float = 0.3
+    max_age: int = 30
+    min_hits: int = 3
+    iou_threshold: float = 0.3
+    delta_t: int = 3
+    asso_func: str = "iou"
+    inertia: float = 0.2
+    w_association_emb: float = 0.5
+    alpha_fixed_emb: float = 0.95
+    aw_param: float = 0.5
+    embedding_off: bool = False
+    aw_off: bool = False
+    Q_xy_scaling: float = 0.01
+    Q_s_scaling: float = 0.0001
+    frame_w: float = 1920.0     # centroid normalisation until set_frame_size latches the image
+    frame_h: float = 1080.0
+
+
+class DeepOcsortEngine:
+    """Handle over ``bx_deepoc_*`` (include/bxdeepocsort.h): ``n_seq`` DeepOCSort sequences in
+    HBM; per frame the appearance contraction (fp64 MFMA), the frame kernel (one wave per
+    sequence) and the embedding update.  Embeddings are float64, ``emb_dim`` wide (any positive
+    width; unused with ``embedding_off``)."""
+
+    STAGES = ["embcost", "frame", "feature"]
+
+    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
+                 emb_dim: int = 512, params: DeepOcsortParams | None = None):
+        p = params or DeepOcsortParams()
+        self.n_seq, self.track_cap, self.det_cap, self.params = n_seq, track_cap, det_cap, p
+        self.emb_dim = 0 if p.embedding_off else int(emb_dim)
+        cfg = N.BxDeepocConfig(
+            n_seq=n_seq, track_cap=track_cap, det_cap=det_cap, emb_dim=self.emb_dim,
+            det_thresh=float(p.det_thresh), iou_threshold=float(p.iou_threshold),
+            inertia=float(p.inertia), q_xy_scaling=float(p.Q_xy_scaling),
+            q_s_scaling=float(p.Q_s_scaling), w_association_emb=float(p.w_association_emb),
+            alpha_fixed_emb=float(p.alpha_fixed_emb), aw_param=float(p.aw_param),
+            max_age=int(p.max_age), min_hits=int(p.min_hits), delta_t=int(p.delta_t),
+            embedding_off=int(bool(p.embedding_off)), aw_off=int(bool(p.aw_off)),
+            asso_kind=_asso_kind(p.asso_func), frame_w=float(p.frame_w), frame_h=float(p.frame_h))
+        self._L = N.load()
+        h = C.c_void_p()
+        N.check(self._L.bx_deepoc_create(C.byref(cfg), C.byref(h)), "bx_deepoc_create")
+        self._h = h
+
+    def slots_used(self, seq: int = 0) -> int:
+        return self.counters(seq)["n_tracks"]
+
+    def grown(self, track_cap: int, det_cap: int) -> "DeepOcsortEngine":
+        """A new engine with larger capacities holding this one's state (bx_deepoc_copy_state)."""
+        e = DeepOcsortEngine(self.n_seq, track_cap, det_cap, self.emb_dim or 1, self.params)
+        N.check(self._L.bx_deepoc_copy_state(e._h, self._h), "bx_deepoc_copy_state")
+        return e
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._L.bx_deepoc_destroy(h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, seq0: int = 0, nseq: int | None = None, stream=None):
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        N.check(self._L.bx_deepoc_reset(self._h, seq0, nseq, stream), "bx_deepoc_reset")
+
+    def step(self, dets, det_off, embs, warps, out, out_count, seq0: int = 0,
+             nseq: int | None = None, stream=None):
+        """One frame for sequences [seq0, seq0+nseq) from device tensors (see bx_deepoc_step):
+        embs float64 [sum N, emb_dim] (None with embedding_off), warps [nseq, 6] or None."""
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        if stream is None:
+            stream = _current_stream()
+        N.check(self._L.bx_deepoc_step(self._h, seq0, nseq, _ptr(dets), _ptr(det_off), _ptr(embs),
+                                       _ptr(warps), _ptr(out), _ptr(out_count), stream),
+                "bx_deepoc_step")
+
+    def update_host(self, seq: int, dets: np.ndarray, embs: np.ndarray | None = None,
+                    warp: np.ndarray | None = None) -> np.ndarray:
+        d = np.ascontiguousarray(dets, dtype=np.float32).reshape(-1, 6)
+        n = d.shape[0]
+        e = None
+        if self.emb_dim and n:
+            if embs is None:
+                raise ValueError("DeepOCSort needs embeddings unless embedding_off")
+            e = np.ascontiguousarray(embs, dtype=np.float64).reshape(n, -1)
+            if e.shape[1] != self.emb_dim:
+                raise ValueError(f"embedding dim {e.shape[1]} != engine emb_dim {self.emb_dim}")
+        w = None if warp is None else np.ascontiguousarray(warp, np.float64).reshape(6)
+        out = np.empty((max(n, 1), 8), np.float64)
+        m = C.c_int(0)
+        N.check(self._L.bx_deepoc_update_host(
+            self._h, seq, d.ctypes.data if n else None, n, _p(e), _p(w), out.ctypes.data,
+            C.byref(m), None), "bx_deepoc_update_host")
+        return out[: m.value].copy()
+
+    def status(self) -> int:
+        s = C.c_int(0)
+        N.check(self._L.bx_deepoc_status(self._h, C.byref(s)), "bx_deepoc_status")
+        return s.value
+
+    def counters(self, seq: int = 0) -> dict:
+        fc, idc, nt = C.c_int(), C.c_int(), C.c_int()
+        N.check(self._L.bx_deepoc_counters_host(self._h, seq, C.byref(fc), C.byref(idc),
+                                                C.byref(nt)), "counters")
+        return {"frame_count": fc.value, "id_count": idc.value, "n_tracks": nt.value}
+
+    def set_id_count(self, seq: int, value: int):
+        N.check(self._L.bx_deepoc_set_id_count(self._h, seq, int(value), None), "set_id_count")
+
+    def set_frame_size(self, seq: int, w: float, h: float):
+        N.check(self._L.bx_deepoc_set_frame_size(self._h, seq, float(w), float(h), None),
+                "set_frame_size")
+
+    def tracks(self, seq: int = 0) -> dict:
+        """Host snapshot of the track list (list order): ids, XYSR means x [7], covariances
+        [7, 7] and, unless embedding_off, embeddings [emb_dim]."""
+        cap = self.track_cap
+        ids = np.zeros(cap, np.int32)
+        x = np.zeros((cap, 7))
+        P = np.zeros((cap, 7, 7))
+        E = np.zeros((cap, max(self.emb_dim, 1)))
+        n = C.c_int()
+        N.check(self._L.bx_deepoc_tracks_host(self._h, seq, cap, ids.ctypes.data, x.ctypes.data,
+                                              P.ctypes.data, E.ctypes.data if self.emb_dim else None,
+                                              C.byref(n)), "tracks")
+        k = min(n.value, cap)
+        snap = {"id": ids[:k], "x": x[:k], "P": P[:k]}
+        if self.emb_dim:
+            snap["emb"] = E[:k]
+        return snap
+
+    def state_set(self, seq: int, ids, x=None, P=None, emb=None) -> None:
+        """Write kf.x [n,7] / kf.P [n,7,7] / emb [n,emb_dim] of live tracks by id."""
+        n, ids, a, b = _state_arrays(ids, x, P, 7, 49)
+        e = None
+        if emb is not None and self.emb_dim:
+            e = np.ascontiguousarray(emb, np.float64).reshape(n, self.emb_dim)
+        N.check(self._L.bx_deepoc_state_set_host(self._h, seq, n, ids.ctypes.data, _p(a), _p(b),
+                                                 _p(e)), "state_set")
+
+    def frame_stats(self, seq0: int = 0, nseq: int | None = None) -> dict:
+        """Last frame over sequences [seq0, seq0+nseq): live tracks, output rows, frame."""
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        a = (C.c_int64 * 3)()
+        N.check(self._L.bx_deepoc_frame_stats_host(self._h, seq0, nseq, a), "frame_stats")
+        return dict(zip(["tracks", "outputs", "frame"], [int(x) for x in a]))
+
+    def probe(self, stage) -> None:
+        """Time one stage per step (name from STAGES or index); None = off."""
+        idx = -1 if stage is None else (self.STAGES.index(stage) if isinstance(stage, str)
+                                        else int(stage))
+        N.check(self._L.bx_deepoc_probe(self._h, idx), "bx_deepoc_probe")
+
+    def probe_read(self):
+        t, n = C.c_double(), C.c_int()
+        N.check(self._L.bx_deepoc_probe_read(self._h, C.byref(t), C.byref(n)), "probe_read")
+        return t.value, n.value
+
+
+def deepoc_embcost(dets_embs, trk_embs, out, stream=None) -> None:
+    """out [nd, nt] = dets_embs [nd, F] @ trk_embs [nt, F].T on device float64 tensors, by the
+    tracker's own MFMA tile (bx_deepoc_embcost)."""
+    nd, F = dets_embs.shape
+    nt = trk_embs.shape[0]
+    if stream is None:
+        stream = _current_stream()
+    N.check(N.load().bx_deepoc_embcost(int(nd), int(nt), int(F), _ptr(dets_embs), _ptr(trk_embs),
+                                       _ptr(out), stream), "bx_deepoc_embcost")
+
+
+@dataclass
 class BoostParams:
     """BoostTrack constructor parameters (boosttrack.py:154-181 names; YAML defaults)."""
 

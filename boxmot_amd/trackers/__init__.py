@@ -1,7 +1,8 @@
 from .boosttrack import BoostTrack
 from .botsort import BotSort
 from .bytetrack import ByteTrack
+from .deepocsort import DeepOcSort
 from .ocsort import OcSort
 from .strongsort import StrongSort
 
-__all__ = ["ByteTrack", "BotSort", "OcSort", "BoostTrack", "StrongSort"]
+__all__ = ["ByteTrack", "BotSort", "OcSort", "BoostTrack", "StrongSort", "DeepOcSort"]
