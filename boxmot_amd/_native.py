@@ -22,6 +22,7 @@ HEADER_BOOST = REPO / "include" / "bxboost.h"
 HEADER_SS = REPO / "include" / "bxstrongsort.h"
 HEADER_DEEPOC = REPO / "include" / "bxdeepocsort.h"
 HEADER_IO = REPO / "include" / "bxio.h"
+HEADER_GSI = REPO / "include" / "bxgsi.h"
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -32,7 +33,7 @@ HIPCC_FLAGS = [
     "-mllvm", "-amdgpu-mfma-vgpr-form=1",
 ]
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
-           "bx_strongsort.hip", "bx_deepocsort.hip", "bx_io.cpp"]
+           "bx_strongsort.hip", "bx_deepocsort.hip", "bx_gsi.hip", "bx_io.cpp"]
 
 
 class NativeUnavailable(RuntimeError):
@@ -223,6 +224,8 @@ EXPORTS = [
     "bx_deepoc_counters_host", "bx_deepoc_set_id_count", "bx_deepoc_set_frame_size",
     "bx_deepoc_tracks_host", "bx_deepoc_state_set_host", "bx_deepoc_frame_stats_host",
     "bx_deepoc_probe", "bx_deepoc_probe_read", "bx_deepoc_embcost",
+    "bx_gsi_plan_workspace_bytes", "bx_gsi_interpolate_plan", "bx_gsi_interpolate",
+    "bx_gsi_workspace_bytes", "bx_gsi_smooth", "bx_gsi_run_host",
 ]
 
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -354,6 +357,16 @@ _SIGS = {
     "bx_deepoc_probe": ([_vp, C.c_int], C.c_int),
     "bx_deepoc_probe_read": ([_vp, _dp, _ip], C.c_int),
     "bx_deepoc_embcost": ([C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_gsi_plan_workspace_bytes": ([C.c_int64, C.POINTER(C.c_size_t)], C.c_int),
+    "bx_gsi_interpolate_plan": ([_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.c_size_t, _vp,
+                                 _vp], C.c_int),
+    "bx_gsi_interpolate": ([_vp, C.c_int64, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp],
+                           C.c_int),
+    "bx_gsi_workspace_bytes": ([_vp, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
+    "bx_gsi_smooth": ([_vp, C.c_int, _vp, C.c_int, C.c_double, C.c_int, _vp, C.c_size_t, _vp,
+                       _vp, _vp], C.c_int),
+    "bx_gsi_run_host": ([_vp, C.c_int64, C.c_int, C.c_int, C.c_double, _vp, C.c_int64,
+                         C.POINTER(C.c_int64), _vp], C.c_int),
 }
 
 _lib = None

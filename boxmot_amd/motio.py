@@ -153,13 +153,16 @@ def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs:
 
 
 def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict | None = None,
-                  frame_sizes: dict | None = None, tracker_kwargs: dict | None = None) -> dict:
+                  frame_sizes: dict | None = None, tracker_kwargs: dict | None = None,
+                  gsi: bool = False, gsi_interval: int = 20, gsi_tau: float = 10) -> dict:
     """process_sequence (val.py:304-354) for every sequence at once.
 
     sequences: name -> packed file (pack_sequence) or BinSequence; frame_ids: name -> the frames
     to iterate (the image list; default: the frames that have detections); frame_sizes: name ->
     (w, h) of its images (OCSort's centroid mode).  Writes ``exp_dir/<name>.txt`` and returns
     name -> the frame ids iterated.  Sequence k's track ids start at 1, as in a fresh process.
+    gsi: apply the GSI post-processing (postprocessing.gsi, with gsi_interval / gsi_tau) to
+    exp_dir after the files are written, as the reference's evaluation flow does last.
     """
     import torch
 
@@ -228,4 +231,8 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
     exp_dir = Path(exp_dir)
     for nm, res in zip(names, results):
         write_mot_results(exp_dir / f"{nm}.txt", np.vstack(res) if res else np.empty((0, 0)))
+    if gsi:
+        from . import postprocessing
+
+        postprocessing.gsi(exp_dir, interval=gsi_interval, tau=gsi_tau)
     return {nm: list(map(int, f)) for nm, f in zip(names, fids)}
