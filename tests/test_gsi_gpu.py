@@ -7,10 +7,13 @@ reference's own spread against three restated solvers (``solver_spread``) and th
 columns must match within 4x that spread (one more summation order; the device exp an ulp from
 libm in K), capped at 1e-3 px.  The smoothing itself moves boxes by 4 to 7 px.
 
-No test here provokes a non-positive pivot: with duplicate frames K is all ones, K + 1e-10*I is
-still positive definite with pivots of ~1e-10, six orders above the factorisation's rounding, so
-neither scikit-learn nor a float64 restatement on the CPU fails on it.  The latch
-(BX_ERR_INVALID per tracklet, raised as LinAlgError) is therefore untested.
+Fixtures beyond the default pair (interval 20, tau 10): ``tiles`` (lengths around the blocked
+path's tile edges), ``deep`` (1201 and 2049 rows at tau = 15, where the factor's off-diagonal is
+~1 — at tau = 10 a tracklet of more than 1000 rows factors the identity), ``params`` (three other
+(interval, tau) pairs, both clips of the length scale), ``wide`` (10-column rows) and ``rows``
+(interpolation only: row counts at the sort's padding and the scan's chunk, duplicate (id, frame)
+rows).  The pivot latch, slot reuse, BX_GSI_MAX_N and the argument checks are in
+test_gsi_paths_gpu.py.
 """
 from pathlib import Path
 
@@ -21,6 +24,8 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 NAMES = ["tiny", "gaps", "mixed", "long", "unsorted"]
+MORE = ["tiles", "deep", "wide"]  # same keys as NAMES
+N_PARAMS, N_ROWS = 3, 6  # sub-cases of gsi_params.npz and gsi_rows.npz (keys suffixed _k)
 FMT = "%d %d %d %d %d %d %d %d %d"
 EXACT = [0, 1, 6, 7, 8]
 
@@ -34,7 +39,7 @@ def fx():
     from boxmot_amd import _native
 
     _native.load()
-    return {n: dict(np.load(GOLDEN / f"gsi_{n}.npz")) for n in NAMES}
+    return {n: dict(np.load(GOLDEN / f"gsi_{n}.npz")) for n in NAMES + MORE + ["params", "rows"]}
 
 
 @pytest.fixture(scope="module")
@@ -43,7 +48,8 @@ def ours(fx):
     from boxmot_amd import gaussian_smooth, linear_interpolation
 
     out = {}
-    for n, z in fx.items():
+    for n in NAMES + MORE:
+        z = fx[n]
         itp = linear_interpolation(z["input"], int(z["interval"]))
         out[n] = (itp, gaussian_smooth(itp, float(z["tau"])))
     return out
@@ -62,14 +68,14 @@ def check_smoothed(got, z, what):
     assert np.isfinite(got).all() and err <= tol(z), (what, err, tol(z))
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + MORE)
 def test_interpolation_is_bitwise(fx, ours, name):
     got, ref = ours[name][0], fx[name]["interpolated"]
     assert got.shape == ref.shape and got.dtype == np.float64
     assert np.array_equal(got.view(np.uint64), ref.view(np.uint64))
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + MORE)
 def test_smoothing_matches_the_reference(fx, ours, name):
     check_smoothed(ours[name][1], fx[name], name)
 
@@ -111,6 +117,68 @@ def test_lds_and_blocked_paths_agree(fx, ours):
     assert err <= tol(z)
     tiny = _gaussian_smooth(ours["tiny"][0], float(fx["tiny"]["tau"]), force_blocked=True)
     check_smoothed(tiny, fx["tiny"], "tiny, blocked path")
+
+
+def test_tile_edge_lengths_on_the_blocked_path(fx, ours):
+    """`tiles` with every tracklet forced through the blocked factorisation: lengths 93..97 (the
+    right-hand-side rows straddle a trailing tile's edge, or form a tile of their own), 128, 160,
+    208, 224 +-1 (a trailing tile of exactly 64 rows, or one row more or less)."""
+    from boxmot_amd.postprocessing import _gaussian_smooth
+
+    z = fx["tiles"]
+    lens = np.unique(z["interpolated"][:, 1], return_counts=True)[1]
+    assert {93, 94, 95, 96, 97, 128, 160, 208, 224} <= set(lens.tolist())
+    forced = _gaussian_smooth(ours["tiles"][0], float(z["tau"]), force_blocked=True)
+    check_smoothed(forced, z, "tiles, every tracklet on the blocked path")
+
+
+@pytest.mark.parametrize("k", range(N_PARAMS))
+def test_other_intervals_and_taus(fx, k):
+    """(interval, tau) = (2, 2): nothing fillable, the length scale of a 1-row tracklet clipped
+    to tau^2; (5, 3): gaps of 3 filled and of 4 not, 30 rows clipped to 1/tau; (50, 10): a
+    48-frame gap filled."""
+    from boxmot_amd import gaussian_smooth, linear_interpolation
+
+    p = fx["params"]
+    z = {key: p[f"{key}_{k}"] for key in ("input", "interval", "tau", "interpolated", "smoothed",
+                                           "solver_spread")}
+    assert (int(z["interval"]), float(z["tau"])) == [(2, 2.0), (5, 3.0), (50, 10.0)][k]
+    itp = linear_interpolation(z["input"], int(z["interval"]))
+    assert itp.shape == z["interpolated"].shape
+    assert np.array_equal(itp.view(np.uint64), z["interpolated"].view(np.uint64))
+    check_smoothed(gaussian_smooth(itp, float(z["tau"])), z, f"params {k}")
+
+
+def test_ten_column_rows(fx, ours):
+    """MOT result rows are 10 wide: interpolation on all 10 columns (bitwise, parametrised above),
+    smoothing reads them at stride 10, and a batch of a 10- and an 8-column array works on the
+    shared 8 columns and returns the bits of the single calls."""
+    from boxmot_amd.postprocessing import gsi_batch
+
+    z, u = fx["wide"], fx["unsorted"]
+    assert z["input"].shape[1] == 10 and ours["wide"][0].shape[1] == 10
+    assert ours["wide"][1].shape == (z["interpolated"].shape[0], 9)
+    assert (int(z["interval"]), float(z["tau"])) == (int(u["interval"]), float(u["tau"]))
+    batch = gsi_batch([z["input"], u["input"]], int(z["interval"]), float(z["tau"]))
+    for n, b in zip(["wide", "unsorted"], batch):
+        assert b.shape == ours[n][1].shape, n
+        assert np.array_equal(b.view(np.uint64), ours[n][1].view(np.uint64)), n
+
+
+@pytest.mark.parametrize("k", range(N_ROWS))
+def test_interpolation_row_counts_and_duplicates(fx, k):
+    """1, 1023, 1024, 1025 and 2048 input rows (the bitonic network's padding; the scan's
+    1024-row chunks and the carry between them, with filled gaps in every chunk), and duplicate
+    (id, frame) rows with different boxes, whose order is np.lexsort's stable one."""
+    from boxmot_amd import linear_interpolation
+
+    r = fx["rows"]
+    inp, ref = r[f"input_{k}"], r[f"interpolated_{k}"]
+    if k < 5:
+        assert inp.shape[0] == [1, 1023, 1024, 1025, 2048][k]
+    got = linear_interpolation(inp, int(r[f"interval_{k}"]))
+    assert got.shape == ref.shape and (k == 0 or ref.shape[0] > inp.shape[0])
+    assert np.array_equal(got.view(np.uint64), ref.view(np.uint64))
 
 
 def test_gsi_on_a_folder(fx, tmp_path):

@@ -49,6 +49,51 @@ def test_fixture_keys_and_shapes(name):
     assert np.array_equal(sm[:, :2], itp[:, :2]) and np.all(sm[:, 8] == -1)
 
 
+@pytest.mark.parametrize("name,tau,ncol", [("tiles", 10, 8), ("deep", 15, 8), ("wide", 10, 10)])
+def test_more_fixture_keys_and_shapes(name, tau, ncol):
+    z = np.load(GOLDEN / f"gsi_{name}.npz")
+    assert sorted(z.files) == ["input", "interpolated", "interval", "smoothed", "solver_spread",
+                               "tau"]
+    inp, itp, sm = z["input"], z["interpolated"], z["smoothed"]
+    assert inp.dtype == itp.dtype == sm.dtype == np.float64
+    assert inp.shape[1] == itp.shape[1] == ncol
+    assert itp.shape[0] > inp.shape[0] and sm.shape == (itp.shape[0], 9)
+    assert int(z["interval"]) == 20 and float(z["tau"]) == tau
+    assert 0 < 4 * float(z["solver_spread"]) < 1e-3  # the bound is the spread's, not the cap
+    assert np.array_equal(np.lexsort((itp[:, 0], itp[:, 1])), np.arange(itp.shape[0]))
+    assert np.array_equal(sm[:, [0, 1, 6, 7]], itp[:, [0, 1, 6, 7]]) and np.all(sm[:, 8] == -1)
+    lens = np.unique(itp[:, 1], return_counts=True)[1].tolist()
+    if name == "tiles":
+        assert lens == [15, 16, 17, 34, 93, 94, 95, 96, 97, 127, 128, 129, 159, 160, 161, 207,
+                        208, 209, 223, 224, 225]
+    elif name == "deep":
+        assert lens == [1201, 2049]
+        # the smoothing does real work on both (on `long`'s 1200 rows it moves boxes by 6e-8 px)
+        for i in (1, 2):
+            assert np.abs(sm[sm[:, 1] == i][:, 2:6] - itp[itp[:, 1] == i][:, 2:6]).max() > 1.0
+        lg = np.load(GOLDEN / "gsi_long.npz")
+        m = lg["smoothed"][:, 1] == 1
+        assert m.sum() == 1200
+        assert np.abs(lg["smoothed"][m][:, 2:6] - lg["interpolated"][m][:, 2:6]).max() < 1e-6
+
+
+def test_params_and_rows_fixtures():
+    p = np.load(GOLDEN / "gsi_params.npz")
+    assert len(p.files) == 18
+    for k, (interval, tau) in enumerate([(2, 2), (5, 3), (50, 10)]):
+        assert (int(p[f"interval_{k}"]), float(p[f"tau_{k}"])) == (interval, tau)
+        assert p[f"smoothed_{k}"].shape == (p[f"interpolated_{k}"].shape[0], 9)
+        assert 0 < 4 * float(p[f"solver_spread_{k}"]) < 1e-3
+    assert p["interpolated_0"].shape == p["input_0"].shape
+    assert p["interpolated_1"].shape[0] == p["input_1"].shape[0] + 6
+    assert p["interpolated_2"].shape[0] == p["input_2"].shape[0] + 48
+    r = np.load(GOLDEN / "gsi_rows.npz")
+    assert len(r.files) == 18 and not any(f.startswith("smoothed") for f in r.files)
+    assert [r[f"input_{k}"].shape[0] for k in range(5)] == [1, 1023, 1024, 1025, 2048]
+    d = r["input_5"]
+    assert np.unique(d[:, :2], axis=0).shape[0] < d.shape[0]  # duplicate (frame, id) rows
+
+
 def test_gsi_leaves_an_empty_file_untouched(tmp_path):
     f = tmp_path / "MOT17-02.txt"
     f.write_text("")
