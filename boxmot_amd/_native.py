@@ -23,6 +23,7 @@ HEADER_SS = REPO / "include" / "bxstrongsort.h"
 HEADER_DEEPOC = REPO / "include" / "bxdeepocsort.h"
 HEADER_IO = REPO / "include" / "bxio.h"
 HEADER_GSI = REPO / "include" / "bxgsi.h"
+HEADER_FEED = REPO / "include" / "bxfeed.h"
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -33,7 +34,8 @@ HIPCC_FLAGS = [
     "-mllvm", "-amdgpu-mfma-vgpr-form=1",
 ]
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
-           "bx_strongsort.hip", "bx_deepocsort.hip", "bx_gsi.hip", "bx_io.cpp"]
+           "bx_strongsort.hip", "bx_deepocsort.hip", "bx_gsi.hip", "bx_feed.hip",
+           "bx_io.cpp"]
 
 
 class NativeUnavailable(RuntimeError):
@@ -226,6 +228,10 @@ EXPORTS = [
     "bx_deepoc_probe", "bx_deepoc_probe_read", "bx_deepoc_embcost",
     "bx_gsi_plan_workspace_bytes", "bx_gsi_interpolate_plan", "bx_gsi_interpolate",
     "bx_gsi_workspace_bytes", "bx_gsi_smooth", "bx_gsi_run_host",
+    "bx_feed_create", "bx_feed_destroy", "bx_feed_upload_host", "bx_feed_shape",
+    "bx_feed_frame_runs", "bx_feed_run", "bx_feed_gather", "bx_feed_append", "bx_feed_status",
+    "bx_feed_result_rows", "bx_feed_results_host", "bx_feed_read_run_host",
+    "bx_feed_write_run_host",
 ]
 
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -367,6 +373,20 @@ _SIGS = {
                        _vp, _vp], C.c_int),
     "bx_gsi_run_host": ([_vp, C.c_int64, C.c_int, C.c_int, C.c_double, _vp, C.c_int64,
                          C.POINTER(C.c_int64), _vp], C.c_int),
+    "bx_feed_create": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                        C.POINTER(C.c_void_p)], C.c_int),
+    "bx_feed_destroy": ([_vp], C.c_int),
+    "bx_feed_upload_host": ([_vp, C.c_int, _vp, _vp], C.c_int),
+    "bx_feed_shape": ([_vp, _ip, _ip], C.c_int),
+    "bx_feed_frame_runs": ([_vp, C.c_int, _ip], C.c_int),
+    "bx_feed_run": ([_vp, C.c_int, C.c_int, _ip, _ip, _ip] + [C.POINTER(C.c_void_p)] * 5, C.c_int),
+    "bx_feed_gather": ([_vp, C.c_int, _vp], C.c_int),
+    "bx_feed_append": ([_vp, C.c_int, _vp], C.c_int),
+    "bx_feed_status": ([_vp, _ip], C.c_int),
+    "bx_feed_result_rows": ([_vp, C.POINTER(C.c_int64)], C.c_int),
+    "bx_feed_results_host": ([_vp, _vp, _vp, _vp], C.c_int),
+    "bx_feed_read_run_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp], C.c_int),
+    "bx_feed_write_run_host": ([_vp, C.c_int, C.c_int, _vp, _vp], C.c_int),
 }
 
 _lib = None

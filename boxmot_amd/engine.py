@@ -656,6 +656,133 @@ def deepoc_embcost(dets_embs, trk_embs, out, stream=None) -> None:
                                        _ptr(out), stream), "bx_deepoc_embcost")
 
 
+class SequenceFeeder:
+    """Handle over ``bx_feed_*`` (include/bxfeed.h): the packed rows of many sequences resident
+    in HBM, gathered per frame index into the batched arrays a ``step`` takes, and the steps'
+    output rows appended on the device as MOT rows; one copy back at the end.
+
+    dets / embs: per sequence its packed rows ([rows, 6], [rows, emb_dim]); tables: per sequence
+    ``(row_start, row_cnt, frame_id)``, one entry per frame index it iterates (``row_cnt`` 0: not
+    stepped).  ``emb_dim`` 0 feeds no embeddings.  ``res_cap``: rows of each sequence's result
+    buffer (default: its detection count); ``guard_rows``: extra rows behind the last buffer.
+    ``schedule[t]`` lists the runs of frame index t as ``(seq0, nseq, rows, dets, det_off, embs,
+    out, out_count)`` with the last five as device addresses."""
+
+    def __init__(self, dets, embs, tables, emb_dim: int, res_cap=None, guard_rows: int = 0):
+        S = len(dets)
+        self.n_seq, self.emb_dim = S, int(emb_dim)
+        rows = np.array([int(np.shape(d)[0]) for d in dets], np.int64)
+        tab_off = np.zeros(S + 1, np.int64)
+        tab_off[1:] = np.cumsum([len(t[1]) for t in tables])
+
+        def column(j, dt):
+            return np.ascontiguousarray(np.concatenate(
+                [np.asarray(t[j], dt).reshape(-1) for t in tables] + [np.empty(0, dt)]))
+
+        start, cnt, fid = column(0, np.int64), column(1, np.int32), column(2, np.int32)
+        cap = None if res_cap is None else np.ascontiguousarray(res_cap, np.int64).reshape(S)
+        self._L = N.load()
+        h = C.c_void_p()
+        N.check(self._L.bx_feed_create(S, self.emb_dim, rows.ctypes.data, tab_off.ctypes.data,
+                                       start.ctypes.data, cnt.ctypes.data, fid.ctypes.data,
+                                       _p(cap), int(guard_rows), C.byref(h)), "bx_feed_create")
+        self._h = h
+        for k in range(S):
+            if not rows[k]:
+                continue
+            d = np.ascontiguousarray(dets[k], np.float32).reshape(-1, 6)
+            e = None
+            if self.emb_dim:
+                e = np.ascontiguousarray(embs[k], np.float64)
+                if e.shape != (rows[k], self.emb_dim):
+                    raise ValueError(f"sequence {k}: embeddings {e.shape} != "
+                                     f"({rows[k]}, {self.emb_dim})")
+            N.check(self._L.bx_feed_upload_host(self._h, k, d.ctypes.data, _p(e)),
+                    "bx_feed_upload_host")
+        nf, mr = C.c_int(), C.c_int()
+        N.check(self._L.bx_feed_shape(self._h, C.byref(nf), C.byref(mr)), "bx_feed_shape")
+        self.n_frames, self.max_runs = nf.value, mr.value
+        self.schedule = []
+        i3 = [C.c_int() for _ in range(3)]
+        p5 = [C.c_void_p() for _ in range(5)]
+        for t in range(self.n_frames):
+            nr = C.c_int()
+            N.check(self._L.bx_feed_frame_runs(self._h, t, C.byref(nr)), "bx_feed_frame_runs")
+            runs = []
+            for r in range(nr.value):
+                N.check(self._L.bx_feed_run(self._h, t, r, *[C.byref(x) for x in i3 + p5]),
+                        "bx_feed_run")
+                runs.append(tuple(x.value for x in i3 + p5))
+            self.schedule.append(runs)
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._L.bx_feed_destroy(h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def gather(self, t: int, stream=None) -> None:
+        """Write every run's dets / embs / det_off of frame index t (one launch)."""
+        if stream is None:
+            stream = _current_stream()
+        N.check(self._L.bx_feed_gather(self._h, int(t), stream), "bx_feed_gather")
+
+    def append(self, t: int, stream=None) -> None:
+        """Append the MOT rows of frame index t from its runs' out / out_count (one launch)."""
+        if stream is None:
+            stream = _current_stream()
+        N.check(self._L.bx_feed_append(self._h, int(t), stream), "bx_feed_append")
+
+    def status(self) -> int:
+        s = C.c_int(0)
+        N.check(self._L.bx_feed_status(self._h, C.byref(s)), "bx_feed_status")
+        return s.value
+
+    def raw_results(self):
+        """The whole result allocation [rows, 9] (guard rows last), each sequence's first row
+        [n_seq + 1] and the rows it appended [n_seq]: the one device-to-host copy."""
+        n = C.c_int64()
+        N.check(self._L.bx_feed_result_rows(self._h, C.byref(n)), "bx_feed_result_rows")
+        res = np.empty((n.value, 9), np.float64)
+        base = np.empty(self.n_seq + 1, np.int64)
+        cnt = np.empty(self.n_seq, np.int64)
+        N.check(self._L.bx_feed_results_host(self._h, res.ctypes.data if n.value else None,
+                                             base.ctypes.data, cnt.ctypes.data),
+                "bx_feed_results_host")
+        return res, base, cnt
+
+    def results(self) -> list:
+        """Per sequence its MOT rows [n, 9]; raises when an append did not fit."""
+        res, base, cnt = self.raw_results()
+        if self.status() != 0:
+            raise RuntimeError(f"feeder status {self.status()} (result buffer overflow)")
+        return [res[base[k]: base[k] + cnt[k]] for k in range(self.n_seq)]
+
+    def read_run(self, t: int, r: int):
+        """Host copies of the gathered (dets, det_off, embs) of run r of frame index t."""
+        _, nseq, rows = self.schedule[t][r][:3]
+        d = np.empty((rows, 6), np.float32)
+        o = np.empty(nseq + 1, np.int32)
+        e = np.empty((rows, self.emb_dim), np.float64) if self.emb_dim else None
+        N.check(self._L.bx_feed_read_run_host(self._h, int(t), int(r), d.ctypes.data,
+                                              o.ctypes.data, _p(e)), "bx_feed_read_run_host")
+        return d, o, e
+
+    def write_run(self, t: int, r: int, out, out_count) -> None:
+        """Set out [rows, 8] / out_count [nseq] of run r of frame index t from host arrays."""
+        _, nseq, rows = self.schedule[t][r][:3]
+        o = np.ascontiguousarray(out, np.float64).reshape(rows, 8)
+        c = np.ascontiguousarray(out_count, np.int32).reshape(nseq)
+        N.check(self._L.bx_feed_write_run_host(self._h, int(t), int(r), o.ctypes.data,
+                                               c.ctypes.data), "bx_feed_write_run_host")
+
+
 @dataclass
 class BoostParams:
     """BoostTrack constructor parameters (boosttrack.py:154-181 names; YAML defaults)."""

@@ -13,8 +13,10 @@ Reference path replaced (muntherr/boxmot @ /root/reference):
   * the process pool of ``engine/val.py:357-405`` (one tracker per sequence per process):
     ``run_sequences`` drives ALL sequences through one batched engine handle, frame index by
     frame index; a sequence without detections at a frame is not updated (``val.py:347``).
+    With ``resident=True`` (DeepOcSort) the per-frame assembly and the row formatting run on the
+    device too (``include/bxfeed.h``): one upload, one copy back.
 
-Everything here is host code in libbxassoc.so; the trackers run on the MI355X engine.
+Everything else here is host code in libbxassoc.so; the trackers run on the MI355X engine.
 """
 from __future__ import annotations
 
@@ -47,6 +49,17 @@ def pack_sequence(det_txt, emb_txt, out_path) -> Path:
     embs = load_txt(emb_txt) if emb_txt is not None else np.empty((dets.shape[0], 0))
     if dets.shape[0] != embs.shape[0]:
         raise ValueError(f"Row mismatch in {det_txt}")  # MOT17.py:152-153
+    return pack_arrays(dets, embs, out_path)
+
+
+def pack_arrays(dets, embs, out_path) -> Path:
+    """Pack one sequence from arrays: dets [rows, 7] (frame, x1, y1, x2, y2, conf, cls) and embs
+    [rows, F] or None, values kept as float64 (no round trip through text)."""
+    dets = np.asarray(dets, np.float64)
+    dets = dets.reshape(dets.shape[0], -1) if dets.size else np.empty((0, 7))
+    embs = np.empty((dets.shape[0], 0)) if embs is None else np.asarray(embs, np.float64)
+    if dets.shape[0] != embs.shape[0]:
+        raise ValueError("detections and embeddings differ in rows")
     if dets.shape[0] and dets.shape[1] != 7:
         raise ValueError("detection rows must be frame, x1, y1, x2, y2, conf, cls")
     fid = dets[:, 0].astype(int) if dets.shape[0] else np.empty(0, int)
@@ -120,6 +133,18 @@ def write_mot_results(txt_path, mot_results: np.ndarray | None) -> None:
 def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs: dict):
     """One engine handle for n_seq sequences, parameterised exactly as the drop-in tracker
     `tracker_type` is by `tracker_kwargs` (create_tracker's YAML defaults when empty)."""
+    if tracker_type == "deepocsort":
+        # not in create_tracker's table and without a YAML: the drop-in's constructor (its
+        # defaults with empty tracker_kwargs) decides the parameters; per_class raises there
+        from .engine import DeepOcsortEngine
+        from .trackers.deepocsort import DeepOcSort
+
+        tr = DeepOcSort(**tracker_kwargs)
+        if tr.engine is not None:  # (embedding_off builds the drop-in's own engine at once)
+            tr.engine.close()
+        tc, dc = tr._caps
+        return DeepOcsortEngine(n_seq=n_seq, track_cap=tc, det_cap=dc, emb_dim=emb_dim,
+                                params=tr._params), np.float32, 8
     from .engine import BoostEngine, Engine, OcsortEngine, SsEngine
     from .tracker_zoo import create_tracker
 
@@ -152,9 +177,50 @@ def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs:
     raise NotImplementedError(f"{tracker_type} is not on the engine")
 
 
+RESIDENT_TRACKERS = ("deepocsort",)  # trackers run_sequences(resident=True) can drive
+
+
+def _resident_results(eng, seqs, fids, F: int, ddt) -> list:
+    """The frame loop of run_sequences with the sequences resident in HBM (engine.SequenceFeeder):
+    one upload, per frame index one gather launch, the steps of its runs and one append launch,
+    one copy back.  Returns each sequence's MOT rows [n, 9]."""
+    from .engine import SequenceFeeder
+
+    feed_emb = F if getattr(eng, "emb_dim", 0) else 0
+    dets, embs, tables = [], [], []
+    for s, f in zip(seqs, fids):
+        if F and s.rows and s.emb_dim not in (0, F):
+            raise ValueError(f"{s.path}: embedding dim {s.emb_dim} != {F}")
+        start, cnt = np.zeros(len(f), np.int64), np.zeros(len(f), np.int64)
+        # (a sequence packed without embeddings among ones that have them is never stepped)
+        for i, x in enumerate(f if (s.emb_dim or not F) else ()):
+            j = s._index.get(int(x))
+            if j is not None:
+                start[i], cnt[i] = s.offsets[j], s.offsets[j + 1] - s.offsets[j]
+        tables.append((start, cnt, np.asarray(f, np.int64)))
+        dets.append(np.asarray(s.dets).astype(ddt))
+        embs.append(s.embs if s.emb_dim == feed_emb else np.zeros((s.rows, feed_emb)))
+    feed = SequenceFeeder(dets, embs, tables, feed_emb)
+    try:
+        for t in range(feed.n_frames):
+            runs = feed.schedule[t]
+            if not runs:
+                continue
+            feed.gather(t)
+            for k, ns, _, pd, po, pe, pout, pcnt in runs:
+                eng.step(pd, po, pe, None, pout, pcnt, seq0=k, nseq=ns)
+            feed.append(t)
+        if eng.status() != 0:
+            raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
+        return feed.results()
+    finally:
+        feed.close()
+
+
 def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict | None = None,
                   frame_sizes: dict | None = None, tracker_kwargs: dict | None = None,
-                  gsi: bool = False, gsi_interval: int = 20, gsi_tau: float = 10) -> dict:
+                  gsi: bool = False, gsi_interval: int = 20, gsi_tau: float = 10,
+                  resident: bool = False) -> dict:
     """process_sequence (val.py:304-354) for every sequence at once.
 
     sequences: name -> packed file (pack_sequence) or BinSequence; frame_ids: name -> the frames
@@ -163,7 +229,14 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
     name -> the frame ids iterated.  Sequence k's track ids start at 1, as in a fresh process.
     gsi: apply the GSI post-processing (postprocessing.gsi, with gsi_interval / gsi_tau) to
     exp_dir after the files are written, as the reference's evaluation flow does last.
+    resident: keep the sequences' detections and embeddings and the result rows in device memory
+    for the whole run (include/bxfeed.h) instead of assembling every frame on the host; the files
+    are byte-identical.  Only for the trackers in RESIDENT_TRACKERS.
     """
+    if resident and tracker_type not in RESIDENT_TRACKERS:
+        raise NotImplementedError(
+            f"run_sequences(resident=True) is not available for {tracker_type}: the "
+            f"device-resident feeder drives {', '.join(RESIDENT_TRACKERS)} only")
     import torch
 
     names = list(sequences)
@@ -177,6 +250,19 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
                 eng.set_frame_size(k, *frame_sizes[nm])
     fids = [np.asarray(frame_ids[nm]) if frame_ids and nm in frame_ids else s.frame_ids
             for nm, s in zip(names, seqs)]
+    if tracker_type == "deepocsort" and frame_sizes:
+        for k, nm in enumerate(names):
+            if nm in frame_sizes:
+                eng.set_frame_size(k, *frame_sizes[nm])
+    if resident:
+        exp_dir = Path(exp_dir)
+        for nm, res in zip(names, _resident_results(eng, seqs, fids, F, ddt)):
+            write_mot_results(exp_dir / f"{nm}.txt", res if res.size else np.empty((0, 0)))
+        if gsi:
+            from . import postprocessing
+
+            postprocessing.gsi(exp_dir, interval=gsi_interval, tau=gsi_tau)
+        return {nm: list(map(int, f)) for nm, f in zip(names, fids)}
     results = [[] for _ in range(S)]
     occ = None
     if getattr(eng, "occlusion_threshold", None) is not None:
