@@ -21,6 +21,7 @@ HEADER_OCS = REPO / "include" / "bxocsort.h"
 HEADER_BOOST = REPO / "include" / "bxboost.h"
 HEADER_SS = REPO / "include" / "bxstrongsort.h"
 HEADER_DEEPOC = REPO / "include" / "bxdeepocsort.h"
+HEADER_HYBRID = REPO / "include" / "bxhybridsort.h"
 HEADER_IO = REPO / "include" / "bxio.h"
 HEADER_GSI = REPO / "include" / "bxgsi.h"
 HEADER_FEED = REPO / "include" / "bxfeed.h"
@@ -34,7 +35,7 @@ HIPCC_FLAGS = [
     "-mllvm", "-amdgpu-mfma-vgpr-form=1",
 ]
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
-           "bx_strongsort.hip", "bx_deepocsort.hip", "bx_gsi.hip", "bx_feed.hip",
+           "bx_strongsort.hip", "bx_deepocsort.hip", "bx_hybridsort.hip", "bx_gsi.hip", "bx_feed.hip",
            "bx_io.cpp"]
 
 
@@ -178,6 +179,17 @@ class BxDeepocConfig(C.Structure):
     ]
 
 
+class BxHybridConfig(C.Structure):
+    _fields_ = [
+        ("n_seq", C.c_int32), ("track_cap", C.c_int32), ("det_cap", C.c_int32),
+        ("emb_dim", C.c_int32), ("det_thresh", C.c_double), ("iou_threshold", C.c_double),
+        ("inertia", C.c_double), ("longterm_reid_weight", C.c_double),
+        ("tcm_first_step_weight", C.c_double), ("max_age", C.c_int32), ("min_hits", C.c_int32),
+        ("delta_t", C.c_int32), ("asso_kind", C.c_int32), ("frame_w", C.c_double),
+        ("frame_h", C.c_double),
+    ]
+
+
 class BxSsConfig(C.Structure):
     _fields_ = [
         ("n_seq", C.c_int32), ("track_cap", C.c_int32), ("det_cap", C.c_int32),
@@ -226,6 +238,12 @@ EXPORTS = [
     "bx_deepoc_counters_host", "bx_deepoc_set_id_count", "bx_deepoc_set_frame_size",
     "bx_deepoc_tracks_host", "bx_deepoc_state_set_host", "bx_deepoc_frame_stats_host",
     "bx_deepoc_probe", "bx_deepoc_probe_read", "bx_deepoc_embcost",
+    "bx_hybrid_create", "bx_hybrid_destroy", "bx_hybrid_reset", "bx_hybrid_step",
+    "bx_hybrid_update_host", "bx_hybrid_copy_state", "bx_hybrid_status",
+    "bx_hybrid_counters_host", "bx_hybrid_set_id_count", "bx_hybrid_set_frame_size",
+    "bx_hybrid_tracks_host", "bx_hybrid_state_set_host", "bx_hybrid_state_bytes",
+    "bx_hybrid_state_save_host", "bx_hybrid_state_load_host", "bx_hybrid_cosdist",
+    "bx_hybrid_bank_mean",
     "bx_gsi_plan_workspace_bytes", "bx_gsi_interpolate_plan", "bx_gsi_interpolate",
     "bx_gsi_workspace_bytes", "bx_gsi_smooth", "bx_gsi_run_host",
     "bx_feed_create", "bx_feed_destroy", "bx_feed_upload_host", "bx_feed_shape",
@@ -363,6 +381,24 @@ _SIGS = {
     "bx_deepoc_probe": ([_vp, C.c_int], C.c_int),
     "bx_deepoc_probe_read": ([_vp, _dp, _ip], C.c_int),
     "bx_deepoc_embcost": ([C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_hybrid_create": ([C.POINTER(BxHybridConfig), C.POINTER(C.c_void_p)], C.c_int),
+    "bx_hybrid_destroy": ([_vp], C.c_int),
+    "bx_hybrid_reset": ([_vp, C.c_int, C.c_int, _vp], C.c_int),
+    "bx_hybrid_step": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_hybrid_update_host": ([_vp, C.c_int, _vp, C.c_int, _vp, _vp, _ip, _vp], C.c_int),
+    "bx_hybrid_copy_state": ([_vp, _vp], C.c_int),
+    "bx_hybrid_status": ([_vp, _ip], C.c_int),
+    "bx_hybrid_counters_host": ([_vp, C.c_int, _ip, _ip, _ip], C.c_int),
+    "bx_hybrid_set_id_count": ([_vp, C.c_int, C.c_int, _vp], C.c_int),
+    "bx_hybrid_set_frame_size": ([_vp, C.c_int, C.c_double, C.c_double, _vp], C.c_int),
+    "bx_hybrid_tracks_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip],
+                              C.c_int),
+    "bx_hybrid_state_set_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp], C.c_int),
+    "bx_hybrid_state_bytes": ([_vp, C.POINTER(C.c_size_t)], C.c_int),
+    "bx_hybrid_state_save_host": ([_vp, C.c_int, _vp, C.c_size_t], C.c_int),
+    "bx_hybrid_state_load_host": ([_vp, C.c_int, _vp, C.c_size_t], C.c_int),
+    "bx_hybrid_cosdist": ([C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_hybrid_bank_mean": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
     "bx_gsi_plan_workspace_bytes": ([C.c_int64, C.POINTER(C.c_size_t)], C.c_int),
     "bx_gsi_interpolate_plan": ([_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.c_size_t, _vp,
                                  _vp], C.c_int),

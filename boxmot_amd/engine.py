@@ -656,6 +656,180 @@ def deepoc_embcost(dets_embs, trk_embs, out, stream=None) -> None:
                                        _ptr(out), stream), "bx_deepoc_embcost")
 
 
+@dataclass
+class HybridsortParams:
+    """HybridSort constructor parameters (hybridsort.py:372-388 names and defaults; the
+    reference gives det_thresh no default)."""
+
+    det_thresh: float = 0.3
+    max_age: int = 30
+    min_hits: int = 3
+    iou_threshold: float = 0.3
+    delta_t: int = 3
+    asso_func: str = "iou"
+    inertia: float = 0.2
+    longterm_reid_weight: float = 0.0
+    TCM_first_step_weight: float = 0.0
+    frame_w: float = 1920.0     # centroid normalisation until set_frame_size latches the image
+    frame_h: float = 1080.0
+
+
+class HybridsortEngine:
+    """Handle over ``bx_hybrid_*`` (include/bxhybridsort.h): ``n_seq`` HybridSort sequences in
+    HBM; per frame the two cosine-distance contractions (fp64 MFMA), the frame kernel (one wave
+    per sequence) and the feature update.  Embeddings are float64, ``emb_dim`` wide."""
+
+    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
+                 emb_dim: int = 512, params: HybridsortParams | None = None):
+        p = params or HybridsortParams()
+        self.n_seq, self.track_cap, self.det_cap, self.params = n_seq, track_cap, det_cap, p
+        self.emb_dim = int(emb_dim)
+        cfg = N.BxHybridConfig(
+            n_seq=n_seq, track_cap=track_cap, det_cap=det_cap, emb_dim=self.emb_dim,
+            det_thresh=float(p.det_thresh), iou_threshold=float(p.iou_threshold),
+            inertia=float(p.inertia), longterm_reid_weight=float(p.longterm_reid_weight),
+            tcm_first_step_weight=float(p.TCM_first_step_weight), max_age=int(p.max_age),
+            min_hits=int(p.min_hits), delta_t=int(p.delta_t), asso_kind=_asso_kind(p.asso_func),
+            frame_w=float(p.frame_w), frame_h=float(p.frame_h))
+        self._L = N.load()
+        h = C.c_void_p()
+        N.check(self._L.bx_hybrid_create(C.byref(cfg), C.byref(h)), "bx_hybrid_create")
+        self._h = h
+
+    def slots_used(self, seq: int = 0) -> int:
+        return self.counters(seq)["n_tracks"]
+
+    def grown(self, track_cap: int, det_cap: int) -> "HybridsortEngine":
+        """A new engine with larger capacities holding this one's state (bx_hybrid_copy_state)."""
+        e = HybridsortEngine(self.n_seq, track_cap, det_cap, self.emb_dim, self.params)
+        N.check(self._L.bx_hybrid_copy_state(e._h, self._h), "bx_hybrid_copy_state")
+        return e
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._L.bx_hybrid_destroy(h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, seq0: int = 0, nseq: int | None = None, stream=None):
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        N.check(self._L.bx_hybrid_reset(self._h, seq0, nseq, stream), "bx_hybrid_reset")
+
+    def step(self, dets, det_off, embs, out, out_count, seq0: int = 0, nseq: int | None = None,
+             stream=None):
+        """One frame for sequences [seq0, seq0+nseq) from device tensors (see bx_hybrid_step):
+        embs float64 [sum N, emb_dim]."""
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        if stream is None:
+            stream = _current_stream()
+        N.check(self._L.bx_hybrid_step(self._h, seq0, nseq, _ptr(dets), _ptr(det_off), _ptr(embs),
+                                       _ptr(out), _ptr(out_count), stream), "bx_hybrid_step")
+
+    def update_host(self, seq: int, dets: np.ndarray, embs: np.ndarray | None = None) -> np.ndarray:
+        d = np.ascontiguousarray(dets, dtype=np.float32).reshape(-1, 6)
+        n = d.shape[0]
+        e = None
+        if n:
+            if embs is None:
+                raise ValueError("HybridSort needs embeddings")
+            e = np.ascontiguousarray(embs, dtype=np.float64).reshape(n, -1)
+            if e.shape[1] != self.emb_dim:
+                raise ValueError(f"embedding dim {e.shape[1]} != engine emb_dim {self.emb_dim}")
+        out = np.empty((max(n, 1), 8), np.float64)
+        m = C.c_int(0)
+        N.check(self._L.bx_hybrid_update_host(
+            self._h, seq, d.ctypes.data if n else None, n, _p(e), out.ctypes.data, C.byref(m),
+            None), "bx_hybrid_update_host")
+        return out[: m.value].copy()
+
+    def status(self) -> int:
+        s = C.c_int(0)
+        N.check(self._L.bx_hybrid_status(self._h, C.byref(s)), "bx_hybrid_status")
+        return s.value
+
+    def counters(self, seq: int = 0) -> dict:
+        fc, idc, nt = C.c_int(), C.c_int(), C.c_int()
+        N.check(self._L.bx_hybrid_counters_host(self._h, seq, C.byref(fc), C.byref(idc),
+                                                C.byref(nt)), "counters")
+        return {"frame_count": fc.value, "id_count": idc.value, "n_tracks": nt.value}
+
+    def set_id_count(self, seq: int, value: int):
+        N.check(self._L.bx_hybrid_set_id_count(self._h, seq, int(value), None), "set_id_count")
+
+    def set_frame_size(self, seq: int, w: float, h: float):
+        N.check(self._L.bx_hybrid_set_frame_size(self._h, seq, float(w), float(h), None),
+                "set_frame_size")
+
+    def tracks(self, seq: int = 0) -> dict:
+        """Host snapshot of the track list (list order): ids, the 9-state means x [9]
+        (u, v, s, score, r and the velocities of the first four), covariances [9, 9], smoothed
+        features [emb_dim], feature-bank means [emb_dim], the four corner velocities [4, 2]
+        (lt, rt, lb, rb as (y, x)) and the number of features pushed into each track's bank."""
+        cap = self.track_cap
+        ids = np.zeros(cap, np.int32)
+        x = np.zeros((cap, 9))
+        P = np.zeros((cap, 9, 9))
+        E = np.zeros((cap, self.emb_dim))
+        M = np.zeros((cap, self.emb_dim))
+        V = np.zeros((cap, 4, 2))
+        bc = np.zeros(cap, np.int32)
+        n = C.c_int()
+        N.check(self._L.bx_hybrid_tracks_host(self._h, seq, cap, ids.ctypes.data, x.ctypes.data,
+                                              P.ctypes.data, E.ctypes.data, M.ctypes.data,
+                                              V.ctypes.data, bc.ctypes.data, C.byref(n)), "tracks")
+        k = min(n.value, cap)
+        return {"id": ids[:k], "x": x[:k], "P": P[:k], "emb": E[:k], "bank_mean": M[:k],
+                "vel": V[:k], "bank_count": bc[:k]}
+
+    def state_set(self, seq: int, ids, x=None, P=None) -> None:
+        """Write kf.x [n,9] / kf.P [n,9,9] of live tracks by id."""
+        n, ids, a, b = _state_arrays(ids, x, P, 9, 81)
+        N.check(self._L.bx_hybrid_state_set_host(self._h, seq, n, ids.ctypes.data, _p(a), _p(b)),
+                "state_set")
+
+    def state_save(self, seq: int = 0) -> np.ndarray:
+        """One sequence's whole tracker state as an opaque byte array (bx_hybrid_state_save_host)."""
+        nb = C.c_size_t()
+        N.check(self._L.bx_hybrid_state_bytes(self._h, C.byref(nb)), "state_bytes")
+        blob = np.empty(nb.value, np.uint8)
+        N.check(self._L.bx_hybrid_state_save_host(self._h, seq, blob.ctypes.data, nb.value),
+                "state_save")
+        return blob
+
+    def state_load(self, seq: int, blob: np.ndarray) -> None:
+        """Write a state_save() blob of an engine with the same track_cap and emb_dim."""
+        b = np.ascontiguousarray(blob, np.uint8)
+        N.check(self._L.bx_hybrid_state_load_host(self._h, seq, b.ctypes.data, b.size),
+                "state_load")
+
+
+def hybrid_cosdist(dets_embs, trk_embs, out, stream=None) -> None:
+    """out [nd, nt] = max(0, 1 - cos(dets_embs [nd, F], trk_embs [nt, F])) on device float64
+    tensors, by the tracker's own MFMA tile (bx_hybrid_cosdist)."""
+    nd, F = dets_embs.shape
+    nt = trk_embs.shape[0]
+    if stream is None:
+        stream = _current_stream()
+    N.check(N.load().bx_hybrid_cosdist(int(nd), int(nt), int(F), _ptr(dets_embs), _ptr(trk_embs),
+                                       _ptr(out), stream), "bx_hybrid_cosdist")
+
+
+def hybrid_bank_mean(bank, pushed, out, stream=None) -> None:
+    """out [nt, F] = mean of the rows present in each feature ring bank [nt, 30, F] after
+    pushed [nt] (int32) pushes, on device tensors (bx_hybrid_bank_mean)."""
+    nt, _, F = bank.shape
+    if stream is None:
+        stream = _current_stream()
+    N.check(N.load().bx_hybrid_bank_mean(int(nt), int(F), _ptr(bank), _ptr(pushed), _ptr(out),
+                                         stream), "bx_hybrid_bank_mean")
+
+
 class SequenceFeeder:
     """Handle over ``bx_feed_*`` (include/bxfeed.h): the packed rows of many sequences resident
     in HBM, gathered per frame index into the batched arrays a ``step`` takes, and the steps'

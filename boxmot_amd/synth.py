@@ -46,6 +46,9 @@ class SyntheticScene:
     # every k-th detection is emitted twice (identical row and embedding, the copy right after
     # it) — a detector without NMS; the duplicates tie the linear assignment (0 = off)
     dup_every: int = 0
+    # scale of the per-detection embedding perturbation (x N(0,1)/sqrt(F)); at 3 the appearance
+    # hardly tells identities apart, so motion and score decide the association
+    emb_noise: float = 0.1
 
     def __post_init__(self):
         rng = np.random.default_rng([self.seed, 0x5CE7E])
@@ -106,7 +109,7 @@ class SyntheticScene:
             dets[:, 5] = np.asarray(self.classes, np.float64)[ids % len(self.classes)]
         embs = None
         if self.base_emb is not None:
-            e = self.base_emb[ids] + 0.1 * rng.standard_normal((m, self.emb_dim)) / math.sqrt(
+            e = self.base_emb[ids] + self.emb_noise * rng.standard_normal((m, self.emb_dim)) / math.sqrt(
                 self.emb_dim
             )
             e /= np.linalg.norm(e, axis=1, keepdims=True)

@@ -1,0 +1,124 @@
+"""HybridSort on the MI355X engine — drop-in for boxmot.trackers.hybridsort.hybridsort.HybridSort
+(reference trackers/hybridsort/hybridsort.py:350-741).
+
+Same constructor signature and defaults (``reid_weights``, ``device``, ``half`` are accepted for
+compatibility; ``det_thresh`` has no default, as in the reference), same ``update(dets, img,
+embs)`` contract and output rows (ids start at 1).  The frame — the 9-state Kalman filter that
+also tracks the detection score, the two appearance distances per pair (smoothed feature and
+30-deep feature-bank mean) on the fp64 matrix cores, the association on asso_func + four-corner
+direction consistency - score difference + appearance, the long-term-ReID correction filter, the
+OCR round, the feature moving average, births and deaths — is three kernel launches.
+
+The reference does not run as published; this follows it with the patches H1-H3 of
+tests/golden/make_golden_hybridsort.py.  Like the reference, column 7 of the
+output rows is a confidence, not a detection index: HybridSort reads ``cls`` and ``det_ind`` from
+the unfiltered frame at an index into the kept detections, ``det_ind`` from its score column
+(hybridsort.py:458,467,604).
+
+Out of scope: the ReID embeddings are an input (``embs``; the reference would run its ReID
+backend), ``use_byte=True`` (the reference's BYTE round cannot run) and ``per_class=True``.
+``create_tracker("hybridsort")`` is not wired up: construct the class directly.  Embeddings are
+float64 on the engine: ``embs`` is converted with ``np.asarray(embs, np.float64)``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ..engine import HybridsortEngine, HybridsortParams
+from ..iou import KINDS
+from .basetracker import BaseTracker, CapacityGuard
+
+
+class HybridSort(BaseTracker):
+    # KalmanBoxTracker.count is a class attribute shared by every instance and reset by each
+    # HybridSort constructor (hybridsort.py:115,176-177,418); output ids are count + 1: mirrored
+    # here as a counter that starts at 1.
+    _id_count = 1
+
+    def __init__(self, reid_weights, device, half, det_thresh, per_class: bool = False,
+                 max_age: int = 30, min_hits: int = 3, iou_threshold: float = 0.3,
+                 delta_t: int = 3, asso_func: str = "iou", inertia: float = 0.2,
+                 longterm_reid_weight: float = 0, TCM_first_step_weight: float = 0,
+                 use_byte: bool = False, track_cap: int = 256, det_cap: int = 256):
+        if use_byte:
+            raise NotImplementedError(
+                "HybridSort(use_byte=True) is not built: the reference's BYTE round calls "
+                "KalmanBoxTracker.update with the wrong arguments, so it defines no behaviour")
+        if per_class:
+            raise NotImplementedError(
+                "HybridSort(per_class=True) is not on the MI355X association engine yet: run one "
+                "HybridSort per class")
+        super().__init__(max_age=max_age, per_class=per_class, asso_func=asso_func)
+        self.max_age = max_age
+        self.min_hits = min_hits
+        self.iou_threshold = iou_threshold
+        self.det_thresh = det_thresh
+        self.delta_t = delta_t
+        self.inertia = inertia
+        self.use_byte = use_byte
+        self.longterm_reid_weight = longterm_reid_weight
+        self.TCM_first_step_weight = TCM_first_step_weight
+        HybridSort._id_count = 1
+        # an unknown asso_func never reaches the engine: setup_decorator raises ValueError for it
+        # on the first update (basetracker.py:140-147), as DeepOcSort's; "iou" only fills the field
+        self._params = HybridsortParams(
+            det_thresh=det_thresh, max_age=max_age, min_hits=min_hits,
+            iou_threshold=iou_threshold, delta_t=delta_t,
+            asso_func=asso_func if asso_func in KINDS else "iou", inertia=inertia,
+            longterm_reid_weight=longterm_reid_weight,
+            TCM_first_step_weight=TCM_first_step_weight)
+        self._caps = (track_cap, det_cap)
+        self._cap = CapacityGuard()
+        self._engine_ids = 1
+        self._frame_latched = False
+        # the embedding width is learnt from the first frame that has detections; empty frames
+        # before it are counted and replayed into the engine once it exists
+        self.engine = None
+        self._empty_before_engine = 0
+
+    def _make_engine(self, emb_dim: int) -> HybridsortEngine:
+        return HybridsortEngine(n_seq=1, track_cap=self._caps[0], det_cap=self._caps[1],
+                                emb_dim=emb_dim, params=self._params)
+
+    @BaseTracker.setup_decorator
+    @BaseTracker.per_class_decorator
+    def update(self, dets: np.ndarray, img: np.ndarray, embs: np.ndarray = None) -> np.ndarray:
+        self.check_inputs(dets, img, embs)
+        n = int(dets.shape[0])
+        if n and embs is None:
+            raise ValueError("HybridSort on the MI355X engine needs `embs`: ReID inference is "
+                             "outside the association path")
+        e = np.asarray(embs, np.float64).reshape(n, -1) if n else None
+        if self.engine is None:
+            if e is None:
+                # nothing to learn the embedding width from yet: an empty frame on an empty
+                # tracker only advances the frame counter; replayed below
+                self.frame_count += 1
+                self._empty_before_engine += 1
+                return np.empty((0, 8))
+            self.engine = self._make_engine(e.shape[1])
+            for _ in range(self._empty_before_engine):
+                self.engine.update_host(0, np.empty((0, 6), np.float32))
+            self._empty_before_engine = 0
+        if not self._frame_latched and self._first_frame_processed:
+            # the engine's centroid frame size follows BaseTracker's first-frame latch
+            self.engine.set_frame_size(0, self.w, self.h)
+            self._frame_latched = True
+        self.frame_count += 1
+        self.engine = self._cap.fit(self.engine, {0: n}, n)
+        if self._engine_ids != HybridSort._id_count:
+            self.engine.set_id_count(0, HybridSort._id_count)
+        out = self.engine.update_host(0, dets, e)
+        self._engine_ids = HybridSort._id_count = self.engine.counters(0)["id_count"]
+        return out if out.shape[0] else np.empty((0, 8))
+
+    @property
+    def active_tracks(self):
+        """Track list snapshot: id, Kalman state (x [9], P [9, 9]), smoothed feature and the
+        number of features pushed into the bank, per track."""
+        if self.engine is None:
+            return []
+        snap = self.engine.tracks(0)
+        return [{"id": int(snap["id"][k]), "x": snap["x"][k], "P": snap["P"][k],
+                 "emb": snap["emb"][k], "bank_count": int(snap["bank_count"][k])}
+                for k in range(snap["id"].shape[0])]

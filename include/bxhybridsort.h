@@ -1,0 +1,126 @@
+/*
+ * bxhybridsort.h — C ABI of the HybridSort engine in libbxassoc.so (MI355X, gfx950).
+ *
+ * Boundary: everything HybridSort.update(dets, img, embs) computes per frame once the ReID
+ * embeddings are given — the 9-state / 5-measurement XYSR Kalman filter that also tracks the
+ * detection score (predict, update, observation-centric re-update), the cosine distances of the
+ * detection features to every track's smoothed feature and to the mean of its 30-deep feature
+ * bank, the association on asso_func + four-corner direction consistency - score difference +
+ * appearance, the long-term-ReID correction filter, the observation-centric recovery (OCR)
+ * round, the feature moving average and bank, births, deaths and the output rows — runs on the
+ * GPU behind these entry points.  One frame is three launches: the two distance contractions
+ * (fp64 MFMA, a 4-wave workgroup per 32x64 tile), the frame (one wave64 workgroup per sequence)
+ * and the feature update (a wave per record).
+ *
+ * Reference interfaces replaced (file:line in muntherr/boxmot):
+ *   bx_hybrid_create/step/update_host  HybridSort.__init__ / HybridSort.update
+ *                                      boxmot/trackers/hybridsort/hybridsort.py:372-741
+ *     KalmanBoxTracker                 hybridsort.py:110-347
+ *     KalmanFilterXYSR (ORU)           boxmot/motion/kalman_filters/aabb/xysr_kf.py:48-291
+ *     associate_4_points_with_score_with_reid   hybridsort/association.py:537-644
+ *     cost_vel                         hybridsort/association.py:328-349
+ *     linear_assignment                hybridsort/association.py:312-325
+ *   bx_hybrid_cosdist                  embedding_distance  hybridsort/association.py:734-751
+ * The reference does not run as published; parity is defined against it with the patches H1-H3
+ * listed in tests/golden/make_golden_hybridsort.py.  use_byte is not built.
+ * ECC is False in the reference, so no camera-motion warp crosses this ABI.
+ *
+ * Conventions as in bxassoc.h: device pointers unless a name ends in _host, asynchronous on
+ * `stream`, every function returns a bx_status (bx_last_error explains failures).
+ */
+#ifndef BXHYBRIDSORT_H
+#define BXHYBRIDSORT_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "bxassoc.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* HybridSort constructor parameters (hybridsort.py:372-388: det_thresh has no default, max_age
+ * 30, min_hits 3, iou_threshold .3, delta_t 3, inertia .2, longterm_reid_weight 0,
+ * TCM_first_step_weight 0).  asso_kind and the frame size as in bx_ocsort_config.  emb_dim is
+ * the embedding width F, any positive value.  det_thresh must be >= 0. */
+typedef struct {
+    int32_t n_seq;      /* independent sequences held by this engine */
+    int32_t track_cap;  /* track slots per sequence (<= 512) */
+    int32_t det_cap;    /* max detections per frame per sequence (<= 512) */
+    int32_t emb_dim;
+    double det_thresh, iou_threshold, inertia;
+    double longterm_reid_weight, tcm_first_step_weight;
+    int32_t max_age, min_hits, delta_t;
+    int32_t asso_kind;
+    double frame_w, frame_h;
+} bx_hybrid_config;
+
+typedef struct bx_hybrid bx_hybrid;
+
+int bx_hybrid_create(const bx_hybrid_config *cfg, bx_hybrid **out);
+int bx_hybrid_destroy(bx_hybrid *e);
+/* Forget all tracks of sequences [seq0, seq0+nseq): frame counter 0, id counter back to 1. */
+int bx_hybrid_reset(bx_hybrid *e, int seq0, int nseq, void *stream);
+/* One frame for sequences [seq0, seq0+nseq) — three launches.
+ *   dets    [sum N][6] float32 (x1,y1,x2,y2,conf,cls)
+ *   det_off [nseq+1] int32 prefix offsets
+ *   embs    [sum N][emb_dim] float64, one row per detection
+ *   out     [sum N][8] float64 rows [x1,y1,x2,y2,id,conf,cls,det_ind], sequence k from row
+ *           det_off[k], in the reference's (reversed track list) order; ids start at 1.  The
+ *           reference reads cls and det_ind from the unfiltered frame at an index into the kept
+ *           detections, and det_ind from its score column (hybridsort.py:458,467,604): column 7
+ *           is a confidence
+ *   out_count [nseq] int32 */
+int bx_hybrid_step(bx_hybrid *e, int seq0, int nseq, const float *dets, const int32_t *det_off,
+                   const double *embs, double *out, int32_t *out_count, void *stream);
+/* Host-memory path for one sequence (the drop-in update): copies in, launches, copies out,
+ * synchronises.  embs [n][emb_dim] (NULL only when n == 0); out must hold n rows. */
+int bx_hybrid_update_host(bx_hybrid *e, int seq, const float *dets, int n, const double *embs,
+                          double *out, int *n_out, void *stream);
+/* Capacity growth (the reference's track list is unbounded): copy every sequence's tracker
+ * state of `src` into `dst`, a fresh engine with the same configuration and sequences and
+ * track_cap / det_cap at least src's (slot ids stay valid).  Synchronous. */
+int bx_hybrid_copy_state(bx_hybrid *dst, bx_hybrid *src);
+/* Latched device status (BX_OK, BX_ERR_TRACK_OVERFLOW or BX_ERR_CAPACITY). */
+int bx_hybrid_status(bx_hybrid *e, int *status);
+int bx_hybrid_counters_host(bx_hybrid *e, int seq, int *frame_count, int *id_count,
+                            int *n_tracks);
+/* KalmanBoxTracker.count is class-global in the reference (hybridsort.py:115,176-177,418); the
+ * Python drop-in mirrors it through this. */
+int bx_hybrid_set_id_count(bx_hybrid *e, int seq, int id_count, void *stream);
+/* Frame size (w, h) of a sequence — BaseTracker latches img.shape on the first frame. */
+int bx_hybrid_set_frame_size(bx_hybrid *e, int seq, double w, double h, void *stream);
+/* Track list of a sequence in list order (host, synchronous): ids [cap], Kalman means x
+ * [cap][9], covariances p [cap][81], smoothed features emb [cap][emb_dim], feature-bank means
+ * bank_mean [cap][emb_dim], corner velocities vel [cap][8] (lt, rt, lb, rb as (y, x); zeros
+ * while the reference holds None) and the number of features pushed into each bank so far,
+ * bank_count [cap] (any may be NULL); *n = number of tracks. */
+int bx_hybrid_tracks_host(bx_hybrid *e, int seq, int cap, int32_t *ids, double *x, double *p,
+                          double *emb, double *bank_mean, double *vel, int32_t *bank_count,
+                          int *n);
+/* Write kf.x [n][9] / kf.P [n][81] of live tracks by id (host, synchronous; either may be
+ * NULL).  BX_ERR_INVALID for an unknown id. */
+int bx_hybrid_state_set_host(bx_hybrid *e, int seq, int n, const int32_t *ids, const double *x,
+                             const double *p);
+/* One sequence's whole tracker state (counters, list order, track records, smoothed features,
+ * banks) as an opaque host blob of bx_hybrid_state_bytes bytes, and back into a sequence of an
+ * engine with the same track_cap and emb_dim.  Host, synchronous. */
+int bx_hybrid_state_bytes(bx_hybrid *e, size_t *bytes);
+int bx_hybrid_state_save_host(bx_hybrid *e, int seq, void *blob, size_t bytes);
+int bx_hybrid_state_load_host(bx_hybrid *e, int seq, const void *blob, size_t bytes);
+/* Op-level distance on plain device arrays, the same tile code as the tracker's:
+ * out [nd][nt] = max(0, 1 - d.t / (|d| |t|)) of dets_embs [nd][F] against trk_embs [nt][F],
+ * float64 (the transpose of embedding_distance(tracks, dets)). */
+int bx_hybrid_cosdist(int nd, int nt, int F, const double *dets_embs, const double *trk_embs,
+                      double *out, void *stream);
+/* Op-level bank mean, the tracker's own: bank [nt][30][F] feature rings (push k in row k % 30),
+ * pushed [nt] pushes so far (> 0); out [nt][F] = mean of the rows present, oldest first. */
+int bx_hybrid_bank_mean(int nt, int F, const double *bank, const int32_t *pushed, double *out,
+                        void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* BXHYBRIDSORT_H */
