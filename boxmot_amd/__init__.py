@@ -1,16 +1,17 @@
 """boxmot_amd — MI355X-native per-frame association engine for BoxMOT trackers.
 
-Drop-in surface: ``create_tracker``, ``get_tracker_config``, ``ByteTrack``, ``BotSort``, ``OcSort``, ``BoostTrack``, ``StrongSort``, ``DeepOcSort``, ``HybridSort`` with the
+Drop-in surface: ``create_tracker``, ``get_tracker_config``, ``ByteTrack``, ``BotSort``, ``OcSort``, ``BoostTrack``, ``StrongSort``, ``DeepOcSort``, ``HybridSort`` (and their per_class forms
+``DeepOcSortPerClass``, ``HybridSortPerClass``) with the
 reference's ``update(dets, img, embs) -> [M, 8]`` contract.  The numerics run in libbxassoc.so
 (HIP, gfx950); ``boxmot_amd.engine.Engine`` / ``OcsortEngine`` / ``BoostEngine`` / ``SsEngine`` / ``DeepOcsortEngine`` / ``HybridsortEngine`` expose the batched many-sequence API.
 ``gsi`` / ``linear_interpolation`` / ``gaussian_smooth`` are the GSI post-processing of MOT result files.
 """
 from .postprocessing import gaussian_smooth, gsi, linear_interpolation
 from .tracker_zoo import create_tracker, get_tracker_config
-from .trackers import (BoostTrack, BotSort, ByteTrack, DeepOcSort, HybridSort, OcSort,
-                       StrongSort)
+from .trackers import (BoostTrack, BotSort, ByteTrack, DeepOcSort, DeepOcSortPerClass,
+                       HybridSort, HybridSortPerClass, OcSort, StrongSort)
 
 __version__ = "0.1.0"
 __all__ = ["create_tracker", "get_tracker_config", "ByteTrack", "BotSort", "OcSort",
            "BoostTrack", "StrongSort", "DeepOcSort", "HybridSort", "gsi", "linear_interpolation",
-           "gaussian_smooth", "__version__"]
+           "gaussian_smooth", "DeepOcSortPerClass", "HybridSortPerClass", "__version__"]

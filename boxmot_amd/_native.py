@@ -25,6 +25,7 @@ HEADER_HYBRID = REPO / "include" / "bxhybridsort.h"
 HEADER_IO = REPO / "include" / "bxio.h"
 HEADER_GSI = REPO / "include" / "bxgsi.h"
 HEADER_FEED = REPO / "include" / "bxfeed.h"
+HEADER_CLASSES = REPO / "include" / "bxclasses.h"
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -36,6 +37,7 @@ HIPCC_FLAGS = [
 ]
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
            "bx_strongsort.hip", "bx_deepocsort.hip", "bx_hybridsort.hip", "bx_gsi.hip", "bx_feed.hip",
+           "bx_classes.hip",
            "bx_io.cpp"]
 
 
@@ -250,6 +252,14 @@ EXPORTS = [
     "bx_feed_frame_runs", "bx_feed_run", "bx_feed_gather", "bx_feed_append", "bx_feed_status",
     "bx_feed_result_rows", "bx_feed_results_host", "bx_feed_read_run_host",
     "bx_feed_write_run_host",
+    "bx_classes_create", "bx_classes_destroy", "bx_classes_shape", "bx_classes_scratch",
+    "bx_classes_split", "bx_classes_merge", "bx_classes_state", "bx_classes_reset",
+    "bx_classes_status", "bx_classes_id_count_host", "bx_classes_set_id_count",
+    "bx_classes_map_host", "bx_classes_copy_state",
+    "bx_deepoc_step_classes", "bx_deepoc_classes_config", "bx_deepoc_classes",
+    "bx_deepoc_update_classes_host", "bx_hybrid_step_classes", "bx_hybrid_classes_config",
+    "bx_hybrid_classes", "bx_hybrid_update_classes_host", "bx_hybrid_probe",
+    "bx_hybrid_probe_read",
 ]
 
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -423,6 +433,34 @@ _SIGS = {
     "bx_feed_results_host": ([_vp, _vp, _vp, _vp], C.c_int),
     "bx_feed_read_run_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp], C.c_int),
     "bx_feed_write_run_host": ([_vp, C.c_int, C.c_int, _vp, _vp], C.c_int),
+    "bx_classes_create": ([C.c_int] * 6 + [C.POINTER(C.c_void_p)], C.c_int),
+    "bx_classes_destroy": ([_vp], C.c_int),
+    "bx_classes_shape": ([_vp, _ip, _ip, _ip, _ip, _ip, _ip], C.c_int),
+    "bx_classes_scratch": ([_vp] + [C.POINTER(C.c_void_p)] * 6, C.c_int),
+    "bx_classes_split": ([_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_classes_merge": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
+                         C.c_int),
+    "bx_classes_state": ([_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
+    "bx_classes_reset": ([_vp, C.c_int, C.c_int, _vp], C.c_int),
+    "bx_classes_status": ([_vp, _ip], C.c_int),
+    "bx_classes_id_count_host": ([_vp, C.c_int, _ip], C.c_int),
+    "bx_classes_set_id_count": ([_vp, C.c_int, C.c_int, _vp], C.c_int),
+    "bx_classes_map_host": ([_vp, C.c_int, C.c_int, C.c_int, _vp, _ip], C.c_int),
+    "bx_classes_copy_state": ([_vp, _vp], C.c_int),
+    "bx_deepoc_step_classes": ([_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+                               C.c_int),
+    "bx_deepoc_classes_config": ([_vp, C.c_int, C.c_int], C.c_int),
+    "bx_deepoc_classes": ([_vp, C.POINTER(C.c_void_p)], C.c_int),
+    "bx_deepoc_update_classes_host": ([_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _ip, _vp,
+                                       _ip, _vp], C.c_int),
+    "bx_hybrid_step_classes": ([_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp],
+                               C.c_int),
+    "bx_hybrid_probe": ([_vp, C.c_int], C.c_int),
+    "bx_hybrid_probe_read": ([_vp, _dp, _ip], C.c_int),
+    "bx_hybrid_classes_config": ([_vp, C.c_int, C.c_int], C.c_int),
+    "bx_hybrid_classes": ([_vp, C.POINTER(C.c_void_p)], C.c_int),
+    "bx_hybrid_update_classes_host": ([_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _ip, _vp, _ip,
+                                       _vp], C.c_int),
 }
 
 _lib = None

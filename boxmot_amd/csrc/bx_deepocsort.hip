@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/bxdeepocsort.h"
+#include "bx_classes_glue.h"
 #include "bx_device.h"
 
 using namespace bx;
@@ -690,6 +691,10 @@ struct bx_deepoc {
   int* p_cnt = nullptr;
   int* p_sq = nullptr;
   int cache_seq = -1;
+  // per_class=True: the class state and the staging of the per-class warps
+  ClsGlue pc;
+  double* h_cwarp = nullptr;
+  double* p_cwarp = nullptr;
   // timing probe
   int probe_stage = -1;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -897,7 +902,7 @@ int bx_deepoc_copy_state(bx_deepoc* dst, bx_deepoc* src) {
   DCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
   dst->cache_seq = -1;
   DCHK(hipDeviceSynchronize());
-  return BX_OK;
+  return cls_glue_copy(dst->pc, src->pc, b.S, b.D, dst->dev.F, 1);
 }
 
 int bx_deepoc_destroy(bx_deepoc* e) {
@@ -919,6 +924,9 @@ int bx_deepoc_destroy(bx_deepoc* e) {
   (void)hipHostFree(e->p_out);
   (void)hipHostFree(e->p_cnt);
   (void)hipHostFree(e->p_sq);
+  cls_glue_free(e->pc);
+  (void)hipFree(e->h_cwarp);
+  (void)hipHostFree(e->p_cwarp);
   delete e;
   return BX_OK;
 }
@@ -931,7 +939,7 @@ int bx_deepoc_reset(bx_deepoc* e, int seq0, int nseq, void* stream) {
   hipLaunchKernelGGL(deepoc_reset_kernel, dim3((nseq * SQO + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, e->dev, seq0, nseq);
   DCHK(hipGetLastError());
-  return BX_OK;
+  return cls_glue_reset(e->pc, seq0, nseq, stream);
 }
 
 int bx_deepoc_step(bx_deepoc* e, int seq0, int nseq, const float* dets, const int32_t* det_off,
@@ -988,10 +996,95 @@ int bx_deepoc_update_host(bx_deepoc* e, int seq, const float* dets, int n, const
   return BX_OK;
 }
 
+// per_class=True (include/bxclasses.h): class c of sequence s is engine sequence s * C + c; the
+// frame is split -> the three launches over the class sequences -> merge, all on `stream`.
+int bx_deepoc_step_classes(bx_deepoc* e, int seq0, int nseq, int n_classes, const float* dets,
+                           const int32_t* det_off, const double* embs, const double* warps,
+                           double* out, int32_t* out_count, void* stream) {
+  if (!e) return bx_record_error(BX_ERR_INVALID, "null engine");
+  if (!e->dev.emb_off && !embs)
+    return bx_record_error(BX_ERR_SHAPE, "DeepOCSort needs embeddings unless embedding_off");
+  e->cache_seq = -1;
+  hipStream_t st = (hipStream_t)stream;
+  return cls_glue_step(e->pc, e->dev.o.S, e->dev.o.D, e->dev.F, 1, e->dev.o.seqst + SO_IDS, SQO,
+                       seq0, nseq, n_classes, dets, det_off, embs, out, out_count, st,
+                       [&](int q0, int nq, const float* d, const int* off, const double* em,
+                           double* o, int* cnt) {
+                         return launch(e, q0, nq, d, off, em, warps, o, cnt, st);
+                       });
+}
+
+int bx_deepoc_classes_config(bx_deepoc* e, int n_classes, int map_cap) {
+  if (!e || map_cap <= 0) return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_classes_config");
+  if (e->pc.cls) return bx_record_error(BX_ERR_INVALID, "the engine's class state already exists");
+  e->pc.map_cap = map_cap;
+  return cls_glue_get(e->pc, e->dev.o.S, e->dev.o.D, e->dev.F, n_classes, 1);
+}
+
+int bx_deepoc_classes(bx_deepoc* e, bx_classes** out) {
+  if (!e || !out) return bx_record_error(BX_ERR_INVALID, "null argument");
+  *out = e->pc.cls;
+  return BX_OK;
+}
+
+int bx_deepoc_update_classes_host(bx_deepoc* e, int seq, int n_classes, const float* dets, int n,
+                                  const double* embs, const double* warps, int* id_count,
+                                  double* out, int* n_out, void* stream) {
+  if (!e || seq < 0 || n < 0 || (n && (!dets || !out)) || !n_out || !id_count)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_update_classes_host");
+  if (n > e->dev.o.D) return bx_record_error(BX_ERR_CAPACITY, "detections exceed det_cap");
+  const size_t F = e->dev.F;
+  if (n && F && !embs)
+    return bx_record_error(BX_ERR_SHAPE, "DeepOCSort needs embeddings unless embedding_off");
+  int rc = cls_glue_get(e->pc, e->dev.o.S, e->dev.o.D, e->dev.F, n_classes, 1);
+  if (rc) return rc;
+  if ((seq + 1) * (long)n_classes > e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
+  hipStream_t st = (hipStream_t)stream;
+  if (n) {
+    memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
+    DCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
+    if (F) {
+      memcpy(e->p_embs, embs, sizeof(double) * F * n);
+      DCHK(hipMemcpyAsync(e->h_embs, e->p_embs, sizeof(double) * F * n, hipMemcpyHostToDevice, st));
+    }
+  }
+  if (warps) {
+    if (!e->h_cwarp) {
+      DCHK(hipMalloc(&e->h_cwarp, sizeof(double) * 6 * n_classes));
+      DCHK(hipHostMalloc(&e->p_cwarp, sizeof(double) * 6 * n_classes));
+    }
+    memcpy(e->p_cwarp, warps, sizeof(double) * 6 * n_classes);
+    DCHK(hipMemcpyAsync(e->h_cwarp, e->p_cwarp, sizeof(double) * 6 * n_classes,
+                        hipMemcpyHostToDevice, st));
+  }
+  e->p_cnt[2] = 0;
+  e->p_cnt[3] = n;
+  DCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
+  if ((rc = cls_glue_put_ids(e->pc, seq, *id_count, st))) return rc;
+  rc = bx_deepoc_step_classes(e, seq, 1, n_classes, e->h_dets, e->h_off, F ? e->h_embs : nullptr,
+                              warps ? e->h_cwarp : nullptr, e->h_out, e->h_cnt, st);
+  if (rc) return rc;
+  DCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+  DCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (n) DCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
+  int cstatus = 0;
+  if ((rc = cls_glue_take_ids(e->pc, seq, id_count, &cstatus, st))) return rc;  // synchronises
+  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
+  if (cnt > 0 && cnt <= n) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
+  *n_out = cnt > 0 && cnt <= n ? cnt : 0;
+  if (status == BX_ERR_CAPACITY || cstatus == BX_ERR_CAPACITY)
+    return bx_record_error(BX_ERR_CAPACITY, "a sequence's detections exceeded det_cap, or a "
+                                            "class's births its id map, on the device");
+  if (status)
+    return bx_record_error(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
+  if (cstatus) return bx_record_error(cstatus, "the class merge met an id the engine never gave out");
+  return BX_OK;
+}
+
 int bx_deepoc_status(bx_deepoc* e, int* status) {
   if (!e || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
   DCHK(hipMemcpy(status, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost));
-  return BX_OK;
+  return cls_glue_status(e->pc, status);
 }
 
 int bx_deepoc_counters_host(bx_deepoc* e, int seq, int* frame_count, int* id_count,

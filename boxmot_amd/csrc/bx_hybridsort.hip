@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/bxhybridsort.h"
+#include "bx_classes_glue.h"
 #include "bx_device.h"
 
 using namespace bx;
@@ -950,6 +951,11 @@ struct bx_hybrid {
   int* p_cnt = nullptr;
   int* p_sq = nullptr;
   int cache_seq = -1;
+  ClsGlue pc;  // per_class=True: the class state
+  // timing probe
+  int probe_stage = -1;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+  int ev_used = 0;
 };
 
 #define HCHK(x)                                                                    \
@@ -959,19 +965,45 @@ struct bx_hybrid {
       return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
   } while (0)
 
+// the timing probe of bx_deepocsort.hip: an event pair around the launch of the probed stage
+static int probe_begin(bx_hybrid* e, int stage, hipStream_t st) {
+  if (e->probe_stage != stage) return BX_OK;
+  if (e->ev_used == (int)e->ev.size()) {
+    hipEvent_t a, b;
+    HCHK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
+    HCHK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
+    e->ev.push_back({a, b});
+  }
+  HCHK(hipEventRecord(e->ev[e->ev_used].first, st));
+  return BX_OK;
+}
+
+static int probe_end(bx_hybrid* e, int stage, hipStream_t st) {
+  if (e->probe_stage != stage) return BX_OK;
+  HCHK(hipEventRecord(e->ev[e->ev_used++].second, st));
+  return BX_OK;
+}
+
 static int launch(bx_hybrid* e, int seq0, int nseq, const float* dets, const int* off,
                   const double* embs, double* out, int* cnt, hipStream_t st) {
   const HybDev& d = e->dev;
+  int rc;
   if (!embs) return bx_record_error(BX_ERR_SHAPE, "HybridSort needs embeddings");
+  if ((rc = probe_begin(e, 0, st))) return rc;
   hipLaunchKernelGGL(hyb_dist_kernel, dim3(nseq, ec_tiles(d.o.D, d.o.T), 2), dim3(256), 0, st, d,
                      seq0, off, embs);
   HCHK(hipGetLastError());
+  if ((rc = probe_end(e, 0, st))) return rc;
+  if ((rc = probe_begin(e, 1, st))) return rc;
   hipLaunchKernelGGL(hyb_frame_kernel, dim3(nseq), dim3(OW), e->lds, st, d, seq0, dets, off, out,
                      cnt);
   HCHK(hipGetLastError());
+  if ((rc = probe_end(e, 1, st))) return rc;
+  if ((rc = probe_begin(e, 2, st))) return rc;
   hipLaunchKernelGGL(hyb_feature_kernel, dim3((d.o.D + 3) / 4, nseq), dim3(256), 0, st, d, seq0,
                      off, embs);
   HCHK(hipGetLastError());
+  if ((rc = probe_end(e, 2, st))) return rc;
   return BX_OK;
 }
 
@@ -1142,11 +1174,15 @@ int bx_hybrid_copy_state(bx_hybrid* dst, bx_hybrid* src) {
   HCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
   dst->cache_seq = -1;
   HCHK(hipDeviceSynchronize());
-  return BX_OK;
+  return cls_glue_copy(dst->pc, src->pc, b.S, b.D, dst->dev.F, 1);
 }
 
 int bx_hybrid_destroy(bx_hybrid* e) {
   if (!e) return BX_OK;
+  for (auto& p : e->ev) {
+    (void)hipEventDestroy(p.first);
+    (void)hipEventDestroy(p.second);
+  }
   (void)hipFree(e->arena);
   (void)hipFree(e->h_dets);
   (void)hipFree(e->h_embs);
@@ -1158,6 +1194,7 @@ int bx_hybrid_destroy(bx_hybrid* e) {
   (void)hipHostFree(e->p_out);
   (void)hipHostFree(e->p_cnt);
   (void)hipHostFree(e->p_sq);
+  cls_glue_free(e->pc);
   delete e;
   return BX_OK;
 }
@@ -1170,7 +1207,7 @@ int bx_hybrid_reset(bx_hybrid* e, int seq0, int nseq, void* stream) {
   hipLaunchKernelGGL(hyb_reset_kernel, dim3((nseq * SQO + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, e->dev, seq0, nseq);
   HCHK(hipGetLastError());
-  return BX_OK;
+  return cls_glue_reset(e->pc, seq0, nseq, stream);
 }
 
 int bx_hybrid_step(bx_hybrid* e, int seq0, int nseq, const float* dets, const int32_t* det_off,
@@ -1218,10 +1255,104 @@ int bx_hybrid_update_host(bx_hybrid* e, int seq, const float* dets, int n, const
   return BX_OK;
 }
 
+int bx_hybrid_probe(bx_hybrid* e, int stage) {
+  if (!e || stage < -1 || stage > 2) return bx_record_error(BX_ERR_INVALID, "bad probe stage");
+  e->probe_stage = stage;
+  e->ev_used = 0;
+  return BX_OK;
+}
+
+int bx_hybrid_probe_read(bx_hybrid* e, double* total_ms, int* count) {
+  if (!e || !total_ms || !count) return bx_record_error(BX_ERR_INVALID, "null argument");
+  double s = 0.0;
+  for (int k = 0; k < e->ev_used; k++) {
+    HCHK(hipEventSynchronize(e->ev[k].second));
+    float ms = 0.f;
+    HCHK(hipEventElapsedTime(&ms, e->ev[k].first, e->ev[k].second));
+    s += ms;
+  }
+  *total_ms = s;
+  *count = e->ev_used;
+  e->ev_used = 0;
+  return BX_OK;
+}
+
+// per_class=True (include/bxclasses.h): class c of sequence s is engine sequence s * C + c; the
+// frame is split -> the three launches over the class sequences -> merge, all on `stream`.
+int bx_hybrid_step_classes(bx_hybrid* e, int seq0, int nseq, int n_classes, const float* dets,
+                           const int32_t* det_off, const double* embs, double* out,
+                           int32_t* out_count, void* stream) {
+  if (!e) return bx_record_error(BX_ERR_INVALID, "null engine");
+  if (!embs) return bx_record_error(BX_ERR_SHAPE, "HybridSort needs embeddings");
+  e->cache_seq = -1;
+  hipStream_t st = (hipStream_t)stream;
+  return cls_glue_step(e->pc, e->dev.o.S, e->dev.o.D, e->dev.F, 1, e->dev.o.seqst + SO_IDS, SQO,
+                       seq0, nseq, n_classes, dets, det_off, embs, out, out_count, st,
+                       [&](int q0, int nq, const float* d, const int* off, const double* em,
+                           double* o, int* cnt) {
+                         return launch(e, q0, nq, d, off, em, o, cnt, st);
+                       });
+}
+
+int bx_hybrid_classes_config(bx_hybrid* e, int n_classes, int map_cap) {
+  if (!e || map_cap <= 0) return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_classes_config");
+  if (e->pc.cls) return bx_record_error(BX_ERR_INVALID, "the engine's class state already exists");
+  e->pc.map_cap = map_cap;
+  return cls_glue_get(e->pc, e->dev.o.S, e->dev.o.D, e->dev.F, n_classes, 1);
+}
+
+int bx_hybrid_classes(bx_hybrid* e, bx_classes** out) {
+  if (!e || !out) return bx_record_error(BX_ERR_INVALID, "null argument");
+  *out = e->pc.cls;
+  return BX_OK;
+}
+
+int bx_hybrid_update_classes_host(bx_hybrid* e, int seq, int n_classes, const float* dets, int n,
+                                  const double* embs, int* id_count, double* out, int* n_out,
+                                  void* stream) {
+  if (!e || seq < 0 || n < 0 || (n && (!dets || !out)) || !n_out || !id_count)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_update_classes_host");
+  if (n > e->dev.o.D) return bx_record_error(BX_ERR_CAPACITY, "detections exceed det_cap");
+  const size_t F = e->dev.F;
+  if (n && !embs) return bx_record_error(BX_ERR_SHAPE, "HybridSort needs embeddings");
+  int rc = cls_glue_get(e->pc, e->dev.o.S, e->dev.o.D, e->dev.F, n_classes, 1);
+  if (rc) return rc;
+  if ((seq + 1) * (long)n_classes > e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
+  hipStream_t st = (hipStream_t)stream;
+  if (n) {
+    memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
+    HCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
+    memcpy(e->p_embs, embs, sizeof(double) * F * n);
+    HCHK(hipMemcpyAsync(e->h_embs, e->p_embs, sizeof(double) * F * n, hipMemcpyHostToDevice, st));
+  }
+  e->p_cnt[2] = 0;
+  e->p_cnt[3] = n;
+  HCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
+  if ((rc = cls_glue_put_ids(e->pc, seq, *id_count, st))) return rc;
+  rc = bx_hybrid_step_classes(e, seq, 1, n_classes, e->h_dets, e->h_off, e->h_embs, e->h_out,
+                              e->h_cnt, st);
+  if (rc) return rc;
+  HCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+  HCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (n) HCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
+  int cstatus = 0;
+  if ((rc = cls_glue_take_ids(e->pc, seq, id_count, &cstatus, st))) return rc;  // synchronises
+  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
+  if (cnt > 0 && cnt <= n) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
+  *n_out = cnt > 0 && cnt <= n ? cnt : 0;
+  if (status == BX_ERR_CAPACITY || cstatus == BX_ERR_CAPACITY)
+    return bx_record_error(BX_ERR_CAPACITY, "a sequence's detections exceeded det_cap, or a "
+                                            "class's births its id map, on the device");
+  if (status)
+    return bx_record_error(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
+  if (cstatus) return bx_record_error(cstatus, "the class merge met an id the engine never gave out");
+  return BX_OK;
+}
+
 int bx_hybrid_status(bx_hybrid* e, int* status) {
   if (!e || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
   HCHK(hipMemcpy(status, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost));
-  return BX_OK;
+  return cls_glue_status(e->pc, status);
 }
 
 int bx_hybrid_counters_host(bx_hybrid* e, int seq, int* frame_count, int* id_count,

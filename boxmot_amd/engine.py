@@ -529,9 +529,12 @@ class DeepOcsortEngine:
     def slots_used(self, seq: int = 0) -> int:
         return self.counters(seq)["n_tracks"]
 
-    def grown(self, track_cap: int, det_cap: int) -> "DeepOcsortEngine":
-        """A new engine with larger capacities holding this one's state (bx_deepoc_copy_state)."""
+    def grown(self, track_cap: int, det_cap: int, map_cap: int | None = None) -> "DeepOcsortEngine":
+        """A new engine with larger capacities holding this one's state (bx_deepoc_copy_state);
+        map_cap: a larger per-class id map (per_class=True engines)."""
         e = DeepOcsortEngine(self.n_seq, track_cap, det_cap, self.emb_dim or 1, self.params)
+        if map_cap is not None:
+            e.classes_config(self.classes().n_classes, map_cap)
         N.check(self._L.bx_deepoc_copy_state(e._h, self._h), "bx_deepoc_copy_state")
         return e
 
@@ -580,6 +583,55 @@ class DeepOcsortEngine:
             self._h, seq, d.ctypes.data if n else None, n, _p(e), _p(w), out.ctypes.data,
             C.byref(m), None), "bx_deepoc_update_host")
         return out[: m.value].copy()
+
+    def step_classes(self, dets, det_off, embs, warps, out, out_count, n_classes: int,
+                     seq0: int = 0, nseq: int | None = None, stream=None):
+        """One per_class=True frame for sequences [seq0, seq0+nseq) of ``n_classes`` classes, on
+        an engine built with ``n_seq = S * n_classes`` (see bx_deepoc_step_classes): ``step``'s
+        arguments per sequence, warps [nseq * n_classes, 6] or None; class split, the three
+        launches over the class sequences and the id merge run on one stream."""
+        nseq = self.n_seq // int(n_classes) - seq0 if nseq is None else nseq
+        if stream is None:
+            stream = _current_stream()
+        N.check(self._L.bx_deepoc_step_classes(
+            self._h, seq0, nseq, int(n_classes), _ptr(dets), _ptr(det_off), _ptr(embs),
+            _ptr(warps), _ptr(out), _ptr(out_count), stream), "bx_deepoc_step_classes")
+
+    def classes_config(self, n_classes: int, map_cap: int) -> None:
+        """Build the class state ahead of the first per-class call with an id map of ``map_cap``
+        births per class sequence."""
+        N.check(self._L.bx_deepoc_classes_config(self._h, int(n_classes), int(map_cap)),
+                "bx_deepoc_classes_config")
+
+    def classes(self):
+        """The engine's class state as a ClassSplit view (None before the first per-class call)."""
+        h = C.c_void_p()
+        N.check(self._L.bx_deepoc_classes(self._h, C.byref(h)), "bx_deepoc_classes")
+        return ClassSplit._view(h, self) if h.value else None
+
+    def update_classes_host(self, seq: int, n_classes: int, dets: np.ndarray,
+                            embs: np.ndarray | None, id_count: int,
+                            warps: np.ndarray | None = None):
+        """per_class=True frame of sequence ``seq`` from host arrays
+        (bx_deepoc_update_classes_host): returns (rows in class order with class-global ids, the
+        advanced class-level id counter).  warps: [n_classes, 2, 3] or None."""
+        d = np.ascontiguousarray(dets, dtype=np.float32).reshape(-1, 6)
+        n = d.shape[0]
+        e = None
+        if self.emb_dim and n:
+            if embs is None:
+                raise ValueError("DeepOCSort needs embeddings unless embedding_off")
+            e = np.ascontiguousarray(embs, dtype=np.float64).reshape(n, -1)
+            if e.shape[1] != self.emb_dim:
+                raise ValueError(f"embedding dim {e.shape[1]} != engine emb_dim {self.emb_dim}")
+        w = None if warps is None else np.ascontiguousarray(warps, np.float64).reshape(
+            int(n_classes) * 6)
+        out = np.empty((max(n, 1), 8), np.float64)
+        m, g = C.c_int(0), C.c_int(int(id_count))
+        N.check(self._L.bx_deepoc_update_classes_host(
+            self._h, seq, int(n_classes), d.ctypes.data if n else None, n, _p(e), _p(w),
+            C.byref(g), out.ctypes.data, C.byref(m), None), "bx_deepoc_update_classes_host")
+        return out[: m.value].copy(), g.value
 
     def status(self) -> int:
         s = C.c_int(0)
@@ -679,6 +731,8 @@ class HybridsortEngine:
     HBM; per frame the two cosine-distance contractions (fp64 MFMA), the frame kernel (one wave
     per sequence) and the feature update.  Embeddings are float64, ``emb_dim`` wide."""
 
+    STAGES = ["dist", "frame", "feature"]
+
     def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
                  emb_dim: int = 512, params: HybridsortParams | None = None):
         p = params or HybridsortParams()
@@ -699,9 +753,12 @@ class HybridsortEngine:
     def slots_used(self, seq: int = 0) -> int:
         return self.counters(seq)["n_tracks"]
 
-    def grown(self, track_cap: int, det_cap: int) -> "HybridsortEngine":
-        """A new engine with larger capacities holding this one's state (bx_hybrid_copy_state)."""
+    def grown(self, track_cap: int, det_cap: int, map_cap: int | None = None) -> "HybridsortEngine":
+        """A new engine with larger capacities holding this one's state (bx_hybrid_copy_state);
+        map_cap: a larger per-class id map (per_class=True engines)."""
         e = HybridsortEngine(self.n_seq, track_cap, det_cap, self.emb_dim, self.params)
+        if map_cap is not None:
+            e.classes_config(self.classes().n_classes, map_cap)
         N.check(self._L.bx_hybrid_copy_state(e._h, self._h), "bx_hybrid_copy_state")
         return e
 
@@ -748,6 +805,52 @@ class HybridsortEngine:
             None), "bx_hybrid_update_host")
         return out[: m.value].copy()
 
+    def step_classes(self, dets, det_off, embs, out, out_count, n_classes: int, seq0: int = 0,
+                     nseq: int | None = None, stream=None):
+        """One per_class=True frame for sequences [seq0, seq0+nseq) of ``n_classes`` classes, on
+        an engine built with ``n_seq = S * n_classes`` (see bx_hybrid_step_classes): ``step``'s
+        arguments per sequence; class split, the three launches over the class sequences and the
+        id merge run on one stream."""
+        nseq = self.n_seq // int(n_classes) - seq0 if nseq is None else nseq
+        if stream is None:
+            stream = _current_stream()
+        N.check(self._L.bx_hybrid_step_classes(
+            self._h, seq0, nseq, int(n_classes), _ptr(dets), _ptr(det_off), _ptr(embs), _ptr(out),
+            _ptr(out_count), stream), "bx_hybrid_step_classes")
+
+    def classes_config(self, n_classes: int, map_cap: int) -> None:
+        """Build the class state ahead of the first per-class call with an id map of ``map_cap``
+        births per class sequence."""
+        N.check(self._L.bx_hybrid_classes_config(self._h, int(n_classes), int(map_cap)),
+                "bx_hybrid_classes_config")
+
+    def classes(self):
+        """The engine's class state as a ClassSplit view (None before the first per-class call)."""
+        h = C.c_void_p()
+        N.check(self._L.bx_hybrid_classes(self._h, C.byref(h)), "bx_hybrid_classes")
+        return ClassSplit._view(h, self) if h.value else None
+
+    def update_classes_host(self, seq: int, n_classes: int, dets: np.ndarray,
+                            embs: np.ndarray | None, id_count: int):
+        """per_class=True frame of sequence ``seq`` from host arrays
+        (bx_hybrid_update_classes_host): returns (rows in class order with class-global ids, the
+        advanced class-level id counter)."""
+        d = np.ascontiguousarray(dets, dtype=np.float32).reshape(-1, 6)
+        n = d.shape[0]
+        e = None
+        if n:
+            if embs is None:
+                raise ValueError("HybridSort needs embeddings")
+            e = np.ascontiguousarray(embs, dtype=np.float64).reshape(n, -1)
+            if e.shape[1] != self.emb_dim:
+                raise ValueError(f"embedding dim {e.shape[1]} != engine emb_dim {self.emb_dim}")
+        out = np.empty((max(n, 1), 8), np.float64)
+        m, g = C.c_int(0), C.c_int(int(id_count))
+        N.check(self._L.bx_hybrid_update_classes_host(
+            self._h, seq, int(n_classes), d.ctypes.data if n else None, n, _p(e), C.byref(g),
+            out.ctypes.data, C.byref(m), None), "bx_hybrid_update_classes_host")
+        return out[: m.value].copy(), g.value
+
     def status(self) -> int:
         s = C.c_int(0)
         N.check(self._L.bx_hybrid_status(self._h, C.byref(s)), "bx_hybrid_status")
@@ -793,6 +896,22 @@ class HybridsortEngine:
         N.check(self._L.bx_hybrid_state_set_host(self._h, seq, n, ids.ctypes.data, _p(a), _p(b)),
                 "state_set")
 
+    def frame_stats(self, seq0: int = 0, nseq: int | None = None) -> dict:
+        """Live tracks over sequences [seq0, seq0+nseq) after the last frame."""
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        return {"tracks": sum(self.counters(q)["n_tracks"] for q in range(seq0, seq0 + nseq))}
+
+    def probe(self, stage) -> None:
+        """Time one stage per step (name from STAGES or index); None = off."""
+        idx = -1 if stage is None else (self.STAGES.index(stage) if isinstance(stage, str)
+                                        else int(stage))
+        N.check(self._L.bx_hybrid_probe(self._h, idx), "bx_hybrid_probe")
+
+    def probe_read(self):
+        t, n = C.c_double(), C.c_int()
+        N.check(self._L.bx_hybrid_probe_read(self._h, C.byref(t), C.byref(n)), "probe_read")
+        return t.value, n.value
+
     def state_save(self, seq: int = 0) -> np.ndarray:
         """One sequence's whole tracker state as an opaque byte array (bx_hybrid_state_save_host)."""
         nb = C.c_size_t()
@@ -828,6 +947,92 @@ def hybrid_bank_mean(bank, pushed, out, stream=None) -> None:
         stream = _current_stream()
     N.check(N.load().bx_hybrid_bank_mean(int(nt), int(F), _ptr(bank), _ptr(pushed), _ptr(out),
                                          stream), "bx_hybrid_bank_mean")
+
+
+class ClassSplit:
+    """Handle over ``bx_classes_*`` (include/bxclasses.h): per_class=True on the device for
+    ``n_seq`` sequences of ``n_classes`` classes — the stable class split of a frame's rows and the
+    merge of the class sequences' output rows under class-global ids.  The engines'
+    ``step_classes`` own one; built directly it drives the two kernels alone."""
+
+    def __init__(self, n_seq: int, n_classes: int, emb_dim: int = 0, row_cap: int = 256,
+                 map_cap: int = 4096, id0: int = 1):
+        self._L = N.load()
+        h = C.c_void_p()
+        N.check(self._L.bx_classes_create(int(n_seq), int(n_classes), int(emb_dim), int(row_cap),
+                                          int(map_cap), int(id0), C.byref(h)), "bx_classes_create")
+        self._h, self._owner = h, None
+        self.n_seq, self.n_classes, self.emb_dim = int(n_seq), int(n_classes), int(emb_dim)
+        self.row_cap, self.map_cap, self.id0 = int(row_cap), int(map_cap), int(id0)
+
+    @classmethod
+    def _view(cls, handle, owner) -> "ClassSplit":
+        v = cls.__new__(cls)
+        v._L, v._h, v._owner = N.load(), handle, owner  # (the owner keeps the state alive)
+        a = [C.c_int() for _ in range(6)]
+        N.check(v._L.bx_classes_shape(handle, *[C.byref(x) for x in a]), "bx_classes_shape")
+        v.n_seq, v.n_classes, v.emb_dim, v.row_cap, v.map_cap, v.id0 = [x.value for x in a]
+        return v
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h and self._owner is None:
+            self._L.bx_classes_destroy(h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def split(self, dets, det_off, embs, o_dets, o_embs, o_off, o_src, nseq: int | None = None,
+              stream=None) -> None:
+        """Device tensors: dets [n, 6] float32, det_off [nseq + 1], embs [n, emb_dim] float64 or
+        None -> class-major o_dets / o_embs, o_off [nseq * n_classes + 1], o_src [n]."""
+        nseq = self.n_seq if nseq is None else nseq
+        if stream is None:
+            stream = _current_stream()
+        N.check(self._L.bx_classes_split(self._h, int(nseq), _ptr(dets), _ptr(det_off), _ptr(embs),
+                                         _ptr(o_dets), _ptr(o_embs), _ptr(o_off), _ptr(o_src),
+                                         stream), "bx_classes_split")
+
+    def merge(self, c_off, c_out, c_cnt, ids, det_off, out, out_count, seq0: int = 0,
+              nseq: int | None = None, ids_stride: int = 1, stream=None) -> None:
+        """Device tensors: the class sequences' det_off / out / out_count of one step and their
+        next-id counters ``ids`` (absolute engine sequence q at ids[q * ids_stride]) -> the
+        sequences' rows from out[det_off[k]] and out_count [nseq]."""
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        if stream is None:
+            stream = _current_stream()
+        N.check(self._L.bx_classes_merge(self._h, int(seq0), int(nseq), _ptr(c_off), _ptr(c_out),
+                                         _ptr(c_cnt), _ptr(ids), int(ids_stride), _ptr(det_off),
+                                         _ptr(out), _ptr(out_count), stream), "bx_classes_merge")
+
+    def reset(self, seq0: int = 0, nseq: int | None = None, stream=None) -> None:
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        N.check(self._L.bx_classes_reset(self._h, seq0, nseq, stream), "bx_classes_reset")
+
+    def status(self) -> int:
+        s = C.c_int(0)
+        N.check(self._L.bx_classes_status(self._h, C.byref(s)), "bx_classes_status")
+        return s.value
+
+    def id_count(self, seq: int = 0) -> int:
+        g = C.c_int(0)
+        N.check(self._L.bx_classes_id_count_host(self._h, seq, C.byref(g)), "id_count")
+        return g.value
+
+    def set_id_count(self, seq: int, value: int) -> None:
+        N.check(self._L.bx_classes_set_id_count(self._h, seq, int(value), None), "set_id_count")
+
+    def id_map(self, seq: int, cls: int) -> np.ndarray:
+        """Class-global ids of the local ids id0, id0 + 1, ... class ``cls`` of ``seq`` gave out."""
+        m = np.zeros(self.map_cap, np.int32)
+        n = C.c_int(0)
+        N.check(self._L.bx_classes_map_host(self._h, seq, cls, self.map_cap, m.ctypes.data,
+                                            C.byref(n)), "bx_classes_map_host")
+        return m[: n.value].copy()
 
 
 class SequenceFeeder:

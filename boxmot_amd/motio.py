@@ -13,7 +13,7 @@ Reference path replaced (muntherr/boxmot @ /root/reference):
   * the process pool of ``engine/val.py:357-405`` (one tracker per sequence per process):
     ``run_sequences`` drives ALL sequences through one batched engine handle, frame index by
     frame index; a sequence without detections at a frame is not updated (``val.py:347``).
-    With ``resident=True`` (DeepOcSort) the per-frame assembly and the row formatting run on the
+    With ``resident=True`` (DeepOcSort, HybridSort) the per-frame assembly and the row formatting run on the
     device too (``include/bxfeed.h``): one upload, one copy back.
 
 Everything else here is host code in libbxassoc.so; the trackers run on the MI355X engine.
@@ -130,21 +130,47 @@ def write_mot_results(txt_path, mot_results: np.ndarray | None) -> None:
 
 
 # ------------------------------------------------------------------------------ the runner
-def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs: dict):
+def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs: dict,
+                    n_classes: int = 0):
     """One engine handle for n_seq sequences, parameterised exactly as the drop-in tracker
-    `tracker_type` is by `tracker_kwargs` (create_tracker's YAML defaults when empty)."""
+    `tracker_type` is by `tracker_kwargs` (create_tracker's YAML defaults when empty).
+    n_classes > 0 (deepocsort, hybridsort): the per_class mode, n_classes class sequences per
+    sequence (step_classes)."""
+    if n_classes and tracker_type not in ("deepocsort", "hybridsort"):
+        raise NotImplementedError(
+            f"run_sequences(n_classes=...) is the per_class mode of deepocsort and hybridsort; "
+            f"for {tracker_type} pass per_class in tracker_kwargs")
     if tracker_type == "deepocsort":
         # not in create_tracker's table and without a YAML: the drop-in's constructor (its
-        # defaults with empty tracker_kwargs) decides the parameters; per_class raises there
+        # defaults with empty tracker_kwargs) decides the parameters; per_class in tracker_kwargs
+        # raises there, the mode is asked for with n_classes
         from .engine import DeepOcsortEngine
-        from .trackers.deepocsort import DeepOcSort
+        from .trackers.deepocsort import DeepOcSort, DeepOcSortPerClass
 
-        tr = DeepOcSort(**tracker_kwargs)
+        tr = DeepOcSortPerClass(nr_classes=n_classes, **tracker_kwargs) if n_classes \
+            else DeepOcSort(**tracker_kwargs)
         if tr.engine is not None:  # (embedding_off builds the drop-in's own engine at once)
             tr.engine.close()
         tc, dc = tr._caps
-        return DeepOcsortEngine(n_seq=n_seq, track_cap=tc, det_cap=dc, emb_dim=emb_dim,
-                                params=tr._params), np.float32, 8
+        eng = DeepOcsortEngine(n_seq=n_seq * (tr.nr_classes if tr.per_class else 1), track_cap=tc,
+                               det_cap=dc, emb_dim=emb_dim, params=tr._params)
+        eng.n_classes = tr.nr_classes if tr.per_class else 0
+        return eng, np.float32, 8
+    if tracker_type == "hybridsort":
+        # as deepocsort; det_thresh has no default in the reference's constructor: the drop-in's
+        # engine parameters' 0.3 stands in when tracker_kwargs leaves it out
+        from .engine import HybridsortEngine, HybridsortParams
+        from .trackers.hybridsort import HybridSort, HybridSortPerClass
+
+        kw = dict(reid_weights=None, device=None, half=False,
+                  det_thresh=HybridsortParams().det_thresh)
+        kw.update(tracker_kwargs)
+        tr = HybridSortPerClass(nr_classes=n_classes, **kw) if n_classes else HybridSort(**kw)
+        tc, dc = tr._caps
+        eng = HybridsortEngine(n_seq=n_seq * (tr.nr_classes if tr.per_class else 1), track_cap=tc,
+                               det_cap=dc, emb_dim=emb_dim, params=tr._params)
+        eng.n_classes = tr.nr_classes if tr.per_class else 0
+        return eng, np.float32, 8
     from .engine import BoostEngine, Engine, OcsortEngine, SsEngine
     from .tracker_zoo import create_tracker
 
@@ -177,10 +203,25 @@ def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs:
     raise NotImplementedError(f"{tracker_type} is not on the engine")
 
 
-RESIDENT_TRACKERS = ("deepocsort",)  # trackers run_sequences(resident=True) can drive
+RESIDENT_TRACKERS = ("deepocsort", "hybridsort")  # trackers run_sequences(resident=True) drives
 
 
-def _resident_results(eng, seqs, fids, F: int, ddt) -> list:
+def _step(eng, tracker_type: str, dets, det_off, embs, out, out_count, seq0: int, nseq: int):
+    """One frame of sequences [seq0, seq0 + nseq) on a DeepOcsortEngine / HybridsortEngine:
+    ``step``, or ``step_classes`` on a per_class engine (HybridsortEngine.step takes no warps)."""
+    C = getattr(eng, "n_classes", 0)
+    if tracker_type == "hybridsort":
+        if C:
+            eng.step_classes(dets, det_off, embs, out, out_count, C, seq0=seq0, nseq=nseq)
+        else:
+            eng.step(dets, det_off, embs, out, out_count, seq0=seq0, nseq=nseq)
+    elif C:
+        eng.step_classes(dets, det_off, embs, None, out, out_count, C, seq0=seq0, nseq=nseq)
+    else:
+        eng.step(dets, det_off, embs, None, out, out_count, seq0=seq0, nseq=nseq)
+
+
+def _resident_results(eng, tracker_type: str, seqs, fids, F: int, ddt) -> list:
     """The frame loop of run_sequences with the sequences resident in HBM (engine.SequenceFeeder):
     one upload, per frame index one gather launch, the steps of its runs and one append launch,
     one copy back.  Returns each sequence's MOT rows [n, 9]."""
@@ -208,7 +249,7 @@ def _resident_results(eng, seqs, fids, F: int, ddt) -> list:
                 continue
             feed.gather(t)
             for k, ns, _, pd, po, pe, pout, pcnt in runs:
-                eng.step(pd, po, pe, None, pout, pcnt, seq0=k, nseq=ns)
+                _step(eng, tracker_type, pd, po, pe, pout, pcnt, k, ns)
             feed.append(t)
         if eng.status() != 0:
             raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
@@ -220,7 +261,7 @@ def _resident_results(eng, seqs, fids, F: int, ddt) -> list:
 def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict | None = None,
                   frame_sizes: dict | None = None, tracker_kwargs: dict | None = None,
                   gsi: bool = False, gsi_interval: int = 20, gsi_tau: float = 10,
-                  resident: bool = False) -> dict:
+                  resident: bool = False, n_classes: int = 0) -> dict:
     """process_sequence (val.py:304-354) for every sequence at once.
 
     sequences: name -> packed file (pack_sequence) or BinSequence; frame_ids: name -> the frames
@@ -232,6 +273,10 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
     resident: keep the sequences' detections and embeddings and the result rows in device memory
     for the whole run (include/bxfeed.h) instead of assembling every frame on the host; the files
     are byte-identical.  Only for the trackers in RESIDENT_TRACKERS.
+    n_classes: > 0 runs deepocsort / hybridsort in their per_class mode over classes
+    0..n_classes-1 (DeepOcSortPerClass / HybridSortPerClass per sequence; ``per_class`` in
+    tracker_kwargs raises for these two, as their plain constructors do), with the class split and
+    the id merge on the device, resident or not.
     """
     if resident and tracker_type not in RESIDENT_TRACKERS:
         raise NotImplementedError(
@@ -243,20 +288,23 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
     seqs = [s if isinstance(s, BinSequence) else BinSequence(s) for s in sequences.values()]
     S = len(seqs)
     F = max([s.emb_dim for s in seqs] + [0])
-    eng, ddt, ncol = _batched_engine(tracker_type, S, F, tracker_kwargs or {})
+    eng, ddt, ncol = _batched_engine(tracker_type, S, F, tracker_kwargs or {}, n_classes) \
+        if n_classes else _batched_engine(tracker_type, S, F, tracker_kwargs or {})
     if tracker_type == "ocsort" and frame_sizes:
         for k, nm in enumerate(names):
             if nm in frame_sizes:
                 eng.set_frame_size(k, *frame_sizes[nm])
     fids = [np.asarray(frame_ids[nm]) if frame_ids and nm in frame_ids else s.frame_ids
             for nm, s in zip(names, seqs)]
-    if tracker_type == "deepocsort" and frame_sizes:
+    if tracker_type in ("deepocsort", "hybridsort") and frame_sizes:
+        C = getattr(eng, "n_classes", 0) or 1  # (per_class: every class sequence of the sequence)
         for k, nm in enumerate(names):
             if nm in frame_sizes:
-                eng.set_frame_size(k, *frame_sizes[nm])
+                for q in range(k * C, (k + 1) * C):
+                    eng.set_frame_size(q, *frame_sizes[nm])
     if resident:
         exp_dir = Path(exp_dir)
-        for nm, res in zip(names, _resident_results(eng, seqs, fids, F, ddt)):
+        for nm, res in zip(names, _resident_results(eng, tracker_type, seqs, fids, F, ddt)):
             write_mot_results(exp_dir / f"{nm}.txt", res if res.size else np.empty((0, 0)))
         if gsi:
             from . import postprocessing
@@ -296,6 +344,12 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
             cnt = torch.empty(k1 - k, dtype=torch.int32, device=dev)
             if tracker_type == "ocsort":
                 eng.step(dd, od, out, cnt, seq0=k, nseq=k1 - k)
+            elif tracker_type in ("deepocsort", "hybridsort"):
+                emb = None
+                if F and eng.emb_dim:
+                    emb = torch.from_numpy(np.concatenate([frame[q][1] for q in range(k, k1)])
+                                           .astype(np.float64)).to(dev)
+                _step(eng, tracker_type, dd, od, emb, out, cnt, k, k1 - k)
             else:
                 emb = None
                 if F and getattr(eng, "with_reid", True) and not (

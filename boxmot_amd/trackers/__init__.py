@@ -1,10 +1,10 @@
 from .boosttrack import BoostTrack
 from .botsort import BotSort
 from .bytetrack import ByteTrack
-from .deepocsort import DeepOcSort
-from .hybridsort import HybridSort
+from .deepocsort import DeepOcSort, DeepOcSortPerClass
+from .hybridsort import HybridSort, HybridSortPerClass
 from .ocsort import OcSort
 from .strongsort import StrongSort
 
 __all__ = ["ByteTrack", "BotSort", "OcSort", "BoostTrack", "StrongSort", "DeepOcSort",
-           "HybridSort"]
+           "HybridSort", "DeepOcSortPerClass", "HybridSortPerClass"]

@@ -79,6 +79,35 @@ class CapacityGuard:
         return eng
 
 
+class ClassMapGuard:
+    """per_class=True on DeepOcSort / HybridSort: every class sequence's device map from engine id
+    to class-global id holds ``cap`` births (include/bxclasses.h).  Like CapacityGuard, before a
+    frame the drop-in checks that the births so far plus the frame's detections fit (an upper
+    bound, re-read from the engine only when it reaches the capacity) and otherwise moves the
+    state into an engine with a map twice as large."""
+
+    def __init__(self, cap: int = 4096):
+        self.cap, self.ub = int(cap), 0
+
+    def fit(self, eng, n_classes: int, n_frame: int):
+        if self.ub + n_frame > self.cap:
+            self.ub = max(eng.counters(c)["id_count"] for c in range(n_classes)) - 1
+            if self.ub + n_frame > self.cap:
+                while self.ub + n_frame > self.cap:
+                    self.cap *= 2
+                eng = eng.grown(eng.track_cap, eng.det_cap, map_cap=self.cap)
+        self.ub += n_frame
+        return eng
+
+    @staticmethod
+    def class_counts(dets, nr_classes: int) -> dict:
+        """Detections per class as the device split keeps them: {class: count > 0}."""
+        cls = np.asarray(dets).reshape(-1, 6)[:, 5].astype(np.float32)
+        ok = (cls >= 0) & (cls < nr_classes) & (cls == np.floor(cls))
+        per = np.bincount(cls[ok].astype(np.int64), minlength=nr_classes)
+        return {c: int(k) for c, k in enumerate(per) if k}
+
+
 class TrackView:
     """Read-only host view of one engine track (what ``active_tracks`` entries expose)."""
 

@@ -18,7 +18,14 @@ Embeddings are float64 on the engine: ``embs`` is converted with ``np.asarray(em
 np.float64)``.  With float32 ``embs`` the reference runs in mixed width — a newborn track keeps
 its float32 row, so ``dets_embs @ trk_embs.T`` is a single-precision product until a track's
 first update and double precision afterwards.  That is not reproduced: here the product is
-always double precision over the converted values.  ``per_class=True`` is not supported yet.
+always double precision over the converted values.
+
+``DeepOcSort(per_class=True)`` still raises NotImplementedError; the mode is the subclass
+``DeepOcSortPerClass`` (basetracker.py:155-201): class c is engine sequence c, all classes share the
+frame counter and the class-level id counter; the class split of the frame's rows and the merge
+of the classes' rows under class-global ids run on the device around the same three launches
+(``DeepOcsortEngine.update_classes_host``, include/bxclasses.h).  The CMC is asked once per class
+id with that class's boxes over ``det_thresh``, as the reference's class calls do.
 """
 from __future__ import annotations
 
@@ -26,11 +33,12 @@ import numpy as np
 
 from ..engine import DeepOcsortEngine, DeepOcsortParams
 from ..iou import KINDS
-from .basetracker import BaseTracker, CapacityGuard
+from .basetracker import BaseTracker, CapacityGuard, ClassMapGuard
 from .botsort import IdentityCMC
 
 
 class DeepOcSort(BaseTracker):
+    _PER_CLASS = False  # DeepOcSortPerClass: the per_class mode is built
     # KalmanBoxTracker.count is a class attribute shared by every instance and set to 1 by each
     # DeepOcSort constructor (deepocsort.py:56,117-118,305): mirrored here.
     _id_count = 1
@@ -43,11 +51,14 @@ class DeepOcSort(BaseTracker):
                  embedding_off: bool = False, cmc_off: bool = False, aw_off: bool = False,
                  Q_xy_scaling: float = 0.01, Q_s_scaling: float = 0.0001,
                  track_cap: int = 256, det_cap: int = 256, **kwargs):
-        if per_class:
+        if per_class and not self._PER_CLASS:
             raise NotImplementedError(
-                "DeepOcSort(per_class=True) is not on the MI355X association engine yet: run one "
-                "DeepOcSort per class, or use OcSort(per_class=True) without the appearance term")
+                "DeepOcSort(per_class=True) is not wired up: the per_class mode on the MI355X "
+                "engine is the class DeepOcSortPerClass")
         super().__init__(max_age=max_age, per_class=per_class, asso_func=asso_func)
+        # (DeepOcSortPerClass sets _nr_classes before this constructor runs: the engine below, one
+        # sequence per class, may be built here)
+        self.nr_classes = int(getattr(self, "_nr_classes", self.nr_classes))
         self.max_age = max_age
         self.min_hits = min_hits
         self.iou_threshold = iou_threshold
@@ -73,6 +84,7 @@ class DeepOcSort(BaseTracker):
             Q_xy_scaling=Q_xy_scaling, Q_s_scaling=Q_s_scaling)
         self._caps = (track_cap, det_cap)
         self._cap = CapacityGuard()
+        self._map = ClassMapGuard()
         self._engine_ids = 1
         self._frame_latched = False
         # the embedding width is learnt from the first frame that has detections; empty frames
@@ -81,7 +93,7 @@ class DeepOcSort(BaseTracker):
         self._empty_before_engine = 0
 
     def _make_engine(self, emb_dim: int) -> DeepOcsortEngine:
-        return DeepOcsortEngine(n_seq=1, track_cap=self._caps[0], det_cap=self._caps[1],
+        return DeepOcsortEngine(n_seq=self.nr_classes if self.per_class else 1, track_cap=self._caps[0], det_cap=self._caps[1],
                                 emb_dim=emb_dim, params=self._params)
 
     @BaseTracker.setup_decorator
@@ -103,17 +115,25 @@ class DeepOcSort(BaseTracker):
                 self.frame_count += 1
                 self._empty_before_engine += 1
                 if not self.cmc_off:
-                    self.cmc.apply(img, np.empty((0, 4)))
-                return np.array([])
+                    for _ in range(self.nr_classes if self.per_class else 1):  # one per class call
+                        self.cmc.apply(img, np.empty((0, 4)))
+                return np.empty((0, 8)) if self.per_class else np.array([])
             self.engine = self._make_engine(e.shape[1])
             for _ in range(self._empty_before_engine):
-                self.engine.update_host(0, np.empty((0, 6), np.float32))
+                if self.per_class:
+                    self.engine.update_classes_host(0, self.nr_classes, np.empty((0, 6), np.float32),
+                                                    None, DeepOcSort._id_count)
+                else:
+                    self.engine.update_host(0, np.empty((0, 6), np.float32))
             self._empty_before_engine = 0
         if not self._frame_latched and self._first_frame_processed:
             # the engine's centroid frame size follows BaseTracker's first-frame latch
-            self.engine.set_frame_size(0, self.w, self.h)
+            for q in range(self.engine.n_seq):
+                self.engine.set_frame_size(q, self.w, self.h)
             self._frame_latched = True
         self.frame_count += 1
+        if self.per_class:
+            return self._update_classes(dets, img, e, n)
         self.engine = self._cap.fit(self.engine, {0: n}, n)
         warp = None
         if not self.cmc_off:
@@ -128,13 +148,60 @@ class DeepOcSort(BaseTracker):
         self._engine_ids = DeepOcSort._id_count = self.engine.counters(0)["id_count"]
         return out if out.shape[0] else np.array([])
 
+    def _update_classes(self, dets, img, e, n):
+        """The per_class=True frame: class c runs as engine sequence c (its births are at most its
+        detections), one native call; the class-level id counter goes in and comes back."""
+        C = self.nr_classes
+        self.engine = self._cap.fit(self.engine, ClassMapGuard.class_counts(dets, C), n)
+        self.engine = self._map.fit(self.engine, C, n)
+        warps = None
+        if not self.cmc_off:
+            # one CMC call per class id, on the boxes of that class's detections over det_thresh
+            # (basetracker.py:175-189 -> deepocsort.py:353)
+            d = np.asarray(dets, np.float32).reshape(-1, 6)
+            warps = np.empty((C, 2, 3), np.float64)
+            for c in range(C):
+                cd = d[d[:, 5] == c]
+                boxes = cd[cd[:, 4] > self.det_thresh][:, :4].astype(np.float64)
+                warps[c] = np.asarray(self.cmc.apply(img, boxes), np.float64).reshape(2, 3)
+            warps = None if np.array_equal(warps, np.broadcast_to(np.eye(2, 3), warps.shape)) \
+                else warps
+        out, DeepOcSort._id_count = self.engine.update_classes_host(
+            0, C, dets, e, DeepOcSort._id_count, warps)
+        return out if out.shape[0] else np.empty((0, 8))
+
     @property
     def active_tracks(self):
         """Track list snapshot: id, XYSR Kalman state (x [7], P [7, 7]) and, unless
-        embedding_off, the embedding per track."""
+        embedding_off, the embedding per track (per_class: the list of the class that ran last,
+        as the reference's swap leaves it)."""
+        return self._seq_tracks(self.nr_classes - 1 if self.per_class else 0)
+
+    def _seq_tracks(self, q):
         if self.engine is None:
             return []
-        snap = self.engine.tracks(0)
+        snap = self.engine.tracks(q)
+        ids = snap["id"]
+        if self.per_class and ids.shape[0]:  # the class-global ids the rows carry
+            ids = self.engine.classes().id_map(0, q)[ids - 1]
         emb = snap.get("emb")
-        return [{"id": int(snap["id"][k]), "x": snap["x"][k], "P": snap["P"][k],
-                 **({} if emb is None else {"emb": emb[k]})} for k in range(snap["id"].shape[0])]
+        return [{"id": int(ids[k]), "x": snap["x"][k], "P": snap["P"][k],
+                 **({} if emb is None else {"emb": emb[k]})} for k in range(ids.shape[0])]
+
+    def _class_active_lists(self):
+        # class c is engine sequence c
+        return [self._seq_tracks(c) for c in range(self.nr_classes)]
+
+
+class DeepOcSortPerClass(DeepOcSort):
+    """DeepOcSort with per_class=True (see the module docstring): the reference's constructor
+    arguments without ``per_class``, plus ``nr_classes`` (BaseTracker's 80; fewer classes keep the
+    engine, one sequence per class, small).  Shares DeepOcSort's class-level id counter."""
+
+    _PER_CLASS = True
+
+    def __init__(self, reid_weights=None, device=None, half: bool = False, nr_classes: int = 80,
+                 **kwargs):
+        kwargs.pop("per_class", None)
+        self._nr_classes = int(nr_classes)
+        super().__init__(reid_weights, device, half, per_class=True, **kwargs)

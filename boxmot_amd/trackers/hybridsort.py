@@ -16,9 +16,14 @@ the unfiltered frame at an index into the kept detections, ``det_ind`` from its 
 (hybridsort.py:458,467,604).
 
 Out of scope: the ReID embeddings are an input (``embs``; the reference would run its ReID
-backend), ``use_byte=True`` (the reference's BYTE round cannot run) and ``per_class=True``.
-``create_tracker("hybridsort")`` is not wired up: construct the class directly.  Embeddings are
-float64 on the engine: ``embs`` is converted with ``np.asarray(embs, np.float64)``.
+backend) and ``use_byte=True`` (the reference's BYTE round cannot run).  Embeddings are float64
+on the engine: ``embs`` is converted with ``np.asarray(embs, np.float64)``.
+
+``HybridSort(per_class=True)`` still raises NotImplementedError; the mode is the subclass
+``HybridSortPerClass`` (basetracker.py:155-201): class c is engine sequence c, all classes share the
+frame counter and the class-level id counter; the class split of the frame's rows and the merge
+of the classes' rows under class-global ids run on the device around the same three launches
+(``HybridsortEngine.update_classes_host``, include/bxclasses.h).
 """
 from __future__ import annotations
 
@@ -26,10 +31,11 @@ import numpy as np
 
 from ..engine import HybridsortEngine, HybridsortParams
 from ..iou import KINDS
-from .basetracker import BaseTracker, CapacityGuard
+from .basetracker import BaseTracker, CapacityGuard, ClassMapGuard
 
 
 class HybridSort(BaseTracker):
+    _PER_CLASS = False  # HybridSortPerClass: the per_class mode is built
     # KalmanBoxTracker.count is a class attribute shared by every instance and reset by each
     # HybridSort constructor (hybridsort.py:115,176-177,418); output ids are count + 1: mirrored
     # here as a counter that starts at 1.
@@ -44,11 +50,13 @@ class HybridSort(BaseTracker):
             raise NotImplementedError(
                 "HybridSort(use_byte=True) is not built: the reference's BYTE round calls "
                 "KalmanBoxTracker.update with the wrong arguments, so it defines no behaviour")
-        if per_class:
+        if per_class and not self._PER_CLASS:
             raise NotImplementedError(
-                "HybridSort(per_class=True) is not on the MI355X association engine yet: run one "
-                "HybridSort per class")
+                "HybridSort(per_class=True) is not wired up: the per_class mode on the MI355X "
+                "engine is the class HybridSortPerClass")
         super().__init__(max_age=max_age, per_class=per_class, asso_func=asso_func)
+        # (HybridSortPerClass sets _nr_classes before this constructor runs, as DeepOcSortPerClass)
+        self.nr_classes = int(getattr(self, "_nr_classes", self.nr_classes))
         self.max_age = max_age
         self.min_hits = min_hits
         self.iou_threshold = iou_threshold
@@ -69,6 +77,7 @@ class HybridSort(BaseTracker):
             TCM_first_step_weight=TCM_first_step_weight)
         self._caps = (track_cap, det_cap)
         self._cap = CapacityGuard()
+        self._map = ClassMapGuard()
         self._engine_ids = 1
         self._frame_latched = False
         # the embedding width is learnt from the first frame that has detections; empty frames
@@ -77,7 +86,7 @@ class HybridSort(BaseTracker):
         self._empty_before_engine = 0
 
     def _make_engine(self, emb_dim: int) -> HybridsortEngine:
-        return HybridsortEngine(n_seq=1, track_cap=self._caps[0], det_cap=self._caps[1],
+        return HybridsortEngine(n_seq=self.nr_classes if self.per_class else 1, track_cap=self._caps[0], det_cap=self._caps[1],
                                 emb_dim=emb_dim, params=self._params)
 
     @BaseTracker.setup_decorator
@@ -98,13 +107,27 @@ class HybridSort(BaseTracker):
                 return np.empty((0, 8))
             self.engine = self._make_engine(e.shape[1])
             for _ in range(self._empty_before_engine):
-                self.engine.update_host(0, np.empty((0, 6), np.float32))
+                if self.per_class:
+                    self.engine.update_classes_host(0, self.nr_classes, np.empty((0, 6), np.float32),
+                                                    None, HybridSort._id_count)
+                else:
+                    self.engine.update_host(0, np.empty((0, 6), np.float32))
             self._empty_before_engine = 0
         if not self._frame_latched and self._first_frame_processed:
             # the engine's centroid frame size follows BaseTracker's first-frame latch
-            self.engine.set_frame_size(0, self.w, self.h)
+            for q in range(self.engine.n_seq):
+                self.engine.set_frame_size(q, self.w, self.h)
             self._frame_latched = True
         self.frame_count += 1
+        if self.per_class:
+            # class c runs as engine sequence c (its births are at most its detections), one
+            # native call; the class-level id counter goes in and comes back
+            C = self.nr_classes
+            self.engine = self._cap.fit(self.engine, ClassMapGuard.class_counts(dets, C), n)
+            self.engine = self._map.fit(self.engine, C, n)
+            out, HybridSort._id_count = self.engine.update_classes_host(
+                0, C, dets, e, HybridSort._id_count)
+            return out if out.shape[0] else np.empty((0, 8))
         self.engine = self._cap.fit(self.engine, {0: n}, n)
         if self._engine_ids != HybridSort._id_count:
             self.engine.set_id_count(0, HybridSort._id_count)
@@ -115,10 +138,34 @@ class HybridSort(BaseTracker):
     @property
     def active_tracks(self):
         """Track list snapshot: id, Kalman state (x [9], P [9, 9]), smoothed feature and the
-        number of features pushed into the bank, per track."""
+        number of features pushed into the bank, per track (per_class: the list of the class that
+        ran last, as the reference's swap leaves it)."""
+        return self._seq_tracks(self.nr_classes - 1 if self.per_class else 0)
+
+    def _seq_tracks(self, q):
         if self.engine is None:
             return []
-        snap = self.engine.tracks(0)
-        return [{"id": int(snap["id"][k]), "x": snap["x"][k], "P": snap["P"][k],
+        snap = self.engine.tracks(q)
+        ids = snap["id"]
+        if self.per_class and ids.shape[0]:  # the class-global ids the rows carry
+            ids = self.engine.classes().id_map(0, q)[ids - 1]
+        return [{"id": int(ids[k]), "x": snap["x"][k], "P": snap["P"][k],
                  "emb": snap["emb"][k], "bank_count": int(snap["bank_count"][k])}
-                for k in range(snap["id"].shape[0])]
+                for k in range(ids.shape[0])]
+
+    def _class_active_lists(self):
+        # class c is engine sequence c
+        return [self._seq_tracks(c) for c in range(self.nr_classes)]
+
+
+class HybridSortPerClass(HybridSort):
+    """HybridSort with per_class=True (see the module docstring): the reference's constructor
+    arguments without ``per_class``, plus ``nr_classes`` (BaseTracker's 80; fewer classes keep the
+    engine, one sequence per class, small).  Shares HybridSort's class-level id counter."""
+
+    _PER_CLASS = True
+
+    def __init__(self, reid_weights, device, half, det_thresh, nr_classes: int = 80, **kwargs):
+        kwargs.pop("per_class", None)
+        self._nr_classes = int(nr_classes)
+        super().__init__(reid_weights, device, half, det_thresh, per_class=True, **kwargs)

@@ -37,6 +37,7 @@
 #include <stdint.h>
 
 #include "bxassoc.h"
+#include "bxclasses.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -83,6 +84,29 @@ int bx_deepoc_step(bx_deepoc *e, int seq0, int nseq, const float *dets, const in
  * must hold n rows. */
 int bx_deepoc_update_host(bx_deepoc *e, int seq, const float *dets, int n, const double *embs,
                           const double *warp, double *out, int *n_out, void *stream);
+/* per_class=True (bxclasses.h): one frame for sequences [seq0, seq0+nseq) of n_classes classes,
+ * on an engine built with n_seq = S * n_classes (class c of sequence s is engine sequence
+ * s * n_classes + c).  bx_deepoc_step's arguments, except: det_off / out / out_count are per
+ * SEQUENCE (a sequence has at most det_cap rows), warps is [nseq * n_classes][6] (one per class
+ * call) or NULL.  Runs class split -> the three launches over the class sequences -> id merge on
+ * `stream`, nothing returning to the host; rows come out in class order with class-global ids.
+ * The first per-class call fixes n_classes: another value is BX_ERR_INVALID.  A class whose
+ * births pass the id map's capacity latches BX_ERR_CAPACITY (bx_deepoc_status). */
+int bx_deepoc_step_classes(bx_deepoc *e, int seq0, int nseq, int n_classes, const float *dets,
+                           const int32_t *det_off, const double *embs, const double *warps,
+                           double *out, int32_t *out_count, void *stream);
+/* Build the class state before the first per-class call with an id map of map_cap births per
+ * class sequence instead of BX_CLASSES_MAP_CAP. */
+int bx_deepoc_classes_config(bx_deepoc *e, int n_classes, int map_cap);
+/* The engine's class state (NULL before the first per-class call): counters and maps are read
+ * through bxclasses.h.  It stays the engine's. */
+int bx_deepoc_classes(bx_deepoc *e, bx_classes **out);
+/* Host form of one per-class frame of sequence seq (the drop-in update): warps_host
+ * [n_classes][6] or NULL; *id_count_host is the class-level id counter, written to the device
+ * before the frame and read back after it.  Synchronises once. */
+int bx_deepoc_update_classes_host(bx_deepoc *e, int seq, int n_classes, const float *dets_host,
+                                  int n, const double *embs_host, const double *warps_host,
+                                  int *id_count_host, double *out_host, int *n_out, void *stream);
 /* Capacity growth (the reference's track list is unbounded): copy every sequence's tracker
  * state of `src` into `dst`, a fresh engine with the same configuration and sequences and
  * track_cap / det_cap at least src's (slot ids stay valid).  Synchronous. */

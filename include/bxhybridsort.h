@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "bxassoc.h"
+#include "bxclasses.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -78,6 +79,32 @@ int bx_hybrid_step(bx_hybrid *e, int seq0, int nseq, const float *dets, const in
  * synchronises.  embs [n][emb_dim] (NULL only when n == 0); out must hold n rows. */
 int bx_hybrid_update_host(bx_hybrid *e, int seq, const float *dets, int n, const double *embs,
                           double *out, int *n_out, void *stream);
+/* per_class=True (bxclasses.h): one frame for sequences [seq0, seq0+nseq) of n_classes classes,
+ * on an engine built with n_seq = S * n_classes (class c of sequence s is engine sequence
+ * s * n_classes + c).  bx_hybrid_step's arguments with det_off / out / out_count per SEQUENCE (a
+ * sequence has at most det_cap rows).  Runs class split -> the three launches over the class
+ * sequences -> id merge on `stream`, nothing returning to the host; rows come out in class order
+ * with class-global ids.  The first per-class call fixes n_classes: another value is
+ * BX_ERR_INVALID.  A class whose births pass the id map's capacity latches BX_ERR_CAPACITY. */
+int bx_hybrid_step_classes(bx_hybrid *e, int seq0, int nseq, int n_classes, const float *dets,
+                           const int32_t *det_off, const double *embs, double *out,
+                           int32_t *out_count, void *stream);
+/* Build the class state before the first per-class call with an id map of map_cap births per
+ * class sequence instead of BX_CLASSES_MAP_CAP. */
+int bx_hybrid_classes_config(bx_hybrid *e, int n_classes, int map_cap);
+/* The engine's class state (NULL before the first per-class call); it stays the engine's. */
+int bx_hybrid_classes(bx_hybrid *e, bx_classes **out);
+/* Host form of one per-class frame of sequence seq (the drop-in update): *id_count_host is the
+ * class-level id counter, written to the device before the frame and read back after it.
+ * Synchronises once. */
+int bx_hybrid_update_classes_host(bx_hybrid *e, int seq, int n_classes, const float *dets_host,
+                                  int n, const double *embs_host, int *id_count_host,
+                                  double *out_host, int *n_out, void *stream);
+/* Timing probe: while stage is 0 (distances), 1 (frame) or 2 (feature update), every step records
+ * a HIP event pair around that launch; -1 turns it off.  probe_read synchronises and returns the
+ * summed milliseconds and the number of pairs since the last read. */
+int bx_hybrid_probe(bx_hybrid *e, int stage);
+int bx_hybrid_probe_read(bx_hybrid *e, double *total_ms, int *count);
 /* Capacity growth (the reference's track list is unbounded): copy every sequence's tracker
  * state of `src` into `dst`, a fresh engine with the same configuration and sequences and
  * track_cap / det_cap at least src's (slot ids stay valid).  Synchronous. */

@@ -1,13 +1,15 @@
 #!/usr/bin/env python
-"""Wall time of DeepOcSort over many sequences, three ways:
+"""Wall time of DeepOcSort (or, with --tracker hybridsort, HybridSort) over many sequences, three
+ways:
 
-  dropins    one fresh single-sequence DeepOcSort drop-in per sequence, one after the other
-  default    motio.run_sequences("deepocsort", ...): one batched engine, frames assembled on the host
+  dropins    one fresh single-sequence drop-in per sequence, one after the other
+  default    motio.run_sequences(tracker, ...): one batched engine, frames assembled on the host
   resident   the same with resident=True: the sequences and the result rows stay in device memory
 
 Every way reads the same packed sequences and writes the same MOT files (checked byte for byte).
 
     python tools/flow_timing.py --seqs 256 --frames 200 --objects 44 --emb-dim 64
+    python tools/flow_timing.py --tracker hybridsort
 """
 import argparse
 import json
@@ -29,10 +31,11 @@ def main():
     ap.add_argument("--emb-dim", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--skip-dropins", action="store_true")
+    ap.add_argument("--tracker", default="deepocsort", choices=["deepocsort", "hybridsort"])
     a = ap.parse_args()
     import torch
 
-    from boxmot_amd import DeepOcSort, motio
+    from boxmot_amd import DeepOcSort, HybridSort, motio
     from boxmot_amd.synth import SyntheticScene
 
     img = np.zeros((1080, 1920, 3), np.uint8)
@@ -53,12 +56,14 @@ def main():
             packed[f"S{k:04d}"] = motio.pack_arrays(d7, np.concatenate(em), tmp / f"{k}.bxmot")
 
         def flow(resident, out):
-            motio.run_sequences("deepocsort", packed, out, resident=resident)
+            motio.run_sequences(a.tracker, packed, out, resident=resident)
 
         def dropins(out):
             for nm, p in packed.items():
                 seq = motio.BinSequence(p)
-                tr = DeepOcSort()
+                # (run_sequences gives HybridSort, whose det_thresh has no default, 0.3)
+                tr = DeepOcSort() if a.tracker == "deepocsort" else HybridSort(None, None, False,
+                                                                               0.3)
                 rows = []
                 for fid in seq.frame_ids:
                     d, e = seq.frame(fid)
@@ -79,7 +84,7 @@ def main():
                 best.append(time.perf_counter() - t0)
             return sorted(best[warm:]), tmp / f"{tag}_{repeats + warm - 1}"
 
-        res = {"seqs": a.seqs, "frames": a.frames, "emb_dim": a.emb_dim,
+        res = {"tracker": a.tracker, "seqs": a.seqs, "frames": a.frames, "emb_dim": a.emb_dim,
                "detections_per_frame": dets_total / (a.seqs * a.frames)}
         t_def, d_def = timed(lambda o: flow(False, o), "default", a.repeats)
         t_res, d_res = timed(lambda o: flow(True, o), "resident", a.repeats)
