@@ -216,7 +216,7 @@ EXPORTS = [
     "bx_kf_multi_predict", "bx_kf_update", "bx_kf_gating_distance", "bx_linear_assignment", "bx_lapjv",
     "bx_linear_assignment_ex", "bx_engine_lap_ties_host", "bx_engine_lap_components_host", "bx_engine_set_lap_stats",
     "bx_engine_force_assoc_build", "bx_legacy_lap_pair", "bx_engine_set_early_features",
-    "bx_engine_inputs_released",
+    "bx_engine_inputs_released", "bx_engine_set_cosine_mode", "bx_engine_embdist_host",
     "bx_engine_copy_state", "bx_engine_slots_used_host", "bx_ocsort_copy_state",
     "bx_boost_copy_state", "bx_ss_copy_state",
     "bx_nn_cosine_distance", "bx_ocsort_create", "bx_ocsort_destroy", "bx_ocsort_reset", "bx_ocsort_step",
@@ -306,6 +306,8 @@ _SIGS = {
     "bx_engine_force_assoc_build": ([_vp, C.c_int], C.c_int),
     "bx_legacy_lap_pair": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
     "bx_engine_inputs_released": ([_vp, _vp], C.c_int),
+    "bx_engine_set_cosine_mode": ([_vp, C.c_int], C.c_int),
+    "bx_engine_embdist_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _ip], C.c_int),
     "bx_engine_copy_state": ([_vp, _vp], C.c_int),
     "bx_ocsort_copy_state": ([_vp, _vp], C.c_int),
     "bx_boost_copy_state": ([_vp, _vp], C.c_int),

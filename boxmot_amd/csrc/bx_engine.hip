@@ -503,22 +503,32 @@ __global__ __launch_bounds__(WG) void gate_kernel(Dev P, int seq0, const float* 
 // (f / n1) / n2 rebuilt from the input row (K1's norms); scipy cdist cosine with its own
 // two-accumulator dots for A.B, |A|, |B|; /2; > appearance_thresh → 1.  Stored in the dense
 // per-sequence [T][D] table K3 reads.
-// scipy's two accumulators are independent chains (even elements into one, odd into the other,
-// summed at the end), so a pair's dots run on TWO lanes — lane 2p the even chain, lane 2p+1 the
-// odd one — and a wave owns COS_P pairs: COS_P = 16 gives ~8 waves per SIMD at C3 (the kernel is
-// load-latency bound; the old 64-pairs-per-wave layout left 2).  Rows stream through LDS in
-// COS_CH = 32-element chunks (one whole 128-B line of each row per chunk: 8 lanes x 16 B), the
-// elementwise divisions done by the loading lane, the next chunk's loads in flight meanwhile.
+// A wave owns COS_P = 16 pairs (4 waves per SIMD by registers; the kernel is load-latency
+// bound).  Rows stream through LDS in COS_CH = 32-element chunks (one whole 128-B line of each
+// row per chunk: 8 lanes x 16 B), the next chunk's loads in flight meanwhile.
+//  * Divisions, by the loading lane: Div32's product form for the lane's whole chunk (A: one
+//    product per element, B: three chained ones, each rounded to fp32 before the next) under ONE
+//    verdict per chunk — RegRow::div's condition folded over every product and balloted once; a
+//    chunk with a tiny / NaN quotient anywhere in the wave (rare) is redone with Div32 itself.
+//  * Dots: scipy's two accumulators are independent sequential chains (even elements into one,
+//    odd into the other, summed at the end).  The staged chunk is de-interleaved by parity, so a
+//    chain's 16 elements are contiguous and read with four 16-byte LDS loads, and the three sums
+//    of a chain are split over the wave's halves: lane (pair p, parity) of the lower half
+//    runs A.B and A.A, the same lane of the upper half B.B (its second slot repeats B.B: idle
+//    work in lockstep) — two conversions and two fused adds per element on the whole wave
+//    instead of two and three in a 16-trip loop on half of it.
+// LDS image per wave and array: [parity][pair][COS_RS] floats, COS_RS = 16 + 4, planes COS_PS
+// apart with COS_PS / 4 = 8 mod 16: the 16 lanes ds_read_b128 serves together (pairs
+// {0,1,6,7,10..13} or {2..5,8,9,14,15}, both parities) then cover all 64 banks once.
 // Grid (n_seq, COS_BLOCKS).
 #ifndef BX_COS_BLOCKS
 #define BX_COS_BLOCKS 2
 #endif
 constexpr int COS_BLOCKS = BX_COS_BLOCKS;
 constexpr int COS_CH = 32;
-#ifndef BX_COS_P
-#define BX_COS_P 16
-#endif
-constexpr int COS_P = BX_COS_P;  // 8 or 16 (a multiple of 8: 8 lanes load a row's chunk)
+constexpr int COS_P = 16;  // a pair's two chains on two lanes: 32 lanes = half a wave
+constexpr int COS_RS = COS_CH / 2 + 4;
+constexpr int COS_PS = COS_P * COS_RS + 32;
 __device__ inline void cos_finish(Dev& P, int s, int slot, int dk, double ab, double aa,
                                   double bb) {
   double c = ab / (sqrt(aa) * sqrt(bb));
@@ -539,11 +549,148 @@ __device__ __forceinline__ void load4(const FT* p, FT* v) {
     v[0] = t0.x; v[1] = t0.y; v[2] = t1.x; v[3] = t1.y;
   }
 }
+// RegRow::div's test of one product: RN32(p) is the correctly rounded quotient
+__device__ __forceinline__ bool div32_fast(double p) { return fabs(p) >= 0x1p-125 || p == 0.0; }
+// float32 rows.  Registers for 4 waves per SIMD (114 VGPRs, no scratch), as before.
+template <int FC>
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void cosine_kernel(Dev P, int seq0, const int* __restrict__ det_off, const float* __restrict__ embs) {
+  using FT = float;
+  constexpr int KR = COS_P / 8;  // row pieces per lane on each side (A: tracks, B: detections)
+  __shared__ __attribute__((aligned(16))) float s_ab[NWAVE][2][2][COS_PS];  // [wave][A|B][parity]
+  const int b = blockIdx.x, s = seq0 + b, T = P.T, D = P.D, F = FC ? FC : P.F, w = wave_id(),
+            lane = lane_id();
+  const int np = P.npair[s], d0 = det_off[b];
+  const uint32_t* pairs = P.pairs + (size_t)s * T * D;
+  const int col = (lane & 7) * 4;  // this lane's 4 elements of every chunk
+  // chain lanes: pair cp, even/odd elements; the upper half runs B.B when the sums are split
+  const int cp = (lane & 31) >> 1, par = lane & 1, half = lane >> 5;
+  float* const s_a = &s_ab[w][0][0][0];
+  float* const s_b = &s_ab[w][1][0][0];
+  const float4* const up = (const float4*)((half ? s_b : s_a) + par * COS_PS + cp * COS_RS);
+  const float4* const vp = (const float4*)(s_b + par * COS_PS + cp * COS_RS);
+  for (int p0 = (blockIdx.y * NWAVE + w) * COS_P; p0 < np; p0 += COS_BLOCKS * NWAVE * COS_P) {
+    // row pieces: pairs (lane >> 3) + 8k, k < KR
+    const FT* arow[KR];
+    const FT* brow[KR];
+    // Div32's reciprocals (the divisors themselves: only the redo needs them)
+    double ra[KR], r1[KR], r2[KR], rb[KR];
+#pragma unroll
+    for (int k = 0; k < KR; k++) {
+      const int pp = p0 + (lane >> 3) + 8 * k;
+      const uint32_t pr = pp < np ? pairs[pp] : pairs[p0];
+      const int slot = pr >> 16, dk = pr & 0xffff;
+      arow[k] = (const FT*)P.feat + ((size_t)s * T + slot) * F + col;
+      brow[k] = embs + (size_t)(d0 + dk) * F + col;
+      ra[k] = Div32(P.tdn[(size_t)s * T + slot]).r;
+      const double* nr = P.dnrm + ((size_t)P.dpar * P.S * D + (size_t)s * D + dk) * 4;
+      r1[k] = Div32((float)nr[0]).r;
+      r2[k] = Div32((float)nr[1]).r;
+      rb[k] = Div32((float)nr[2]).r;
+    }
+    // this lane's chains: lower half c0 = A.B, c1 = A.A; upper half c0 = B.B (and again in c1:
+    // the halves run in lockstep, so the upper half's second sum is idle work, not extra time)
+    double c0s = 0.0, c1s = 0.0;
+    FT av[KR][4], bv[KR][4];  // raw elements of the current chunk; the next chunk's in flight
+#pragma unroll
+    for (int k = 0; k < KR; k++) { load4(arow[k], av[k]); load4(brow[k], bv[k]); }
+    for (int c0 = 0; c0 < F; c0 += COS_CH) {
+      FT nav[KR][4], nbv[KR][4];
+      const int cn = c0 + COS_CH < F ? c0 + COS_CH : c0;
+#pragma unroll
+      for (int k = 0; k < KR; k++) { load4(arow[k] + cn, nav[k]); load4(brow[k] + cn, nbv[k]); }
+      float fa[KR][4], fb[KR][4];
+      bool fast = true;
+#pragma unroll
+      for (int k = 0; k < KR; k++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const double pa = (double)av[k][q] * ra[k];
+          const double p1 = (double)bv[k][q] * r1[k];
+          const double p2 = (double)(float)p1 * r2[k];
+          const double p3 = (double)(float)p2 * rb[k];
+          fast &= div32_fast(pa) & div32_fast(p1) & div32_fast(p2) & div32_fast(p3);
+          fa[k][q] = (float)pa;
+          fb[k][q] = (float)p3;
+          // round now: left to itself the compiler sinks these conversions below the verdict
+          // and keeps 16 fp64 products alive across it (162 VGPRs instead of 114)
+          asm volatile("" : "+v"(fa[k][q]), "+v"(fb[k][q]));
+        }
+      // wave-uniform.  The rare redo re-reads its operands (cached) instead of holding the
+      // divisors and the raw chunk in registers across the verdict.
+      if (__builtin_expect(__ballot(!fast) != 0ull, 0)) {
+#pragma unroll
+        for (int k = 0; k < KR; k++) {
+          const int pp = p0 + (lane >> 3) + 8 * k;
+          const uint32_t pr = pp < np ? pairs[pp] : pairs[p0];
+          const int slot = pr >> 16, dk = pr & 0xffff;
+          const double* nr = P.dnrm + ((size_t)P.dpar * P.S * D + (size_t)s * D + dk) * 4;
+          const Div32 da(P.tdn[(size_t)s * T + slot]), db((float)nr[2]);
+          const Div32 c1((float)nr[0]), c2((float)nr[1]);
+          FT ae[4], be[4];
+          load4(arow[k] + c0, ae);
+          load4(brow[k] + c0, be);
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            fa[k][q] = da(ae[q]);
+            fb[k][q] = db(c2(c1(be[q])));
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < KR; k++) {
+        const int o = ((lane >> 3) + 8 * k) * COS_RS + (col >> 1);
+        *(float2*)(s_a + o) = make_float2(fa[k][0], fa[k][2]);
+        *(float2*)(s_a + COS_PS + o) = make_float2(fa[k][1], fa[k][3]);
+        *(float2*)(s_b + o) = make_float2(fb[k][0], fb[k][2]);
+        *(float2*)(s_b + COS_PS + o) = make_float2(fb[k][1], fb[k][3]);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      {
+        float4 u[COS_CH / 8], v[COS_CH / 8];
+#pragma unroll
+        for (int j = 0; j < COS_CH / 8; j++) { u[j] = up[j]; v[j] = vp[j]; }
+#pragma unroll
+        for (int j = 0; j < COS_CH / 8; j++) {
+          const float ue[4] = {u[j].x, u[j].y, u[j].z, u[j].w};
+          const float ve[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            // products of two floats are exact in fp64: fma rounds identically to acc + x*y
+            const double x = (double)ue[q], y = (double)ve[q];
+            c0s = __builtin_fma(x, y, c0s);
+            c1s = __builtin_fma(x, x, c1s);
+          }
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int k = 0; k < KR; k++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) { av[k][q] = nav[k][q]; bv[k][q] = nbv[k][q]; }
+    }
+    const double ab = c0s, aa = c1s, bb = __shfl_xor(c0s, 32);
+    // even chain + odd chain, as scipy adds its two accumulators
+    const double ab1 = __shfl_xor(ab, 1), aa1 = __shfl_xor(aa, 1), bb1 = __shfl_xor(bb, 1);
+    if (lane < 2 * COS_P && par == 0 && p0 + cp < np) {
+      const uint32_t pr = pairs[p0 + cp];
+      cos_finish(P, s, pr >> 16, pr & 0xffff, ab + ab1, aa + aa1, bb + bb1);
+    }
+  }
+}
+
+// float64 embeddings (twice the row registers): the per-element form — Div32 with its own test
+// on every element, the chains on the lower 32 lanes reading the interleaved image dword by
+// dword.  122 VGPRs, no scratch, 4 waves per SIMD; the chunk-verdict kernel above needs 128 + spills
+// for fp64 rows, and no benchmark covers them, so they stay here.
 template <typename FT, int FC>
-__global__ __launch_bounds__(WG) void cosine_kernel(Dev P, int seq0, const int* __restrict__ det_off,
+__global__ __launch_bounds__(WG) void cosine_kernel_f64(Dev P, int seq0, const int* __restrict__ det_off,
                                                     const FT* __restrict__ embs) {
   constexpr int KR = COS_P / 8;  // row pieces per lane on each side (A: tracks, B: detections)
   // row stride COS_CH + 2: the 32 chain lanes (pair p, parity) read banks 2p + parity
+  static_assert(sizeof(FT) == 8, "float32 rows take cosine_kernel");
   __shared__ float s_a[NWAVE][COS_P][COS_CH + 2], s_b[NWAVE][COS_P][COS_CH + 2];
   const int b = blockIdx.x, s = seq0 + b, T = P.T, D = P.D, F = FC ? FC : P.F, w = wave_id(),
             lane = lane_id();
@@ -614,6 +761,12 @@ __global__ __launch_bounds__(WG) void cosine_kernel(Dev P, int seq0, const int* 
       cos_finish(P, s, pr >> 16, pr & 0xffff, ab + ab1, aa + aa1, bb + bb1);
     }
   }
+}
+
+template <typename FT, int FC>
+constexpr auto cosine_rows_kernel() {
+  if constexpr (sizeof(FT) == 4) return &cosine_kernel<FC>;
+  else return &cosine_kernel_f64<FT, FC>;
 }
 
 // any F: thread per pair, element by element (same arithmetic as above)
@@ -1844,6 +1997,7 @@ struct bx_engine {
   // for the K5 that last read its half of dnrm (ev_k5[parity]), not for the previous frame —
   // the caller guarantees each step's inputs are complete when the step is called
   bool early = false;
+  int cos_mode = 0;  // bx_engine_set_cosine_mode: 1 = K1c always as cosine_kernel_any
   hipStream_t k1s = nullptr;
   hipEvent_t ev_k1 = nullptr, ev_k5[2] = {nullptr, nullptr};
   bool k5_rec[2] = {false, false};
@@ -2003,14 +2157,18 @@ int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int*
     if (early) HIPCHK(hipStreamWaitEvent(st, e->ev_k1, 0));
     if (!early || e->side_pending)
       if (int rc = join(0)) return rc;
-    if (d.F == REG_F && (BX_FC_MASK & 4))
+    if (e->cos_mode == 1)
       BX_PROBED(BX_STAGE_COSINE,
-                hipLaunchKernelGGL((cosine_kernel<FT, REG_F>), dim3(nseq, COS_BLOCKS), dim3(WG), 0,
-                                   st, d, seq0, det_off, (const FT*)embs));
+                hipLaunchKernelGGL(cosine_kernel_any<FT>, dim3(nseq, COS_BLOCKS), dim3(WG), 0, st,
+                                   d, seq0, det_off, (const FT*)embs));
+    else if (d.F == REG_F && (BX_FC_MASK & 4))
+      BX_PROBED(BX_STAGE_COSINE,
+                hipLaunchKernelGGL((cosine_rows_kernel<FT, REG_F>()), dim3(nseq, COS_BLOCKS), dim3(WG),
+                                   0, st, d, seq0, det_off, (const FT*)embs));
     else if (d.F % COS_CH == 0)
       BX_PROBED(BX_STAGE_COSINE,
-                hipLaunchKernelGGL((cosine_kernel<FT, 0>), dim3(nseq, COS_BLOCKS), dim3(WG), 0, st,
-                                   d, seq0, det_off, (const FT*)embs));
+                hipLaunchKernelGGL((cosine_rows_kernel<FT, 0>()), dim3(nseq, COS_BLOCKS), dim3(WG), 0,
+                                   st, d, seq0, det_off, (const FT*)embs));
     else
       BX_PROBED(BX_STAGE_COSINE,
                 hipLaunchKernelGGL(cosine_kernel_any<FT>, dim3(nseq, COS_BLOCKS), dim3(WG), 0, st,
@@ -2755,6 +2913,45 @@ int bx_engine_set_early_features(bx_engine* e, int on) {
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (e->k1s) HIPCHK(hipStreamSynchronize(e->k1s));
   e->early = on != 0;
+  return BX_OK;
+}
+
+int bx_engine_set_cosine_mode(bx_engine* e, int mode) {
+  if (!e || mode < 0 || mode > 1) return set_err(BX_ERR_INVALID, "bad cosine mode");
+  if (int rc = settle(e)) return rc;
+  e->cos_mode = mode;
+  return BX_OK;
+}
+
+int bx_engine_embdist_host(bx_engine* e, int seq, int cap, uint32_t* pairs_out, double* dist_out,
+                           int* n_out) {
+  if (int rc = settle(e)) return rc;
+  if (!e || !n_out || seq < 0 || seq >= e->dev.S || cap < 0 || (cap && (!pairs_out || !dist_out)))
+    return set_err(BX_ERR_INVALID, "bad arguments to bx_engine_embdist_host");
+  const Dev& d = e->dev;
+  *n_out = 0;
+  if (!d.with_reid) return BX_OK;
+  HIPCHK(hipDeviceSynchronize());
+  int n = 0;  // K6 moved the frame's pair count here when it cleared npair for the next frame
+  HIPCHK(hipMemcpy(&n, d.seq + (size_t)seq * SQ_STRIDE + SQ_NPAIR, sizeof(int),
+                   hipMemcpyDeviceToHost));
+  if (n < 0 || (size_t)n > (size_t)d.T * d.D)
+    return set_err(BX_ERR_INVALID, "bx_engine_embdist_host: pair count out of range");
+  *n_out = n;
+  if (n > cap) return set_err(BX_ERR_CAPACITY, "bx_engine_embdist_host: cap below the pair count");
+  if (!n) return BX_OK;
+  const size_t TD = (size_t)d.T * d.D;
+  std::vector<double> tab(TD);
+  HIPCHK(hipMemcpy(pairs_out, d.pairs + (size_t)seq * TD, sizeof(uint32_t) * n,
+                   hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tab.data(), d.etab + (size_t)seq * TD, sizeof(double) * TD,
+                   hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; i++) {
+    const size_t slot = pairs_out[i] >> 16, dk = pairs_out[i] & 0xffff;
+    if (slot >= (size_t)d.T || dk >= (size_t)d.D)
+      return set_err(BX_ERR_INVALID, "bx_engine_embdist_host: pair word out of range");
+    dist_out[i] = tab[slot * d.D + dk];
+  }
   return BX_OK;
 }
 

@@ -215,6 +215,22 @@ class Engine:
         N.check(self._L.bx_engine_set_early_features(self._h, int(bool(on))),
                 "bx_engine_set_early_features")
 
+    def set_cosine_mode(self, mode: int) -> None:
+        """0: the embedding-distance kernel picked from the feature width (default); 1: always
+        the element-by-element restatement (bx_engine_set_cosine_mode).  Same bits either way."""
+        N.check(self._L.bx_engine_set_cosine_mode(self._h, int(mode)), "bx_engine_set_cosine_mode")
+
+    def embdist_host(self, seq: int = 0):
+        """(pair words uint32 [n] = slot << 16 | detection, distances float64 [n]) of the last
+        step's gated pairs of sequence ``seq`` (bx_engine_embdist_host), in the gate's order."""
+        cap = self.track_cap * self.det_cap
+        pairs, dist = np.empty(cap, np.uint32), np.empty(cap, np.float64)
+        n = C.c_int(0)
+        N.check(self._L.bx_engine_embdist_host(self._h, seq, cap, pairs.ctypes.data,
+                                               dist.ctypes.data, C.byref(n)),
+                "bx_engine_embdist_host")
+        return pairs[: n.value].copy(), dist[: n.value].copy()
+
     def set_overlap(self, on: bool = True) -> None:
         """Leave each step's feature EMA (K5) unjoined on the side stream (bx_engine_set_overlap):
         the caller keeps a step's input tensors unmodified until the next step is enqueued."""

@@ -173,6 +173,18 @@ int bx_engine_force_assoc_build(bx_engine *e, int mode);
 /* Turn the component counting of bx_engine_lap_components_host on (off by default: it costs the
  * association kernel reductions and atomics per LAP).  Diagnostic; settles overlap mode first. */
 int bx_engine_set_lap_stats(bx_engine *e, int on);
+/* Which kernel computes the embedding distances of the gated pairs (BoT-SORT with ReID): 0
+ * (default) the one picked from the feature width, 1 always the element-by-element restatement
+ * (cosine_kernel_any).  Both give identical bits; tests run one against the other.  Settles
+ * overlap mode first. */
+int bx_engine_set_cosine_mode(bx_engine *e, int mode);
+/* The gated (track, detection) pairs of sequence `seq` in the last step and their embedding
+ * distances as the association read them (host, synchronous): pairs_out [cap] receives the pair
+ * words (track slot << 16 | detection index, in the gate's order, which is not deterministic),
+ * dist_out [cap] the distances, *n_out the pair count (also when it exceeds cap, which is
+ * BX_ERR_CAPACITY).  Valid until the next step; 0 pairs for an engine without ReID. */
+int bx_engine_embdist_host(bx_engine *e, int seq, int cap, uint32_t *pairs_out, double *dist_out,
+                           int *n_out);
 
 /* Capacity growth (the reference's track lists are unbounded: bytetrack.py:272-346): copy every
  * sequence's tracker state of `src` into `dst`, a fresh engine with the same kind, sequences and
