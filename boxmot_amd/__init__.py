@@ -5,7 +5,9 @@ Drop-in surface: ``create_tracker``, ``get_tracker_config``, ``ByteTrack``, ``Bo
 reference's ``update(dets, img, embs) -> [M, 8]`` contract.  The numerics run in libbxassoc.so
 (HIP, gfx950); ``boxmot_amd.engine.Engine`` / ``OcsortEngine`` / ``BoostEngine`` / ``SsEngine`` / ``DeepOcsortEngine`` / ``HybridsortEngine`` expose the batched many-sequence API.
 ``gsi`` / ``linear_interpolation`` / ``gaussian_smooth`` are the GSI post-processing of MOT result files.
+``evaluate_mot`` / ``mot_summary`` are the HOTA / CLEAR / Identity evaluation of MOT result files.
 """
+from .evaluation import evaluate_mot, mot_summary
 from .postprocessing import gaussian_smooth, gsi, linear_interpolation
 from .tracker_zoo import create_tracker, get_tracker_config
 from .trackers import (BoostTrack, BotSort, ByteTrack, DeepOcSort, DeepOcSortPerClass,
@@ -14,4 +16,5 @@ from .trackers import (BoostTrack, BotSort, ByteTrack, DeepOcSort, DeepOcSortPer
 __version__ = "0.1.0"
 __all__ = ["create_tracker", "get_tracker_config", "ByteTrack", "BotSort", "OcSort",
            "BoostTrack", "StrongSort", "DeepOcSort", "HybridSort", "gsi", "linear_interpolation",
-           "gaussian_smooth", "DeepOcSortPerClass", "HybridSortPerClass", "__version__"]
+           "gaussian_smooth", "DeepOcSortPerClass", "HybridSortPerClass", "evaluate_mot",
+           "mot_summary", "__version__"]

@@ -26,6 +26,7 @@ HEADER_IO = REPO / "include" / "bxio.h"
 HEADER_GSI = REPO / "include" / "bxgsi.h"
 HEADER_FEED = REPO / "include" / "bxfeed.h"
 HEADER_CLASSES = REPO / "include" / "bxclasses.h"
+HEADER_EVAL = REPO / "include" / "bxeval.h"
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -37,7 +38,7 @@ HIPCC_FLAGS = [
 ]
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
            "bx_strongsort.hip", "bx_deepocsort.hip", "bx_hybridsort.hip", "bx_gsi.hip", "bx_feed.hip",
-           "bx_classes.hip",
+           "bx_classes.hip", "bx_eval.hip",
            "bx_io.cpp"]
 
 
@@ -260,6 +261,7 @@ EXPORTS = [
     "bx_deepoc_update_classes_host", "bx_hybrid_step_classes", "bx_hybrid_classes_config",
     "bx_hybrid_classes", "bx_hybrid_update_classes_host", "bx_hybrid_probe",
     "bx_hybrid_probe_read",
+    "bx_eval_create", "bx_eval_destroy", "bx_eval_capacity", "bx_eval_run_host",
 ]
 
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -463,6 +465,10 @@ _SIGS = {
     "bx_hybrid_classes": ([_vp, C.POINTER(C.c_void_p)], C.c_int),
     "bx_hybrid_update_classes_host": ([_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _ip, _vp, _ip,
                                        _vp], C.c_int),
+    "bx_eval_create": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "bx_eval_destroy": ([_vp], C.c_int),
+    "bx_eval_capacity": ([_vp, _ip, _ip, _ip, _ip], C.c_int),
+    "bx_eval_run_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
 }
 
 _lib = None
