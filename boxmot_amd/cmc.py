@@ -1,0 +1,318 @@
+"""Camera-motion compensation on the GPU: the ECC image alignment of ``motion/cmc/ecc.py``.
+
+Reference stage replaced (``boxmot/motion/cmc/ecc.py:63-128`` with ``base_cmc.py:27-43``): grey
+conversion, the resize to ``scale`` and ``cv2.findTransformECC`` against the previous frame, on the
+host, once per frame.  Here both stages run in libbxassoc.so (``include/bxcmc.h``; DESIGN.md 2.14
+is the contract): a preprocessing kernel in exact integer arithmetic and one persistent workgroup
+per camera that runs the whole ECC iteration in fp64.  ``ECC`` is the reference's class for one
+camera (``tracker.cmc = ECC()``); ``EccBatch`` aligns many cameras per call and returns the warps
+as the device tensor the engines' ``warps`` argument takes (no host synchronisation when its
+inputs are on the device).  There is no CPU fallback: without the
+library or a HIP device the calls raise ``NativeUnavailable``.
+
+Agreement with OpenCV's own ``findTransformECC`` is unmeasured.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+
+# cv2's values
+MOTION_TRANSLATION, MOTION_EUCLIDEAN, MOTION_AFFINE, MOTION_HOMOGRAPHY = 0, 1, 2, 3
+
+# per-stream result codes (include/bxcmc.h); NO_FRAME is EccBatch's own: the stream was not listed
+OK, FIRST_FRAME, NOT_CONVERGED, NO_FRAME = 0, 1, 2, 3
+
+
+def _check_mode(warp_mode) -> int:
+    if warp_mode == MOTION_HOMOGRAPHY:
+        raise NotImplementedError("MOTION_HOMOGRAPHY is not supported: no engine takes a 3x3 warp")
+    if warp_mode not in (MOTION_TRANSLATION, MOTION_EUCLIDEAN, MOTION_AFFINE):
+        raise ValueError(f"unknown warp_mode {warp_mode!r}")
+    return int(warp_mode)
+
+
+def _scale_arg(scale) -> float:
+    """The C ABI's scale: 0 for 'no resize' (None, or a ratio >= 1)."""
+    if scale is None:
+        return 0.0
+    if isinstance(scale, (list, tuple, np.ndarray)):
+        raise NotImplementedError("scale as [W, H] is not supported (the reference's preprocess "
+                                  "cannot take it either): give a ratio")
+    s = float(scale)
+    if not s > 0:
+        raise ValueError(f"scale must be positive, got {scale!r}")
+    return 0.0 if s >= 1 else s
+
+
+def work_size(H: int, W: int, scale) -> tuple:
+    """(h, w) of the working image of an H x W frame: round-half-even of the scaled sides."""
+    s = _scale_arg(scale)
+    if s == 0.0:
+        return int(H), int(W)
+    return int(round(H * s)), int(round(W * s))
+
+
+def _frame_dims(shape, grayscale: bool):
+    """(n, H, W, channels) of a frame batch [n, H, W, 3] or [n, H, W]."""
+    if len(shape) == 3:
+        return int(shape[0]), int(shape[1]), int(shape[2]), 1
+    if len(shape) == 4 and shape[3] in (1, 3):
+        if shape[3] == 3 and not grayscale:
+            raise NotImplementedError("ECC aligns single-channel images: grayscale=False needs "
+                                      "grey frames")
+        return int(shape[0]), int(shape[1]), int(shape[2]), int(shape[3])
+    raise ValueError(f"frames must be [n, H, W, 3] or [n, H, W], got {tuple(shape)}")
+
+
+class _Handle:
+    """One ``bx_ecc`` handle."""
+
+    def __init__(self, n_streams: int, max_h: int, max_w: int):
+        import torch  # (first, as everywhere in the package: one HIP runtime per process)
+
+        self._h = C.c_void_p()
+        self._L = N.load()
+        if N.device_count() == 0 or not torch.cuda.is_available():
+            raise N.NativeUnavailable("ECC needs a HIP device")
+        self.n_streams, self.max_h, self.max_w = int(n_streams), int(max_h), int(max_w)
+        N.check(self._L.bx_ecc_create(self.n_streams, self.max_h, self.max_w, C.byref(self._h)),
+                "bx_ecc_create")
+
+    def close(self):
+        if self._h:
+            self._L.bx_ecc_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream: int = -1):
+        from .engine import _current_stream
+
+        N.check(self._L.bx_ecc_reset(self._h, int(stream), _current_stream()), "bx_ecc_reset")
+
+    def status(self) -> int:
+        st = C.c_int(0)
+        N.check(self._L.bx_ecc_status(self._h, C.byref(st)), "bx_ecc_status")
+        return st.value
+
+    def state(self, stream: int = 0, planes: bool = True):
+        """(has_prev, grey uint8 [h, w], gx float32 [h, w], gy float32 [h, w]) of a stream: its
+        previous image and the gradients of the last frame it was given (synchronises)."""
+        hp, hh, ww = C.c_int(0), C.c_int(0), C.c_int(0)
+        cap = self.max_h * self.max_w
+        g = np.zeros(cap, np.uint8)
+        gx, gy = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        N.check(self._L.bx_ecc_state_host(
+            self._h, int(stream), C.byref(hp), C.byref(hh), C.byref(ww),
+            g.ctypes.data if planes else None, gx.ctypes.data if planes else None,
+            gy.ctypes.data if planes else None), "bx_ecc_state_host")
+        h, w = hh.value, ww.value
+        if not planes or not hp.value:
+            return bool(hp.value), None, None, None
+        cut = lambda a: a[: h * w].reshape(h, w).copy()  # noqa: E731
+        return True, cut(g), cut(gx), cut(gy)
+
+
+class EccBatch:
+    """ECC for ``n_streams`` cameras: one ``apply`` aligns a frame of each listed stream to that
+    stream's previous frame, all on the current stream.  With device inputs (frames a CUDA tensor,
+    ``streams`` ``None`` or a CUDA tensor, ``init_warps`` ``None`` or a CUDA tensor) nothing inside
+    synchronises the host with the device: two launches and a few device fills are enqueued.  A
+    numpy ``frames`` array, a list of ``streams`` or host ``init_warps`` are copied to the device
+    first, and that copy waits for the stream.
+
+    ``max_h`` / ``max_w`` bound the working image (after the resize); left ``None`` they are taken
+    from the first frames.  The other arguments are ``ECC``'s.
+    """
+
+    def __init__(self, n_streams: int, warp_mode: int = MOTION_TRANSLATION, eps: float = 1e-5,
+                 max_iter: int = 100, scale=0.15, align: bool = False, grayscale: bool = True,
+                 max_h: int | None = None, max_w: int | None = None):
+        if align:
+            raise NotImplementedError("align=True (prev_img_aligned) is not supported")
+        if n_streams < 1:
+            raise ValueError("n_streams must be at least 1")
+        self.n_streams = int(n_streams)
+        self.warp_mode, self.eps, self.max_iter = warp_mode, float(eps), int(max_iter)
+        self.scale, self.grayscale = scale, grayscale
+        self._cap = (max_h, max_w)
+        self._handle = None
+        self._all = None  # device arange(n_streams)
+        self._eye = None  # device [n_streams, 6] identity warps
+
+    def _ensure(self, H: int, W: int) -> _Handle:
+        if self._handle is None:
+            h, w = work_size(H, W, self.scale)
+            self._handle = _Handle(self.n_streams, self._cap[0] or h, self._cap[1] or w)
+        return self._handle
+
+    def close(self):
+        if self._handle is not None:
+            self._handle.close()
+            self._handle = None
+
+    def reset(self, stream: int = -1):
+        """Forget the previous image of one stream (default: of all)."""
+        if self._handle is not None:
+            self._handle.reset(stream)
+
+    def status(self) -> int:
+        return 0 if self._handle is None else self._handle.status()
+
+    def state(self, stream: int = 0):
+        if self._handle is None:
+            return False, None, None, None
+        return self._handle.state(stream)
+
+    def apply(self, frames, streams=None, init_warps=None):
+        """frames: numpy array or CUDA uint8 tensor ``[n, H, W, 3]`` (BGR) or ``[n, H, W]``
+        (grey); streams: the stream of each frame (default ``0..n-1``), all different.  A list or
+        numpy ``streams`` is checked here (range, duplicates: ``ValueError``).  A CUDA tensor
+        cannot be read without a synchronisation, so it is not checked: an index out of range
+        skips that frame and latches ``status()``; an index listed twice is undefined behaviour
+        (two workgroups race on that stream's images; the results of that stream are garbage, the
+        accesses stay in bounds).
+
+        Returns CUDA tensors over all streams: warps float64 ``[n_streams, 6]`` (row-major 2x3,
+        the engines' ``warps`` argument), rho float64, iterations int32, code int32 ``[n_streams]``
+        (``OK`` / ``FIRST_FRAME`` / ``NOT_CONVERGED``; ``NO_FRAME`` with the identity warp for a
+        stream that was not listed).  ``init_warps`` (``[n_streams, 6]``, working scale) starts
+        the iterations elsewhere than at the identity.
+        """
+        import torch
+
+        from .engine import _current_stream
+
+        mode = _check_mode(self.warp_mode)
+        scale = _scale_arg(self.scale)
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8:
+                raise ValueError("frames must be uint8")
+            n, H, W, ch = _frame_dims(frames.shape, self.grayscale)
+            hd = self._ensure(H, W)
+            frames = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
+        else:
+            if frames.dtype != torch.uint8 or not frames.is_cuda:
+                raise ValueError("frames must be a numpy array or a CUDA uint8 tensor")
+            n, H, W, ch = _frame_dims(frames.shape, self.grayscale)
+            hd = self._ensure(H, W)
+            frames = frames.contiguous()
+        S = self.n_streams
+        if streams is None:
+            if n > S:
+                raise ValueError(f"capacity exceeded: {n} frames for {S} streams")
+            if self._all is None:
+                self._all = torch.arange(S, dtype=torch.int32, device="cuda")
+            sd = self._all
+        elif isinstance(streams, torch.Tensor) and streams.is_cuda:
+            sd = streams.to(torch.int32).contiguous()
+        else:
+            sh = np.asarray(streams, np.int64).reshape(-1)
+            if sh.size and (sh.min() < 0 or sh.max() >= S):
+                raise ValueError("invalid argument: stream index out of range")
+            if np.unique(sh).size != sh.size:
+                raise ValueError("invalid argument: a stream is listed twice")
+            sd = torch.from_numpy(sh.astype(np.int32)).cuda()
+        if streams is not None and sd.numel() != n:
+            raise ValueError(f"{n} frames but {sd.numel()} stream indices")
+        iw = None
+        if init_warps is not None:
+            iw = torch.as_tensor(np.asarray(init_warps, np.float64).reshape(S, 6)
+                                 if not isinstance(init_warps, torch.Tensor) else init_warps)
+            iw = iw.to(device="cuda", dtype=torch.float64).reshape(S, 6).contiguous()
+        if self._eye is None:  # device fills only: a tensor built from host values would copy
+            self._eye = torch.zeros(S, 6, dtype=torch.float64, device="cuda")  # and synchronise
+            self._eye[:, 0] = 1.0
+            self._eye[:, 4] = 1.0
+        warps = self._eye.clone()
+        rho = torch.zeros(S, dtype=torch.float64, device="cuda")
+        iters = torch.zeros(S, dtype=torch.int32, device="cuda")
+        code = torch.full((S,), NO_FRAME, dtype=torch.int32, device="cuda")
+        N.check(hd._L.bx_ecc_apply(
+            hd._h, n, H, W, ch, frames.data_ptr(), sd.data_ptr(), mode, self.eps, self.max_iter,
+            scale, None if iw is None else iw.data_ptr(), warps.data_ptr(), rho.data_ptr(),
+            iters.data_ptr(), code.data_ptr(), _current_stream()), "bx_ecc_apply")
+        self._keep = (frames, sd, iw)  # alive until the next call: the launches are asynchronous
+        return warps, rho, iters, code
+
+
+class ECC:
+    """The reference's ``ECC`` (``motion/cmc/ecc.py``): ``apply(img, dets)`` returns the 2x3
+    float32 warp from the previous frame to this one, the identity on the first frame and when the
+    iteration does not converge.  ``dets`` is ignored, as in the reference.  One camera; the device
+    handle is built at the first frame from the image size.  ``last`` holds the float64 warp, rho,
+    the iteration count and the code of the last call."""
+
+    def __init__(self, warp_mode: int = MOTION_TRANSLATION, eps: float = 1e-5, max_iter: int = 100,
+                 scale: float = 0.15, align: bool = False, grayscale: bool = True) -> None:
+        self.align = align
+        self.grayscale = grayscale
+        self.scale = scale
+        self.warp_mode = warp_mode
+        self.termination_criteria = (3, max_iter, eps)  # cv2.TERM_CRITERIA_EPS | _COUNT
+        self.prev_img_aligned = None
+        self.last = None
+        self._handle = None
+
+    @property
+    def prev_img(self):
+        """The previous grey image at working scale (None before the first frame)."""
+        if self._handle is None:
+            return None
+        return self._handle.state(0)[1]
+
+    def reset(self):
+        if self._handle is not None:
+            self._handle.reset(0)
+
+    def apply(self, img: np.ndarray, dets: np.ndarray = None, init_warp=None) -> np.ndarray:
+        mode = _check_mode(self.warp_mode)
+        if self.align:
+            raise NotImplementedError("align=True (prev_img_aligned) is not supported")
+        scale = _scale_arg(self.scale)
+        img = np.ascontiguousarray(img)
+        if img.dtype != np.uint8:
+            raise ValueError("img must be uint8")
+        if img.ndim == 2:
+            H, W, ch = img.shape[0], img.shape[1], 1
+        else:
+            _, H, W, ch = _frame_dims((1,) + img.shape, self.grayscale)
+        if self._handle is None:
+            h, w = work_size(H, W, self.scale)
+            self._handle = _Handle(1, h, w)
+        hd = self._handle
+        _, max_iter, eps = self.termination_criteria
+        streams = np.zeros(1, np.int32)
+        warp = np.zeros((1, 6), np.float64)
+        rho = np.zeros(1, np.float64)
+        iters, code = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        iw = None if init_warp is None else np.ascontiguousarray(init_warp, np.float64).reshape(1, 6)
+        from .engine import _current_stream
+
+        N.check(hd._L.bx_ecc_apply_host(
+            hd._h, 1, H, W, ch, img.ctypes.data, streams.ctypes.data, mode, float(eps),
+            int(max_iter), scale, None if iw is None else iw.ctypes.data, warp.ctypes.data,
+            rho.ctypes.data, iters.ctypes.data, code.ctypes.data, _current_stream()),
+            "bx_ecc_apply_host")
+        self.last = {"warp": warp.reshape(2, 3).copy(), "rho": float(rho[0]),
+                     "iterations": int(iters[0]), "code": int(code[0])}
+        return warp.reshape(2, 3).astype(np.float32)
+
+
+def get_cmc_method(cmc_method):
+    """``motion/cmc/__init__.py``'s lookup: the class of a method name, ``None`` for an unknown
+    one.  Only ECC runs here; the feature-based methods name themselves."""
+    if cmc_method == "ecc":
+        return ECC
+    if cmc_method in ("orb", "sof", "sift"):
+        raise NotImplementedError(f"cmc method '{cmc_method}' is not supported: it is feature-based "
+                                  "and defined by OpenCV; assign your own object to tracker.cmc")
+    return None
