@@ -28,6 +28,7 @@ HEADER_FEED = REPO / "include" / "bxfeed.h"
 HEADER_CLASSES = REPO / "include" / "bxclasses.h"
 HEADER_EVAL = REPO / "include" / "bxeval.h"
 HEADER_CMC = REPO / "include" / "bxcmc.h"
+HEADER_REID = REPO / "include" / "bxreid.h"
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -39,7 +40,7 @@ HIPCC_FLAGS = [
 ]
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
            "bx_strongsort.hip", "bx_deepocsort.hip", "bx_hybridsort.hip", "bx_gsi.hip", "bx_feed.hip",
-           "bx_classes.hip", "bx_eval.hip", "bx_cmc.hip",
+           "bx_classes.hip", "bx_eval.hip", "bx_cmc.hip", "bx_reid.hip",
            "bx_io.cpp"]
 
 
@@ -265,6 +266,7 @@ EXPORTS = [
     "bx_eval_create", "bx_eval_destroy", "bx_eval_capacity", "bx_eval_run_host",
     "bx_ecc_create", "bx_ecc_destroy", "bx_ecc_reset", "bx_ecc_work_size", "bx_ecc_apply",
     "bx_ecc_apply_host", "bx_ecc_status", "bx_ecc_state_host",
+    "bx_reid_crops", "bx_reid_normalize",
 ]
 
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -482,6 +484,9 @@ _SIGS = {
                            C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "bx_ecc_status": ([_vp, _ip], C.c_int),
     "bx_ecc_state_host": ([_vp, C.c_int, _ip, _ip, _ip, _vp, _vp, _vp], C.c_int),
+    "bx_reid_crops": ([_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int]
+                      + [C.c_float] * 6 + [C.c_int, _vp, _vp, _vp], C.c_int),
+    "bx_reid_normalize": ([_vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, C.c_int, _vp], C.c_int),
 }
 
 _lib = None

@@ -22,6 +22,7 @@
 #include "../../include/bxassoc.h"
 #include "../../include/bxcmc.h"
 #include "bx_device.h"
+#include "bx_resize.h"
 
 int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
 
@@ -75,25 +76,7 @@ __device__ __forceinline__ unsigned grey_at(const uint8_t* f, int W, int ch, int
   return (1868u * p[0] + 9617u * p[1] + 4899u * p[2] + 8192u) >> 14;
 }
 
-// source index pair and 11-bit weight of output index d on an axis of source length L
-__device__ __forceinline__ void axis_tap(int d, double scale, int L, int& s0, int& s1,
-                                         unsigned& q) {
-  const double f = ((double)d + 0.5) / scale - 0.5;
-  const double fl = floor(f);
-  double a = f - fl;
-  if (fl < 0.0) {
-    s0 = 0;
-    a = 0.0;
-  } else if (fl >= (double)(L - 1)) {
-    s0 = L - 1;
-    a = 0.0;
-  } else {
-    s0 = (int)fl;
-  }
-  s1 = min(s0 + 1, L - 1);
-  q = (unsigned)rint(a * 2048.0);
-}
-
+// (axis_tap and blend_q11, the resize rule itself, live in bx_resize.h: the ReID crops share them)
 __device__ __forceinline__ unsigned work_pixel(const PrepArgs& a, const uint8_t* f, int x, int y) {
   if (!a.resize) return grey_at(f, a.W, a.ch, x, y);
   int x0, x1, y0, y1;
@@ -102,8 +85,7 @@ __device__ __forceinline__ unsigned work_pixel(const PrepArgs& a, const uint8_t*
   axis_tap(y, a.scale, a.H, y0, y1, qy);
   const unsigned g00 = grey_at(f, a.W, a.ch, x0, y0), g01 = grey_at(f, a.W, a.ch, x1, y0);
   const unsigned g10 = grey_at(f, a.W, a.ch, x0, y1), g11 = grey_at(f, a.W, a.ch, x1, y1);
-  const unsigned px = 2048u - qx, py = 2048u - qy;
-  return (g00 * px * py + g01 * qx * py + g10 * px * qy + g11 * qx * qy + (1u << 21)) >> 22;
+  return blend_q11(g00, g01, g10, g11, qx, qy);
 }
 
 __device__ __forceinline__ int reflect101(int i, int n) {

@@ -38,6 +38,19 @@ def class_warps(cmc, img, dets: np.ndarray, nr_classes: int, conv=_reshape_warp)
     return out
 
 
+def model_embs(tracker, dets, img, embs, wanted: bool = True):
+    """The embeddings of an update: the caller's ``embs``, or, when they are missing and a ReID
+    backend is attached (``tracker.model``, e.g. a ``boxmot_amd.ReidFrontEnd``), the backend's
+    ``get_features(dets[:, 0:4], img)`` as in the reference (botsort.py:107-111).  The reference
+    embeds only the detections that pass its thresholds; rows are independent, so embedding all of
+    them gives those rows the same values.  Without a model ``None`` stays ``None`` and the
+    tracker raises as before."""
+    model = getattr(tracker, "model", None)
+    if embs is not None or model is None or not wanted or not len(dets):
+        return embs
+    return model.get_features(np.asarray(dets)[:, 0:4], img)
+
+
 def _pow2(n: int) -> int:
     return 1 << max(0, int(n) - 1).bit_length()
 

@@ -20,7 +20,7 @@ from __future__ import annotations
 import numpy as np
 
 from ..engine import BoostEngine, BoostParams
-from .basetracker import BaseTracker, CapacityGuard, _with_index, class_warps
+from .basetracker import BaseTracker, CapacityGuard, _with_index, class_warps, model_embs
 
 
 def _boost_warp(w) -> np.ndarray:
@@ -44,6 +44,7 @@ class BoostTrack(BaseTracker):
     # KalmanBoxTracker.count is class-global and never reset by BoostTrack (boosttrack.py:50,
     # 53-56): every instance continues the same id sequence.
     _id_count = 0
+    model = None  # a ReID backend (get_features(xyxys, img)): embeds when `embs` is missing
 
     def __init__(self, reid_weights=None, device=None, half: bool = False, max_age: int = 60,
                  min_hits: int = 3, det_thresh: float = 0.6, iou_threshold: float = 0.3,
@@ -98,6 +99,7 @@ class BoostTrack(BaseTracker):
     @BaseTracker.per_class_decorator
     def update(self, dets: np.ndarray, img: np.ndarray, embs: np.ndarray = None) -> np.ndarray:
         self.check_inputs(dets, img, embs)
+        embs = model_embs(self, dets, img, embs, self.with_reid)
         if self.with_reid and embs is None and len(dets):
             raise ValueError("BoostTrack with_reid on the engine needs precomputed embeddings")
         if self.engine is None:  # with_reid: the embedding dimension arrives with the first frame

@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 
 from ..engine import Engine, EngineParams
-from .basetracker import BaseTracker, CapacityGuard, _with_index, class_warps
+from .basetracker import BaseTracker, CapacityGuard, _with_index, class_warps, model_embs
 
 
 class IdentityCMC:
@@ -27,6 +27,8 @@ def _xywh_box(mean):
 
 
 class BotSort(BaseTracker):
+    model = None  # a ReID backend (get_features(xyxys, img)): embeds when `embs` is missing
+
     def __init__(self, reid_weights=None, device=None, half: bool = False,
                  per_class: bool = False, track_high_thresh: float = 0.5,
                  track_low_thresh: float = 0.1, new_track_thresh: float = 0.6,
@@ -65,6 +67,7 @@ class BotSort(BaseTracker):
     @BaseTracker.per_class_decorator
     def update(self, dets: np.ndarray, img: np.ndarray, embs: np.ndarray = None) -> np.ndarray:
         self.check_inputs(dets, img, embs)
+        embs = model_embs(self, dets, img, embs, self.with_reid)
         if self.with_reid and dets.shape[0] and embs is None:
             raise ValueError("BotSort(with_reid=True) on the MI355X engine needs `embs`: ReID "
                              "inference is outside the association path")

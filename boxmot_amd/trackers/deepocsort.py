@@ -33,7 +33,7 @@ import numpy as np
 
 from ..engine import DeepOcsortEngine, DeepOcsortParams
 from ..iou import KINDS
-from .basetracker import BaseTracker, CapacityGuard, ClassMapGuard
+from .basetracker import BaseTracker, CapacityGuard, ClassMapGuard, model_embs
 from .botsort import IdentityCMC
 
 
@@ -42,6 +42,7 @@ class DeepOcSort(BaseTracker):
     # KalmanBoxTracker.count is a class attribute shared by every instance and set to 1 by each
     # DeepOcSort constructor (deepocsort.py:56,117-118,305): mirrored here.
     _id_count = 1
+    model = None  # a ReID backend (get_features(xyxys, img)): embeds when `embs` is missing
 
     def __init__(self, reid_weights=None, device=None, half: bool = False,
                  per_class: bool = False, det_thresh: float = 0.3, max_age: int = 30,
@@ -101,6 +102,7 @@ class DeepOcSort(BaseTracker):
     def update(self, dets: np.ndarray, img: np.ndarray, embs: np.ndarray = None) -> np.ndarray:
         self.check_inputs(dets, img, embs)
         n = int(dets.shape[0])
+        embs = model_embs(self, dets, img, embs, not self.embedding_off)
         if not self.embedding_off and n and embs is None:
             raise ValueError("DeepOcSort(embedding_off=False) on the MI355X engine needs `embs`: "
                              "ReID inference is outside the association path")

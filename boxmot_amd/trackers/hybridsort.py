@@ -31,7 +31,7 @@ import numpy as np
 
 from ..engine import HybridsortEngine, HybridsortParams
 from ..iou import KINDS
-from .basetracker import BaseTracker, CapacityGuard, ClassMapGuard
+from .basetracker import BaseTracker, CapacityGuard, ClassMapGuard, model_embs
 
 
 class HybridSort(BaseTracker):
@@ -40,6 +40,7 @@ class HybridSort(BaseTracker):
     # HybridSort constructor (hybridsort.py:115,176-177,418); output ids are count + 1: mirrored
     # here as a counter that starts at 1.
     _id_count = 1
+    model = None  # a ReID backend (get_features(xyxys, img)): embeds when `embs` is missing
 
     def __init__(self, reid_weights, device, half, det_thresh, per_class: bool = False,
                  max_age: int = 30, min_hits: int = 3, iou_threshold: float = 0.3,
@@ -94,6 +95,7 @@ class HybridSort(BaseTracker):
     def update(self, dets: np.ndarray, img: np.ndarray, embs: np.ndarray = None) -> np.ndarray:
         self.check_inputs(dets, img, embs)
         n = int(dets.shape[0])
+        embs = model_embs(self, dets, img, embs)
         if n and embs is None:
             raise ValueError("HybridSort on the MI355X engine needs `embs`: ReID inference is "
                              "outside the association path")

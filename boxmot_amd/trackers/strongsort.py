@@ -26,7 +26,7 @@ import numpy as np
 
 from ..engine import SsEngine, SsParams
 from ..occlusion import OcclusionHandler
-from .basetracker import BaseTracker, CapacityGuard
+from .basetracker import BaseTracker, CapacityGuard, model_embs
 from .boosttrack import IdentityCMC
 
 
@@ -37,6 +37,8 @@ def _born_confirmed() -> bool:
 
 
 class StrongSort:
+    model = None  # a ReID backend (get_features(xyxys, img)): embeds when `embs` is missing
+
     def __init__(self, reid_weights=None, device=None, half: bool = False, per_class: bool = False,
                  min_conf: float = 0.1, max_cos_dist=0.15, max_iou_dist=0.7, max_age=50,
                  n_init=2, nn_budget=150, mc_lambda=0.995, ema_alpha=0.9, conf_thresh_high=0.7,
@@ -86,6 +88,7 @@ class StrongSort:
         assert dets.shape[1] == 6, "Unsupported 'dets' 2nd dimension lenght, valid lenghts is 6"
         if embs is not None:
             assert dets.shape[0] == embs.shape[0], "Missmatch between detections and embeddings sizes"
+        embs = model_embs(self, dets, img, embs)
         if embs is None and np.any(dets[:, 4] >= self.min_conf):
             raise ValueError("StrongSort on the engine needs precomputed embeddings")
         self.frame_count += 1
