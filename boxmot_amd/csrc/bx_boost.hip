@@ -31,11 +31,10 @@
 
 #include "../../include/bxboost.h"
 #include "bx_device.h"
+#include "bx_host.h"
 
 using namespace bx;
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
-hipError_t bx_lds_attr(const void* kern, size_t bytes);  // bx_engine.hip (never lowers a limit)
 
 namespace {
 
@@ -1066,21 +1065,9 @@ struct bx_boost {
   bx_boost_config cfg;
   void* arena = nullptr;
   size_t lds = 0;
-  // host-path staging
-  float* h_dets = nullptr;
-  int* h_off = nullptr;
-  double* h_embs = nullptr;
-  double* h_warp = nullptr;
-  double* h_out = nullptr;
-  int* h_cnt = nullptr;
-  // pinned mirrors for update_host (asynchronous copies, one sync per frame) and the counters
-  // row of the last update_host sequence (bx_boost_counters_host answers from it)
-  float* p_dets = nullptr;
-  double* p_embs = nullptr;
-  double* p_warp = nullptr;
-  double* p_out = nullptr;
-  int* p_cnt = nullptr;
-  int* p_sq = nullptr;
+  // update_host staging; sg.p_sq: the counters row of the last update_host sequence
+  // (bx_boost_counters_host answers from it)
+  BxStaging sg;
   int cache_seq = -1;
   // per_class host path (bx_boost_update_classes_host): class offsets [C][2], counts [C], the
   // held frame counter
@@ -1089,36 +1076,8 @@ struct bx_boost {
   int* h_ccnt = nullptr;
   int* h_hold = nullptr;
   double* h_cwarp = nullptr;  // [C][6] the class calls' warps
-  // timing probe
-  int probe_stage = -1;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  int ev_used = 0;
+  BxProbe probe;  // stages: 0 embcost, 1 frame, 2 feature
 };
-
-#define BCHK(x)                                                                    \
-  do {                                                                             \
-    hipError_t _e = (x);                                                           \
-    if (_e != hipSuccess)                                                          \
-      return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
-
-static int probe_begin(bx_boost* e, int stage, hipStream_t st) {
-  if (e->probe_stage != stage) return BX_OK;
-  if (e->ev_used == (int)e->ev.size()) {
-    hipEvent_t a, b;
-    BCHK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-    BCHK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
-    e->ev.push_back({a, b});
-  }
-  BCHK(hipEventRecord(e->ev[e->ev_used].first, st));
-  return BX_OK;
-}
-
-static int probe_end(bx_boost* e, int stage, hipStream_t st) {
-  if (e->probe_stage != stage) return BX_OK;
-  BCHK(hipEventRecord(e->ev[e->ev_used++].second, st));
-  return BX_OK;
-}
 
 static int launch(bx_boost* e, int seq0, int nseq, const float* dets, const int* off,
                   const double* embs, const double* warps, double* out, int* cnt, hipStream_t st) {
@@ -1126,23 +1085,23 @@ static int launch(bx_boost* e, int seq0, int nseq, const float* dets, const int*
   int rc;
   if (d.reid) {
     if (!embs) return bx_record_error(BX_ERR_SHAPE, "with_reid BoostTrack needs embeddings");
-    if ((rc = probe_begin(e, 0, st))) return rc;
+    if ((rc = e->probe.begin(0, st))) return rc;
     hipLaunchKernelGGL(boost_embcost_kernel, dim3(nseq, ec_tiles(d.D, d.T)), dim3(256), 0, st, d,
                        seq0, off, embs);
-    BCHK(hipGetLastError());
-    if ((rc = probe_end(e, 0, st))) return rc;
+    BX_HIPCHK(hipGetLastError());
+    if ((rc = e->probe.end(0, st))) return rc;
   }
-  if ((rc = probe_begin(e, 1, st))) return rc;
+  if ((rc = e->probe.begin(1, st))) return rc;
   hipLaunchKernelGGL(boost_frame_kernel, dim3(nseq), dim3(frame_threads(nseq)), e->lds, st, d, seq0, dets, off,
                      d.use_ecc ? warps : nullptr, out, cnt);
-  BCHK(hipGetLastError());
-  if ((rc = probe_end(e, 1, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(1, st))) return rc;
   if (d.reid) {
-    if ((rc = probe_begin(e, 2, st))) return rc;
+    if ((rc = e->probe.begin(2, st))) return rc;
     hipLaunchKernelGGL(boost_feature_kernel, dim3((d.D + 3) / 4, nseq), dim3(256), 0, st, d, seq0,
                        embs);
-    BCHK(hipGetLastError());
-    if ((rc = probe_end(e, 2, st))) return rc;
+    BX_HIPCHK(hipGetLastError());
+    if ((rc = e->probe.end(2, st))) return rc;
   }
   return BX_OK;
 }
@@ -1161,116 +1120,108 @@ int bx_boost_create(const bx_boost_config* c, bx_boost** out) {
     return bx_record_error(BX_ERR_NO_DEVICE, "no HIP device visible");
   bx_boost* e = new bx_boost();
   e->cfg = *c;
-  BstDev& d = e->dev;
-  d.S = c->n_seq;
-  d.T = c->track_cap;
-  d.D = c->det_cap;
-  d.N = d.T > d.D ? d.T : d.D;
-  d.reid = c->with_reid ? 1 : 0;
-  d.F = d.reid ? c->emb_dim : 0;
-  d.det_thresh = c->det_thresh;
-  d.iou_thr = c->iou_threshold;
-  d.min_box_area = c->min_box_area;
-  d.ar_thresh = c->aspect_ratio_thresh;
-  d.l_iou = c->lambda_iou;
-  d.l_mhd = c->lambda_mhd;
-  d.l_shape = c->lambda_shape;
-  d.dlo_coef = c->dlo_boost_coef;
-  d.max_age = c->max_age;
-  d.min_hits = c->min_hits;
-  d.use_ecc = c->use_ecc != 0;
-  d.use_dlo = c->use_dlo_boost != 0;
-  d.use_duo = c->use_duo_boost != 0;
-  d.s_sim_corr = c->s_sim_corr != 0;
-  d.rich_s = c->use_rich_s != 0;
-  d.use_sb = c->use_sb != 0;
-  d.use_vt = c->use_vt != 0;
-  // LDS: the fixed part plus as much cost matrix as keeps every sequence's workgroup resident
-  // at once (256 CUs; at least 40 KB, i.e. 4 workgroups per CU, at most 152 KB)
-  long cap = 160L * 1024 / ((d.S + 255) / 256);
-  if (cap > 152L * 1024) cap = 152L * 1024;
-  if (cap < 40L * 1024) cap = 40L * 1024;
-  // the frame's track rows in LDS too when the cap leaves room for them beside the cost matrix
-  // (up to 512 sequences: cap >= 80 KB)
-  d.tb_lds = 0;
-  size_t fixed = lds_bytes(d.D, d.T, d.N, 0, 0);
-  if (d.S <= 512 && (long)(fixed + (size_t)d.T * TBB * 8) + 64 * 8 <= cap) {
-    d.tb_lds = 1;
-    fixed = lds_bytes(d.D, d.T, d.N, 0, 1);
-  }
-  long budget = cap - (long)fixed;
-  int cl = budget > 0 ? (int)(budget / 8) : 0;
-  if (cl > d.D * d.T) cl = d.D * d.T;
-  if (cl < 64) cl = 64;
-  d.cost_lds = cl;
-  e->lds = lds_bytes(d.D, d.T, d.N, cl, d.tb_lds);
-  if (e->lds > 160 * 1024) {
-    delete e;
-    return bx_record_error(BX_ERR_INVALID, "track_cap/det_cap too large for one workgroup's LDS");
-  }
-  const bool need_g = (long)d.D * d.T > cl;
-  // get_confidence table: 0.9 ** k for k <= max_age + 1 (a track is dropped once its
-  // time_since_update exceeds max_age), from the host's libm pow like Python's float pow
-  d.ntab = c->max_age + 8;
-  std::vector<double> tab(d.ntab);
-  for (int k = 0; k < d.ntab; k++) tab[k] = std::pow(0.9, (double)k);
-  const size_t S = d.S, T = d.T, D = d.D, F = d.F;
-  size_t off = 0;
-  auto carve_b = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_trk = carve_b(S * T * sizeof(BstTrk));
-  const size_t o_sq = carve_b(S * SQB * sizeof(int));
-  const size_t o_ord = carve_b(S * T * sizeof(int));
-  const size_t o_tb = carve_b(S * T * TBB * sizeof(double));
-  const size_t o_cg = need_g ? carve_b(S * D * T * sizeof(double)) : 0;
-  // the DLO numerators spill only with use_dlo && rich_s (boost_frame_kernel's E staging)
-  const bool need_eg = need_g && d.use_dlo && d.rich_s;
-  const size_t o_eg = need_eg ? carve_b(S * D * T * sizeof(double)) : 0;
-  const size_t o_ec = d.reid ? carve_b(S * D * T * sizeof(double)) : 0;
-  const size_t o_emb = d.reid ? carve_b(S * T * F * sizeof(double)) : 0;
-  const size_t o_rec = d.reid ? carve_b(S * D * 2 * sizeof(int)) : 0;
-  const size_t o_reca = d.reid ? carve_b(S * D * sizeof(double)) : 0;
-  const size_t o_tab = carve_b(tab.size() * sizeof(double));
-  const size_t o_st = carve_b(sizeof(int) * 4);
+  // everything that can fail runs in `fill`: a failure frees what was allocated so far
+  auto fill = [&]() -> int {
+    BstDev& d = e->dev;
+    d.S = c->n_seq;
+    d.T = c->track_cap;
+    d.D = c->det_cap;
+    d.N = d.T > d.D ? d.T : d.D;
+    d.reid = c->with_reid ? 1 : 0;
+    d.F = d.reid ? c->emb_dim : 0;
+    d.det_thresh = c->det_thresh;
+    d.iou_thr = c->iou_threshold;
+    d.min_box_area = c->min_box_area;
+    d.ar_thresh = c->aspect_ratio_thresh;
+    d.l_iou = c->lambda_iou;
+    d.l_mhd = c->lambda_mhd;
+    d.l_shape = c->lambda_shape;
+    d.dlo_coef = c->dlo_boost_coef;
+    d.max_age = c->max_age;
+    d.min_hits = c->min_hits;
+    d.use_ecc = c->use_ecc != 0;
+    d.use_dlo = c->use_dlo_boost != 0;
+    d.use_duo = c->use_duo_boost != 0;
+    d.s_sim_corr = c->s_sim_corr != 0;
+    d.rich_s = c->use_rich_s != 0;
+    d.use_sb = c->use_sb != 0;
+    d.use_vt = c->use_vt != 0;
+    // LDS: the fixed part plus as much cost matrix as keeps every sequence's workgroup resident
+    // at once (256 CUs; at least 40 KB, i.e. 4 workgroups per CU, at most 152 KB)
+    long cap = 160L * 1024 / ((d.S + 255) / 256);
+    if (cap > 152L * 1024) cap = 152L * 1024;
+    if (cap < 40L * 1024) cap = 40L * 1024;
+    // the frame's track rows in LDS too when the cap leaves room for them beside the cost matrix
+    // (up to 512 sequences: cap >= 80 KB)
+    d.tb_lds = 0;
+    size_t fixed = lds_bytes(d.D, d.T, d.N, 0, 0);
+    if (d.S <= 512 && (long)(fixed + (size_t)d.T * TBB * 8) + 64 * 8 <= cap) {
+      d.tb_lds = 1;
+      fixed = lds_bytes(d.D, d.T, d.N, 0, 1);
+    }
+    long budget = cap - (long)fixed;
+    int cl = budget > 0 ? (int)(budget / 8) : 0;
+    if (cl > d.D * d.T) cl = d.D * d.T;
+    if (cl < 64) cl = 64;
+    d.cost_lds = cl;
+    e->lds = lds_bytes(d.D, d.T, d.N, cl, d.tb_lds);
+    if (e->lds > 160 * 1024)
+      return bx_record_error(BX_ERR_INVALID, "track_cap/det_cap too large for one workgroup's LDS");
+    const bool need_g = (long)d.D * d.T > cl;
+    // get_confidence table: 0.9 ** k for k <= max_age + 1 (a track is dropped once its
+    // time_since_update exceeds max_age), from the host's libm pow like Python's float pow
+    d.ntab = c->max_age + 8;
+    std::vector<double> tab(d.ntab);
+    for (int k = 0; k < d.ntab; k++) tab[k] = std::pow(0.9, (double)k);
+    const size_t S = d.S, T = d.T, D = d.D, F = d.F;
+    BxCarve carve_b;
+    const size_t o_trk = carve_b(S * T * sizeof(BstTrk));
+    const size_t o_sq = carve_b(S * SQB * sizeof(int));
+    const size_t o_ord = carve_b(S * T * sizeof(int));
+    const size_t o_tb = carve_b(S * T * TBB * sizeof(double));
+    const size_t o_cg = need_g ? carve_b(S * D * T * sizeof(double)) : 0;
+    // the DLO numerators spill only with use_dlo && rich_s (boost_frame_kernel's E staging)
+    const bool need_eg = need_g && d.use_dlo && d.rich_s;
+    const size_t o_eg = need_eg ? carve_b(S * D * T * sizeof(double)) : 0;
+    const size_t o_ec = d.reid ? carve_b(S * D * T * sizeof(double)) : 0;
+    const size_t o_emb = d.reid ? carve_b(S * T * F * sizeof(double)) : 0;
+    const size_t o_rec = d.reid ? carve_b(S * D * 2 * sizeof(int)) : 0;
+    const size_t o_reca = d.reid ? carve_b(S * D * sizeof(double)) : 0;
+    const size_t o_tab = carve_b(tab.size() * sizeof(double));
+    const size_t o_st = carve_b(sizeof(int) * 4);
 #ifdef BX_PHASE_TIMING
-  const size_t o_dbg = carve_b(S * BST_DBG * sizeof(unsigned long long));
+    const size_t o_dbg = carve_b(S * BST_DBG * sizeof(unsigned long long));
 #endif
-  if (hipMalloc(&e->arena, off) != hipSuccess) {
-    delete e;
-    return bx_record_error(BX_ERR_HIP, "hipMalloc of the BoostTrack arena failed");
-  }
-  BCHK(hipMemset(e->arena, 0, off));
-  char* base = (char*)e->arena;
-  d.trk = (BstTrk*)(base + o_trk);
-  d.seqst = (int*)(base + o_sq);
-  d.order = (int*)(base + o_ord);
-  d.tb = (double*)(base + o_tb);
-  d.cost_g = need_g ? (double*)(base + o_cg) : nullptr;
-  d.e_g = need_eg ? (double*)(base + o_eg) : nullptr;
-  d.ec = d.reid ? (double*)(base + o_ec) : nullptr;
-  d.emb = d.reid ? (double*)(base + o_emb) : nullptr;
-  d.rec = d.reid ? (int*)(base + o_rec) : nullptr;
-  d.rec_a = d.reid ? (double*)(base + o_reca) : nullptr;
-  d.conf_tab = (const double*)(base + o_tab);
-  d.status = (int*)(base + o_st);
+    if (hipMalloc(&e->arena, carve_b.off) != hipSuccess)
+      return bx_record_error(BX_ERR_HIP, "hipMalloc of the BoostTrack arena failed");
+    BX_HIPCHK(hipMemset(e->arena, 0, carve_b.off));
+    char* base = (char*)e->arena;
+    d.trk = (BstTrk*)(base + o_trk);
+    d.seqst = (int*)(base + o_sq);
+    d.order = (int*)(base + o_ord);
+    d.tb = (double*)(base + o_tb);
+    d.cost_g = need_g ? (double*)(base + o_cg) : nullptr;
+    d.e_g = need_eg ? (double*)(base + o_eg) : nullptr;
+    d.ec = d.reid ? (double*)(base + o_ec) : nullptr;
+    d.emb = d.reid ? (double*)(base + o_emb) : nullptr;
+    d.rec = d.reid ? (int*)(base + o_rec) : nullptr;
+    d.rec_a = d.reid ? (double*)(base + o_reca) : nullptr;
+    d.conf_tab = (const double*)(base + o_tab);
+    d.status = (int*)(base + o_st);
 #ifdef BX_PHASE_TIMING
-  d.dbg = (unsigned long long*)(base + o_dbg);
+    d.dbg = (unsigned long long*)(base + o_dbg);
 #else
-  d.dbg = nullptr;
+    d.dbg = nullptr;
 #endif
-  BCHK(hipMemcpy(base + o_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-  BCHK(bx_lds_attr((const void*)boost_frame_kernel, e->lds));
-  BCHK(hipMalloc(&e->h_dets, sizeof(float) * 6 * D));
-  BCHK(hipMalloc(&e->h_off, sizeof(int) * 2));
-  if (d.reid) BCHK(hipMalloc(&e->h_embs, sizeof(double) * D * F));
-  BCHK(hipMalloc(&e->h_warp, sizeof(double) * 6));
-  BCHK(hipMalloc(&e->h_out, sizeof(double) * 8 * D));
-  BCHK(hipMalloc(&e->h_cnt, sizeof(int)));
-  BCHK(hipHostMalloc(&e->p_dets, sizeof(float) * 6 * d.D));
-  BCHK(hipHostMalloc(&e->p_embs, sizeof(double) * (size_t)d.D * (d.F ? d.F : 1)));
-  BCHK(hipHostMalloc(&e->p_warp, sizeof(double) * 8));
-  BCHK(hipHostMalloc(&e->p_out, sizeof(double) * 8 * d.D));
-  BCHK(hipHostMalloc(&e->p_cnt, sizeof(int) * 4));
-  BCHK(hipHostMalloc(&e->p_sq, sizeof(int) * SQB));
+    BX_HIPCHK(hipMemcpy(base + o_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    BX_HIPCHK(bx_lds_attr((const void*)boost_frame_kernel, e->lds));
+    return e->sg.alloc(sizeof(float) * 6 * D, sizeof(double) * D * F, 8, 8, d.D, SQB);
+  };
+  const int rc = fill();
+  if (rc) {
+    bx_boost_destroy(e);
+    return rc;
+  }
   *out = e;
   return BX_OK;
 }
@@ -1282,41 +1233,27 @@ int bx_boost_copy_state(bx_boost* dst, bx_boost* src) {
     return bx_record_error(BX_ERR_INVALID, "bx_boost_copy_state: destination must match the "
                                            "source's sequences and ReID and have at least its "
                                            "capacities");
-  BCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   const size_t S = a.S, Ta = a.T, Tb = b.T, F = a.F;
-  BCHK(hipMemcpy2D(b.trk, Tb * sizeof(BstTrk), a.trk, Ta * sizeof(BstTrk), Ta * sizeof(BstTrk), S,
+  BX_HIPCHK(hipMemcpy2D(b.trk, Tb * sizeof(BstTrk), a.trk, Ta * sizeof(BstTrk), Ta * sizeof(BstTrk), S,
                    hipMemcpyDeviceToDevice));
-  BCHK(hipMemcpy2D(b.order, Tb * sizeof(int), a.order, Ta * sizeof(int), Ta * sizeof(int), S,
+  BX_HIPCHK(hipMemcpy2D(b.order, Tb * sizeof(int), a.order, Ta * sizeof(int), Ta * sizeof(int), S,
                    hipMemcpyDeviceToDevice));
   if (a.reid && F)
-    BCHK(hipMemcpy2D(b.emb, Tb * F * sizeof(double), a.emb, Ta * F * sizeof(double),
+    BX_HIPCHK(hipMemcpy2D(b.emb, Tb * F * sizeof(double), a.emb, Ta * F * sizeof(double),
                      Ta * F * sizeof(double), S, hipMemcpyDeviceToDevice));
-  BCHK(hipMemcpy(b.seqst, a.seqst, S * SQB * sizeof(int), hipMemcpyDeviceToDevice));
-  BCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.seqst, a.seqst, S * SQB * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
   dst->cache_seq = -1;
-  BCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   return BX_OK;
 }
 
 int bx_boost_destroy(bx_boost* e) {
   if (!e) return BX_OK;
-  for (auto& p : e->ev) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->h_dets);
-  (void)hipFree(e->h_off);
-  (void)hipFree(e->h_embs);
-  (void)hipFree(e->h_warp);
-  (void)hipFree(e->h_out);
-  (void)hipFree(e->h_cnt);
-  (void)hipHostFree(e->p_dets);
-  (void)hipHostFree(e->p_embs);
-  (void)hipHostFree(e->p_warp);
-  (void)hipHostFree(e->p_out);
-  (void)hipHostFree(e->p_cnt);
-  (void)hipHostFree(e->p_sq);
+  e->sg.free();
   (void)hipFree(e->h_coff);
   (void)hipFree(e->h_ccnt);
   (void)hipFree(e->h_hold);
@@ -1332,7 +1269,7 @@ int bx_boost_reset(bx_boost* e, int seq0, int nseq, void* stream) {
   e->cache_seq = -1;
   hipLaunchKernelGGL(boost_reset_kernel, dim3((nseq * SQB + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, e->dev, seq0, nseq);
-  BCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -1355,35 +1292,23 @@ int bx_boost_update_host(bx_boost* e, int seq, const float* dets, int n, const d
   hipStream_t st = (hipStream_t)stream;
   // pinned mirrors: asynchronous copies in, the frame, rows (at most n) + count + status +
   // counters back, one synchronisation
-  if (n) {
-    memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
-    BCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
-  }
-  if (n && e->dev.reid) {
-    memcpy(e->p_embs, embs, sizeof(double) * (size_t)n * e->dev.F);
-    BCHK(hipMemcpyAsync(e->h_embs, e->p_embs, sizeof(double) * (size_t)n * e->dev.F,
-                        hipMemcpyHostToDevice, st));
-  }
-  if (warp) {
-    memcpy(e->p_warp, warp, sizeof(double) * 6);
-    BCHK(hipMemcpyAsync(e->h_warp, e->p_warp, sizeof(double) * 6, hipMemcpyHostToDevice, st));
-  }
-  e->p_cnt[2] = 0;
-  e->p_cnt[3] = n;
-  BCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
+  BxStaging& sg = e->sg;
+  int rc;
+  if (n && (rc = sg.put(sg.h_dets, sg.p_dets, dets, sizeof(float) * 6 * n, st))) return rc;
+  if (n && e->dev.reid &&
+      (rc = sg.put(sg.h_embs, sg.p_embs, embs, sizeof(double) * (size_t)n * e->dev.F, st)))
+    return rc;
+  if (warp && (rc = sg.put(sg.h_warp, sg.p_warp, warp, sizeof(double) * 6, st))) return rc;
+  if ((rc = sg.put_off(n, st))) return rc;
   e->cache_seq = -1;
-  int rc = launch(e, seq, 1, e->h_dets, e->h_off, e->dev.reid ? e->h_embs : nullptr,
-                  warp ? e->h_warp : nullptr, e->h_out, e->h_cnt, st);
+  rc = launch(e, seq, 1, (float*)sg.h_dets, sg.h_off, (double*)sg.h_embs,
+              warp ? sg.h_warp : nullptr, sg.h_out, sg.h_cnt, st);
   if (rc) return rc;
-  BCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  BCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.status, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (n) BCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
-  BCHK(hipMemcpyAsync(e->p_sq, e->dev.seqst + (size_t)seq * SQB, sizeof(int) * SQB,
-                      hipMemcpyDeviceToHost, st));
-  BCHK(hipStreamSynchronize(st));
-  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
+  if ((rc = sg.take(e->dev.status, e->dev.seqst + (size_t)seq * SQB, n, st))) return rc;
+  BX_HIPCHK(hipStreamSynchronize(st));
+  const int cnt = sg.p_cnt[0], status = sg.p_cnt[1];
   e->cache_seq = seq;
-  if (cnt) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
+  if (cnt) memcpy(out, sg.p_out, sizeof(double) * 8 * cnt);
   *n_out = cnt;
   if (status)
     return bx_record_error(status, status == BX_ERR_CAPACITY ? "detections exceed det_cap"
@@ -1412,10 +1337,10 @@ int bx_boost_update_classes_host(bx_boost* e, int seq, const float* dets, int n,
   e->cache_seq = -1;
   if (!e->n_classes) {
     e->n_classes = C;
-    BCHK(hipMalloc(&e->h_coff, sizeof(int) * 2 * C));
-    BCHK(hipMalloc(&e->h_ccnt, sizeof(int) * C));
-    BCHK(hipMalloc(&e->h_hold, sizeof(int)));
-    BCHK(hipMalloc(&e->h_cwarp, sizeof(double) * 6 * C));
+    BX_HIPCHK(hipMalloc(&e->h_coff, sizeof(int) * 2 * C));
+    BX_HIPCHK(hipMalloc(&e->h_ccnt, sizeof(int) * C));
+    BX_HIPCHK(hipMalloc(&e->h_hold, sizeof(int)));
+    BX_HIPCHK(hipMalloc(&e->h_cwarp, sizeof(double) * 6 * C));
   }
   auto cls_of = [&](int i) -> int {
     const float v = dets[6 * i + 5];
@@ -1438,34 +1363,34 @@ int bx_boost_update_classes_host(bx_boost* e, int seq, const float* dets, int n,
   }
   std::vector<int> hoff(2 * C);
   for (int c = 0; c < C; c++) { hoff[2 * c] = 0; hoff[2 * c + 1] = cnt[c + 1] - cnt[c]; }
-  if (m) BCHK(hipMemcpyAsync(e->h_dets, hd.data(), sizeof(float) * 6 * m, hipMemcpyHostToDevice, st));
+  if (m) BX_HIPCHK(hipMemcpyAsync((float*)e->sg.h_dets, hd.data(), sizeof(float) * 6 * m, hipMemcpyHostToDevice, st));
   if (m && reid)
-    BCHK(hipMemcpyAsync(e->h_embs, he.data(), sizeof(double) * (size_t)m * F, hipMemcpyHostToDevice, st));
-  BCHK(hipMemcpyAsync(e->h_coff, hoff.data(), sizeof(int) * 2 * C, hipMemcpyHostToDevice, st));
-  if (warps) BCHK(hipMemcpyAsync(e->h_cwarp, warps, sizeof(double) * 6 * C, hipMemcpyHostToDevice, st));
+    BX_HIPCHK(hipMemcpyAsync((double*)e->sg.h_embs, he.data(), sizeof(double) * (size_t)m * F, hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemcpyAsync(e->h_coff, hoff.data(), sizeof(int) * 2 * C, hipMemcpyHostToDevice, st));
+  if (warps) BX_HIPCHK(hipMemcpyAsync(e->h_cwarp, warps, sizeof(double) * 6 * C, hipMemcpyHostToDevice, st));
   for (int c = 0; c < C; c++) {
     hipLaunchKernelGGL(boost_hold_frame_kernel, dim3(1), dim3(1), 0, st, e->dev.seqst, seq,
                        e->h_hold, c == 0 ? 1 : 0);
-    BCHK(hipGetLastError());
+    BX_HIPCHK(hipGetLastError());
     // class call c's camera_update warp (boosttrack.py:243-246 runs cmc.apply per class call)
     const double* wc = warps ? e->h_cwarp + 6 * (size_t)c : nullptr;
-    int rc = launch(e, seq, 1, e->h_dets + 6 * (size_t)cnt[c], e->h_coff + 2 * c,
-                    reid ? e->h_embs + (size_t)F * cnt[c] : nullptr, wc,
-                    e->h_out + 8 * (size_t)cnt[c], e->h_ccnt + c, st);
+    int rc = launch(e, seq, 1, (float*)e->sg.h_dets + 6 * (size_t)cnt[c], e->h_coff + 2 * c,
+                    reid ? (double*)e->sg.h_embs + (size_t)F * cnt[c] : nullptr, wc,
+                    e->sg.h_out + 8 * (size_t)cnt[c], e->h_ccnt + c, st);
     if (rc) return rc;
   }
   std::vector<int> oc(C);
   std::vector<double> ho((size_t)8 * (m ? m : 1));
-  BCHK(hipMemcpyAsync(oc.data(), e->h_ccnt, sizeof(int) * C, hipMemcpyDeviceToHost, st));
-  if (m) BCHK(hipMemcpyAsync(ho.data(), e->h_out, sizeof(double) * 8 * m, hipMemcpyDeviceToHost, st));
-  BCHK(hipStreamSynchronize(st));
+  BX_HIPCHK(hipMemcpyAsync(oc.data(), e->h_ccnt, sizeof(int) * C, hipMemcpyDeviceToHost, st));
+  if (m) BX_HIPCHK(hipMemcpyAsync(ho.data(), e->sg.h_out, sizeof(double) * 8 * m, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   int k = 0;
   for (int c = 0; c < C; c++)
     for (int j = 0; j < oc[c]; j++, k++)
       if (out) memcpy(out + 8 * (size_t)k, &ho[8 * ((size_t)cnt[c] + j)], 8 * sizeof(double));
   *n_out = k;
   int status = 0;
-  BCHK(hipMemcpy(&status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(&status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   if (status)
     return bx_record_error(status, status == BX_ERR_CAPACITY ? "detections exceed det_cap"
                                                              : "a sequence ran out of track slots (raise track_cap)");
@@ -1477,7 +1402,7 @@ int bx_kf_boost_initiate(int n, const double* z, double* x, double* P, void* str
   if (!n) return BX_OK;
   hipLaunchKernelGGL(kf_boost_kernel, dim3((8 * n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      0, n, x, P, z);
-  BCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 int bx_kf_boost_predict(int n, double* x, double* P, void* stream) {
@@ -1485,7 +1410,7 @@ int bx_kf_boost_predict(int n, double* x, double* P, void* stream) {
   if (!n) return BX_OK;
   hipLaunchKernelGGL(kf_boost_kernel, dim3((8 * n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      1, n, x, P, (const double*)nullptr);
-  BCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 int bx_kf_boost_update(int n, double* x, double* P, const double* z, void* stream) {
@@ -1493,7 +1418,7 @@ int bx_kf_boost_update(int n, double* x, double* P, const double* z, void* strea
   if (!n) return BX_OK;
   hipLaunchKernelGGL(kf_boost_kernel, dim3((8 * n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      2, n, x, P, z);
-  BCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 int bx_kf_boost_mh_dist(int nd, const double* dets, int nt, const double* x, const double* P,
@@ -1504,13 +1429,13 @@ int bx_kf_boost_mh_dist(int nd, const double* dets, int nt, const double* x, con
   if (!m) return BX_OK;
   hipLaunchKernelGGL(kf_boost_mh_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, nd, dets, nt, x, P, out);
-  BCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
 int bx_boost_status(bx_boost* e, int* status) {
   if (!e || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
-  BCHK(hipMemcpy(status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
@@ -1518,10 +1443,10 @@ int bx_boost_counters_host(bx_boost* e, int seq, int* frame_count, int* id_count
   if (!e || seq < 0 || seq >= e->dev.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
   int s[SQB];
   if (seq == e->cache_seq) {
-    memcpy(s, e->p_sq, sizeof(s));
+    memcpy(s, e->sg.p_sq, sizeof(s));
   } else {
-    BCHK(hipDeviceSynchronize());
-    BCHK(hipMemcpy(s, e->dev.seqst + (size_t)seq * SQB, sizeof(s), hipMemcpyDeviceToHost));
+    BX_HIPCHK(hipDeviceSynchronize());
+    BX_HIPCHK(hipMemcpy(s, e->dev.seqst + (size_t)seq * SQB, sizeof(s), hipMemcpyDeviceToHost));
   }
   if (frame_count) *frame_count = s[SB_FRAME];
   if (id_count) *id_count = s[SB_IDS];
@@ -1532,9 +1457,9 @@ int bx_boost_counters_host(bx_boost* e, int seq, int* frame_count, int* id_count
 int bx_boost_set_id_count(bx_boost* e, int seq, int id_count, void* stream) {
   if (!e || seq < 0 || seq >= e->dev.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
   e->cache_seq = -1;
-  BCHK(hipMemcpyAsync(e->dev.seqst + (size_t)seq * SQB + SB_IDS, &id_count, sizeof(int),
+  BX_HIPCHK(hipMemcpyAsync(e->dev.seqst + (size_t)seq * SQB + SB_IDS, &id_count, sizeof(int),
                       hipMemcpyHostToDevice, (hipStream_t)stream));
-  BCHK(hipStreamSynchronize((hipStream_t)stream));
+  BX_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return BX_OK;
 }
 
@@ -1542,23 +1467,23 @@ int bx_boost_tracks_host(bx_boost* e, int seq, int cap, int32_t* ids, double* x,
                          double* emb, int* n) {
   if (!e || seq < 0 || seq >= e->dev.S || cap < 0 || !n)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_boost_tracks_host");
-  BCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   int s[SQB];
-  BCHK(hipMemcpy(s, e->dev.seqst + (size_t)seq * SQB, sizeof(s), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(s, e->dev.seqst + (size_t)seq * SQB, sizeof(s), hipMemcpyDeviceToHost));
   const int nt = s[SB_NTR];
   std::vector<int> ord(nt);
   if (nt)
-    BCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
+    BX_HIPCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
                    hipMemcpyDeviceToHost));
   for (int k = 0; k < nt && k < cap; k++) {
     BstTrk t;
-    BCHK(hipMemcpy(&t, e->dev.trk + (size_t)seq * e->dev.T + ord[k], sizeof(BstTrk),
+    BX_HIPCHK(hipMemcpy(&t, e->dev.trk + (size_t)seq * e->dev.T + ord[k], sizeof(BstTrk),
                    hipMemcpyDeviceToHost));
     if (ids) ids[k] = t.id;
     if (x) memcpy(x + 8 * k, t.x, sizeof(t.x));
     if (p) memcpy(p + 64 * k, t.P, sizeof(t.P));
     if (emb && e->dev.reid)
-      BCHK(hipMemcpy(emb + (size_t)k * e->dev.F,
+      BX_HIPCHK(hipMemcpy(emb + (size_t)k * e->dev.F,
                      e->dev.emb + ((size_t)seq * e->dev.T + ord[k]) * e->dev.F,
                      sizeof(double) * e->dev.F, hipMemcpyDeviceToHost));
   }
@@ -1570,26 +1495,26 @@ int bx_boost_state_set_host(bx_boost* e, int seq, int n, const int32_t* ids, con
                             const double* p) {
   if (!e || seq < 0 || seq >= e->dev.S || n < 0 || (n && !ids))
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_boost_state_set_host");
-  BCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   int s[SQB];
-  BCHK(hipMemcpy(s, e->dev.seqst + (size_t)seq * SQB, sizeof(s), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(s, e->dev.seqst + (size_t)seq * SQB, sizeof(s), hipMemcpyDeviceToHost));
   const int nt = s[SB_NTR];
   std::vector<int> ord(nt);
   if (nt)
-    BCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
+    BX_HIPCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
                    hipMemcpyDeviceToHost));
   for (int j = 0; j < n; j++) {
     BstTrk* dt = nullptr;
     BstTrk t;
     for (int k = 0; k < nt && !dt; k++) {
       BstTrk* cand = e->dev.trk + (size_t)seq * e->dev.T + ord[k];
-      BCHK(hipMemcpy(&t, cand, sizeof(BstTrk), hipMemcpyDeviceToHost));
+      BX_HIPCHK(hipMemcpy(&t, cand, sizeof(BstTrk), hipMemcpyDeviceToHost));
       if (t.id == ids[j]) dt = cand;
     }
     if (!dt) return bx_record_error(BX_ERR_INVALID, "state_set: no live track with that id");
     if (x) memcpy(t.x, x + 8 * j, sizeof(t.x));
     if (p) memcpy(t.P, p + 64 * j, sizeof(t.P));
-    BCHK(hipMemcpy(dt, &t, sizeof(BstTrk), hipMemcpyHostToDevice));
+    BX_HIPCHK(hipMemcpy(dt, &t, sizeof(BstTrk), hipMemcpyHostToDevice));
   }
   return BX_OK;
 }
@@ -1598,9 +1523,9 @@ int bx_boost_frame_stats_host(bx_boost* e, int seq0, int nseq, int64_t* sums) {
   if (!e || !sums || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.S)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_boost_frame_stats_host");
   std::vector<int> s((size_t)nseq * SQB);
-  BCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   if (nseq)
-    BCHK(hipMemcpy(s.data(), e->dev.seqst + (size_t)seq0 * SQB, sizeof(int) * s.size(),
+    BX_HIPCHK(hipMemcpy(s.data(), e->dev.seqst + (size_t)seq0 * SQB, sizeof(int) * s.size(),
                    hipMemcpyDeviceToHost));
   int64_t a[7] = {0, 0, 0, 0, 0, 0, 0};
   for (int k = 0; k < nseq; k++) {
@@ -1620,32 +1545,21 @@ int bx_boost_frame_stats_host(bx_boost* e, int seq0, int nseq, int64_t* sums) {
 // diagnostic (not in the public header): the phase stamps of every sequence, [S][BST_DBG]
 int bx_boost_debug_host(bx_boost* e, unsigned long long* out) {
   if (!e || !out || !e->dev.dbg) return bx_record_error(BX_ERR_INVALID, "not a timing build");
-  BCHK(hipDeviceSynchronize());
-  BCHK(hipMemcpy(out, e->dev.dbg, sizeof(unsigned long long) * BST_DBG * e->dev.S,
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(out, e->dev.dbg, sizeof(unsigned long long) * BST_DBG * e->dev.S,
                  hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
 int bx_boost_probe(bx_boost* e, int stage) {
   if (!e) return bx_record_error(BX_ERR_INVALID, "null engine");
-  e->probe_stage = stage;
-  e->ev_used = 0;
+  e->probe.set(stage);
   return BX_OK;
 }
 
 int bx_boost_probe_read(bx_boost* e, double* total_ms, int* count) {
   if (!e || !total_ms || !count) return bx_record_error(BX_ERR_INVALID, "null argument");
-  double s = 0.0;
-  for (int k = 0; k < e->ev_used; k++) {
-    BCHK(hipEventSynchronize(e->ev[k].second));
-    float ms = 0.f;
-    BCHK(hipEventElapsedTime(&ms, e->ev[k].first, e->ev[k].second));
-    s += ms;
-  }
-  *total_ms = s;
-  *count = e->ev_used;
-  e->ev_used = 0;
-  return BX_OK;
+  return e->probe.read(total_ms, count);
 }
 
 }  // extern "C"

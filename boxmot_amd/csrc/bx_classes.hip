@@ -26,8 +26,8 @@
 #include <vector>
 
 #include "../../include/bxclasses.h"
+#include "bx_host.h"
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
 
 namespace {
 
@@ -254,13 +254,6 @@ struct bx_classes {
   int* s_cnt = nullptr;
 };
 
-#define CCHK(x)                                                                    \
-  do {                                                                             \
-    hipError_t _e = (x);                                                           \
-    if (_e != hipSuccess)                                                          \
-      return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
-
 extern "C" {
 
 int bx_classes_create(int n_seq, int n_classes, int emb_dim, int row_cap, int map_cap, int id0,
@@ -285,17 +278,16 @@ int bx_classes_create(int n_seq, int n_classes, int emb_dim, int row_cap, int ma
     d.row_cap = row_cap;
     d.map_cap = map_cap;
     d.id0 = id0;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    BxCarve carve;
     const size_t o_hist = carve(S * C * 4), o_lids = carve(S * C * 4), o_g = carve(S * 4);
     const size_t o_tot = carve(S * 4);
     const size_t o_map = carve(S * C * (size_t)map_cap * 4), o_st = carve(16);
     const size_t o_sd = carve(R * 6 * 4), o_se = carve(R * (F ? F : 1) * 8);
     const size_t o_so = carve((S * C + 1) * 4), o_ss = carve(R * 4), o_sr = carve(R * 8 * 8);
     const size_t o_sc = carve(S * C * 4);
-    if (hipMalloc(&c->arena, off) != hipSuccess)
+    if (hipMalloc(&c->arena, carve.off) != hipSuccess)
       return bx_record_error(BX_ERR_HIP, "hipMalloc of the class state failed");
-    CCHK(hipMemset(c->arena, 0, off));
+    BX_HIPCHK(hipMemset(c->arena, 0, carve.off));
     char* b = (char*)c->arena;
     d.hist = (int*)(b + o_hist);
     d.tot = (int*)(b + o_tot);
@@ -310,8 +302,8 @@ int bx_classes_create(int n_seq, int n_classes, int emb_dim, int row_cap, int ma
     c->s_out = (double*)(b + o_sr);
     c->s_cnt = (int*)(b + o_sc);
     std::vector<int> one(S * C, id0);
-    CCHK(hipMemcpy(d.lids, one.data(), S * C * 4, hipMemcpyHostToDevice));
-    CCHK(hipMemcpy(d.gctr, one.data(), S * 4, hipMemcpyHostToDevice));
+    BX_HIPCHK(hipMemcpy(d.lids, one.data(), S * C * 4, hipMemcpyHostToDevice));
+    BX_HIPCHK(hipMemcpy(d.gctr, one.data(), S * 4, hipMemcpyHostToDevice));
     return BX_OK;
   };
   const int rc = fill();
@@ -371,10 +363,10 @@ int bx_classes_split(bx_classes* c, int nseq, const float* dets, const int32_t* 
     return bx_record_error(BX_ERR_INVALID, "bx_classes_split: dets must be 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(class_count_kernel, dim3(nseq), dim3(CW), 0, st, c->dev, dets, det_off);
-  CCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(class_split_kernel, dim3(nseq), dim3(CW), 0, st, c->dev, nseq, dets, det_off,
                      embs, o_dets, o_embs, o_off, o_src);
-  CCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -388,7 +380,7 @@ int bx_classes_merge(bx_classes* c, int seq0, int nseq, const int32_t* c_off, co
     return bx_record_error(BX_ERR_INVALID, "bx_classes_merge: out rows must be 16-byte aligned");
   hipLaunchKernelGGL(class_merge_kernel, dim3(nseq), dim3(CW), 0, (hipStream_t)stream, c->dev,
                      seq0, c_off, c_out, c_cnt, ids, ids_stride, det_off, out, out_count);
-  CCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -398,30 +390,30 @@ int bx_classes_reset(bx_classes* c, int seq0, int nseq, void* stream) {
   if (!nseq) return BX_OK;
   hipLaunchKernelGGL(class_reset_kernel, dim3((nseq * c->dev.C + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, c->dev, seq0, nseq);
-  CCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
 int bx_classes_status(bx_classes* c, int* status) {
   if (!c || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
-  CCHK(hipDeviceSynchronize());
-  CCHK(hipMemcpy(status, c->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(status, c->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
 int bx_classes_id_count_host(bx_classes* c, int seq, int* id_count) {
   if (!c || seq < 0 || seq >= c->dev.S || !id_count)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_classes_id_count_host");
-  CCHK(hipDeviceSynchronize());
-  CCHK(hipMemcpy(id_count, c->dev.gctr + seq, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(id_count, c->dev.gctr + seq, sizeof(int), hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
 int bx_classes_set_id_count(bx_classes* c, int seq, int id_count, void* stream) {
   if (!c || seq < 0 || seq >= c->dev.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  CCHK(hipMemcpyAsync(c->dev.gctr + seq, &id_count, sizeof(int), hipMemcpyHostToDevice,
+  BX_HIPCHK(hipMemcpyAsync(c->dev.gctr + seq, &id_count, sizeof(int), hipMemcpyHostToDevice,
                       (hipStream_t)stream));
-  CCHK(hipStreamSynchronize((hipStream_t)stream));
+  BX_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return BX_OK;
 }
 
@@ -431,14 +423,14 @@ int bx_classes_map_host(bx_classes* c, int seq, int cls, int cap, int32_t* map_h
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_classes_map_host");
   const size_t q = (size_t)seq * c->dev.C + cls;
   int now = 0;
-  CCHK(hipDeviceSynchronize());
-  CCHK(hipMemcpy(&now, c->dev.lids + q, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(&now, c->dev.lids + q, sizeof(int), hipMemcpyDeviceToHost));
   int m = now - c->dev.id0;
   if (m > c->dev.map_cap) m = c->dev.map_cap;
   *n = m;
   if (m > cap) m = cap;
   if (m > 0)
-    CCHK(hipMemcpy(map_host, c->dev.map + q * (size_t)c->dev.map_cap, sizeof(int) * m,
+    BX_HIPCHK(hipMemcpy(map_host, c->dev.map + q * (size_t)c->dev.map_cap, sizeof(int) * m,
                    hipMemcpyDeviceToHost));
   return BX_OK;
 }
@@ -452,13 +444,13 @@ int bx_classes_copy_state(bx_classes* dst, bx_classes* src) {
                                            "source's sequences, classes, emb_dim and id0 and at "
                                            "least its map_cap and row_cap");
   const size_t Q = (size_t)a.S * a.C;
-  CCHK(hipDeviceSynchronize());
-  CCHK(hipMemcpy(b.lids, a.lids, Q * sizeof(int), hipMemcpyDeviceToDevice));
-  CCHK(hipMemcpy(b.gctr, a.gctr, (size_t)a.S * sizeof(int), hipMemcpyDeviceToDevice));
-  CCHK(hipMemcpy2D(b.map, (size_t)b.map_cap * sizeof(int), a.map, (size_t)a.map_cap * sizeof(int),
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(b.lids, a.lids, Q * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.gctr, a.gctr, (size_t)a.S * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy2D(b.map, (size_t)b.map_cap * sizeof(int), a.map, (size_t)a.map_cap * sizeof(int),
                    (size_t)a.map_cap * sizeof(int), Q, hipMemcpyDeviceToDevice));
-  CCHK(hipMemcpy(b.status, a.status, sizeof(int), hipMemcpyDeviceToDevice));
-  CCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(b.status, a.status, sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipDeviceSynchronize());
   return BX_OK;
 }
 

@@ -5,8 +5,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/bxclasses.h"
+#include "bx_host.h"
 
-int bx_record_error(int code, const char* msg);
 
 struct ClsGlue {
   bx_classes* cls = nullptr;
@@ -91,27 +91,22 @@ inline int cls_glue_status(ClsGlue& g, int* status) {
   return bx_classes_status(g.cls, status);
 }
 
-#define GCHK(x)                                                             \
-  do {                                                                      \
-    if ((x) != hipSuccess) return bx_record_error(BX_ERR_HIP, #x " failed"); \
-  } while (0)
-
 // the host form's class-level id counter: written before the frame, read back (with the class
 // status) after it; take synchronises the stream
 inline int cls_glue_put_ids(ClsGlue& g, int seq, int id_count, hipStream_t st) {
   void *ctr, *status;
   bx_classes_state(g.cls, &ctr, &status);
   g.p_g[0] = id_count;
-  GCHK(hipMemcpyAsync((int*)ctr + seq, g.p_g, sizeof(int), hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemcpyAsync((int*)ctr + seq, g.p_g, sizeof(int), hipMemcpyHostToDevice, st));
   return BX_OK;
 }
 
 inline int cls_glue_take_ids(ClsGlue& g, int seq, int* id_count, int* cstatus, hipStream_t st) {
   void *ctr, *status;
   bx_classes_state(g.cls, &ctr, &status);
-  GCHK(hipMemcpyAsync(g.p_g + 1, (int*)ctr + seq, sizeof(int), hipMemcpyDeviceToHost, st));
-  GCHK(hipMemcpyAsync(g.p_g + 2, status, sizeof(int), hipMemcpyDeviceToHost, st));
-  GCHK(hipStreamSynchronize(st));
+  BX_HIPCHK(hipMemcpyAsync(g.p_g + 1, (int*)ctr + seq, sizeof(int), hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(g.p_g + 2, status, sizeof(int), hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   *id_count = g.p_g[1];
   *cstatus = g.p_g[2];
   return BX_OK;

@@ -23,20 +23,14 @@
 #include "../../include/bxcmc.h"
 #include "bx_device.h"
 #include "bx_resize.h"
+#include "bx_host.h"
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
 
 using namespace bx;
 
 namespace {
 
 int cm_err(int code, const std::string& msg) { return bx_record_error(code, msg.c_str()); }
-#define CMCHK(x)                                                            \
-  do {                                                                      \
-    hipError_t _e = (x);                                                    \
-    if (_e != hipSuccess) return cm_err(BX_ERR_HIP, hipGetErrorString(_e)); \
-  } while (0)
-
 constexpr int ET = BX_ECC_THREADS, EW = ET / WAVE;  // 1024 threads = 16 waves
 constexpr int PT = 256;                              // threads of a prep workgroup
 
@@ -425,7 +419,7 @@ int launch(CmHandle* H_, int n, int H, int W, int ch, const uint8_t* frames, con
     hipLaunchKernelGGL(cmc_ecc_kernel<BX_ECC_EUCLIDEAN>, dim3(n), dim3(ET), 0, st, H_->d, a);
   else
     hipLaunchKernelGGL(cmc_ecc_kernel<BX_ECC_AFFINE>, dim3(n), dim3(ET), 0, st, H_->d, a);
-  CMCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -533,9 +527,9 @@ int bx_ecc_reset(void* h, int stream, void* hip_stream) {
   if (stream >= H_->d.n_streams) return cm_err(BX_ERR_INVALID, "stream index out of range");
   hipStream_t st = (hipStream_t)hip_stream;
   if (stream < 0)
-    CMCHK(hipMemsetAsync(H_->d.has_prev, 0, (size_t)H_->d.n_streams * 4, st));
+    BX_HIPCHK(hipMemsetAsync(H_->d.has_prev, 0, (size_t)H_->d.n_streams * 4, st));
   else
-    CMCHK(hipMemsetAsync(H_->d.has_prev + stream, 0, 4, st));
+    BX_HIPCHK(hipMemsetAsync(H_->d.has_prev + stream, 0, 4, st));
   return BX_OK;
 }
 
@@ -577,28 +571,28 @@ int bx_ecc_apply_host(void* h, int n, int H, int W, int channels, const uint8_t*
   hipStream_t st = (hipStream_t)hip_stream;
   const size_t fb = (size_t)n * H * W * channels;
   if (fb > H_->sframes_bytes) {
-    CMCHK(hipStreamSynchronize(st));
+    BX_HIPCHK(hipStreamSynchronize(st));
     if (H_->sframes) (void)hipFree(H_->sframes);
     H_->sframes = nullptr;
     H_->sframes_bytes = 0;
-    CMCHK(hipMalloc(&H_->sframes, fb));
+    BX_HIPCHK(hipMalloc(&H_->sframes, fb));
     H_->sframes_bytes = fb;
   }
-  CMCHK(hipMemcpyAsync(H_->sframes, frames_host, fb, hipMemcpyHostToDevice, st));
-  CMCHK(hipMemcpyAsync(H_->sstreams, streams_host, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemcpyAsync(H_->sframes, frames_host, fb, hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemcpyAsync(H_->sstreams, streams_host, (size_t)n * 4, hipMemcpyHostToDevice, st));
   if (init_warps_host)
-    CMCHK(hipMemcpyAsync(H_->sinit, init_warps_host, (size_t)S * 48, hipMemcpyHostToDevice, st));
+    BX_HIPCHK(hipMemcpyAsync(H_->sinit, init_warps_host, (size_t)S * 48, hipMemcpyHostToDevice, st));
   rc = launch(H_, n, H, W, channels, H_->sframes, H_->sstreams, warp_mode, eps, max_iter, scale,
               hh, ww, init_warps_host ? H_->sinit : nullptr, H_->swarps, H_->srho, H_->siters,
               H_->scode, st);
   if (rc != BX_OK) return rc;
   std::vector<double> wv((size_t)S * 6), rv(S);
   std::vector<int32_t> iv(S), cv(S);
-  CMCHK(hipMemcpyAsync(wv.data(), H_->swarps, (size_t)S * 48, hipMemcpyDeviceToHost, st));
-  CMCHK(hipMemcpyAsync(rv.data(), H_->srho, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-  CMCHK(hipMemcpyAsync(iv.data(), H_->siters, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-  CMCHK(hipMemcpyAsync(cv.data(), H_->scode, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-  CMCHK(hipStreamSynchronize(st));
+  BX_HIPCHK(hipMemcpyAsync(wv.data(), H_->swarps, (size_t)S * 48, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(rv.data(), H_->srho, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(iv.data(), H_->siters, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(cv.data(), H_->scode, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   for (int k = 0; k < n; k++) {
     const int s = streams_host[k];
     for (int q = 0; q < 6; q++) warps_host[(size_t)s * 6 + q] = wv[(size_t)s * 6 + q];
@@ -612,8 +606,8 @@ int bx_ecc_apply_host(void* h, int n, int H, int W, int channels, const uint8_t*
 int bx_ecc_status(void* h, int* status) {
   CmHandle* H_ = (CmHandle*)h;
   if (!H_ || !status) return cm_err(BX_ERR_INVALID, "null argument");
-  CMCHK(hipDeviceSynchronize());
-  CMCHK(hipMemcpy(status, H_->d.status, 4, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(status, H_->d.status, 4, hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
@@ -623,14 +617,14 @@ int bx_ecc_state_host(void* h, int stream, int* has_prev, int* hh, int* ww, uint
   if (!H_ || !has_prev || !hh || !ww) return cm_err(BX_ERR_INVALID, "null argument");
   const CmDev& d = H_->d;
   if (stream < 0 || stream >= d.n_streams) return cm_err(BX_ERR_INVALID, "stream index out of range");
-  CMCHK(hipDeviceSynchronize());
-  CMCHK(hipMemcpy(has_prev, d.has_prev + stream, 4, hipMemcpyDeviceToHost));
-  CMCHK(hipMemcpy(hh, d.ph + stream, 4, hipMemcpyDeviceToHost));
-  CMCHK(hipMemcpy(ww, d.pw + stream, 4, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(has_prev, d.has_prev + stream, 4, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(hh, d.ph + stream, 4, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(ww, d.pw + stream, 4, hipMemcpyDeviceToHost));
   const size_t o = (size_t)stream * d.cap;
-  if (grey) CMCHK(hipMemcpy(grey, d.prev + o, d.cap, hipMemcpyDeviceToHost));
-  if (gx) CMCHK(hipMemcpy(gx, d.gx + o, (size_t)d.cap * 4, hipMemcpyDeviceToHost));
-  if (gy) CMCHK(hipMemcpy(gy, d.gy + o, (size_t)d.cap * 4, hipMemcpyDeviceToHost));
+  if (grey) BX_HIPCHK(hipMemcpy(grey, d.prev + o, d.cap, hipMemcpyDeviceToHost));
+  if (gx) BX_HIPCHK(hipMemcpy(gx, d.gx + o, (size_t)d.cap * 4, hipMemcpyDeviceToHost));
+  if (gy) BX_HIPCHK(hipMemcpy(gy, d.gy + o, (size_t)d.cap * 4, hipMemcpyDeviceToHost));
   return BX_OK;
 }
 

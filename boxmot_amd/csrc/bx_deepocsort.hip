@@ -28,15 +28,15 @@
 #include "../../include/bxdeepocsort.h"
 #include "bx_classes_glue.h"
 #include "bx_device.h"
+#include "bx_host.h"
 
 using namespace bx;
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
-hipError_t bx_lds_attr(const void* kern, size_t bytes);  // bx_engine.hip (never lowers a limit)
 
 namespace {
 
 #include "bx_ocs_device.h"
+#include "bx_ocs_host.h"
 #include "bx_embtile.h"
 
 // OCSort's device record (o.min_conf unused, o.use_byte 0) plus the appearance state.  Per
@@ -672,59 +672,17 @@ __global__ void deepoc_reset_kernel(DocDev g, int seq0, int nseq) {
 
 }  // namespace
 
-struct bx_deepoc {
+struct bx_deepoc : OcsHost {
   DocDev dev;
   bx_deepoc_config cfg;
   void* arena = nullptr;
   size_t lds = 0;
-  // host-path staging and pinned mirrors for update_host
-  float* h_dets = nullptr;
-  double* h_embs = nullptr;
-  double* h_warp = nullptr;
-  int* h_off = nullptr;
-  double* h_out = nullptr;
-  int* h_cnt = nullptr;
-  float* p_dets = nullptr;
-  double* p_embs = nullptr;
-  double* p_warp = nullptr;
-  double* p_out = nullptr;
-  int* p_cnt = nullptr;
-  int* p_sq = nullptr;
-  int cache_seq = -1;
   // per_class=True: the class state and the staging of the per-class warps
   ClsGlue pc;
   double* h_cwarp = nullptr;
   double* p_cwarp = nullptr;
-  // timing probe
-  int probe_stage = -1;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  int ev_used = 0;
+  BxProbe probe;  // stages: 0 embcost, 1 frame, 2 feature
 };
-
-#define DCHK(x)                                                                    \
-  do {                                                                             \
-    hipError_t _e = (x);                                                           \
-    if (_e != hipSuccess)                                                          \
-      return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
-
-static int probe_begin(bx_deepoc* e, int stage, hipStream_t st) {
-  if (e->probe_stage != stage) return BX_OK;
-  if (e->ev_used == (int)e->ev.size()) {
-    hipEvent_t a, b;
-    DCHK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-    DCHK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
-    e->ev.push_back({a, b});
-  }
-  DCHK(hipEventRecord(e->ev[e->ev_used].first, st));
-  return BX_OK;
-}
-
-static int probe_end(bx_deepoc* e, int stage, hipStream_t st) {
-  if (e->probe_stage != stage) return BX_OK;
-  DCHK(hipEventRecord(e->ev[e->ev_used++].second, st));
-  return BX_OK;
-}
 
 static int launch(bx_deepoc* e, int seq0, int nseq, const float* dets, const int* off,
                   const double* embs, const double* warps, double* out, int* cnt, hipStream_t st) {
@@ -733,23 +691,23 @@ static int launch(bx_deepoc* e, int seq0, int nseq, const float* dets, const int
   int rc;
   if (emb && !embs) return bx_record_error(BX_ERR_SHAPE, "DeepOCSort needs embeddings unless embedding_off");
   if (emb) {
-    if ((rc = probe_begin(e, 0, st))) return rc;
+    if ((rc = e->probe.begin(0, st))) return rc;
     hipLaunchKernelGGL(deepoc_embcost_kernel, dim3(nseq, ec_tiles(d.o.D, d.o.T)), dim3(256), 0, st,
                        d, seq0, off, embs);
-    DCHK(hipGetLastError());
-    if ((rc = probe_end(e, 0, st))) return rc;
+    BX_HIPCHK(hipGetLastError());
+    if ((rc = e->probe.end(0, st))) return rc;
   }
-  if ((rc = probe_begin(e, 1, st))) return rc;
+  if ((rc = e->probe.begin(1, st))) return rc;
   hipLaunchKernelGGL(deepoc_frame_kernel, dim3(nseq), dim3(OW), e->lds, st, d, seq0, dets, off,
                      warps, out, cnt);
-  DCHK(hipGetLastError());
-  if ((rc = probe_end(e, 1, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(1, st))) return rc;
   if (emb) {
-    if ((rc = probe_begin(e, 2, st))) return rc;
+    if ((rc = e->probe.begin(2, st))) return rc;
     hipLaunchKernelGGL(deepoc_feature_kernel, dim3((d.o.D + 3) / 4, nseq), dim3(256), 0, st, d,
                        seq0, off, embs);
-    DCHK(hipGetLastError());
-    if ((rc = probe_end(e, 2, st))) return rc;
+    BX_HIPCHK(hipGetLastError());
+    if ((rc = e->probe.end(2, st))) return rc;
   }
   return BX_OK;
 }
@@ -772,6 +730,7 @@ int bx_deepoc_create(const bx_deepoc_config* c, bx_deepoc** out) {
     return bx_record_error(BX_ERR_NO_DEVICE, "no HIP device visible");
   bx_deepoc* e = new bx_deepoc();
   e->cfg = *c;
+  e->o = &e->dev.o;
   // everything that can fail runs in `fill`: a failure frees what was allocated so far
   auto fill = [&]() -> int {
     DocDev& dd = e->dev;
@@ -799,23 +758,13 @@ int bx_deepoc_create(const bx_deepoc_config* c, bx_deepoc** out) {
     dd.w_emb = c->w_association_emb;
     dd.alpha_fixed = c->alpha_fixed_emb;
     dd.aw_param = c->aw_param;
-    // LDS: the fixed part plus as much cost matrix as keeps ~4 workgroups per CU resident
-    const size_t extra = doc_lds_extra(d.D, d.T);
-    const size_t fixed = lds_bytes(d.D, d.T, d.N, 0) + extra;
-    long budget = 40 * 1024 - (long)fixed;
-    int cl = budget > 0 ? (int)(budget / 8) : 0;
-    if (cl > d.D * d.T) cl = d.D * d.T;
-    if (cl < 64) cl = 64;
-    d.cost_lds = cl;
-    dd.x_off = (int)lds_bytes(d.D, d.T, d.N, cl);
-    e->lds = (size_t)dd.x_off + extra;
-    if (e->lds > 160 * 1024) {
-      return bx_record_error(BX_ERR_INVALID, "track_cap/det_cap too large for one workgroup's LDS");
-    }
-    const bool need_g = (long)d.D * d.T > cl;
+    size_t x_off;
+    int rc = ocs_lds_budget(d, doc_lds_extra(d.D, d.T), &x_off, &e->lds);
+    if (rc) return rc;
+    dd.x_off = (int)x_off;
+    const bool need_g = (long)d.D * d.T > d.cost_lds;
     const size_t S = d.S, T = d.T, D = d.D, F = dd.F;
-    size_t off = 0;
-    auto carve_b = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    BxCarve carve_b;
     const size_t o_trk = carve_b(S * T * sizeof(OcsTrk));
     const size_t o_sq = carve_b(S * SQO * sizeof(int));
     const size_t o_ord = carve_b(S * T * sizeof(int));
@@ -828,10 +777,9 @@ int bx_deepoc_create(const bx_deepoc_config* c, bx_deepoc** out) {
     const size_t o_em = carve_b(F ? S * D * T * sizeof(double) : 8);
     const size_t o_rec = carve_b(S * D * sizeof(int));
     const size_t o_ra = carve_b(S * D * sizeof(double));
-    if (hipMalloc(&e->arena, off) != hipSuccess) {
+    if (hipMalloc(&e->arena, carve_b.off) != hipSuccess)
       return bx_record_error(BX_ERR_HIP, "hipMalloc of the DeepOCSort arena failed");
-    }
-    DCHK(hipMemset(e->arena, 0, off));
+    BX_HIPCHK(hipMemset(e->arena, 0, carve_b.off));
     char* base = (char*)e->arena;
     d.trk = (OcsTrk*)(base + o_trk);
     d.seqst = (int*)(base + o_sq);
@@ -846,31 +794,9 @@ int bx_deepoc_create(const bx_deepoc_config* c, bx_deepoc** out) {
     dd.em = (double*)(base + o_em);
     dd.rec = (int*)(base + o_rec);
     dd.rec_a = (double*)(base + o_ra);
-    {
-      std::vector<double> f(2 * S);
-      for (size_t k = 0; k < S; k++) {
-        f[2 * k] = c->frame_w;
-        f[2 * k + 1] = c->frame_h;
-      }
-      DCHK(hipMemcpy(d.fsz, f.data(), sizeof(double) * 2 * S, hipMemcpyHostToDevice));
-      std::vector<int> sq(S * SQO, 0);
-      for (size_t k = 0; k < S; k++) sq[k * SQO + SO_IDS] = 1;
-      DCHK(hipMemcpy(d.seqst, sq.data(), sizeof(int) * sq.size(), hipMemcpyHostToDevice));
-    }
-    DCHK(bx_lds_attr((const void*)deepoc_frame_kernel, e->lds));
-    DCHK(hipMalloc(&e->h_dets, sizeof(float) * 6 * D));
-    DCHK(hipMalloc(&e->h_embs, sizeof(double) * D * (F ? F : 1)));
-    DCHK(hipMalloc(&e->h_warp, sizeof(double) * 6));
-    DCHK(hipMalloc(&e->h_off, sizeof(int) * 2));
-    DCHK(hipMalloc(&e->h_out, sizeof(double) * 8 * D));
-    DCHK(hipMalloc(&e->h_cnt, sizeof(int)));
-    DCHK(hipHostMalloc(&e->p_dets, sizeof(float) * 6 * D));
-    DCHK(hipHostMalloc(&e->p_embs, sizeof(double) * D * (F ? F : 1)));
-    DCHK(hipHostMalloc(&e->p_warp, sizeof(double) * 6));
-    DCHK(hipHostMalloc(&e->p_out, sizeof(double) * 8 * D));
-    DCHK(hipHostMalloc(&e->p_cnt, sizeof(int) * 4));
-    DCHK(hipHostMalloc(&e->p_sq, sizeof(int) * SQO));
-    return BX_OK;
+    if ((rc = ocs_upload_initial(d, c->frame_w, c->frame_h, 1))) return rc;
+    BX_HIPCHK(bx_lds_attr((const void*)deepoc_frame_kernel, e->lds));
+    return e->sg.alloc(sizeof(float) * 6 * D, sizeof(double) * D * F, 6, 8, d.D, SQO);
   };
   const int rc = fill();
   if (rc) {
@@ -888,42 +814,28 @@ int bx_deepoc_copy_state(bx_deepoc* dst, bx_deepoc* src) {
     return bx_record_error(BX_ERR_INVALID, "bx_deepoc_copy_state: destination must have the "
                                            "source's sequences and embedding width and at least "
                                            "its capacities");
-  DCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   const size_t S = a.S, Ta = a.T, Tb = b.T, F = src->dev.F;
-  DCHK(hipMemcpy2D(b.trk, Tb * sizeof(OcsTrk), a.trk, Ta * sizeof(OcsTrk), Ta * sizeof(OcsTrk), S,
+  BX_HIPCHK(hipMemcpy2D(b.trk, Tb * sizeof(OcsTrk), a.trk, Ta * sizeof(OcsTrk), Ta * sizeof(OcsTrk), S,
                    hipMemcpyDeviceToDevice));
-  DCHK(hipMemcpy2D(b.order, Tb * sizeof(int), a.order, Ta * sizeof(int), Ta * sizeof(int), S,
+  BX_HIPCHK(hipMemcpy2D(b.order, Tb * sizeof(int), a.order, Ta * sizeof(int), Ta * sizeof(int), S,
                    hipMemcpyDeviceToDevice));
   if (F)
-    DCHK(hipMemcpy2D(dst->dev.emb, Tb * F * sizeof(double), src->dev.emb, Ta * F * sizeof(double),
+    BX_HIPCHK(hipMemcpy2D(dst->dev.emb, Tb * F * sizeof(double), src->dev.emb, Ta * F * sizeof(double),
                      Ta * F * sizeof(double), S, hipMemcpyDeviceToDevice));
-  DCHK(hipMemcpy(b.seqst, a.seqst, S * SQO * sizeof(int), hipMemcpyDeviceToDevice));
-  DCHK(hipMemcpy(b.fsz, a.fsz, S * 2 * sizeof(double), hipMemcpyDeviceToDevice));
-  DCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.seqst, a.seqst, S * SQO * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.fsz, a.fsz, S * 2 * sizeof(double), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
   dst->cache_seq = -1;
-  DCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   return cls_glue_copy(dst->pc, src->pc, b.S, b.D, dst->dev.F, 1);
 }
 
 int bx_deepoc_destroy(bx_deepoc* e) {
   if (!e) return BX_OK;
-  for (auto& p : e->ev) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->h_dets);
-  (void)hipFree(e->h_embs);
-  (void)hipFree(e->h_warp);
-  (void)hipFree(e->h_off);
-  (void)hipFree(e->h_out);
-  (void)hipFree(e->h_cnt);
-  (void)hipHostFree(e->p_dets);
-  (void)hipHostFree(e->p_embs);
-  (void)hipHostFree(e->p_warp);
-  (void)hipHostFree(e->p_out);
-  (void)hipHostFree(e->p_cnt);
-  (void)hipHostFree(e->p_sq);
+  e->sg.free();
   cls_glue_free(e->pc);
   (void)hipFree(e->h_cwarp);
   (void)hipHostFree(e->p_cwarp);
@@ -938,7 +850,7 @@ int bx_deepoc_reset(bx_deepoc* e, int seq0, int nseq, void* stream) {
   e->cache_seq = -1;
   hipLaunchKernelGGL(deepoc_reset_kernel, dim3((nseq * SQO + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, e->dev, seq0, nseq);
-  DCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return cls_glue_reset(e->pc, seq0, nseq, stream);
 }
 
@@ -960,40 +872,17 @@ int bx_deepoc_update_host(bx_deepoc* e, int seq, const float* dets, int n, const
   if (n && F && !embs)
     return bx_record_error(BX_ERR_SHAPE, "DeepOCSort needs embeddings unless embedding_off");
   hipStream_t st = (hipStream_t)stream;
-  if (n) {
-    memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
-    DCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
-    if (F) {
-      memcpy(e->p_embs, embs, sizeof(double) * F * n);
-      DCHK(hipMemcpyAsync(e->h_embs, e->p_embs, sizeof(double) * F * n, hipMemcpyHostToDevice, st));
-    }
-  }
-  if (warp) {
-    memcpy(e->p_warp, warp, sizeof(double) * 6);
-    DCHK(hipMemcpyAsync(e->h_warp, e->p_warp, sizeof(double) * 6, hipMemcpyHostToDevice, st));
-  }
-  e->p_cnt[2] = 0;
-  e->p_cnt[3] = n;
-  DCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
-  e->cache_seq = -1;
-  int rc = launch(e, seq, 1, e->h_dets, e->h_off, e->h_embs, warp ? e->h_warp : nullptr, e->h_out,
-                  e->h_cnt, st);
-  if (rc) return rc;
-  DCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  DCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (n) DCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
-  DCHK(hipMemcpyAsync(e->p_sq, e->dev.o.seqst + (size_t)seq * SQO, sizeof(int) * SQO,
-                      hipMemcpyDeviceToHost, st));
-  DCHK(hipStreamSynchronize(st));
-  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
-  e->cache_seq = seq;
-  if (cnt) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
-  *n_out = cnt;
-  if (status == BX_ERR_CAPACITY)
-    return bx_record_error(BX_ERR_CAPACITY, "a sequence's detections exceeded det_cap on the device");
-  if (status)
-    return bx_record_error(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
-  return BX_OK;
+  BxStaging& sg = e->sg;
+  int rc;
+  if (n && F && (rc = sg.put(sg.h_embs, sg.p_embs, embs, sizeof(double) * F * n, st))) return rc;
+  if (warp && (rc = sg.put(sg.h_warp, sg.p_warp, warp, sizeof(double) * 6, st))) return rc;
+  return ocs_update_host_roundtrip(
+      *e, seq, dets, n, out, n_out, st, true,
+      [&] {
+        return launch(e, seq, 1, (float*)sg.h_dets, sg.h_off, (double*)sg.h_embs,
+                      warp ? sg.h_warp : nullptr, sg.h_out, sg.h_cnt, st);
+      },
+      OcsStreamSync{st});
 }
 
 // per_class=True (include/bxclasses.h): class c of sequence s is engine sequence s * C + c; the
@@ -1040,97 +929,45 @@ int bx_deepoc_update_classes_host(bx_deepoc* e, int seq, int n_classes, const fl
   if (rc) return rc;
   if ((seq + 1) * (long)n_classes > e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
   hipStream_t st = (hipStream_t)stream;
-  if (n) {
-    memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
-    DCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
-    if (F) {
-      memcpy(e->p_embs, embs, sizeof(double) * F * n);
-      DCHK(hipMemcpyAsync(e->h_embs, e->p_embs, sizeof(double) * F * n, hipMemcpyHostToDevice, st));
-    }
-  }
+  BxStaging& sg = e->sg;
+  if (n && F && (rc = sg.put(sg.h_embs, sg.p_embs, embs, sizeof(double) * F * n, st))) return rc;
   if (warps) {
     if (!e->h_cwarp) {
-      DCHK(hipMalloc(&e->h_cwarp, sizeof(double) * 6 * n_classes));
-      DCHK(hipHostMalloc(&e->p_cwarp, sizeof(double) * 6 * n_classes));
+      BX_HIPCHK(hipMalloc(&e->h_cwarp, sizeof(double) * 6 * n_classes));
+      BX_HIPCHK(hipHostMalloc(&e->p_cwarp, sizeof(double) * 6 * n_classes));
     }
     memcpy(e->p_cwarp, warps, sizeof(double) * 6 * n_classes);
-    DCHK(hipMemcpyAsync(e->h_cwarp, e->p_cwarp, sizeof(double) * 6 * n_classes,
+    BX_HIPCHK(hipMemcpyAsync(e->h_cwarp, e->p_cwarp, sizeof(double) * 6 * n_classes,
                         hipMemcpyHostToDevice, st));
   }
-  e->p_cnt[2] = 0;
-  e->p_cnt[3] = n;
-  DCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
-  if ((rc = cls_glue_put_ids(e->pc, seq, *id_count, st))) return rc;
-  rc = bx_deepoc_step_classes(e, seq, 1, n_classes, e->h_dets, e->h_off, F ? e->h_embs : nullptr,
-                              warps ? e->h_cwarp : nullptr, e->h_out, e->h_cnt, st);
-  if (rc) return rc;
-  DCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  DCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (n) DCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
-  int cstatus = 0;
-  if ((rc = cls_glue_take_ids(e->pc, seq, id_count, &cstatus, st))) return rc;  // synchronises
-  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
-  if (cnt > 0 && cnt <= n) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
-  *n_out = cnt > 0 && cnt <= n ? cnt : 0;
-  if (status == BX_ERR_CAPACITY || cstatus == BX_ERR_CAPACITY)
-    return bx_record_error(BX_ERR_CAPACITY, "a sequence's detections exceeded det_cap, or a "
-                                            "class's births its id map, on the device");
-  if (status)
-    return bx_record_error(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
-  if (cstatus) return bx_record_error(cstatus, "the class merge met an id the engine never gave out");
-  return BX_OK;
+  return ocs_update_host_roundtrip(
+      *e, -1, dets, n, out, n_out, st, true,
+      [&] {
+        if (int r = cls_glue_put_ids(e->pc, seq, *id_count, st)) return r;
+        return bx_deepoc_step_classes(e, seq, 1, n_classes, (float*)sg.h_dets, sg.h_off,
+                                      F ? (double*)sg.h_embs : nullptr,
+                                      warps ? e->h_cwarp : nullptr, sg.h_out, sg.h_cnt, st);
+      },
+      [&](int* cstatus) { return cls_glue_take_ids(e->pc, seq, id_count, cstatus, st); });
 }
 
 int bx_deepoc_status(bx_deepoc* e, int* status) {
   if (!e || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
-  DCHK(hipMemcpy(status, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(status, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost));
   return cls_glue_status(e->pc, status);
 }
 
 int bx_deepoc_counters_host(bx_deepoc* e, int seq, int* frame_count, int* id_count,
                             int* n_tracks) {
-  if (!e || seq < 0 || seq >= e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  int s[SQO];
-  if (seq == e->cache_seq) {
-    memcpy(s, e->p_sq, sizeof(s));
-  } else {
-    DCHK(hipDeviceSynchronize());
-    DCHK(hipMemcpy(s, e->dev.o.seqst + (size_t)seq * SQO, sizeof(s), hipMemcpyDeviceToHost));
-  }
-  if (frame_count) *frame_count = s[SO_FRAME];
-  if (id_count) *id_count = s[SO_IDS];
-  if (n_tracks) *n_tracks = s[SO_NTR];
-  return BX_OK;
+  return ocs_counters(e, seq, frame_count, id_count, n_tracks);
 }
 
 int bx_deepoc_set_id_count(bx_deepoc* e, int seq, int id_count, void* stream) {
-  if (!e || seq < 0 || seq >= e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  e->cache_seq = -1;
-  DCHK(hipMemcpyAsync(e->dev.o.seqst + (size_t)seq * SQO + SO_IDS, &id_count, sizeof(int),
-                      hipMemcpyHostToDevice, (hipStream_t)stream));
-  DCHK(hipStreamSynchronize((hipStream_t)stream));
-  return BX_OK;
+  return ocs_set_id_count(e, seq, id_count, stream);
 }
 
 int bx_deepoc_set_frame_size(bx_deepoc* e, int seq, double w, double h, void* stream) {
-  if (!e || seq < 0 || seq >= e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  const double f[2] = {w, h};
-  DCHK(hipMemcpyAsync(e->dev.o.fsz + 2 * (size_t)seq, f, sizeof(f), hipMemcpyHostToDevice,
-                      (hipStream_t)stream));
-  DCHK(hipStreamSynchronize((hipStream_t)stream));
-  return BX_OK;
-}
-
-// the list order of a sequence, on the host
-static int list_order(bx_deepoc* e, int seq, std::vector<int>& ord) {
-  DCHK(hipDeviceSynchronize());
-  int s[SQO];
-  DCHK(hipMemcpy(s, e->dev.o.seqst + (size_t)seq * SQO, sizeof(s), hipMemcpyDeviceToHost));
-  ord.resize(s[SO_NTR]);
-  if (s[SO_NTR])
-    DCHK(hipMemcpy(ord.data(), e->dev.o.order + (size_t)seq * e->dev.o.T, sizeof(int) * s[SO_NTR],
-                   hipMemcpyDeviceToHost));
-  return BX_OK;
+  return ocs_set_frame_size(e, seq, w, h, stream);
 }
 
 int bx_deepoc_tracks_host(bx_deepoc* e, int seq, int cap, int32_t* ids, double* x, double* p,
@@ -1138,19 +975,19 @@ int bx_deepoc_tracks_host(bx_deepoc* e, int seq, int cap, int32_t* ids, double* 
   if (!e || seq < 0 || seq >= e->dev.o.S || cap < 0 || !n)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_tracks_host");
   std::vector<int> ord;
-  int rc = list_order(e, seq, ord);
+  int rc = ocs_list_order(e->dev.o, seq, ord);
   if (rc) return rc;
   const int nt = (int)ord.size();
   const size_t F = e->dev.F, T = e->dev.o.T;
   for (int k = 0; k < nt && k < cap; k++) {
     OcsTrk t;
-    DCHK(hipMemcpy(&t, e->dev.o.trk + (size_t)seq * T + ord[k], sizeof(OcsTrk),
+    BX_HIPCHK(hipMemcpy(&t, e->dev.o.trk + (size_t)seq * T + ord[k], sizeof(OcsTrk),
                    hipMemcpyDeviceToHost));
     if (ids) ids[k] = t.id;
     if (x) memcpy(x + 7 * k, t.x, sizeof(t.x));
     if (p) memcpy(p + 49 * k, t.P, sizeof(t.P));
     if (emb && F)
-      DCHK(hipMemcpy(emb + F * k, e->dev.emb + ((size_t)seq * T + ord[k]) * F, sizeof(double) * F,
+      BX_HIPCHK(hipMemcpy(emb + F * k, e->dev.emb + ((size_t)seq * T + ord[k]) * F, sizeof(double) * F,
                      hipMemcpyDeviceToHost));
   }
   *n = nt;
@@ -1162,70 +999,37 @@ int bx_deepoc_state_set_host(bx_deepoc* e, int seq, int n, const int32_t* ids, c
   if (!e || seq < 0 || seq >= e->dev.o.S || n < 0 || (n && !ids))
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_state_set_host");
   std::vector<int> ord;
-  int rc = list_order(e, seq, ord);
+  int rc = ocs_list_order(e->dev.o, seq, ord);
   if (rc) return rc;
-  const int nt = (int)ord.size();
   const size_t F = e->dev.F, T = e->dev.o.T;
   for (int j = 0; j < n; j++) {
-    OcsTrk* dt = nullptr;
     OcsTrk t;
-    int slot = -1;
-    for (int k = 0; k < nt && !dt; k++) {
-      OcsTrk* cand = e->dev.o.trk + (size_t)seq * T + ord[k];
-      DCHK(hipMemcpy(&t, cand, sizeof(OcsTrk), hipMemcpyDeviceToHost));
-      if (t.id == ids[j]) dt = cand, slot = ord[k];
-    }
-    if (!dt) return bx_record_error(BX_ERR_INVALID, "state_set: no live track with that id");
+    int slot;
+    if ((rc = ocs_find_track(e->dev.o, e->dev.o.trk, seq, ord, ids[j], t, &slot))) return rc;
     if (x) memcpy(t.x, x + 7 * j, sizeof(t.x));
     if (p) memcpy(t.P, p + 49 * j, sizeof(t.P));
-    DCHK(hipMemcpy(dt, &t, sizeof(OcsTrk), hipMemcpyHostToDevice));
+    BX_HIPCHK(hipMemcpy(e->dev.o.trk + (size_t)seq * T + slot, &t, sizeof(OcsTrk),
+                   hipMemcpyHostToDevice));
     if (emb && F)
-      DCHK(hipMemcpy(e->dev.emb + ((size_t)seq * T + slot) * F, emb + F * j, sizeof(double) * F,
+      BX_HIPCHK(hipMemcpy(e->dev.emb + ((size_t)seq * T + slot) * F, emb + F * j, sizeof(double) * F,
                      hipMemcpyHostToDevice));
   }
   return BX_OK;
 }
 
 int bx_deepoc_frame_stats_host(bx_deepoc* e, int seq0, int nseq, int64_t* sums) {
-  if (!e || !sums || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.o.S)
-    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_frame_stats_host");
-  std::vector<int> s((size_t)nseq * SQO);
-  DCHK(hipDeviceSynchronize());
-  if (nseq)
-    DCHK(hipMemcpy(s.data(), e->dev.o.seqst + (size_t)seq0 * SQO, sizeof(int) * s.size(),
-                   hipMemcpyDeviceToHost));
-  int64_t t = 0, o = 0, f = 0;
-  for (int k = 0; k < nseq; k++) {
-    t += s[(size_t)k * SQO + SO_NTR];
-    o += s[(size_t)k * SQO + SO_NOUT];
-    f = s[(size_t)k * SQO + SO_FRAME] > f ? s[(size_t)k * SQO + SO_FRAME] : f;
-  }
-  sums[0] = t;
-  sums[1] = o;
-  sums[2] = f;
-  return BX_OK;
+  return ocs_frame_stats(e, "bx_deepoc_frame_stats_host", seq0, nseq, sums);
 }
 
 int bx_deepoc_probe(bx_deepoc* e, int stage) {
   if (!e || stage < -1 || stage > 2) return bx_record_error(BX_ERR_INVALID, "bad probe stage");
-  e->probe_stage = stage;
-  e->ev_used = 0;
+  e->probe.set(stage);
   return BX_OK;
 }
 
 int bx_deepoc_probe_read(bx_deepoc* e, double* total_ms, int* count) {
   if (!e || !total_ms || !count) return bx_record_error(BX_ERR_INVALID, "null argument");
-  double s = 0.0;
-  for (int k = 0; k < e->ev_used; k++) {
-    DCHK(hipEventSynchronize(e->ev[k].second));
-    float ms = 0.f;
-    DCHK(hipEventElapsedTime(&ms, e->ev[k].first, e->ev[k].second));
-    s += ms;
-  }
-  *total_ms = s;
-  *count = e->ev_used;
-  e->ev_used = 0;
-  return BX_OK;
+  return e->probe.read(total_ms, count);
 }
 
 int bx_deepoc_embcost(int nd, int nt, int F, const double* dets_embs, const double* trk_embs,
@@ -1235,7 +1039,7 @@ int bx_deepoc_embcost(int nd, int nt, int F, const double* dets_embs, const doub
   if (!nd || !nt) return BX_OK;
   hipLaunchKernelGGL(deepoc_embcost_op_kernel, dim3(ec_tiles(nd, nt)), dim3(256), 0,
                      (hipStream_t)stream, nd, nt, F, dets_embs, trk_embs, out);
-  DCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 

@@ -30,6 +30,7 @@
 
 #include "../../include/bxassoc.h"
 #include "bx_device.h"
+#include "bx_host.h"
 
 using namespace bx;
 
@@ -177,13 +178,6 @@ int set_err(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-#define HIPCHK(x)                                                                          \
-  do {                                                                                     \
-    hipError_t _e = (x);                                                                   \
-    if (_e != hipSuccess)                                                                  \
-      return set_err(BX_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e));          \
-  } while (0)
-
 // Device-side view of an engine (passed by value to every kernel).
 struct Dev {
   int S, T, D, F, kind, emb_f64, with_reid, fuse_first, max_time_lost, elds;
@@ -1959,29 +1953,12 @@ struct bx_engine {
   Dev dev;
   int device;
   size_t lds_assoc, lds_finish;
-  // stage timing probe (bx_engine_probe)
-  int probe_stage = -1;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> probe_ev;
-  size_t probe_used = 0;
-  void* arena;
-  size_t arena_bytes;
-  // host-path staging (device)
-  float* h_dets;
-  void* h_embs;
-  int* h_off;
-  double* h_out;
-  int* h_cnt;
-  double* h_warp;
-  // pinned host mirrors of the staging buffers (update_host: true async copies, one sync):
-  // dets, embs, offsets + counters, warp, output rows, out count + status
-  float* p_dets = nullptr;
-  char* p_embs = nullptr;
-  int* p_off = nullptr;
-  double* p_warp = nullptr;
-  double* p_out = nullptr;
-  int* p_cnt = nullptr;
-  int* p_seq = nullptr;     // the sequence's counters row after the last update_host
-  int cache_seq = -1;       // sequence whose counters p_seq holds (-1: none / stale)
+  BxProbe probe;  // stage timing probe (bx_engine_probe)
+  void* arena = nullptr;
+  size_t arena_bytes = 0;
+  // update_host staging; sg.p_sq: the sequence's counters row after the last update_host
+  BxStaging sg;
+  int cache_seq = -1;       // sequence whose counters sg.p_sq holds (-1: none / stale)
   int* h_lapmark = nullptr;  // host-mapped helper-wave cue (Dev::lapmark)
   uint32_t nlaunch = 0;      // association launches so far (the cue's clock; wraps, compared mod 2^32)
   int force_help = -1;       // bx_engine_force_assoc_build: -1 cue-driven, 0 / 1 that build always
@@ -2016,8 +1993,6 @@ struct bx_engine {
   double* h_cwarp = nullptr;  // [C][6] the class calls' warps
 };
 
-hipError_t bx_lds_attr(const void* kern, size_t bytes);  // below (never lowers a limit)
-
 namespace {
 
 template <typename T>
@@ -2031,7 +2006,7 @@ T* carve(char*& p, size_t n) {
 // the dynamic-LDS limit for > 64 KiB, per device and never lowered (bx_lds_attr, below)
 int lds_attr(const void* kern, size_t bytes) {
   if (bytes <= 65536) return BX_OK;
-  HIPCHK(bx_lds_attr(kern, bytes));
+  BX_HIPCHK(bx_lds_attr(kern, bytes));
   return BX_OK;
 }
 
@@ -2060,60 +2035,42 @@ int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int*
   // behind it on the side stream and that frame's join before K1c covers both (measured: 0.615
   // -> 0.599 ms/step at C3; a greater or lesser side-stream priority measured slower).
   if (reid && !e->side) {
-    HIPCHK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
+    BX_HIPCHK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
     for (int k = 0; k < 2; k++) {
-      HIPCHK(hipEventCreateWithFlags(&e->ev_fork[k], hipEventDisableTiming | hipEventDisableSystemFence));
-      HIPCHK(hipEventCreateWithFlags(&e->ev_join[k], hipEventDisableTiming | hipEventDisableSystemFence));
+      BX_HIPCHK(hipEventCreateWithFlags(&e->ev_fork[k], hipEventDisableTiming | hipEventDisableSystemFence));
+      BX_HIPCHK(hipEventCreateWithFlags(&e->ev_join[k], hipEventDisableTiming | hipEventDisableSystemFence));
     }
   }
   hipStream_t side = e->side;
   auto fork = [&](int k) -> int {
-    HIPCHK(hipEventRecord(e->ev_fork[k], st));
-    HIPCHK(hipStreamWaitEvent(side, e->ev_fork[k], 0));
+    BX_HIPCHK(hipEventRecord(e->ev_fork[k], st));
+    BX_HIPCHK(hipStreamWaitEvent(side, e->ev_fork[k], 0));
     return BX_OK;
   };
   auto join = [&](int k) -> int {
-    HIPCHK(hipEventRecord(e->ev_join[k], side));
-    HIPCHK(hipStreamWaitEvent(st, e->ev_join[k], 0));
-    return BX_OK;
-  };
-  auto probe_begin = [&](int stage, hipStream_t st) -> int {
-    if (stage != e->probe_stage) return BX_OK;
-    if (e->probe_used == e->probe_ev.size()) {
-      hipEvent_t a, b;
-      // timing-only events: no system-scope fence (cache writeback/invalidate) on record, so
-      // the probe does not perturb the kernels around it
-      HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-      HIPCHK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
-      e->probe_ev.emplace_back(a, b);
-    }
-    HIPCHK(hipEventRecord(e->probe_ev[e->probe_used].first, st));
-    return BX_OK;
-  };
-  auto probe_end = [&](int stage, hipStream_t st) -> int {
-    if (stage != e->probe_stage) return BX_OK;
-    HIPCHK(hipEventRecord(e->probe_ev[e->probe_used++].second, st));
+    BX_HIPCHK(hipEventRecord(e->ev_join[k], side));
+    BX_HIPCHK(hipStreamWaitEvent(st, e->ev_join[k], 0));
     return BX_OK;
   };
   // a probed stage is timed by events on the stream it is launched on
 #define BX_PROBED_ON(stage, sstream, ...)                     \
   do {                                                        \
-    if (int rc_ = probe_begin(stage, sstream)) return rc_;    \
+    if (int rc_ = e->probe.begin(stage, sstream)) return rc_; \
     __VA_ARGS__;                                              \
-    HIPCHK(hipGetLastError());                                \
-    if (int rc_ = probe_end(stage, sstream)) return rc_;      \
+    BX_HIPCHK(hipGetLastError());                                \
+    if (int rc_ = e->probe.end(stage, sstream)) return rc_;   \
   } while (0)
 #define BX_PROBED(stage, ...) BX_PROBED_ON(stage, st, __VA_ARGS__)
   const int gy_det64 = (d.D + K1_DETS - 1) / K1_DETS, gy_slot = (d.T + WG - 1) / WG;
   if (early && !e->k1s) {
-    HIPCHK(hipStreamCreateWithFlags(&e->k1s, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&e->ev_k1, hipEventDisableTiming | hipEventDisableSystemFence));
+    BX_HIPCHK(hipStreamCreateWithFlags(&e->k1s, hipStreamNonBlocking));
+    BX_HIPCHK(hipEventCreateWithFlags(&e->ev_k1, hipEventDisableTiming | hipEventDisableSystemFence));
     for (int k = 0; k < 2; k++)
-      HIPCHK(hipEventCreateWithFlags(&e->ev_k5[k], hipEventDisableTiming | hipEventDisableSystemFence));
+      BX_HIPCHK(hipEventCreateWithFlags(&e->ev_k5[k], hipEventDisableTiming | hipEventDisableSystemFence));
   }
   // early features: K1 on k1s after only the K5 two launches back (the last reader of this
   // dnrm half; K1c of that launch came before that K5); else on the side stream, forked here
-  if (early && e->k5_rec[par]) HIPCHK(hipStreamWaitEvent(e->k1s, e->ev_k5[par], 0));
+  if (early && e->k5_rec[par]) BX_HIPCHK(hipStreamWaitEvent(e->k1s, e->ev_k5[par], 0));
   hipStream_t k1st = early ? e->k1s : side;
   if (reid && !early)
     if (int rc = fork(0)) return rc;
@@ -2139,7 +2096,7 @@ int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int*
     BX_PROBED_ON(BX_STAGE_DET_FEATURES, k1st,
                  hipLaunchKernelGGL((det_feature_kernel<FT, NPF, 0>), dim3(nseq, gy_det64),
                                     dim3(WG), 0, k1st, d, seq0, dets, det_off, (const FT*)embs));
-  if (early) HIPCHK(hipEventRecord(e->ev_k1, e->k1s));
+  if (early) BX_HIPCHK(hipEventRecord(e->ev_k1, e->k1s));
   if (gmc)
     BX_PROBED(BX_STAGE_PREDICT,
               hipLaunchKernelGGL((predict_kernel<KIND, true>), dim3(nseq, gy_slot), dim3(WG), 0,
@@ -2154,7 +2111,7 @@ int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int*
               hipLaunchKernelGGL(gate_kernel<KIND>, dim3(nseq, GATE_BLOCKS), dim3(WG), glds, st,
                                  d, seq0, dets, det_off));
     // K1c reads K1's norms and the smooth features the last K5 wrote (overlap mode: unjoined)
-    if (early) HIPCHK(hipStreamWaitEvent(st, e->ev_k1, 0));
+    if (early) BX_HIPCHK(hipStreamWaitEvent(st, e->ev_k1, 0));
     if (!early || e->side_pending)
       if (int rc = join(0)) return rc;
     if (e->cos_mode == 1)
@@ -2204,7 +2161,7 @@ int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int*
     if (int rc = fork(1)) return rc;
     if (int rc = launch_k5()) return rc;
     if (early) {  // the last reader of this dnrm half: the launch after next's K1 waits for it
-      HIPCHK(hipEventRecord(e->ev_k5[par], side));
+      BX_HIPCHK(hipEventRecord(e->ev_k5[par], side));
       e->k5_rec[par] = true;
     }
   }
@@ -2239,7 +2196,7 @@ static int settle(bx_engine* e) {
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (e->side_pending) {
     e->side_pending = false;
-    HIPCHK(hipStreamSynchronize(e->side));
+    BX_HIPCHK(hipStreamSynchronize(e->side));
   }
   return BX_OK;
 }
@@ -2302,108 +2259,98 @@ int bx_engine_create(const bx_config* cfg, bx_engine** out) {
     return set_err(BX_ERR_NO_DEVICE, "no HIP device visible");
   auto* e = new bx_engine();
   e->cfg = *cfg;
-  HIPCHK(hipGetDevice(&e->device));
-  const int S = cfg->n_seq, T = cfg->track_cap, D = cfg->det_cap;
-  const int F = reid ? cfg->emb_dim : 0;
-  const size_t fs = cfg->emb_f64 ? 8 : 4;
-  Dev& d = e->dev;
-  d.S = S; d.T = T; d.D = D; d.F = F; d.kind = cfg->kind; d.emb_f64 = cfg->emb_f64;
-  d.with_reid = reid; d.fuse_first = cfg->fuse_first_associate;
-  d.elds = ELDS_DEFAULT;
-  d.lap_stats = 0;
-  d.jvs_stride = (jv_bytes(T + D) + 255) & ~size_t(255);
-  d.match_thresh = cfg->match_thresh;
-  d.max_time_lost = (int)(cfg->frame_rate / 30.0 * cfg->track_buffer);
-  if (cfg->kind == BX_BYTETRACK) {
-    d.low = cfg->min_conf; d.high = cfg->track_thresh; d.new_thresh = cfg->track_thresh;
-  } else {
-    d.low = cfg->track_low_thresh; d.high = cfg->track_high_thresh;
-    d.new_thresh = cfg->new_track_thresh;
-  }
-  d.prox = cfg->proximity_thresh;
-  d.app = cfg->appearance_thresh;
-  const size_t ST = (size_t)S * T;
-  const size_t SD = (size_t)S * D, FF = F ? F : 1;
-  const size_t FS = F > REG_F ? F : 1;  // twice-normalised det rows kept only for wide features
-  // carve the arena twice: once from a null base to size it, once for real
-  auto layout = [&](char* p) {
-    char* p0 = p;
-    d.seq = carve<int>(p, (size_t)S * SQ_STRIDE);
-    d.act = carve<uint16_t>(p, ST);
-    d.lost = carve<uint16_t>(p, ST);
-    d.act2 = carve<uint16_t>(p, ST);
-    d.lost2 = carve<uint16_t>(p, ST);
-    d.flags = carve<uint32_t>(p, ST);
-    d.frame_id = carve<int>(p, ST);
-    d.start = carve<int>(p, ST);
-    d.id = carve<int>(p, ST);
-    d.tlen = carve<int>(p, ST);
-    d.detind = carve<int>(p, ST);
-    d.conf = carve<double>(p, ST);
-    d.cls = carve<double>(p, ST);
-    d.kf = carve<double>(p, ST * KF_STRIDE);
-    d.feat = carve<char>(p, fs * ST * FF);
-    d.clsh = carve<double>(p, ST * CLS_HIST * 2);
-    d.ncls = carve<int>(p, ST);
-    d.gcol = carve<uint16_t>(p, ST * D);
-    d.gcost = carve<double>(p, ST * D);
-    d.rec = carve<int2>(p, SD);
-    d.dnrm = carve<double>(p, 2 * SD * 4);
-    d.tdn = carve<float>(p, reid ? ST : 1);
-    d.pairs = carve<uint32_t>(p, reid ? ST * D : 1);
-    d.npair = carve<int>(p, S);
-    d.etab = carve<double>(p, reid ? ST * D : 1);
-    d.jvs = carve<unsigned char>(p, (size_t)S * d.jvs_stride);
-    d.fscr = carve<char>(p, fs * SD * FS);
-    d.status = carve<int>(p, 16);
-    return (size_t)(p - p0);
-  };
-  const size_t bytes = layout(nullptr);
-  e->arena_bytes = bytes;
-  if (hipMalloc(&e->arena, bytes) != hipSuccess) {
-    delete e;
-    return set_err(BX_ERR_HIP, "hipMalloc of the engine arena failed");
-  }
-  layout((char*)e->arena);
-  d.dbg = nullptr;
-#ifdef BX_PHASE_TIMING
-  HIPCHK(hipMalloc(&d.dbg, sizeof(unsigned long long) * BX_DBG_STRIDE * S));
-  HIPCHK(hipMemset(d.dbg, 0, sizeof(unsigned long long) * BX_DBG_STRIDE * S));
-#endif
-  HIPCHK(hipMemset(e->arena, 0, bytes));
-  e->lds_assoc = LdsA(T, D, d.elds).total;
-  e->lds_finish = LdsF(T).total;
-  {
-    const LdsA Lo(T, D, d.elds);  // the LAP helper scratch overlays tboxf .. dconf
-    if (lap_helper_bytes((T + 7) & ~7, (D + 7) & ~7) > Lo.o_dconf - Lo.o_tboxf) {
-      (void)hipFree(e->arena);
-      delete e;
-      return set_err(BX_ERR_INVALID, "LAP helper scratch does not fit its LDS overlay");
+  // everything that can fail runs in `fill`: a failure frees what was allocated so far
+  auto fill = [&]() -> int {
+    BX_HIPCHK(hipGetDevice(&e->device));
+    const int S = cfg->n_seq, T = cfg->track_cap, D = cfg->det_cap;
+    const int F = reid ? cfg->emb_dim : 0;
+    const size_t fs = cfg->emb_f64 ? 8 : 4;
+    Dev& d = e->dev;
+    d.S = S; d.T = T; d.D = D; d.F = F; d.kind = cfg->kind; d.emb_f64 = cfg->emb_f64;
+    d.with_reid = reid; d.fuse_first = cfg->fuse_first_associate;
+    d.elds = ELDS_DEFAULT;
+    d.lap_stats = 0;
+    d.jvs_stride = (jv_bytes(T + D) + 255) & ~size_t(255);
+    d.match_thresh = cfg->match_thresh;
+    d.max_time_lost = (int)(cfg->frame_rate / 30.0 * cfg->track_buffer);
+    if (cfg->kind == BX_BYTETRACK) {
+      d.low = cfg->min_conf; d.high = cfg->track_thresh; d.new_thresh = cfg->track_thresh;
+    } else {
+      d.low = cfg->track_low_thresh; d.high = cfg->track_high_thresh;
+      d.new_thresh = cfg->new_track_thresh;
     }
+    d.prox = cfg->proximity_thresh;
+    d.app = cfg->appearance_thresh;
+    const size_t ST = (size_t)S * T;
+    const size_t SD = (size_t)S * D, FF = F ? F : 1;
+    const size_t FS = F > REG_F ? F : 1;  // twice-normalised det rows kept only for wide features
+    // carve the arena twice: once from a null base to size it, once for real
+    auto layout = [&](char* p) {
+      char* p0 = p;
+      d.seq = carve<int>(p, (size_t)S * SQ_STRIDE);
+      d.act = carve<uint16_t>(p, ST);
+      d.lost = carve<uint16_t>(p, ST);
+      d.act2 = carve<uint16_t>(p, ST);
+      d.lost2 = carve<uint16_t>(p, ST);
+      d.flags = carve<uint32_t>(p, ST);
+      d.frame_id = carve<int>(p, ST);
+      d.start = carve<int>(p, ST);
+      d.id = carve<int>(p, ST);
+      d.tlen = carve<int>(p, ST);
+      d.detind = carve<int>(p, ST);
+      d.conf = carve<double>(p, ST);
+      d.cls = carve<double>(p, ST);
+      d.kf = carve<double>(p, ST * KF_STRIDE);
+      d.feat = carve<char>(p, fs * ST * FF);
+      d.clsh = carve<double>(p, ST * CLS_HIST * 2);
+      d.ncls = carve<int>(p, ST);
+      d.gcol = carve<uint16_t>(p, ST * D);
+      d.gcost = carve<double>(p, ST * D);
+      d.rec = carve<int2>(p, SD);
+      d.dnrm = carve<double>(p, 2 * SD * 4);
+      d.tdn = carve<float>(p, reid ? ST : 1);
+      d.pairs = carve<uint32_t>(p, reid ? ST * D : 1);
+      d.npair = carve<int>(p, S);
+      d.etab = carve<double>(p, reid ? ST * D : 1);
+      d.jvs = carve<unsigned char>(p, (size_t)S * d.jvs_stride);
+      d.fscr = carve<char>(p, fs * SD * FS);
+      d.status = carve<int>(p, 16);
+      return (size_t)(p - p0);
+    };
+    const size_t bytes = layout(nullptr);
+    e->arena_bytes = bytes;
+    if (hipMalloc(&e->arena, bytes) != hipSuccess)
+      return set_err(BX_ERR_HIP, "hipMalloc of the engine arena failed");
+    layout((char*)e->arena);
+    d.dbg = nullptr;
+#ifdef BX_PHASE_TIMING
+    BX_HIPCHK(hipMalloc(&d.dbg, sizeof(unsigned long long) * BX_DBG_STRIDE * S));
+    BX_HIPCHK(hipMemset(d.dbg, 0, sizeof(unsigned long long) * BX_DBG_STRIDE * S));
+#endif
+    BX_HIPCHK(hipMemset(e->arena, 0, bytes));
+    e->lds_assoc = LdsA(T, D, d.elds).total;
+    e->lds_finish = LdsF(T).total;
+    {
+      const LdsA Lo(T, D, d.elds);  // the LAP helper scratch overlays tboxf .. dconf
+      if (lap_helper_bytes((T + 7) & ~7, (D + 7) & ~7) > Lo.o_dconf - Lo.o_tboxf)
+        return set_err(BX_ERR_INVALID, "LAP helper scratch does not fit its LDS overlay");
+    }
+    if (e->lds_assoc > 160 * 1024 || e->lds_finish > 160 * 1024)
+      return set_err(BX_ERR_INVALID, "track_cap/det_cap too large for one workgroup's LDS");
+    // host-path staging for one sequence
+    if (int rc = e->sg.alloc(sizeof(float) * 6 * D, fs * (size_t)D * (F ? F : 1), 6, 8, D, SQ_STRIDE))
+      return rc;
+    // the LAPs' helper-wave cue, written by the association kernel, read by the host at launch
+    BX_HIPCHK(hipHostMalloc(&e->h_lapmark, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    *e->h_lapmark = (int)(0u - (BX_HELP_WINDOW + 1u));  // "long ago" on the wrapping clock
+    BX_HIPCHK(hipHostGetDevicePointer((void**)&e->dev.lapmark, e->h_lapmark, 0));
+    return BX_OK;
+  };
+  const int rc = fill();
+  if (rc) {
+    bx_engine_destroy(e);
+    return rc;
   }
-  if (e->lds_assoc > 160 * 1024 || e->lds_finish > 160 * 1024) {
-    (void)hipFree(e->arena);
-    delete e;
-    return set_err(BX_ERR_INVALID, "track_cap/det_cap too large for one workgroup's LDS");
-  }
-  // host-path staging for one sequence
-  HIPCHK(hipMalloc(&e->h_dets, sizeof(float) * 6 * D));
-  HIPCHK(hipMalloc(&e->h_embs, fs * (size_t)D * (F ? F : 1)));
-  HIPCHK(hipMalloc(&e->h_off, sizeof(int) * 2));
-  HIPCHK(hipMalloc(&e->h_out, sizeof(double) * 8 * D));
-  HIPCHK(hipMalloc(&e->h_cnt, sizeof(int)));
-  HIPCHK(hipMalloc(&e->h_warp, sizeof(double) * 6));
-  HIPCHK(hipHostMalloc(&e->p_dets, sizeof(float) * 6 * D));
-  HIPCHK(hipHostMalloc(&e->p_embs, fs * (size_t)D * (F ? F : 1)));
-  HIPCHK(hipHostMalloc(&e->p_off, sizeof(int) * 2));
-  HIPCHK(hipHostMalloc(&e->p_warp, sizeof(double) * 6));
-  HIPCHK(hipHostMalloc(&e->p_out, sizeof(double) * 8 * D));
-  HIPCHK(hipHostMalloc(&e->p_cnt, sizeof(int) * 2));
-  HIPCHK(hipHostMalloc(&e->p_seq, sizeof(int) * SQ_STRIDE));
-  // the LAPs' helper-wave cue, written by the association kernel, read by the host at launch
-  HIPCHK(hipHostMalloc(&e->h_lapmark, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-  *e->h_lapmark = (int)(0u - (BX_HELP_WINDOW + 1u));  // "long ago" on the wrapping clock
-  HIPCHK(hipHostGetDevicePointer((void**)&e->dev.lapmark, e->h_lapmark, 0));
   *out = e;
   return BX_OK;
 }
@@ -2424,25 +2371,13 @@ int bx_engine_destroy(bx_engine* e) {
     (void)hipEventDestroy(e->ev_k1);
     for (int k = 0; k < 2; k++) (void)hipEventDestroy(e->ev_k5[k]);
   }
-  for (auto& ev : e->probe_ev) {
-    (void)hipEventDestroy(ev.first);
-    (void)hipEventDestroy(ev.second);
-  }
+  e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->h_dets);
-  (void)hipFree(e->h_embs);
-  (void)hipFree(e->h_off);
-  (void)hipFree(e->h_out);
-  (void)hipFree(e->h_cnt);
-  (void)hipFree(e->h_warp);
-  (void)hipHostFree(e->p_dets);
+#ifdef BX_PHASE_TIMING
+  (void)hipFree(e->dev.dbg);
+#endif
+  e->sg.free();
   if (e->h_lapmark) (void)hipHostFree(e->h_lapmark);
-  (void)hipHostFree(e->p_embs);
-  (void)hipHostFree(e->p_off);
-  (void)hipHostFree(e->p_warp);
-  (void)hipHostFree(e->p_out);
-  (void)hipHostFree(e->p_cnt);
-  (void)hipHostFree(e->p_seq);
   for (char* p : e->park) (void)hipFree(p);
   (void)hipFree(e->h_coff);
   (void)hipFree(e->h_ccnt);
@@ -2458,10 +2393,10 @@ int bx_engine_reset(bx_engine* e, int seq0, int nseq, void* stream) {
   e->cache_seq = -1;
   hipLaunchKernelGGL(reset_kernel, dim3(nseq), dim3(256), 0, (hipStream_t)stream, e->dev.seq,
                      e->dev.flags, e->dev.T, seq0, nseq);
-  HIPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   for (int s = seq0; s < seq0 + nseq && e->n_classes; s++)
     if (e->park[s]) {  // parked class lists are gone with the tracks
-      HIPCHK(hipMemsetAsync(e->park[s] + park_npark_off(e), 0, sizeof(int) * (e->n_classes + 1),
+      BX_HIPCHK(hipMemsetAsync(e->park[s] + park_npark_off(e), 0, sizeof(int) * (e->n_classes + 1),
                             (hipStream_t)stream));
       e->cur_cls[s] = 0;
     }
@@ -2505,29 +2440,22 @@ int bx_engine_update_host(bx_engine* e, int seq, const float* dets, int n, const
   const size_t fs = e->cfg.emb_f64 ? 8 : 4;
   // inputs through pinned mirrors (asynchronous DMA), the frame, then the rows (at most n), the
   // count and the status back in one go: a single synchronisation per frame
-  const bool ecopy = n && e->dev.with_reid;
-  if (n) memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
-  if (ecopy) memcpy(e->p_embs, embs, fs * (size_t)n * e->dev.F);
-  e->p_off[0] = 0;
-  e->p_off[1] = n;
-  if (warp) memcpy(e->p_warp, warp, sizeof(double) * 6);
-  if (n) HIPCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
-  if (ecopy)
-    HIPCHK(hipMemcpyAsync(e->h_embs, e->p_embs, fs * (size_t)n * e->dev.F, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(e->h_off, e->p_off, sizeof(int) * 2, hipMemcpyHostToDevice, st));
-  if (warp) HIPCHK(hipMemcpyAsync(e->h_warp, e->p_warp, sizeof(double) * 6, hipMemcpyHostToDevice, st));
-  int rc = bx_engine_step(e, seq, 1, e->h_dets, e->h_off, e->h_embs, warp ? e->h_warp : nullptr,
-                          e->h_out, e->h_cnt, stream);
+  BxStaging& sg = e->sg;
+  int rc;
+  if (n && (rc = sg.put(sg.h_dets, sg.p_dets, dets, sizeof(float) * 6 * n, st))) return rc;
+  if (n && e->dev.with_reid &&
+      (rc = sg.put(sg.h_embs, sg.p_embs, embs, fs * (size_t)n * e->dev.F, st)))
+    return rc;
+  if ((rc = sg.put_off(n, st))) return rc;
+  if (warp && (rc = sg.put(sg.h_warp, sg.p_warp, warp, sizeof(double) * 6, st))) return rc;
+  rc = bx_engine_step(e, seq, 1, (float*)sg.h_dets, sg.h_off, sg.h_embs,
+                      warp ? sg.h_warp : nullptr, sg.h_out, sg.h_cnt, stream);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.status, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (n) HIPCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(e->p_seq, e->dev.seq + (size_t)seq * SQ_STRIDE, sizeof(int) * SQ_STRIDE,
-                        hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if ((rc = sg.take(e->dev.status, e->dev.seq + (size_t)seq * SQ_STRIDE, n, st))) return rc;
+  BX_HIPCHK(hipStreamSynchronize(st));
   e->cache_seq = seq;  // bx_engine_counters_host answers from it until the next device change
-  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
-  if (cnt && out) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
+  const int cnt = sg.p_cnt[0], status = sg.p_cnt[1];
+  if (cnt && out) memcpy(out, sg.p_out, sizeof(double) * 8 * cnt);
   *n_out = cnt;
   if (status & (1 << BX_ERR_TRACK_OVERFLOW))
     return set_err(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
@@ -2559,14 +2487,14 @@ int bx_engine_update_classes_host(bx_engine* e, int seq, const float* dets, int 
     e->n_classes = C;
     e->park.assign(e->dev.S, nullptr);
     e->cur_cls.assign(e->dev.S, 0);
-    HIPCHK(hipMalloc(&e->h_coff, sizeof(int) * 2 * C));
-    HIPCHK(hipMalloc(&e->h_ccnt, sizeof(int) * C));
-    HIPCHK(hipMalloc(&e->h_cwarp, sizeof(double) * 6 * C));
+    BX_HIPCHK(hipMalloc(&e->h_coff, sizeof(int) * 2 * C));
+    BX_HIPCHK(hipMalloc(&e->h_ccnt, sizeof(int) * C));
+    BX_HIPCHK(hipMalloc(&e->h_cwarp, sizeof(double) * 6 * C));
   }
   if (!e->park[seq]) {
     const size_t bytes = park_npark_off(e) + sizeof(int) * (C + 1);
-    HIPCHK(hipMalloc(&e->park[seq], bytes));
-    HIPCHK(hipMemset(e->park[seq], 0, bytes));
+    BX_HIPCHK(hipMalloc(&e->park[seq], bytes));
+    BX_HIPCHK(hipMemset(e->park[seq], 0, bytes));
   }
   uint16_t* park = (uint16_t*)e->park[seq];
   int* npark = (int*)(e->park[seq] + park_npark_off(e));
@@ -2598,35 +2526,35 @@ int bx_engine_update_classes_host(bx_engine* e, int seq, const float* dets, int 
   }
   std::vector<int> hoff(2 * C);
   for (int c = 0; c < C; c++) { hoff[2 * c] = 0; hoff[2 * c + 1] = cnt[c + 1] - cnt[c]; }
-  if (m) HIPCHK(hipMemcpyAsync(e->h_dets, hd.data(), sizeof(float) * 6 * m, hipMemcpyHostToDevice, st));
-  if (m && reid) HIPCHK(hipMemcpyAsync(e->h_embs, he.data(), fs * (size_t)m * F, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(e->h_coff, hoff.data(), sizeof(int) * 2 * C, hipMemcpyHostToDevice, st));
-  if (warps) HIPCHK(hipMemcpyAsync(e->h_cwarp, warps, sizeof(double) * 6 * C, hipMemcpyHostToDevice, st));
+  if (m) BX_HIPCHK(hipMemcpyAsync((float*)e->sg.h_dets, hd.data(), sizeof(float) * 6 * m, hipMemcpyHostToDevice, st));
+  if (m && reid) BX_HIPCHK(hipMemcpyAsync(e->sg.h_embs, he.data(), fs * (size_t)m * F, hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemcpyAsync(e->h_coff, hoff.data(), sizeof(int) * 2 * C, hipMemcpyHostToDevice, st));
+  if (warps) BX_HIPCHK(hipMemcpyAsync(e->h_cwarp, warps, sizeof(double) * 6 * C, hipMemcpyHostToDevice, st));
   for (int c = 0; c < C; c++) {
     hipLaunchKernelGGL(class_swap_kernel, dim3(1), dim3(WG), 0, st, e->dev, seq, park, npark, C,
                        e->cur_cls[seq], c, c == 0 ? 1 : 0);
-    HIPCHK(hipGetLastError());
+    BX_HIPCHK(hipGetLastError());
     e->cur_cls[seq] = c;
-    const char* ep = reid ? (const char*)e->h_embs + fs * F * (size_t)cnt[c] : nullptr;
+    const char* ep = reid ? (const char*)e->sg.h_embs + fs * F * (size_t)cnt[c] : nullptr;
     // class call c's warp (an identity warp is no warp, as in bx_engine_update_host's callers)
     const bool wc = warps && !is_identity_warp(warps + 6 * (size_t)c);
-    int rc = bx_engine_step(e, seq, 1, e->h_dets + 6 * (size_t)cnt[c], e->h_coff + 2 * c, ep,
+    int rc = bx_engine_step(e, seq, 1, (float*)e->sg.h_dets + 6 * (size_t)cnt[c], e->h_coff + 2 * c, ep,
                             wc ? e->h_cwarp + 6 * (size_t)c : nullptr,
-                            e->h_out + 8 * (size_t)cnt[c], e->h_ccnt + c, stream);
+                            e->sg.h_out + 8 * (size_t)cnt[c], e->h_ccnt + c, stream);
     if (rc) return rc;
   }
   std::vector<int> oc(C);
-  HIPCHK(hipMemcpyAsync(oc.data(), e->h_ccnt, sizeof(int) * C, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(oc.data(), e->h_ccnt, sizeof(int) * C, hipMemcpyDeviceToHost, st));
   std::vector<double> ho((size_t)8 * (m ? m : 1));
-  if (m) HIPCHK(hipMemcpyAsync(ho.data(), e->h_out, sizeof(double) * 8 * m, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if (m) BX_HIPCHK(hipMemcpyAsync(ho.data(), e->sg.h_out, sizeof(double) * 8 * m, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   int k = 0;
   for (int c = 0; c < C; c++)
     for (int j = 0; j < oc[c]; j++, k++)
       if (out) memcpy(out + 8 * (size_t)k, &ho[8 * ((size_t)cnt[c] + j)], 8 * sizeof(double));
   *n_out = k;
   int status = 0;
-  HIPCHK(hipMemcpy(&status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(&status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   if (status & (1 << BX_ERR_TRACK_OVERFLOW))
     return set_err(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
   return BX_OK;
@@ -2636,8 +2564,8 @@ int bx_engine_update_classes_host(bx_engine* e, int seq, const float* dets, int 
 // diagnostic only: copy the [S][32] phase stamps of the last launch to the host
 int bx_debug_stamps_host(bx_engine* e, unsigned long long* out) {
   if (int rc = settle(e)) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, e->dev.dbg, sizeof(unsigned long long) * BX_DBG_STRIDE * e->dev.S,
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(out, e->dev.dbg, sizeof(unsigned long long) * BX_DBG_STRIDE * e->dev.S,
                    hipMemcpyDeviceToHost));
   return BX_OK;
 }
@@ -2647,7 +2575,7 @@ int bx_engine_status(bx_engine* e, int* status) {
   if (int rc = settle(e)) return rc;
   if (!e || !status) return set_err(BX_ERR_INVALID, "null argument");
   int s = 0;
-  HIPCHK(hipMemcpy(&s, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(&s, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   *status = (s & (1 << BX_ERR_TRACK_OVERFLOW)) ? BX_ERR_TRACK_OVERFLOW
             : (s & (1 << BX_ERR_CAPACITY))     ? BX_ERR_CAPACITY
                                                : BX_OK;
@@ -2659,7 +2587,7 @@ int bx_engine_frame_stats_host(bx_engine* e, int seq0, int nseq, int64_t* sums) 
   if (!e || !sums || seq0 < 0 || nseq <= 0 || seq0 + nseq > e->dev.S)
     return set_err(BX_ERR_INVALID, "bad arguments to bx_engine_frame_stats_host");
   std::vector<int> v((size_t)nseq * SQ_STRIDE);
-  HIPCHK(hipMemcpy(v.data(), e->dev.seq + (size_t)seq0 * SQ_STRIDE, sizeof(int) * v.size(),
+  BX_HIPCHK(hipMemcpy(v.data(), e->dev.seq + (size_t)seq0 * SQ_STRIDE, sizeof(int) * v.size(),
                    hipMemcpyDeviceToHost));
   const int idx[7] = {SQ_NDET, SQ_NHIGH, SQ_NA, SQ_NL, SQ_NREC, SQ_NPAIR, SQ_FC};
   for (int k = 0; k < 7; k++) {
@@ -2675,7 +2603,7 @@ int bx_engine_lap_ties_host(bx_engine* e, int seq0, int nseq, int64_t* total) {
   if (!e || !total || seq0 < 0 || nseq <= 0 || seq0 + nseq > e->dev.S)
     return set_err(BX_ERR_INVALID, "bad arguments to bx_engine_lap_ties_host");
   std::vector<int> v((size_t)nseq * SQ_STRIDE);
-  HIPCHK(hipMemcpy(v.data(), e->dev.seq + (size_t)seq0 * SQ_STRIDE, sizeof(int) * v.size(),
+  BX_HIPCHK(hipMemcpy(v.data(), e->dev.seq + (size_t)seq0 * SQ_STRIDE, sizeof(int) * v.size(),
                    hipMemcpyDeviceToHost));
   int64_t t = 0;
   for (int q = 0; q < nseq; q++) t += v[(size_t)q * SQ_STRIDE + SQ_NTIE];
@@ -2688,7 +2616,7 @@ int bx_engine_lap_components_host(bx_engine* e, int seq0, int nseq, int64_t* sum
   if (!e || !sums || seq0 < 0 || nseq <= 0 || seq0 + nseq > e->dev.S)
     return set_err(BX_ERR_INVALID, "bad arguments to bx_engine_lap_components_host");
   std::vector<int> v((size_t)nseq * SQ_STRIDE);
-  HIPCHK(hipMemcpy(v.data(), e->dev.seq + (size_t)seq0 * SQ_STRIDE, sizeof(int) * v.size(),
+  BX_HIPCHK(hipMemcpy(v.data(), e->dev.seq + (size_t)seq0 * SQ_STRIDE, sizeof(int) * v.size(),
                    hipMemcpyDeviceToHost));
   sums[0] = sums[1] = sums[2] = 0;
   for (int q = 0; q < nseq; q++) {
@@ -2701,25 +2629,14 @@ int bx_engine_lap_components_host(bx_engine* e, int seq0, int nseq, int64_t* sum
 
 int bx_engine_probe(bx_engine* e, int stage) {
   if (!e || stage >= BX_STAGE_COUNT) return set_err(BX_ERR_INVALID, "bad probe stage");
-  e->probe_stage = stage < 0 ? -1 : stage;
-  e->probe_used = 0;
+  e->probe.set(stage);
   return BX_OK;
 }
 
 int bx_engine_probe_read(bx_engine* e, double* total_ms, int* count) {
   if (int rc = settle(e)) return rc;
   if (!e || !total_ms || !count) return set_err(BX_ERR_INVALID, "null argument");
-  double t = 0.0;
-  for (size_t k = 0; k < e->probe_used; k++) {
-    HIPCHK(hipEventSynchronize(e->probe_ev[k].second));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e->probe_ev[k].first, e->probe_ev[k].second));
-    t += ms;
-  }
-  *total_ms = t;
-  *count = (int)e->probe_used;
-  e->probe_used = 0;
-  return BX_OK;
+  return e->probe.read(total_ms, count);
 }
 
 int bx_engine_counters_host(bx_engine* e, int seq, int* frame_count, int* id_count, int* n_active,
@@ -2728,9 +2645,9 @@ int bx_engine_counters_host(bx_engine* e, int seq, int* frame_count, int* id_cou
   if (!e || seq < 0 || seq >= e->dev.S) return set_err(BX_ERR_INVALID, "bad sequence");
   int v[SQ_STRIDE];
   if (seq == e->cache_seq)
-    memcpy(v, e->p_seq, sizeof(v));
+    memcpy(v, e->sg.p_sq, sizeof(v));
   else
-    HIPCHK(hipMemcpy(v, e->dev.seq + (size_t)seq * SQ_STRIDE, sizeof(v), hipMemcpyDeviceToHost));
+    BX_HIPCHK(hipMemcpy(v, e->dev.seq + (size_t)seq * SQ_STRIDE, sizeof(v), hipMemcpyDeviceToHost));
   if (frame_count) *frame_count = v[SQ_FC];
   if (id_count) *id_count = v[SQ_IDC];
   if (n_active) *n_active = v[SQ_NA];
@@ -2744,7 +2661,7 @@ int bx_engine_set_id_count(bx_engine* e, int seq, int id_count, void* stream) {
   e->cache_seq = -1;
   hipLaunchKernelGGL(set_id_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, e->dev.seq, seq,
                      id_count);
-  HIPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -2762,18 +2679,18 @@ int snapshot_slots(bx_engine* e, int seq, const std::vector<int>& slots, int32_t
     else
       hipLaunchKernelGGL(materialize_kernel<KIND_BOT>, dim3((T + WG - 1) / WG), dim3(WG), 0, 0,
                          e->dev, seq);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
+    BX_HIPCHK(hipGetLastError());
+    BX_HIPCHK(hipDeviceSynchronize());
   }
   std::vector<uint32_t> fl(T);
   std::vector<int> id(T), fid(T), st(T);
   std::vector<double> kf((size_t)KF_STRIDE * T);
   const size_t sT = (size_t)seq * T;
-  HIPCHK(hipMemcpy(fl.data(), e->dev.flags + sT, 4 * T, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(id.data(), e->dev.id + sT, 4 * T, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(fid.data(), e->dev.frame_id + sT, 4 * T, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(st.data(), e->dev.start + sT, 4 * T, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(kf.data(), e->dev.kf + sT * KF_STRIDE, 8 * KF_STRIDE * (size_t)T,
+  BX_HIPCHK(hipMemcpy(fl.data(), e->dev.flags + sT, 4 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(id.data(), e->dev.id + sT, 4 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(fid.data(), e->dev.frame_id + sT, 4 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(st.data(), e->dev.start + sT, 4 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(kf.data(), e->dev.kf + sT * KF_STRIDE, 8 * KF_STRIDE * (size_t)T,
                    hipMemcpyDeviceToHost));
   for (size_t k = 0; k < slots.size(); k++) {
     const int slot = slots[k];
@@ -2795,18 +2712,18 @@ int bx_engine_tracks_host(bx_engine* e, int seq, int cap, int32_t* ids, int32_t*
   if (int rc = settle(e)) return rc;
   if (!e || seq < 0 || seq >= e->dev.S) return set_err(BX_ERR_INVALID, "bad sequence");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   const int T = e->dev.T;
   int v[SQ_STRIDE];
-  HIPCHK(hipMemcpy(v, e->dev.seq + (size_t)seq * SQ_STRIDE, sizeof(v), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(v, e->dev.seq + (size_t)seq * SQ_STRIDE, sizeof(v), hipMemcpyDeviceToHost));
   const int na = v[SQ_NA], nl = v[SQ_NL];
   if (n_active) *n_active = na;
   if (n_lost) *n_lost = nl;
   if (na + nl > cap) return set_err(BX_ERR_CAPACITY, "cap too small for the live tracks");
   std::vector<uint16_t> act(T), lost(T);
   const size_t sT = (size_t)seq * T;
-  HIPCHK(hipMemcpy(act.data(), e->dev.act + sT, 2 * T, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(lost.data(), e->dev.lost + sT, 2 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(act.data(), e->dev.act + sT, 2 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(lost.data(), e->dev.lost + sT, 2 * T, hipMemcpyDeviceToHost));
   std::vector<int> slots(na + nl);
   for (int k = 0; k < na + nl; k++) slots[k] = k < na ? act[k] : lost[k - na];
   return snapshot_slots(e, seq, slots, ids, state, is_activated, frame_id, start_frame, mean, cov);
@@ -2826,14 +2743,14 @@ int bx_engine_class_tracks_host(bx_engine* e, int seq, int n_classes, int cap, i
   std::vector<int> slots;
   for (int c = 0; c <= C; c++) cls_off[c] = 0;
   if (!e->n_classes || !e->park[seq]) return BX_OK;  // no per-class call yet: every list empty
-  HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   int v[SQ_STRIDE];
-  HIPCHK(hipMemcpy(v, e->dev.seq + (size_t)seq * SQ_STRIDE, sizeof(v), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(v, e->dev.seq + (size_t)seq * SQ_STRIDE, sizeof(v), hipMemcpyDeviceToHost));
   std::vector<uint16_t> act(T), park((size_t)C * T);
   std::vector<int> npark(C);
-  HIPCHK(hipMemcpy(act.data(), e->dev.act + (size_t)seq * T, 2 * T, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(park.data(), e->park[seq], 2 * (size_t)C * T, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(npark.data(), e->park[seq] + park_npark_off(e), sizeof(int) * C,
+  BX_HIPCHK(hipMemcpy(act.data(), e->dev.act + (size_t)seq * T, 2 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(park.data(), e->park[seq], 2 * (size_t)C * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(npark.data(), e->park[seq] + park_npark_off(e), sizeof(int) * C,
                    hipMemcpyDeviceToHost));
   // the class that ran last holds the engine's active list, every other class its parked one
   const int cur = e->cur_cls[seq];
@@ -2851,17 +2768,17 @@ int bx_engine_state_set_host(bx_engine* e, int seq, int n, const int32_t* ids, c
   if (int rc = settle(e)) return rc;
   if (!e || seq < 0 || seq >= e->dev.S || n < 0 || (n && !ids))
     return set_err(BX_ERR_INVALID, "bad arguments to bx_engine_state_set_host");
-  HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   const int T = e->dev.T;
   const size_t sT = (size_t)seq * T;
   int v[SQ_STRIDE];
-  HIPCHK(hipMemcpy(v, e->dev.seq + (size_t)seq * SQ_STRIDE, sizeof(v), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(v, e->dev.seq + (size_t)seq * SQ_STRIDE, sizeof(v), hipMemcpyDeviceToHost));
   const int na = v[SQ_NA], nl = v[SQ_NL];
   std::vector<uint16_t> act(T), lost(T);
   std::vector<int> id(T);
-  HIPCHK(hipMemcpy(act.data(), e->dev.act + sT, 2 * T, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(lost.data(), e->dev.lost + sT, 2 * T, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(id.data(), e->dev.id + sT, 4 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(act.data(), e->dev.act + sT, 2 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(lost.data(), e->dev.lost + sT, 2 * T, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(id.data(), e->dev.id + sT, 4 * T, hipMemcpyDeviceToHost));
   for (int j = 0; j < n; j++) {
     int slot = -1;
     for (int k = 0; k < na + nl && slot < 0; k++) {
@@ -2871,10 +2788,10 @@ int bx_engine_state_set_host(bx_engine* e, int seq, int n, const int32_t* ids, c
     if (slot < 0) return set_err(BX_ERR_INVALID, "state_set: no live track with that id");
     double* kf = e->dev.kf + (sT + slot) * KF_STRIDE;
     uint32_t f;
-    HIPCHK(hipMemcpy(&f, e->dev.flags + sT + slot, 4, hipMemcpyDeviceToHost));
+    BX_HIPCHK(hipMemcpy(&f, e->dev.flags + sT + slot, 4, hipMemcpyDeviceToHost));
     if (cov && pend_of(f)) {  // the set covariance is current: its pending predicts are void
       f &= ~F_PEND_MASK;
-      HIPCHK(hipMemcpy(e->dev.flags + sT + slot, &f, 4, hipMemcpyHostToDevice));
+      BX_HIPCHK(hipMemcpy(e->dev.flags + sT + slot, &f, 4, hipMemcpyHostToDevice));
     } else if (pend_of(f)) {  // keep the covariance: apply its pending predicts (with the
       // operands of the mean they were made from) before the mean changes
       if (e->cfg.kind == BX_BYTETRACK)
@@ -2883,13 +2800,13 @@ int bx_engine_state_set_host(bx_engine* e, int seq, int n, const int32_t* ids, c
       else
         hipLaunchKernelGGL(materialize_kernel<KIND_BOT>, dim3((T + WG - 1) / WG), dim3(WG), 0,
                            0, e->dev, seq);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipDeviceSynchronize());
+      BX_HIPCHK(hipGetLastError());
+      BX_HIPCHK(hipDeviceSynchronize());
     }
-    if (mean) HIPCHK(hipMemcpy(kf, mean + 8 * j, 8 * 8, hipMemcpyHostToDevice));
-    if (cov) HIPCHK(hipMemcpy(kf + 8, cov + 64 * j, 64 * 8, hipMemcpyHostToDevice));
+    if (mean) BX_HIPCHK(hipMemcpy(kf, mean + 8 * j, 8 * 8, hipMemcpyHostToDevice));
+    if (cov) BX_HIPCHK(hipMemcpy(kf + 8, cov + 64 * j, 64 * 8, hipMemcpyHostToDevice));
   }
-  HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   return BX_OK;
 }
 
@@ -2911,7 +2828,7 @@ int bx_engine_set_early_features(bx_engine* e, int on) {
   if (!e) return set_err(BX_ERR_INVALID, "null engine");
   if (int rc = settle(e)) return rc;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (e->k1s) HIPCHK(hipStreamSynchronize(e->k1s));
+  if (e->k1s) BX_HIPCHK(hipStreamSynchronize(e->k1s));
   e->early = on != 0;
   return BX_OK;
 }
@@ -2931,9 +2848,9 @@ int bx_engine_embdist_host(bx_engine* e, int seq, int cap, uint32_t* pairs_out, 
   const Dev& d = e->dev;
   *n_out = 0;
   if (!d.with_reid) return BX_OK;
-  HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   int n = 0;  // K6 moved the frame's pair count here when it cleared npair for the next frame
-  HIPCHK(hipMemcpy(&n, d.seq + (size_t)seq * SQ_STRIDE + SQ_NPAIR, sizeof(int),
+  BX_HIPCHK(hipMemcpy(&n, d.seq + (size_t)seq * SQ_STRIDE + SQ_NPAIR, sizeof(int),
                    hipMemcpyDeviceToHost));
   if (n < 0 || (size_t)n > (size_t)d.T * d.D)
     return set_err(BX_ERR_INVALID, "bx_engine_embdist_host: pair count out of range");
@@ -2942,9 +2859,9 @@ int bx_engine_embdist_host(bx_engine* e, int seq, int cap, uint32_t* pairs_out, 
   if (!n) return BX_OK;
   const size_t TD = (size_t)d.T * d.D;
   std::vector<double> tab(TD);
-  HIPCHK(hipMemcpy(pairs_out, d.pairs + (size_t)seq * TD, sizeof(uint32_t) * n,
+  BX_HIPCHK(hipMemcpy(pairs_out, d.pairs + (size_t)seq * TD, sizeof(uint32_t) * n,
                    hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(tab.data(), d.etab + (size_t)seq * TD, sizeof(double) * TD,
+  BX_HIPCHK(hipMemcpy(tab.data(), d.etab + (size_t)seq * TD, sizeof(double) * TD,
                    hipMemcpyDeviceToHost));
   for (int i = 0; i < n; i++) {
     const size_t slot = pairs_out[i] >> 16, dk = pairs_out[i] & 0xffff;
@@ -2966,7 +2883,7 @@ int bx_engine_set_overlap(bx_engine* e, int on) {
 // larger [S][T'][...]
 static int copy_rows(void* dst, size_t dp, const void* src, size_t sp, size_t row_bytes, int S) {
   if (!row_bytes || !S) return BX_OK;
-  HIPCHK(hipMemcpy2D(dst, dp, src, sp, row_bytes, S, hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy2D(dst, dp, src, sp, row_bytes, S, hipMemcpyDeviceToDevice));
   return BX_OK;
 }
 
@@ -2981,7 +2898,7 @@ int bx_engine_copy_state(bx_engine* dst, bx_engine* src) {
                    "bx_engine_copy_state: destination must match the source's sequences, kind and "
                    "features and have at least its capacities");
   std::lock_guard<std::recursive_mutex> l1(src->mu), l2(dst->mu);
-  HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   const int S = a.S;
   const size_t Ta = a.T, Tb = b.T, fs = a.emb_f64 ? 8 : 4;
   auto rows = [&](void* d, const void* s_, size_t per_slot) {
@@ -3001,9 +2918,9 @@ int bx_engine_copy_state(bx_engine* dst, bx_engine* src) {
     if ((rc = rows(b.feat, a.feat, fs * a.F))) return rc;
     if ((rc = rows(b.tdn, a.tdn, 4))) return rc;
   }
-  HIPCHK(hipMemcpy(b.seq, a.seq, sizeof(int) * SQ_STRIDE * S, hipMemcpyDeviceToDevice));
-  HIPCHK(hipMemcpy(b.npair, a.npair, sizeof(int) * S, hipMemcpyDeviceToDevice));
-  HIPCHK(hipMemcpy(b.status, a.status, sizeof(int) * 16, hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.seq, a.seq, sizeof(int) * SQ_STRIDE * S, hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.npair, a.npair, sizeof(int) * S, hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.status, a.status, sizeof(int) * 16, hipMemcpyDeviceToDevice));
   dst->overlap = src->overlap;
   dst->cache_seq = -1;
   // per_class state: parked class lists [C][T] (+ their lengths and the held frame counter)
@@ -3015,24 +2932,24 @@ int bx_engine_copy_state(bx_engine* dst, bx_engine* src) {
       dst->n_classes = C;
       dst->park.assign(S, nullptr);
       dst->cur_cls.assign(S, 0);
-      HIPCHK(hipMalloc(&dst->h_coff, sizeof(int) * 2 * C));
-      HIPCHK(hipMalloc(&dst->h_ccnt, sizeof(int) * C));
-      HIPCHK(hipMalloc(&dst->h_cwarp, sizeof(double) * 6 * C));
+      BX_HIPCHK(hipMalloc(&dst->h_coff, sizeof(int) * 2 * C));
+      BX_HIPCHK(hipMalloc(&dst->h_ccnt, sizeof(int) * C));
+      BX_HIPCHK(hipMalloc(&dst->h_cwarp, sizeof(double) * 6 * C));
     }
     for (int q = 0; q < S; q++) {
       dst->cur_cls[q] = src->cur_cls[q];
       if (!src->park[q]) continue;
       if (!dst->park[q]) {
         const size_t bytes = park_npark_off(dst) + sizeof(int) * (C + 1);
-        HIPCHK(hipMalloc(&dst->park[q], bytes));
-        HIPCHK(hipMemset(dst->park[q], 0, bytes));
+        BX_HIPCHK(hipMalloc(&dst->park[q], bytes));
+        BX_HIPCHK(hipMemset(dst->park[q], 0, bytes));
       }
       if ((rc = copy_rows(dst->park[q], Tb * 2, src->park[q], Ta * 2, Ta * 2, C))) return rc;
-      HIPCHK(hipMemcpy(dst->park[q] + park_npark_off(dst), src->park[q] + park_npark_off(src),
+      BX_HIPCHK(hipMemcpy(dst->park[q] + park_npark_off(dst), src->park[q] + park_npark_off(src),
                        sizeof(int) * (C + 1), hipMemcpyDeviceToDevice));
     }
   }
-  HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   return BX_OK;
 }
 
@@ -3040,7 +2957,7 @@ int bx_engine_slots_used_host(bx_engine* e, int seq, int* used) {
   if (int rc = settle(e)) return rc;
   if (!e || !used || seq < 0 || seq >= e->dev.S) return set_err(BX_ERR_INVALID, "bad sequence");
   std::vector<uint32_t> f(e->dev.T);
-  HIPCHK(hipMemcpy(f.data(), e->dev.flags + (size_t)seq * e->dev.T, sizeof(uint32_t) * f.size(),
+  BX_HIPCHK(hipMemcpy(f.data(), e->dev.flags + (size_t)seq * e->dev.T, sizeof(uint32_t) * f.size(),
                    hipMemcpyDeviceToHost));
   int n = 0;
   for (uint32_t x : f) n += (x & F_INUSE) != 0;
@@ -3053,8 +2970,8 @@ int bx_engine_inputs_released(bx_engine* e, void* stream) {
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!e->side_pending) return BX_OK;
   // the last step's K5 is the last reader of its dets / det_off / embs: order `stream` after it
-  HIPCHK(hipEventRecord(e->ev_join[1], e->side));
-  HIPCHK(hipStreamWaitEvent((hipStream_t)stream, e->ev_join[1], 0));
+  BX_HIPCHK(hipEventRecord(e->ev_join[1], e->side));
+  BX_HIPCHK(hipStreamWaitEvent((hipStream_t)stream, e->ev_join[1], 0));
   return BX_OK;
 }
 

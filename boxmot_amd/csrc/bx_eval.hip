@@ -28,8 +28,8 @@
 #include "../../include/bxassoc.h"
 #include "../../include/bxeval.h"
 #include "bx_device.h"
+#include "bx_host.h"
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
 
 using namespace bx;
 
@@ -38,12 +38,6 @@ namespace {
 #include "bx_jv.h"
 
 int ev_err(int code, const std::string& msg) { return bx_record_error(code, msg.c_str()); }
-#define EVCHK(x)                                                            \
-  do {                                                                      \
-    hipError_t _e = (x);                                                    \
-    if (_e != hipSuccess) return ev_err(BX_ERR_HIP, hipGetErrorString(_e)); \
-  } while (0)
-
 constexpr int NA = BX_EVAL_NALPHA, NF = BX_EVAL_NF, LDS_N = BX_EVAL_LDS_N;
 constexpr double EPS = DBL_EPSILON;
 constexpr double ID_BIG = 1e10;  // fn and fp of an entry no assignment may use
@@ -800,7 +794,7 @@ int bx_eval_run_host(void* h, int n_seq, int benchmark, const int32_t* seq_frame
   const size_t o_idc = cv.take(CC * 8), o_jvg = cv.take(jv_total);
   const size_t o_gl = cv.take(NGI * 4), o_tl = cv.take(NTI * 4);
   if (cv.off > E.arena_bytes) {
-    if (E.arena) EVCHK(hipFree(E.arena));
+    if (E.arena) BX_HIPCHK(hipFree(E.arena));
     E.arena = nullptr, E.arena_bytes = 0;
     if (hipMalloc(&E.arena, cv.off) != hipSuccess) {
       E.arena = nullptr;
@@ -814,24 +808,24 @@ int bx_eval_run_host(void* h, int n_seq, int benchmark, const int32_t* seq_frame
   auto up = [&](size_t o, const void* src, size_t bytes) {
     return bytes ? hipMemcpyAsync(A + o, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
   };
-  EVCHK(up(o_gbox, gs.box.data(), (size_t)NG * 32));
-  EVCHK(up(o_tbox, ts.box.data(), (size_t)NT * 32));
-  EVCHK(up(o_gid, gs.id.data(), (size_t)NG * 4));
-  EVCHK(up(o_tid, ts.id.data(), (size_t)NT * 4));
-  EVCHK(up(o_gcls, gs.cls.data(), (size_t)NG * 4));
-  EVCHK(up(o_gzm, gs.zm.data(), (size_t)NG * 4));
-  EVCHK(up(o_gfoff, gs.foff.data(), (size_t)(F + 1) * 4));
-  EVCHK(up(o_tfoff, ts.foff.data(), (size_t)(F + 1) * 4));
-  EVCHK(up(o_ioff, ioff.data(), (size_t)(F + 1) * 8));
-  EVCHK(up(o_fseq, fseq.data(), (size_t)F * 4));
-  EVCHK(up(o_fbase, fbase.data(), (size_t)(S + 1) * 4));
-  EVCHK(up(o_gidoff, gs.idoff.data(), (size_t)(S + 1) * 4));
-  EVCHK(up(o_tidoff, ts.idoff.data(), (size_t)(S + 1) * 4));
-  EVCHK(up(o_moff, moff.data(), (size_t)(S + 1) * 8));
-  EVCHK(up(o_coff, coff.data(), (size_t)(S + 1) * 8));
-  EVCHK(up(o_jvoff, jvoff.data(), (size_t)S * 8));
-  EVCHK(hipMemsetAsync(A + z0, 0, z1 - z0, st));
-  EVCHK(hipMemsetAsync(A + z1, 0xff, p1 - z1, st));
+  BX_HIPCHK(up(o_gbox, gs.box.data(), (size_t)NG * 32));
+  BX_HIPCHK(up(o_tbox, ts.box.data(), (size_t)NT * 32));
+  BX_HIPCHK(up(o_gid, gs.id.data(), (size_t)NG * 4));
+  BX_HIPCHK(up(o_tid, ts.id.data(), (size_t)NT * 4));
+  BX_HIPCHK(up(o_gcls, gs.cls.data(), (size_t)NG * 4));
+  BX_HIPCHK(up(o_gzm, gs.zm.data(), (size_t)NG * 4));
+  BX_HIPCHK(up(o_gfoff, gs.foff.data(), (size_t)(F + 1) * 4));
+  BX_HIPCHK(up(o_tfoff, ts.foff.data(), (size_t)(F + 1) * 4));
+  BX_HIPCHK(up(o_ioff, ioff.data(), (size_t)(F + 1) * 8));
+  BX_HIPCHK(up(o_fseq, fseq.data(), (size_t)F * 4));
+  BX_HIPCHK(up(o_fbase, fbase.data(), (size_t)(S + 1) * 4));
+  BX_HIPCHK(up(o_gidoff, gs.idoff.data(), (size_t)(S + 1) * 4));
+  BX_HIPCHK(up(o_tidoff, ts.idoff.data(), (size_t)(S + 1) * 4));
+  BX_HIPCHK(up(o_moff, moff.data(), (size_t)(S + 1) * 8));
+  BX_HIPCHK(up(o_coff, coff.data(), (size_t)(S + 1) * 8));
+  BX_HIPCHK(up(o_jvoff, jvoff.data(), (size_t)S * 8));
+  BX_HIPCHK(hipMemsetAsync(A + z0, 0, z1 - z0, st));
+  BX_HIPCHK(hipMemsetAsync(A + z1, 0xff, p1 - z1, st));
 
   EvDev g;
   g.S = S, g.F = F, g.mot20 = benchmark == 20;
@@ -866,21 +860,21 @@ int bx_eval_run_host(void* h, int n_seq, int benchmark, const int32_t* seq_frame
   cap = (cap + 63) / 64 * 64;
   const size_t lds = ev_frame_lds(cap);
   hipLaunchKernelGGL(ev_pre_kernel, dim3(F), dim3(OW), lds, st, g, cap);
-  EVCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(ev_hota1_kernel, dim3(S), dim3(FT), (size_t)cap * 16, st, g, cap);
-  EVCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(ev_hota2_kernel, dim3(F), dim3(OW), lds, st, g, cap, al);
-  EVCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(ev_clear_kernel, dim3(S), dim3(OW), lds, st, g, cap);
-  EVCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(ev_identity_kernel, dim3(S), dim3(OW), jv_bytes(LDS_N), st, g);
-  EVCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(ev_finish_kernel, dim3(S), dim3(FT), 0, st, g);
-  EVCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(ev_combine_kernel, dim3(1), dim3(OW), 0, st, g);
-  EVCHK(hipGetLastError());
-  EVCHK(hipMemcpyAsync(out_host, g.out, (size_t)(S + 1) * NF * 8, hipMemcpyDeviceToHost, st));
-  EVCHK(hipStreamSynchronize(st));
+  BX_HIPCHK(hipGetLastError());
+  BX_HIPCHK(hipMemcpyAsync(out_host, g.out, (size_t)(S + 1) * NF * 8, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   return BX_OK;
 }
 

@@ -21,8 +21,8 @@
 #include <vector>
 
 #include "../../include/bxfeed.h"
+#include "bx_host.h"
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
 
 namespace {
 
@@ -177,13 +177,6 @@ struct bx_feed {
   std::vector<void*> allocs;
 };
 
-#define FCHK(x)                                                                    \
-  do {                                                                             \
-    hipError_t _e = (x);                                                           \
-    if (_e != hipSuccess)                                                          \
-      return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
-
 static void feed_free(bx_feed* f) {
   for (void* p : f->allocs) (void)hipFree(p);
   delete f;
@@ -280,7 +273,7 @@ int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_
     d.F = emb_dim;
     auto dev_alloc = [&](void** p, size_t bytes) -> int {
       *p = nullptr;
-      FCHK(hipMalloc(p, bytes ? bytes : 256));
+      BX_HIPCHK(hipMalloc(p, bytes ? bytes : 256));
       f->allocs.push_back(*p);
       return BX_OK;
     };
@@ -288,7 +281,7 @@ int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_
       void* q = nullptr;
       int rc = dev_alloc(&q, bytes);
       if (rc) return rc;
-      if (bytes) FCHK(hipMemcpy(q, src, bytes, hipMemcpyHostToDevice));
+      if (bytes) BX_HIPCHK(hipMemcpy(q, src, bytes, hipMemcpyHostToDevice));
       *p = q;
       return BX_OK;
     };
@@ -311,11 +304,11 @@ int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_
     if ((rc = dev_alloc((void**)&d.res, sizeof(double) * 9 * f->res_rows))) return rc;
     if ((rc = dev_alloc((void**)&d.res_n, sizeof(long long) * S))) return rc;
     if ((rc = dev_alloc((void**)&d.status, 256))) return rc;
-    FCHK(hipMemset(d.res, 0xFF, sizeof(double) * 9 * f->res_rows));
-    FCHK(hipMemset(d.res_n, 0, sizeof(long long) * S));
-    FCHK(hipMemset(d.g_cnt, 0, sizeof(int) * S));
-    FCHK(hipMemset(d.status, 0, 256));
-    FCHK(hipDeviceSynchronize());
+    BX_HIPCHK(hipMemset(d.res, 0xFF, sizeof(double) * 9 * f->res_rows));
+    BX_HIPCHK(hipMemset(d.res_n, 0, sizeof(long long) * S));
+    BX_HIPCHK(hipMemset(d.g_cnt, 0, sizeof(int) * S));
+    BX_HIPCHK(hipMemset(d.status, 0, 256));
+    BX_HIPCHK(hipDeviceSynchronize());
     return BX_OK;
   };
   const int rc = fill();
@@ -337,9 +330,9 @@ int bx_feed_upload_host(bx_feed* f, int seq, const float* dets, const double* em
   const long long r0 = f->seq_row0[seq], n = f->seq_row0[seq + 1] - r0;
   if (n == 0) return BX_OK;
   if (!dets || (f->F && !embs)) return bx_record_error(BX_ERR_INVALID, "null rows");
-  FCHK(hipMemcpy((float*)f->dev.dets + r0 * 6, dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice));
+  BX_HIPCHK(hipMemcpy((float*)f->dev.dets + r0 * 6, dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice));
   if (f->F)
-    FCHK(hipMemcpy((double*)f->dev.embs + r0 * f->F, embs, sizeof(double) * f->F * n,
+    BX_HIPCHK(hipMemcpy((double*)f->dev.embs + r0 * f->F, embs, sizeof(double) * f->F * n,
                    hipMemcpyHostToDevice));
   return BX_OK;
 }
@@ -382,7 +375,7 @@ int bx_feed_gather(bx_feed* f, int t, void* stream) {
   if (nr == 0) return BX_OK;
   hipLaunchKernelGGL(feed_gather_kernel, dim3(f->S), dim3(FW), 0, (hipStream_t)stream, f->dev, t,
                      f->run_off[t], nr);
-  FCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -393,14 +386,14 @@ int bx_feed_append(bx_feed* f, int t, void* stream) {
   if (nr == 0) return BX_OK;
   hipLaunchKernelGGL(feed_append_kernel, dim3(f->S), dim3(FW), 0, (hipStream_t)stream, f->dev, t,
                      f->run_off[t], nr);
-  FCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
 int bx_feed_status(bx_feed* f, int* status) {
   if (!f || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
-  FCHK(hipDeviceSynchronize());
-  FCHK(hipMemcpy(status, f->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(status, f->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
@@ -413,11 +406,11 @@ int bx_feed_result_rows(bx_feed* f, int64_t* rows) {
 int bx_feed_results_host(bx_feed* f, double* res, int64_t* base, int64_t* n) {
   if (!f || !base || !n || (f->res_rows && !res))
     return bx_record_error(BX_ERR_INVALID, "null argument");
-  FCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   if (f->res_rows)
-    FCHK(hipMemcpy(res, f->dev.res, sizeof(double) * 9 * f->res_rows, hipMemcpyDeviceToHost));
+    BX_HIPCHK(hipMemcpy(res, f->dev.res, sizeof(double) * 9 * f->res_rows, hipMemcpyDeviceToHost));
   static_assert(sizeof(long long) == sizeof(int64_t), "int64 layout");
-  FCHK(hipMemcpy(n, f->dev.res_n, sizeof(int64_t) * f->S, hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(n, f->dev.res_n, sizeof(int64_t) * f->S, hipMemcpyDeviceToHost));
   for (int k = 0; k <= f->S; k++) base[k] = f->res_base[k];
   return BX_OK;
 }
@@ -428,15 +421,15 @@ int bx_feed_read_run_host(bx_feed* f, int t, int r, float* dets, int32_t* det_of
   const Run& u = f->runs[i];
   const FeedDev& d = f->dev;
   const size_t rows = (size_t)f->run_rows[i];
-  FCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   if (dets)
-    FCHK(hipMemcpy(dets, d.g_dets + (size_t)u.row0 * 6, sizeof(float) * 6 * rows,
+    BX_HIPCHK(hipMemcpy(dets, d.g_dets + (size_t)u.row0 * 6, sizeof(float) * 6 * rows,
                    hipMemcpyDeviceToHost));
   if (det_off)
-    FCHK(hipMemcpy(det_off, d.g_off + u.off0, sizeof(int) * (u.k1 - u.k0 + 1),
+    BX_HIPCHK(hipMemcpy(det_off, d.g_off + u.off0, sizeof(int) * (u.k1 - u.k0 + 1),
                    hipMemcpyDeviceToHost));
   if (embs && f->F)
-    FCHK(hipMemcpy(embs, d.g_embs + (size_t)u.row0 * f->F, sizeof(double) * f->F * rows,
+    BX_HIPCHK(hipMemcpy(embs, d.g_embs + (size_t)u.row0 * f->F, sizeof(double) * f->F * rows,
                    hipMemcpyDeviceToHost));
   return BX_OK;
 }
@@ -447,10 +440,10 @@ int bx_feed_write_run_host(bx_feed* f, int t, int r, const double* out, const in
   if (!out || !out_count) return bx_record_error(BX_ERR_INVALID, "null argument");
   const Run& u = f->runs[i];
   const FeedDev& d = f->dev;
-  FCHK(hipDeviceSynchronize());
-  FCHK(hipMemcpy(d.g_out + (size_t)u.row0 * 8, out, sizeof(double) * 8 * (size_t)f->run_rows[i],
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(d.g_out + (size_t)u.row0 * 8, out, sizeof(double) * 8 * (size_t)f->run_rows[i],
                  hipMemcpyHostToDevice));
-  FCHK(hipMemcpy(d.g_cnt + u.k0, out_count, sizeof(int) * (u.k1 - u.k0), hipMemcpyHostToDevice));
+  BX_HIPCHK(hipMemcpy(d.g_cnt + u.k0, out_count, sizeof(int) * (u.k1 - u.k0), hipMemcpyHostToDevice));
   return BX_OK;
 }
 

@@ -29,21 +29,14 @@
 #include "../../include/bxassoc.h"
 #include "../../include/bxgsi.h"
 #include "bx_device.h"
+#include "bx_host.h"
 
-hipError_t bx_lds_attr(const void* kern, size_t bytes);  // bx_engine.hip (never lowers a limit)
-int bx_record_error(int code, const char* msg);          // bx_engine.hip (shared bx_last_error)
 
 using namespace bx;
 
 namespace {
 
 int gsi_err(int code, const std::string& msg) { return bx_record_error(code, msg.c_str()); }
-#define GSICHK(x)                                                            \
-  do {                                                                       \
-    hipError_t _e = (x);                                                     \
-    if (_e != hipSuccess) return gsi_err(BX_ERR_HIP, hipGetErrorString(_e)); \
-  } while (0)
-
 constexpr int LDS_N = BX_GSI_LDS_N, NB = BX_GSI_NB, MAX_N = BX_GSI_MAX_N;
 constexpr int TILE = 64, TLD = 66;  // trailing tile edge, padded leading dimension in LDS
 constexpr int MAX_SLOTS = 512;      // persistent workgroups of the blocked kernel
@@ -509,7 +502,7 @@ int bx_gsi_interpolate_plan(const double* rows, const int32_t* seq, int64_t R, i
   gsi_scan_kernel<<<1, 1024, 0, st>>>(keys, (int)R, interval, (int*)(w + l.cnt),
                                       (int*)(w + l.opos), (int*)(w + l.tidx),
                                       (long long*)counts);
-  GSICHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -524,7 +517,7 @@ int bx_gsi_interpolate(const double* rows, int64_t R, int C, const void* ws, dou
       (const Key*)(w + l.keys), rows, (int)R, C, (const int*)(w + l.cnt),
       (const int*)(w + l.opos), (const int*)(w + l.tidx), out, out_seq, (long long)cap,
       track_off);
-  GSICHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -549,11 +542,11 @@ int bx_gsi_smooth(const double* rows, int C, const int32_t* track_off_host, int 
   if (ws_bytes < p.total) return gsi_err(BX_ERR_CAPACITY, "gsi: smoothing workspace too small");
   hipStream_t st = (hipStream_t)stream;
   int32_t* off = (int32_t*)ws;
-  GSICHK(hipMemcpyAsync(off, track_off_host, ((size_t)n_tracks + 1) * 4, hipMemcpyHostToDevice, st));
-  GSICHK(hipMemsetAsync(status, 0, (size_t)n_tracks * 4, st));
+  BX_HIPCHK(hipMemcpyAsync(off, track_off_host, ((size_t)n_tracks + 1) * 4, hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemsetAsync(status, 0, (size_t)n_tracks * 4, st));
   if (p.max_lds) {
     const size_t lds = (layout_doubles(p.max_lds) + p.max_lds) * 8;
-    GSICHK(bx_lds_attr((const void*)gsi_smooth_lds_kernel, lds));
+    BX_HIPCHK(bx_lds_attr((const void*)gsi_smooth_lds_kernel, lds));
     gsi_smooth_lds_kernel<<<n_tracks, WG, lds, st>>>(rows, C, off, tau, out, status);
   }
   if (p.n_blk) {
@@ -562,7 +555,7 @@ int bx_gsi_smooth(const double* rows, int C, const int32_t* track_off_host, int 
                                                       force_blocked ? 0 : LDS_N, tau, slots,
                                                       p.slot_doubles, out, status);
   }
-  GSICHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -587,40 +580,40 @@ int bx_gsi_run_host(const double* rows_host, int64_t R, int C, int interval, dou
   size_t pbytes = 0;
   if (const int rc = bx_gsi_plan_workspace_bytes(R, &pbytes)) return rc;
   void *d_rows, *d_plan, *d_counts;
-  GSICHK(bufs.get(&d_rows, (size_t)R * C * 8));
-  GSICHK(bufs.get(&d_plan, pbytes));
-  GSICHK(bufs.get(&d_counts, 16));
-  GSICHK(hipMemcpyAsync(d_rows, rows_host, (size_t)R * C * 8, hipMemcpyHostToDevice, st));
+  BX_HIPCHK(bufs.get(&d_rows, (size_t)R * C * 8));
+  BX_HIPCHK(bufs.get(&d_plan, pbytes));
+  BX_HIPCHK(bufs.get(&d_counts, 16));
+  BX_HIPCHK(hipMemcpyAsync(d_rows, rows_host, (size_t)R * C * 8, hipMemcpyHostToDevice, st));
   if (const int rc = bx_gsi_interpolate_plan((const double*)d_rows, nullptr, R, C, interval,
                                              d_plan, pbytes, (int64_t*)d_counts, st))
     return rc;
   int64_t counts[2] = {0, 0};
-  GSICHK(hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, st));
-  GSICHK(hipStreamSynchronize(st));
+  BX_HIPCHK(hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   *n_out = counts[0];
   if (counts[0] > cap || !out_host)
     return gsi_err(BX_ERR_CAPACITY, "gsi: output holds fewer rows than the interpolation yields");
   const int nt = (int)counts[1];
   void *d_interp, *d_off, *d_out, *d_status, *d_ws;
-  GSICHK(bufs.get(&d_interp, (size_t)counts[0] * C * 8));
-  GSICHK(bufs.get(&d_off, ((size_t)nt + 1) * 4));
+  BX_HIPCHK(bufs.get(&d_interp, (size_t)counts[0] * C * 8));
+  BX_HIPCHK(bufs.get(&d_off, ((size_t)nt + 1) * 4));
   if (const int rc = bx_gsi_interpolate((const double*)d_rows, R, C, d_plan, (double*)d_interp,
                                         nullptr, counts[0], (int32_t*)d_off, st))
     return rc;
   std::vector<int32_t> off((size_t)nt + 1), status((size_t)nt);
-  GSICHK(hipMemcpyAsync(off.data(), d_off, off.size() * 4, hipMemcpyDeviceToHost, st));
-  GSICHK(hipStreamSynchronize(st));
+  BX_HIPCHK(hipMemcpyAsync(off.data(), d_off, off.size() * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   size_t sbytes = 0;
   if (const int rc = bx_gsi_workspace_bytes(off.data(), nt, 0, &sbytes)) return rc;
-  GSICHK(bufs.get(&d_ws, sbytes));
-  GSICHK(bufs.get(&d_out, (size_t)counts[0] * 9 * 8));
-  GSICHK(bufs.get(&d_status, (size_t)nt * 4));
+  BX_HIPCHK(bufs.get(&d_ws, sbytes));
+  BX_HIPCHK(bufs.get(&d_out, (size_t)counts[0] * 9 * 8));
+  BX_HIPCHK(bufs.get(&d_status, (size_t)nt * 4));
   if (const int rc = bx_gsi_smooth((const double*)d_interp, C, off.data(), nt, tau, 0, d_ws, sbytes,
                                    (double*)d_out, (int32_t*)d_status, st))
     return rc;
-  GSICHK(hipMemcpyAsync(out_host, d_out, (size_t)counts[0] * 9 * 8, hipMemcpyDeviceToHost, st));
-  GSICHK(hipMemcpyAsync(status.data(), d_status, status.size() * 4, hipMemcpyDeviceToHost, st));
-  GSICHK(hipStreamSynchronize(st));
+  BX_HIPCHK(hipMemcpyAsync(out_host, d_out, (size_t)counts[0] * 9 * 8, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(status.data(), d_status, status.size() * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   for (int k = 0; k < nt; k++)
     if (status[k] != BX_OK)
       return gsi_err(BX_ERR_INVALID, "gsi: tracklet " + std::to_string(k) +

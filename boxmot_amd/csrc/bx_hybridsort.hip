@@ -34,15 +34,15 @@
 #include "../../include/bxhybridsort.h"
 #include "bx_classes_glue.h"
 #include "bx_device.h"
+#include "bx_host.h"
 
 using namespace bx;
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
-hipError_t bx_lds_attr(const void* kern, size_t bytes);  // bx_engine.hip (never lowers a limit)
 
 namespace {
 
 #include "bx_ocs_device.h"
+#include "bx_ocs_host.h"
 #include "bx_embtile.h"
 
 constexpr int HX = 9, HZ = 5;  // state [u v s c r du dv ds dc], measurement [u v s c r]
@@ -934,76 +934,35 @@ __global__ void hyb_reset_kernel(HybDev g, int seq0, int nseq) {
 
 }  // namespace
 
-struct bx_hybrid {
+struct bx_hybrid : OcsHost {
   HybDev dev;
   bx_hybrid_config cfg;
   void* arena = nullptr;
   size_t lds = 0;
-  // host-path staging and pinned mirrors for update_host
-  float* h_dets = nullptr;
-  double* h_embs = nullptr;
-  int* h_off = nullptr;
-  double* h_out = nullptr;
-  int* h_cnt = nullptr;
-  float* p_dets = nullptr;
-  double* p_embs = nullptr;
-  double* p_out = nullptr;
-  int* p_cnt = nullptr;
-  int* p_sq = nullptr;
-  int cache_seq = -1;
-  ClsGlue pc;  // per_class=True: the class state
-  // timing probe
-  int probe_stage = -1;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  int ev_used = 0;
+  ClsGlue pc;     // per_class=True: the class state
+  BxProbe probe;  // stages: 0 distances, 1 frame, 2 feature
 };
-
-#define HCHK(x)                                                                    \
-  do {                                                                             \
-    hipError_t _e = (x);                                                           \
-    if (_e != hipSuccess)                                                          \
-      return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
-
-// the timing probe of bx_deepocsort.hip: an event pair around the launch of the probed stage
-static int probe_begin(bx_hybrid* e, int stage, hipStream_t st) {
-  if (e->probe_stage != stage) return BX_OK;
-  if (e->ev_used == (int)e->ev.size()) {
-    hipEvent_t a, b;
-    HCHK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-    HCHK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
-    e->ev.push_back({a, b});
-  }
-  HCHK(hipEventRecord(e->ev[e->ev_used].first, st));
-  return BX_OK;
-}
-
-static int probe_end(bx_hybrid* e, int stage, hipStream_t st) {
-  if (e->probe_stage != stage) return BX_OK;
-  HCHK(hipEventRecord(e->ev[e->ev_used++].second, st));
-  return BX_OK;
-}
 
 static int launch(bx_hybrid* e, int seq0, int nseq, const float* dets, const int* off,
                   const double* embs, double* out, int* cnt, hipStream_t st) {
   const HybDev& d = e->dev;
   int rc;
   if (!embs) return bx_record_error(BX_ERR_SHAPE, "HybridSort needs embeddings");
-  if ((rc = probe_begin(e, 0, st))) return rc;
+  if ((rc = e->probe.begin(0, st))) return rc;
   hipLaunchKernelGGL(hyb_dist_kernel, dim3(nseq, ec_tiles(d.o.D, d.o.T), 2), dim3(256), 0, st, d,
                      seq0, off, embs);
-  HCHK(hipGetLastError());
-  if ((rc = probe_end(e, 0, st))) return rc;
-  if ((rc = probe_begin(e, 1, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(0, st))) return rc;
+  if ((rc = e->probe.begin(1, st))) return rc;
   hipLaunchKernelGGL(hyb_frame_kernel, dim3(nseq), dim3(OW), e->lds, st, d, seq0, dets, off, out,
                      cnt);
-  HCHK(hipGetLastError());
-  if ((rc = probe_end(e, 1, st))) return rc;
-  if ((rc = probe_begin(e, 2, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(1, st))) return rc;
+  if ((rc = e->probe.begin(2, st))) return rc;
   hipLaunchKernelGGL(hyb_feature_kernel, dim3((d.o.D + 3) / 4, nseq), dim3(256), 0, st, d, seq0,
                      off, embs);
-  HCHK(hipGetLastError());
-  if ((rc = probe_end(e, 2, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(2, st))) return rc;
   return BX_OK;
 }
 
@@ -1032,6 +991,7 @@ int bx_hybrid_create(const bx_hybrid_config* c, bx_hybrid** out) {
     return bx_record_error(BX_ERR_NO_DEVICE, "no HIP device visible");
   bx_hybrid* e = new bx_hybrid();
   e->cfg = *c;
+  e->o = &e->dev.o;
   // everything that can fail runs in `fill`: a failure frees what was allocated so far
   auto fill = [&]() -> int {
     HybDev& dd = e->dev;
@@ -1060,23 +1020,13 @@ int bx_hybrid_create(const bx_hybrid_config* c, bx_hybrid** out) {
     dd.q[8] *= 0.01;
     dd.q[7] *= 0.01;
     for (int k = 5; k < HX; k++) dd.q[k] *= 0.01;
-    // LDS: the fixed part plus as much cost matrix as keeps ~4 workgroups per CU resident
-    const size_t extra = ((size_t)d.T * 4 + 7) / 8 * 8;
-    const size_t fixed = lds_bytes(d.D, d.T, d.N, 0) + extra;
-    long budget = 40 * 1024 - (long)fixed;
-    int cl = budget > 0 ? (int)(budget / 8) : 0;
-    if (cl > d.D * d.T) cl = d.D * d.T;
-    if (cl < 64) cl = 64;
-    d.cost_lds = cl;
-    dd.x_off = (int)lds_bytes(d.D, d.T, d.N, cl);
-    e->lds = (size_t)dd.x_off + extra;
-    if (e->lds > 160 * 1024) {
-      return bx_record_error(BX_ERR_INVALID, "track_cap/det_cap too large for one workgroup's LDS");
-    }
-    const bool need_g = (long)d.D * d.T > cl;
+    size_t x_off;
+    int rc = ocs_lds_budget(d, ((size_t)d.T * 4 + 7) / 8 * 8, &x_off, &e->lds);
+    if (rc) return rc;
+    dd.x_off = (int)x_off;
+    const bool need_g = (long)d.D * d.T > d.cost_lds;
     const size_t S = d.S, T = d.T, D = d.D, F = dd.F;
-    size_t off = 0;
-    auto carve_b = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    BxCarve carve_b;
     const size_t o_trk = carve_b(S * T * sizeof(HybTrk));
     const size_t o_sq = carve_b(S * SQO * sizeof(int));
     const size_t o_ord = carve_b(S * T * sizeof(int));
@@ -1091,10 +1041,9 @@ int bx_hybrid_create(const bx_hybrid_config* c, bx_hybrid** out) {
     const size_t o_ec = carve_b(S * 2 * D * T * sizeof(double));
     const size_t o_rec = carve_b(S * D * sizeof(int));
     const size_t o_rb = carve_b(S * D * sizeof(int));
-    if (hipMalloc(&e->arena, off) != hipSuccess) {
+    if (hipMalloc(&e->arena, carve_b.off) != hipSuccess)
       return bx_record_error(BX_ERR_HIP, "hipMalloc of the HybridSort arena failed");
-    }
-    HCHK(hipMemset(e->arena, 0, off));
+    BX_HIPCHK(hipMemset(e->arena, 0, carve_b.off));
     char* base = (char*)e->arena;
     dd.trk = (HybTrk*)(base + o_trk);
     d.trk = nullptr;
@@ -1112,29 +1061,9 @@ int bx_hybrid_create(const bx_hybrid_config* c, bx_hybrid** out) {
     dd.ec = (double*)(base + o_ec);
     dd.rec = (int*)(base + o_rec);
     dd.rec_b = (int*)(base + o_rb);
-    {
-      std::vector<double> f(2 * S);
-      for (size_t k = 0; k < S; k++) {
-        f[2 * k] = c->frame_w;
-        f[2 * k + 1] = c->frame_h;
-      }
-      HCHK(hipMemcpy(d.fsz, f.data(), sizeof(double) * 2 * S, hipMemcpyHostToDevice));
-      std::vector<int> sq(S * SQO, 0);
-      for (size_t k = 0; k < S; k++) sq[k * SQO + SO_IDS] = 1;
-      HCHK(hipMemcpy(d.seqst, sq.data(), sizeof(int) * sq.size(), hipMemcpyHostToDevice));
-    }
-    HCHK(bx_lds_attr((const void*)hyb_frame_kernel, e->lds));
-    HCHK(hipMalloc(&e->h_dets, sizeof(float) * 6 * D));
-    HCHK(hipMalloc(&e->h_embs, sizeof(double) * D * F));
-    HCHK(hipMalloc(&e->h_off, sizeof(int) * 2));
-    HCHK(hipMalloc(&e->h_out, sizeof(double) * 8 * D));
-    HCHK(hipMalloc(&e->h_cnt, sizeof(int)));
-    HCHK(hipHostMalloc(&e->p_dets, sizeof(float) * 6 * D));
-    HCHK(hipHostMalloc(&e->p_embs, sizeof(double) * D * F));
-    HCHK(hipHostMalloc(&e->p_out, sizeof(double) * 8 * D));
-    HCHK(hipHostMalloc(&e->p_cnt, sizeof(int) * 4));
-    HCHK(hipHostMalloc(&e->p_sq, sizeof(int) * SQO));
-    return BX_OK;
+    if ((rc = ocs_upload_initial(d, c->frame_w, c->frame_h, 1))) return rc;
+    BX_HIPCHK(bx_lds_attr((const void*)hyb_frame_kernel, e->lds));
+    return e->sg.alloc(sizeof(float) * 6 * D, sizeof(double) * D * F, 0, 8, d.D, SQO);
   };
   const int rc = fill();
   if (rc) {
@@ -1152,7 +1081,7 @@ int bx_hybrid_copy_state(bx_hybrid* dst, bx_hybrid* src) {
     return bx_record_error(BX_ERR_INVALID, "bx_hybrid_copy_state: destination must have the "
                                            "source's sequences and embedding width and at least "
                                            "its capacities");
-  HCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   const size_t S = a.S, Ta = a.T, Tb = b.T, F = src->dev.F;
   // [S][T][per_track] arrays: a sequence's tracks are one run in both engines
   auto rows = [&](void* d, const void* s, size_t per_track) {
@@ -1163,37 +1092,25 @@ int bx_hybrid_copy_state(bx_hybrid* dst, bx_hybrid* src) {
     }
     return hipSuccess;
   };
-  HCHK(rows(dst->dev.trk, src->dev.trk, sizeof(HybTrk)));
-  HCHK(rows(b.order, a.order, sizeof(int)));
-  HCHK(rows(dst->dev.bcnt, src->dev.bcnt, sizeof(int)));
-  HCHK(rows(dst->dev.smooth, src->dev.smooth, F * sizeof(double)));
-  HCHK(rows(dst->dev.lmean, src->dev.lmean, F * sizeof(double)));
-  HCHK(rows(dst->dev.bank, src->dev.bank, BANK * F * sizeof(double)));
-  HCHK(hipMemcpy(b.seqst, a.seqst, S * SQO * sizeof(int), hipMemcpyDeviceToDevice));
-  HCHK(hipMemcpy(b.fsz, a.fsz, S * 2 * sizeof(double), hipMemcpyDeviceToDevice));
-  HCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(rows(dst->dev.trk, src->dev.trk, sizeof(HybTrk)));
+  BX_HIPCHK(rows(b.order, a.order, sizeof(int)));
+  BX_HIPCHK(rows(dst->dev.bcnt, src->dev.bcnt, sizeof(int)));
+  BX_HIPCHK(rows(dst->dev.smooth, src->dev.smooth, F * sizeof(double)));
+  BX_HIPCHK(rows(dst->dev.lmean, src->dev.lmean, F * sizeof(double)));
+  BX_HIPCHK(rows(dst->dev.bank, src->dev.bank, BANK * F * sizeof(double)));
+  BX_HIPCHK(hipMemcpy(b.seqst, a.seqst, S * SQO * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.fsz, a.fsz, S * 2 * sizeof(double), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
   dst->cache_seq = -1;
-  HCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   return cls_glue_copy(dst->pc, src->pc, b.S, b.D, dst->dev.F, 1);
 }
 
 int bx_hybrid_destroy(bx_hybrid* e) {
   if (!e) return BX_OK;
-  for (auto& p : e->ev) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->h_dets);
-  (void)hipFree(e->h_embs);
-  (void)hipFree(e->h_off);
-  (void)hipFree(e->h_out);
-  (void)hipFree(e->h_cnt);
-  (void)hipHostFree(e->p_dets);
-  (void)hipHostFree(e->p_embs);
-  (void)hipHostFree(e->p_out);
-  (void)hipHostFree(e->p_cnt);
-  (void)hipHostFree(e->p_sq);
+  e->sg.free();
   cls_glue_free(e->pc);
   delete e;
   return BX_OK;
@@ -1206,7 +1123,7 @@ int bx_hybrid_reset(bx_hybrid* e, int seq0, int nseq, void* stream) {
   e->cache_seq = -1;
   hipLaunchKernelGGL(hyb_reset_kernel, dim3((nseq * SQO + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, e->dev, seq0, nseq);
-  HCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return cls_glue_reset(e->pc, seq0, nseq, stream);
 }
 
@@ -1226,55 +1143,27 @@ int bx_hybrid_update_host(bx_hybrid* e, int seq, const float* dets, int n, const
   const size_t F = e->dev.F;
   if (n && !embs) return bx_record_error(BX_ERR_SHAPE, "HybridSort needs embeddings");
   hipStream_t st = (hipStream_t)stream;
-  if (n) {
-    memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
-    HCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
-    memcpy(e->p_embs, embs, sizeof(double) * F * n);
-    HCHK(hipMemcpyAsync(e->h_embs, e->p_embs, sizeof(double) * F * n, hipMemcpyHostToDevice, st));
-  }
-  e->p_cnt[2] = 0;
-  e->p_cnt[3] = n;
-  HCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
-  e->cache_seq = -1;
-  int rc = launch(e, seq, 1, e->h_dets, e->h_off, e->h_embs, e->h_out, e->h_cnt, st);
-  if (rc) return rc;
-  HCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  HCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (n) HCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
-  HCHK(hipMemcpyAsync(e->p_sq, e->dev.o.seqst + (size_t)seq * SQO, sizeof(int) * SQO,
-                      hipMemcpyDeviceToHost, st));
-  HCHK(hipStreamSynchronize(st));
-  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
-  e->cache_seq = seq;
-  if (cnt) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
-  *n_out = cnt;
-  if (status == BX_ERR_CAPACITY)
-    return bx_record_error(BX_ERR_CAPACITY, "a sequence's detections exceeded det_cap on the device");
-  if (status)
-    return bx_record_error(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
-  return BX_OK;
+  BxStaging& sg = e->sg;
+  int rc;
+  if (n && (rc = sg.put(sg.h_embs, sg.p_embs, embs, sizeof(double) * F * n, st))) return rc;
+  return ocs_update_host_roundtrip(
+      *e, seq, dets, n, out, n_out, st, true,
+      [&] {
+        return launch(e, seq, 1, (float*)sg.h_dets, sg.h_off, (double*)sg.h_embs, sg.h_out,
+                      sg.h_cnt, st);
+      },
+      OcsStreamSync{st});
 }
 
 int bx_hybrid_probe(bx_hybrid* e, int stage) {
   if (!e || stage < -1 || stage > 2) return bx_record_error(BX_ERR_INVALID, "bad probe stage");
-  e->probe_stage = stage;
-  e->ev_used = 0;
+  e->probe.set(stage);
   return BX_OK;
 }
 
 int bx_hybrid_probe_read(bx_hybrid* e, double* total_ms, int* count) {
   if (!e || !total_ms || !count) return bx_record_error(BX_ERR_INVALID, "null argument");
-  double s = 0.0;
-  for (int k = 0; k < e->ev_used; k++) {
-    HCHK(hipEventSynchronize(e->ev[k].second));
-    float ms = 0.f;
-    HCHK(hipEventElapsedTime(&ms, e->ev[k].first, e->ev[k].second));
-    s += ms;
-  }
-  *total_ms = s;
-  *count = e->ev_used;
-  e->ev_used = 0;
-  return BX_OK;
+  return e->probe.read(total_ms, count);
 }
 
 // per_class=True (include/bxclasses.h): class c of sequence s is engine sequence s * C + c; the
@@ -1319,86 +1208,35 @@ int bx_hybrid_update_classes_host(bx_hybrid* e, int seq, int n_classes, const fl
   if (rc) return rc;
   if ((seq + 1) * (long)n_classes > e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
   hipStream_t st = (hipStream_t)stream;
-  if (n) {
-    memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
-    HCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
-    memcpy(e->p_embs, embs, sizeof(double) * F * n);
-    HCHK(hipMemcpyAsync(e->h_embs, e->p_embs, sizeof(double) * F * n, hipMemcpyHostToDevice, st));
-  }
-  e->p_cnt[2] = 0;
-  e->p_cnt[3] = n;
-  HCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
-  if ((rc = cls_glue_put_ids(e->pc, seq, *id_count, st))) return rc;
-  rc = bx_hybrid_step_classes(e, seq, 1, n_classes, e->h_dets, e->h_off, e->h_embs, e->h_out,
-                              e->h_cnt, st);
-  if (rc) return rc;
-  HCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  HCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (n) HCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
-  int cstatus = 0;
-  if ((rc = cls_glue_take_ids(e->pc, seq, id_count, &cstatus, st))) return rc;  // synchronises
-  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
-  if (cnt > 0 && cnt <= n) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
-  *n_out = cnt > 0 && cnt <= n ? cnt : 0;
-  if (status == BX_ERR_CAPACITY || cstatus == BX_ERR_CAPACITY)
-    return bx_record_error(BX_ERR_CAPACITY, "a sequence's detections exceeded det_cap, or a "
-                                            "class's births its id map, on the device");
-  if (status)
-    return bx_record_error(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
-  if (cstatus) return bx_record_error(cstatus, "the class merge met an id the engine never gave out");
-  return BX_OK;
+  BxStaging& sg = e->sg;
+  if (n && (rc = sg.put(sg.h_embs, sg.p_embs, embs, sizeof(double) * F * n, st))) return rc;
+  return ocs_update_host_roundtrip(
+      *e, -1, dets, n, out, n_out, st, true,
+      [&] {
+        if (int r = cls_glue_put_ids(e->pc, seq, *id_count, st)) return r;
+        return bx_hybrid_step_classes(e, seq, 1, n_classes, (float*)sg.h_dets, sg.h_off,
+                                      (double*)sg.h_embs, sg.h_out, sg.h_cnt, st);
+      },
+      [&](int* cstatus) { return cls_glue_take_ids(e->pc, seq, id_count, cstatus, st); });
 }
 
 int bx_hybrid_status(bx_hybrid* e, int* status) {
   if (!e || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
-  HCHK(hipMemcpy(status, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(status, e->dev.o.status, sizeof(int), hipMemcpyDeviceToHost));
   return cls_glue_status(e->pc, status);
 }
 
 int bx_hybrid_counters_host(bx_hybrid* e, int seq, int* frame_count, int* id_count,
                             int* n_tracks) {
-  if (!e || seq < 0 || seq >= e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  int s[SQO];
-  if (seq == e->cache_seq) {
-    memcpy(s, e->p_sq, sizeof(s));
-  } else {
-    HCHK(hipDeviceSynchronize());
-    HCHK(hipMemcpy(s, e->dev.o.seqst + (size_t)seq * SQO, sizeof(s), hipMemcpyDeviceToHost));
-  }
-  if (frame_count) *frame_count = s[SO_FRAME];
-  if (id_count) *id_count = s[SO_IDS];
-  if (n_tracks) *n_tracks = s[SO_NTR];
-  return BX_OK;
+  return ocs_counters(e, seq, frame_count, id_count, n_tracks);
 }
 
 int bx_hybrid_set_id_count(bx_hybrid* e, int seq, int id_count, void* stream) {
-  if (!e || seq < 0 || seq >= e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  e->cache_seq = -1;
-  HCHK(hipMemcpyAsync(e->dev.o.seqst + (size_t)seq * SQO + SO_IDS, &id_count, sizeof(int),
-                      hipMemcpyHostToDevice, (hipStream_t)stream));
-  HCHK(hipStreamSynchronize((hipStream_t)stream));
-  return BX_OK;
+  return ocs_set_id_count(e, seq, id_count, stream);
 }
 
 int bx_hybrid_set_frame_size(bx_hybrid* e, int seq, double w, double h, void* stream) {
-  if (!e || seq < 0 || seq >= e->dev.o.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  const double f[2] = {w, h};
-  HCHK(hipMemcpyAsync(e->dev.o.fsz + 2 * (size_t)seq, f, sizeof(f), hipMemcpyHostToDevice,
-                      (hipStream_t)stream));
-  HCHK(hipStreamSynchronize((hipStream_t)stream));
-  return BX_OK;
-}
-
-// the list order of a sequence, on the host
-static int list_order(bx_hybrid* e, int seq, std::vector<int>& ord) {
-  HCHK(hipDeviceSynchronize());
-  int s[SQO];
-  HCHK(hipMemcpy(s, e->dev.o.seqst + (size_t)seq * SQO, sizeof(s), hipMemcpyDeviceToHost));
-  ord.resize(s[SO_NTR]);
-  if (s[SO_NTR])
-    HCHK(hipMemcpy(ord.data(), e->dev.o.order + (size_t)seq * e->dev.o.T, sizeof(int) * s[SO_NTR],
-                   hipMemcpyDeviceToHost));
-  return BX_OK;
+  return ocs_set_frame_size(e, seq, w, h, stream);
 }
 
 int bx_hybrid_tracks_host(bx_hybrid* e, int seq, int cap, int32_t* ids, double* x, double* p,
@@ -1407,26 +1245,26 @@ int bx_hybrid_tracks_host(bx_hybrid* e, int seq, int cap, int32_t* ids, double* 
   if (!e || seq < 0 || seq >= e->dev.o.S || cap < 0 || !n)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_tracks_host");
   std::vector<int> ord;
-  int rc = list_order(e, seq, ord);
+  int rc = ocs_list_order(e->dev.o, seq, ord);
   if (rc) return rc;
   const int nt = (int)ord.size();
   const size_t F = e->dev.F, T = e->dev.o.T;
   for (int k = 0; k < nt && k < cap; k++) {
     HybTrk t;
     const size_t ts = (size_t)seq * T + ord[k];
-    HCHK(hipMemcpy(&t, e->dev.trk + ts, sizeof(HybTrk), hipMemcpyDeviceToHost));
+    BX_HIPCHK(hipMemcpy(&t, e->dev.trk + ts, sizeof(HybTrk), hipMemcpyDeviceToHost));
     if (ids) ids[k] = t.id;
     if (x) memcpy(x + HX * k, t.x, sizeof(t.x));
     if (p) memcpy(p + HX * HX * k, t.P, sizeof(t.P));
     if (emb)
-      HCHK(hipMemcpy(emb + F * k, e->dev.smooth + ts * F, sizeof(double) * F, hipMemcpyDeviceToHost));
+      BX_HIPCHK(hipMemcpy(emb + F * k, e->dev.smooth + ts * F, sizeof(double) * F, hipMemcpyDeviceToHost));
     if (bank_mean)
-      HCHK(hipMemcpy(bank_mean + F * k, e->dev.lmean + ts * F, sizeof(double) * F,
+      BX_HIPCHK(hipMemcpy(bank_mean + F * k, e->dev.lmean + ts * F, sizeof(double) * F,
                      hipMemcpyDeviceToHost));
     if (vel)  // zeros until the second update, as the reference's None is read
       for (int c = 0; c < 8; c++) vel[8 * k + c] = t.has_vel ? t.vel[c >> 1][c & 1] : 0.0;
     if (bank_count)
-      HCHK(hipMemcpy(bank_count + k, e->dev.bcnt + ts, sizeof(int), hipMemcpyDeviceToHost));
+      BX_HIPCHK(hipMemcpy(bank_count + k, e->dev.bcnt + ts, sizeof(int), hipMemcpyDeviceToHost));
   }
   *n = nt;
   return BX_OK;
@@ -1437,22 +1275,16 @@ int bx_hybrid_state_set_host(bx_hybrid* e, int seq, int n, const int32_t* ids, c
   if (!e || seq < 0 || seq >= e->dev.o.S || n < 0 || (n && !ids))
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_state_set_host");
   std::vector<int> ord;
-  int rc = list_order(e, seq, ord);
+  int rc = ocs_list_order(e->dev.o, seq, ord);
   if (rc) return rc;
-  const int nt = (int)ord.size();
-  const size_t T = e->dev.o.T;
   for (int j = 0; j < n; j++) {
-    HybTrk* dt = nullptr;
     HybTrk t;
-    for (int k = 0; k < nt && !dt; k++) {
-      HybTrk* cand = e->dev.trk + (size_t)seq * T + ord[k];
-      HCHK(hipMemcpy(&t, cand, sizeof(HybTrk), hipMemcpyDeviceToHost));
-      if (t.id == ids[j]) dt = cand;
-    }
-    if (!dt) return bx_record_error(BX_ERR_INVALID, "state_set: no live track with that id");
+    int slot;
+    if ((rc = ocs_find_track(e->dev.o, e->dev.trk, seq, ord, ids[j], t, &slot))) return rc;
     if (x) memcpy(t.x, x + HX * j, sizeof(t.x));
     if (p) memcpy(t.P, p + HX * HX * j, sizeof(t.P));
-    HCHK(hipMemcpy(dt, &t, sizeof(HybTrk), hipMemcpyHostToDevice));
+    BX_HIPCHK(hipMemcpy(e->dev.trk + (size_t)seq * e->dev.o.T + slot, &t, sizeof(HybTrk),
+                   hipMemcpyHostToDevice));
   }
   return BX_OK;
 }
@@ -1468,7 +1300,7 @@ int bx_hybrid_state_bytes(bx_hybrid* e, size_t* bytes) {
 static int state_xfer(bx_hybrid* e, int seq, char* blob, bool save) {
   const HybDev& d = e->dev;
   const size_t T = d.o.T, F = d.F;
-  HCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   size_t off = 0;
   auto part = [&](void* dev, size_t bytes) {
     const hipError_t r = save ? hipMemcpy(blob + off, dev, bytes, hipMemcpyDeviceToHost)
@@ -1476,13 +1308,13 @@ static int state_xfer(bx_hybrid* e, int seq, char* blob, bool save) {
     off += bytes;
     return r;
   };
-  HCHK(part(d.o.seqst + (size_t)seq * SQO, SQO * sizeof(int)));
-  HCHK(part(d.o.order + (size_t)seq * T, T * sizeof(int)));
-  HCHK(part(d.bcnt + (size_t)seq * T, T * sizeof(int)));
-  HCHK(part(d.trk + (size_t)seq * T, T * sizeof(HybTrk)));
-  HCHK(part(d.smooth + (size_t)seq * T * F, T * F * sizeof(double)));
-  HCHK(part(d.lmean + (size_t)seq * T * F, T * F * sizeof(double)));
-  HCHK(part(d.bank + (size_t)seq * T * BANK * F, T * BANK * F * sizeof(double)));
+  BX_HIPCHK(part(d.o.seqst + (size_t)seq * SQO, SQO * sizeof(int)));
+  BX_HIPCHK(part(d.o.order + (size_t)seq * T, T * sizeof(int)));
+  BX_HIPCHK(part(d.bcnt + (size_t)seq * T, T * sizeof(int)));
+  BX_HIPCHK(part(d.trk + (size_t)seq * T, T * sizeof(HybTrk)));
+  BX_HIPCHK(part(d.smooth + (size_t)seq * T * F, T * F * sizeof(double)));
+  BX_HIPCHK(part(d.lmean + (size_t)seq * T * F, T * F * sizeof(double)));
+  BX_HIPCHK(part(d.bank + (size_t)seq * T * BANK * F, T * BANK * F * sizeof(double)));
   e->cache_seq = -1;
   return BX_OK;
 }
@@ -1507,7 +1339,7 @@ int bx_hybrid_cosdist(int nd, int nt, int F, const double* dets_embs, const doub
   if (!nd || !nt) return BX_OK;
   hipLaunchKernelGGL(hyb_dist_op_kernel, dim3(ec_tiles(nd, nt)), dim3(256), 0, (hipStream_t)stream,
                      nd, nt, F, dets_embs, trk_embs, out);
-  HCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -1518,7 +1350,7 @@ int bx_hybrid_bank_mean(int nt, int F, const double* bank, const int32_t* pushed
   if (!nt) return BX_OK;
   hipLaunchKernelGGL(hyb_bank_mean_op_kernel, dim3(nt), dim3(64), 0, (hipStream_t)stream, nt, F,
                      bank, pushed, out);
-  HCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 

@@ -18,9 +18,8 @@
 
 #include "../../include/bxassoc.h"
 #include "bx_device.h"
+#include "bx_host.h"
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
-hipError_t bx_lds_attr(const void* kern, size_t bytes);  // bx_engine.hip (never lowers a limit)
 
 namespace {
 
@@ -328,13 +327,6 @@ int grid_for(size_t n, int per = 256) {
   return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
 
-#define NCHK(x)                                                                          \
-  do {                                                                                   \
-    hipError_t _e = (x);                                                                 \
-    if (_e != hipSuccess)                                                                \
-      return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -353,7 +345,7 @@ int bx_nn_cosine_distance(const double* samples, int G, const int32_t* off, int 
   const size_t b_den = (size_t)(G + D) * 8, b_tgt = (size_t)(G ? G : 1) * 4,
                b_key = (size_t)T * D * 8;
   char* ws = nullptr;
-  NCHK(hipMallocAsync((void**)&ws, b_sh + b_dh + b_den + b_tgt + b_key + 1024, st));
+  BX_HIPCHK(hipMallocAsync((void**)&ws, b_sh + b_dh + b_den + b_tgt + b_key + 1024, st));
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   double* sh = (double*)ws;
   double* dh = (double*)(ws + al(b_sh));
@@ -370,7 +362,7 @@ int bx_nn_cosine_distance(const double* samples, int G, const int32_t* off, int 
   hipLaunchKernelGGL(nn_norm_kernel, dim3((D + 3) / 4), dim3(256), 0, st, feats, D, F, den + G);
   hipLaunchKernelGGL(nn_scale_kernel, dim3(grid_for((size_t)D * F)), dim3(256), 0, st, feats,
                      den + G, (size_t)D * F, F, dh);
-  NCHK(hipMemsetAsync(keys, 0, b_key, st));
+  BX_HIPCHK(hipMemsetAsync(keys, 0, b_key, st));
   if (G) {
     hipLaunchKernelGGL(nn_row_target_kernel, dim3(T), dim3(256), 0, st, off, T, tgt);
     // the 128 x 256 tile when its grid covers the CUs (one 8-wave workgroup each), else 64 x 64
@@ -384,8 +376,8 @@ int bx_nn_cosine_distance(const double* samples, int G, const int32_t* off, int 
   }
   hipLaunchKernelGGL(nn_finish_kernel, dim3(grid_for((size_t)T * D)), dim3(256), 0, st, keys, off,
                      T, D, out);
-  NCHK(hipGetLastError());
-  NCHK(hipFreeAsync(ws, st));
+  BX_HIPCHK(hipGetLastError());
+  BX_HIPCHK(hipFreeAsync(ws, st));
   return BX_OK;
 }
 

@@ -27,15 +27,14 @@
 
 #include "../../include/bxocsort.h"
 #include "bx_device.h"
+#include "bx_host.h"
 
 using namespace bx;
-
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
-hipError_t bx_lds_attr(const void* kern, size_t bytes);  // bx_engine.hip (never lowers a limit)
 
 namespace {
 
 #include "bx_ocs_device.h"
+#include "bx_ocs_host.h"
 
 __global__ void __launch_bounds__(OW)
     ocsort_frame_kernel(OcsDev g, int seq0, const float* __restrict__ dets,
@@ -529,24 +528,12 @@ __global__ __launch_bounds__(256) void kf_xysr_kernel(int op, int n, double* __r
 
 }  // namespace
 
-struct bx_ocsort {
+struct bx_ocsort : OcsHost {
   OcsDev dev;
   bx_ocsort_config cfg;
   void* arena = nullptr;
   size_t lds = 0;
   int device = 0;
-  // host-path staging
-  float* h_dets = nullptr;
-  int* h_off = nullptr;
-  double* h_out = nullptr;
-  int* h_cnt = nullptr;
-  // pinned mirrors for update_host (asynchronous copies, one sync per frame) and the counters
-  // row of the last update_host sequence (bx_ocsort_counters_host answers from it)
-  float* p_dets = nullptr;
-  double* p_out = nullptr;
-  int* p_cnt = nullptr;
-  int* p_sq = nullptr;
-  int cache_seq = -1;
   // per_class host path (bx_ocsort_update_classes_host): per sequence the local -> class-global
   // track id map and the local id counter the map covers; class offsets [C+1], counts [C]
   std::vector<std::vector<int>> gid;
@@ -554,35 +541,17 @@ struct bx_ocsort {
   int* h_coff = nullptr;
   int* h_ccnt = nullptr;
   int ncls_alloc = 0;
-  // timing probe
-  bool probe_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  int ev_used = 0;
+  BxProbe probe;  // the frame kernel is stage 0
 };
-
-#define OCHK(x)                                                                    \
-  do {                                                                             \
-    hipError_t _e = (x);                                                           \
-    if (_e != hipSuccess)                                                          \
-      return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
 
 static int launch(bx_ocsort* e, int seq0, int nseq, const float* dets, const int* off,
                   double* out, int* cnt, hipStream_t st) {
-  if (e->probe_on) {
-    if (e->ev_used == (int)e->ev.size()) {
-      hipEvent_t a, b;
-      OCHK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-      OCHK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
-      e->ev.push_back({a, b});
-    }
-    OCHK(hipEventRecord(e->ev[e->ev_used].first, st));
-  }
+  int rc;
+  if ((rc = e->probe.begin(0, st))) return rc;
   hipLaunchKernelGGL(ocsort_frame_kernel, dim3(nseq), dim3(OW), e->lds, st, e->dev, seq0, dets,
                      off, out, cnt);
-  OCHK(hipGetLastError());
-  if (e->probe_on) OCHK(hipEventRecord(e->ev[e->ev_used++].second, st));
-  return BX_OK;
+  BX_HIPCHK(hipGetLastError());
+  return e->probe.end(0, st);
 }
 
 extern "C" {
@@ -597,92 +566,73 @@ int bx_ocsort_create(const bx_ocsort_config* c, bx_ocsort** out) {
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0)
     return bx_record_error(BX_ERR_NO_DEVICE, "no HIP device visible");
+  if (c->asso_kind < ASSO_IOU || c->asso_kind > ASSO_CENTROID)
+    return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
   bx_ocsort* e = new bx_ocsort();
   e->cfg = *c;
-  OCHK(hipGetDevice(&e->device));
-  OcsDev& d = e->dev;
-  d.S = c->n_seq;
-  d.T = c->track_cap;
-  d.D = c->det_cap;
-  d.N = d.T > d.D ? d.T : d.D;
-  d.min_conf = c->min_conf;
-  d.det_thresh = c->det_thresh;
-  d.asso_threshold = c->asso_threshold;
-  d.inertia = c->inertia;
-  d.q_xy = 1.0 * c->q_xy_scaling;
-  d.q_s = 1.0 * c->q_s_scaling;
-  d.max_age = c->max_age;
-  d.min_hits = c->min_hits;
-  d.delta_t = c->delta_t;
-  d.use_byte = c->use_byte;
-  if (c->asso_kind < ASSO_IOU || c->asso_kind > ASSO_CENTROID) {
-    delete e;
-    return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
-  }
-  d.asso_kind = c->asso_kind;
-  // basetracker.py:59-62: max_obs = 50, or max_age + 5 when max_age >= 50
-  d.max_obs = c->max_age >= 50 ? c->max_age + 5 : 50;
-  // LDS: the fixed part plus as much cost matrix as keeps ~4 workgroups per CU resident
-  const size_t fixed = lds_bytes(d.D, d.T, d.N, 0);
-  long budget = 40 * 1024 - (long)fixed;
-  int cl = budget > 0 ? (int)(budget / 8) : 0;
-  if (cl > d.D * d.T) cl = d.D * d.T;
-  if (cl < 64) cl = 64;
-  d.cost_lds = cl;
-  e->lds = lds_bytes(d.D, d.T, d.N, cl);
-  if (e->lds > 160 * 1024) {
-    delete e;
-    return bx_record_error(BX_ERR_INVALID, "track_cap/det_cap too large for one workgroup's LDS");
-  }
-  const bool need_g = (long)d.D * d.T > cl;
-  const size_t S = d.S, T = d.T;
-  size_t off = 0;
-  auto carve_b = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_trk = carve_b(S * T * sizeof(OcsTrk));
-  const size_t o_sq = carve_b(S * SQO * sizeof(int));
-  const size_t o_ord = carve_b(S * T * sizeof(int));
-  const size_t o_tb = carve_b(S * T * TB * sizeof(double));
-  const size_t o_cg = need_g ? carve_b(S * (size_t)d.D * T * sizeof(double)) : 0;
-  const size_t o_st = carve_b(sizeof(int) * 4);
-  const size_t o_fsz = carve_b(S * 2 * sizeof(double));
+  e->o = &e->dev;
+  // everything that can fail runs in `fill`: a failure frees what was allocated so far
+  auto fill = [&]() -> int {
+    BX_HIPCHK(hipGetDevice(&e->device));
+    OcsDev& d = e->dev;
+    d.S = c->n_seq;
+    d.T = c->track_cap;
+    d.D = c->det_cap;
+    d.N = d.T > d.D ? d.T : d.D;
+    d.min_conf = c->min_conf;
+    d.det_thresh = c->det_thresh;
+    d.asso_threshold = c->asso_threshold;
+    d.inertia = c->inertia;
+    d.q_xy = 1.0 * c->q_xy_scaling;
+    d.q_s = 1.0 * c->q_s_scaling;
+    d.max_age = c->max_age;
+    d.min_hits = c->min_hits;
+    d.delta_t = c->delta_t;
+    d.use_byte = c->use_byte;
+    d.asso_kind = c->asso_kind;
+    // basetracker.py:59-62: max_obs = 50, or max_age + 5 when max_age >= 50
+    d.max_obs = c->max_age >= 50 ? c->max_age + 5 : 50;
+    size_t x_off;
+    int rc = ocs_lds_budget(d, 0, &x_off, &e->lds);
+    if (rc) return rc;
+    const bool need_g = (long)d.D * d.T > d.cost_lds;
+    const size_t S = d.S, T = d.T;
+    BxCarve carve_b;
+    const size_t o_trk = carve_b(S * T * sizeof(OcsTrk));
+    const size_t o_sq = carve_b(S * SQO * sizeof(int));
+    const size_t o_ord = carve_b(S * T * sizeof(int));
+    const size_t o_tb = carve_b(S * T * TB * sizeof(double));
+    const size_t o_cg = need_g ? carve_b(S * (size_t)d.D * T * sizeof(double)) : 0;
+    const size_t o_st = carve_b(sizeof(int) * 4);
+    const size_t o_fsz = carve_b(S * 2 * sizeof(double));
 #ifdef BX_PHASE_TIMING
-  const size_t o_dbg = carve_b(S * OCS_DBG * sizeof(unsigned long long));
+    const size_t o_dbg = carve_b(S * OCS_DBG * sizeof(unsigned long long));
 #endif
-  if (hipMalloc(&e->arena, off) != hipSuccess) {
-    delete e;
-    return bx_record_error(BX_ERR_HIP, "hipMalloc of the OCSort arena failed");
-  }
-  OCHK(hipMemset(e->arena, 0, off));
-  char* base = (char*)e->arena;
-  d.trk = (OcsTrk*)(base + o_trk);
-  d.seqst = (int*)(base + o_sq);
-  d.order = (int*)(base + o_ord);
-  d.tb = (double*)(base + o_tb);
-  d.cost_g = need_g ? (double*)(base + o_cg) : nullptr;
-  d.status = (int*)(base + o_st);
-  d.fsz = (double*)(base + o_fsz);
-  {
-    std::vector<double> f(2 * S);
-    for (size_t k = 0; k < S; k++) {
-      f[2 * k] = c->frame_w;
-      f[2 * k + 1] = c->frame_h;
-    }
-    OCHK(hipMemcpy(d.fsz, f.data(), sizeof(double) * 2 * S, hipMemcpyHostToDevice));
-  }
+    if (hipMalloc(&e->arena, carve_b.off) != hipSuccess)
+      return bx_record_error(BX_ERR_HIP, "hipMalloc of the OCSort arena failed");
+    BX_HIPCHK(hipMemset(e->arena, 0, carve_b.off));
+    char* base = (char*)e->arena;
+    d.trk = (OcsTrk*)(base + o_trk);
+    d.seqst = (int*)(base + o_sq);
+    d.order = (int*)(base + o_ord);
+    d.tb = (double*)(base + o_tb);
+    d.cost_g = need_g ? (double*)(base + o_cg) : nullptr;
+    d.status = (int*)(base + o_st);
+    d.fsz = (double*)(base + o_fsz);
 #ifdef BX_PHASE_TIMING
-  d.dbg = (unsigned long long*)(base + o_dbg);
+    d.dbg = (unsigned long long*)(base + o_dbg);
 #else
-  d.dbg = nullptr;
+    d.dbg = nullptr;
 #endif
-  OCHK(bx_lds_attr((const void*)ocsort_frame_kernel, e->lds));
-  OCHK(hipMalloc(&e->h_dets, sizeof(float) * 6 * d.D));
-  OCHK(hipMalloc(&e->h_off, sizeof(int) * 2));
-  OCHK(hipMalloc(&e->h_out, sizeof(double) * 8 * d.D));
-  OCHK(hipMalloc(&e->h_cnt, sizeof(int)));
-  OCHK(hipHostMalloc(&e->p_dets, sizeof(float) * 6 * d.D));
-  OCHK(hipHostMalloc(&e->p_out, sizeof(double) * 8 * d.D));
-  OCHK(hipHostMalloc(&e->p_cnt, sizeof(int) * 4));
-  OCHK(hipHostMalloc(&e->p_sq, sizeof(int) * SQO));
+    if ((rc = ocs_upload_initial(d, c->frame_w, c->frame_h, 0))) return rc;
+    BX_HIPCHK(bx_lds_attr((const void*)ocsort_frame_kernel, e->lds));
+    return e->sg.alloc(sizeof(float) * 6 * d.D, 0, 0, 8, d.D, SQO);
+  };
+  const int rc = fill();
+  if (rc) {
+    bx_ocsort_destroy(e);
+    return rc;
+  }
   *out = e;
   return BX_OK;
 }
@@ -693,38 +643,28 @@ int bx_ocsort_copy_state(bx_ocsort* dst, bx_ocsort* src) {
   if (a.S != b.S || b.T < a.T || b.D < a.D)
     return bx_record_error(BX_ERR_INVALID, "bx_ocsort_copy_state: destination must have the "
                                            "source's sequences and at least its capacities");
-  OCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   const size_t S = a.S, Ta = a.T, Tb = b.T;
   // per-slot records [S][T] and the list order [S][T]; per-sequence scalars and frame sizes
-  OCHK(hipMemcpy2D(b.trk, Tb * sizeof(OcsTrk), a.trk, Ta * sizeof(OcsTrk), Ta * sizeof(OcsTrk), S,
+  BX_HIPCHK(hipMemcpy2D(b.trk, Tb * sizeof(OcsTrk), a.trk, Ta * sizeof(OcsTrk), Ta * sizeof(OcsTrk), S,
                    hipMemcpyDeviceToDevice));
-  OCHK(hipMemcpy2D(b.order, Tb * sizeof(int), a.order, Ta * sizeof(int), Ta * sizeof(int), S,
+  BX_HIPCHK(hipMemcpy2D(b.order, Tb * sizeof(int), a.order, Ta * sizeof(int), Ta * sizeof(int), S,
                    hipMemcpyDeviceToDevice));
-  OCHK(hipMemcpy(b.seqst, a.seqst, S * SQO * sizeof(int), hipMemcpyDeviceToDevice));
-  OCHK(hipMemcpy(b.fsz, a.fsz, S * 2 * sizeof(double), hipMemcpyDeviceToDevice));
-  OCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.seqst, a.seqst, S * SQO * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.fsz, a.fsz, S * 2 * sizeof(double), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
   dst->gid = src->gid;
   dst->lids = src->lids;
   dst->cache_seq = -1;
-  OCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   return BX_OK;
 }
 
 int bx_ocsort_destroy(bx_ocsort* e) {
   if (!e) return BX_OK;
-  for (auto& p : e->ev) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->h_dets);
-  (void)hipFree(e->h_off);
-  (void)hipFree(e->h_out);
-  (void)hipFree(e->h_cnt);
-  (void)hipHostFree(e->p_dets);
-  (void)hipHostFree(e->p_out);
-  (void)hipHostFree(e->p_cnt);
-  (void)hipHostFree(e->p_sq);
+  e->sg.free();
   (void)hipFree(e->h_coff);
   (void)hipFree(e->h_ccnt);
   delete e;
@@ -738,7 +678,7 @@ int bx_ocsort_reset(bx_ocsort* e, int seq0, int nseq, void* stream) {
   e->cache_seq = -1;
   hipLaunchKernelGGL(ocsort_reset_kernel, dim3((nseq * SQO + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, e->dev, seq0, nseq);
-  OCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   for (int s = seq0; s < seq0 + nseq && !e->lids.empty(); s++) {
     e->lids[s] = 0;
     e->gid[s].clear();
@@ -760,31 +700,10 @@ int bx_ocsort_update_host(bx_ocsort* e, int seq, const float* dets, int n, doubl
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ocsort_update_host");
   if (n > e->dev.D) return bx_record_error(BX_ERR_CAPACITY, "detections exceed det_cap");
   hipStream_t st = (hipStream_t)stream;
-  // pinned mirrors: asynchronous copies in, the frame, rows (at most n) + count + status +
-  // counters back, one synchronisation
-  if (n) {
-    memcpy(e->p_dets, dets, sizeof(float) * 6 * n);
-    OCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
-  }
-  e->p_cnt[2] = 0;
-  e->p_cnt[3] = n;
-  OCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
-  e->cache_seq = -1;
-  int rc = launch(e, seq, 1, e->h_dets, e->h_off, e->h_out, e->h_cnt, st);
-  if (rc) return rc;
-  OCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  OCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.status, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (n) OCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
-  OCHK(hipMemcpyAsync(e->p_sq, e->dev.seqst + (size_t)seq * SQO, sizeof(int) * SQO,
-                      hipMemcpyDeviceToHost, st));
-  OCHK(hipStreamSynchronize(st));
-  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
-  e->cache_seq = seq;
-  if (cnt) memcpy(out, e->p_out, sizeof(double) * 8 * cnt);
-  *n_out = cnt;
-  if (status)
-    return bx_record_error(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
-  return BX_OK;
+  return ocs_update_host_roundtrip(
+      *e, seq, dets, n, out, n_out, st, false,
+      [&] { return launch(e, seq, 1, (float*)e->sg.h_dets, e->sg.h_off, e->sg.h_out, e->sg.h_cnt, st); },
+      OcsStreamSync{st});
 }
 
 // per_class=True (basetracker.py:155-201): OCSort keeps all of its state in active_tracks, so
@@ -808,8 +727,8 @@ int bx_ocsort_update_classes_host(bx_ocsort* e, int seq0, int n_classes, const f
   if (e->ncls_alloc < C) {
     (void)hipFree(e->h_coff);
     (void)hipFree(e->h_ccnt);
-    OCHK(hipMalloc(&e->h_coff, sizeof(int) * (C + 1)));
-    OCHK(hipMalloc(&e->h_ccnt, sizeof(int) * C));
+    BX_HIPCHK(hipMalloc(&e->h_coff, sizeof(int) * (C + 1)));
+    BX_HIPCHK(hipMalloc(&e->h_ccnt, sizeof(int) * C));
     e->ncls_alloc = C;
   }
   auto cls_of = [&](int i) -> int {
@@ -827,20 +746,20 @@ int bx_ocsort_update_classes_host(bx_ocsort* e, int seq0, int n_classes, const f
     const int c = cls_of(i);
     if (c >= 0) memcpy(&hd[6 * (size_t)fill[c]++], dets + 6 * (size_t)i, 6 * sizeof(float));
   }
-  if (m) OCHK(hipMemcpyAsync(e->h_dets, hd.data(), sizeof(float) * 6 * m, hipMemcpyHostToDevice, st));
-  OCHK(hipMemcpyAsync(e->h_coff, cnt.data(), sizeof(int) * (C + 1), hipMemcpyHostToDevice, st));
+  if (m) BX_HIPCHK(hipMemcpyAsync((float*)e->sg.h_dets, hd.data(), sizeof(float) * 6 * m, hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemcpyAsync(e->h_coff, cnt.data(), sizeof(int) * (C + 1), hipMemcpyHostToDevice, st));
   e->cache_seq = -1;
-  int rc = launch(e, seq0, C, e->h_dets, e->h_coff, e->h_out, e->h_ccnt, st);
+  int rc = launch(e, seq0, C, (float*)e->sg.h_dets, e->h_coff, e->sg.h_out, e->h_ccnt, st);
   if (rc) return rc;
   std::vector<int> oc(C), sq((size_t)C * SQO);
   std::vector<double> ho((size_t)8 * (m ? m : 1));
-  OCHK(hipMemcpyAsync(oc.data(), e->h_ccnt, sizeof(int) * C, hipMemcpyDeviceToHost, st));
-  if (m) OCHK(hipMemcpyAsync(ho.data(), e->h_out, sizeof(double) * 8 * m, hipMemcpyDeviceToHost, st));
-  OCHK(hipMemcpyAsync(sq.data(), e->dev.seqst + (size_t)seq0 * SQO, sizeof(int) * C * SQO,
+  BX_HIPCHK(hipMemcpyAsync(oc.data(), e->h_ccnt, sizeof(int) * C, hipMemcpyDeviceToHost, st));
+  if (m) BX_HIPCHK(hipMemcpyAsync(ho.data(), e->sg.h_out, sizeof(double) * 8 * m, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(sq.data(), e->dev.seqst + (size_t)seq0 * SQO, sizeof(int) * C * SQO,
                       hipMemcpyDeviceToHost, st));
-  OCHK(hipStreamSynchronize(st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   int status = 0;
-  OCHK(hipMemcpy(&status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(&status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   if (status)
     return bx_record_error(BX_ERR_TRACK_OVERFLOW, "a sequence ran out of track slots (raise track_cap)");
   int g = *id_count;
@@ -871,7 +790,7 @@ static int kf_xysr_launch(int op, int n, double* x, double* P, const double* arg
   if (!n) return BX_OK;
   hipLaunchKernelGGL(kf_xysr_kernel, dim3((8 * n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      op, n, x, P, arg, q_xy, q_s);
-  OCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -888,59 +807,34 @@ int bx_kf_xysr_update(int n, double* x, double* P, const double* z, void* stream
 
 int bx_ocsort_status(bx_ocsort* e, int* status) {
   if (!e || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
-  OCHK(hipMemcpy(status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
 int bx_ocsort_counters_host(bx_ocsort* e, int seq, int* frame_count, int* id_count,
                             int* n_tracks) {
-  if (!e || seq < 0 || seq >= e->dev.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  int s[SQO];
-  if (seq == e->cache_seq) {
-    memcpy(s, e->p_sq, sizeof(s));
-  } else {
-    OCHK(hipDeviceSynchronize());
-    OCHK(hipMemcpy(s, e->dev.seqst + (size_t)seq * SQO, sizeof(s), hipMemcpyDeviceToHost));
-  }
-  if (frame_count) *frame_count = s[SO_FRAME];
-  if (id_count) *id_count = s[SO_IDS];
-  if (n_tracks) *n_tracks = s[SO_NTR];
-  return BX_OK;
+  return ocs_counters(e, seq, frame_count, id_count, n_tracks);
 }
 
 int bx_ocsort_set_id_count(bx_ocsort* e, int seq, int id_count, void* stream) {
-  if (!e || seq < 0 || seq >= e->dev.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  e->cache_seq = -1;
-  OCHK(hipMemcpyAsync(e->dev.seqst + (size_t)seq * SQO + SO_IDS, &id_count, sizeof(int),
-                      hipMemcpyHostToDevice, (hipStream_t)stream));
-  OCHK(hipStreamSynchronize((hipStream_t)stream));
-  return BX_OK;
+  return ocs_set_id_count(e, seq, id_count, stream);
 }
 
 int bx_ocsort_set_frame_size(bx_ocsort* e, int seq, double w, double h, void* stream) {
-  if (!e || seq < 0 || seq >= e->dev.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
-  const double f[2] = {w, h};
-  OCHK(hipMemcpyAsync(e->dev.fsz + 2 * (size_t)seq, f, sizeof(f), hipMemcpyHostToDevice,
-                      (hipStream_t)stream));
-  OCHK(hipStreamSynchronize((hipStream_t)stream));
-  return BX_OK;
+  return ocs_set_frame_size(e, seq, w, h, stream);
 }
 
 int bx_ocsort_tracks_host(bx_ocsort* e, int seq, int cap, int32_t* ids, double* x, double* p,
                           int* n) {
   if (!e || seq < 0 || seq >= e->dev.S || cap < 0 || !n)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ocsort_tracks_host");
-  OCHK(hipDeviceSynchronize());
-  int s[SQO];
-  OCHK(hipMemcpy(s, e->dev.seqst + (size_t)seq * SQO, sizeof(s), hipMemcpyDeviceToHost));
-  const int nt = s[SO_NTR];
-  std::vector<int> ord(nt);
-  if (nt)
-    OCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
-                   hipMemcpyDeviceToHost));
+  std::vector<int> ord;
+  int rc = ocs_list_order(e->dev, seq, ord);
+  if (rc) return rc;
+  const int nt = (int)ord.size();
   for (int k = 0; k < nt && k < cap; k++) {
     OcsTrk t;
-    OCHK(hipMemcpy(&t, e->dev.trk + (size_t)seq * e->dev.T + ord[k], sizeof(OcsTrk),
+    BX_HIPCHK(hipMemcpy(&t, e->dev.trk + (size_t)seq * e->dev.T + ord[k], sizeof(OcsTrk),
                    hipMemcpyDeviceToHost));
     // a per-class sequence reports the class-global id its rows carry (minus one)
     const bool g = seq < (int)e->gid.size() && t.id >= 0 && t.id < (int)e->gid[seq].size();
@@ -956,79 +850,43 @@ int bx_ocsort_state_set_host(bx_ocsort* e, int seq, int n, const int32_t* ids, c
                              const double* p) {
   if (!e || seq < 0 || seq >= e->dev.S || n < 0 || (n && !ids))
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ocsort_state_set_host");
-  OCHK(hipDeviceSynchronize());
-  int s[SQO];
-  OCHK(hipMemcpy(s, e->dev.seqst + (size_t)seq * SQO, sizeof(s), hipMemcpyDeviceToHost));
-  const int nt = s[SO_NTR];
-  std::vector<int> ord(nt);
-  if (nt)
-    OCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
-                   hipMemcpyDeviceToHost));
+  std::vector<int> ord;
+  int rc = ocs_list_order(e->dev, seq, ord);
+  if (rc) return rc;
   for (int j = 0; j < n; j++) {
-    OcsTrk* dt = nullptr;
     OcsTrk t;
-    for (int k = 0; k < nt && !dt; k++) {
-      OcsTrk* cand = e->dev.trk + (size_t)seq * e->dev.T + ord[k];
-      OCHK(hipMemcpy(&t, cand, sizeof(OcsTrk), hipMemcpyDeviceToHost));
-      if (t.id == ids[j]) dt = cand;
-    }
-    if (!dt) return bx_record_error(BX_ERR_INVALID, "state_set: no live track with that id");
+    int slot;
+    if ((rc = ocs_find_track(e->dev, e->dev.trk, seq, ord, ids[j], t, &slot))) return rc;
     if (x) memcpy(t.x, x + 7 * j, sizeof(t.x));
     if (p) memcpy(t.P, p + 49 * j, sizeof(t.P));
-    OCHK(hipMemcpy(dt, &t, sizeof(OcsTrk), hipMemcpyHostToDevice));
+    BX_HIPCHK(hipMemcpy(e->dev.trk + (size_t)seq * e->dev.T + slot, &t, sizeof(OcsTrk),
+                   hipMemcpyHostToDevice));
   }
   return BX_OK;
 }
 
 int bx_ocsort_frame_stats_host(bx_ocsort* e, int seq0, int nseq, int64_t* sums) {
-  if (!e || !sums || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.S)
-    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ocsort_frame_stats_host");
-  std::vector<int> s((size_t)nseq * SQO);
-  OCHK(hipDeviceSynchronize());
-  if (nseq)
-    OCHK(hipMemcpy(s.data(), e->dev.seqst + (size_t)seq0 * SQO, sizeof(int) * s.size(),
-                   hipMemcpyDeviceToHost));
-  int64_t t = 0, o = 0, f = 0;
-  for (int k = 0; k < nseq; k++) {
-    t += s[(size_t)k * SQO + SO_NTR];
-    o += s[(size_t)k * SQO + SO_NOUT];
-    f = s[(size_t)k * SQO + SO_FRAME] > f ? s[(size_t)k * SQO + SO_FRAME] : f;
-  }
-  sums[0] = t;
-  sums[1] = o;
-  sums[2] = f;
-  return BX_OK;
+  return ocs_frame_stats(e, "bx_ocsort_frame_stats_host", seq0, nseq, sums);
 }
 
 // diagnostic (not in the public header): the phase stamps of every sequence, [S][OCS_DBG]
 int bx_ocsort_debug_host(bx_ocsort* e, unsigned long long* out) {
   if (!e || !out || !e->dev.dbg) return bx_record_error(BX_ERR_INVALID, "not a timing build");
-  OCHK(hipDeviceSynchronize());
-  OCHK(hipMemcpy(out, e->dev.dbg, sizeof(unsigned long long) * OCS_DBG * e->dev.S,
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(out, e->dev.dbg, sizeof(unsigned long long) * OCS_DBG * e->dev.S,
                  hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
 int bx_ocsort_probe(bx_ocsort* e, int on) {
   if (!e) return bx_record_error(BX_ERR_INVALID, "null engine");
-  e->probe_on = on != 0;
-  e->ev_used = 0;
+  e->probe.set(on != 0 ? 0 : -1);
   return BX_OK;
 }
 
 int bx_ocsort_probe_read(bx_ocsort* e, double* total_ms, int* count) {
   if (!e || !total_ms || !count) return bx_record_error(BX_ERR_INVALID, "null argument");
-  double s = 0.0;
-  for (int k = 0; k < e->ev_used; k++) {
-    OCHK(hipEventSynchronize(e->ev[k].second));
-    float ms = 0.f;
-    OCHK(hipEventElapsedTime(&ms, e->ev[k].first, e->ev[k].second));
-    s += ms;
-  }
-  *total_ms = s;
-  *count = e->ev_used;
-  e->ev_used = 0;
-  return BX_OK;
+  return e->probe.read(total_ms, count);
 }
 
 }  // extern "C"

@@ -7,22 +7,15 @@
 
 #include "../../include/bxassoc.h"
 #include "bx_device.h"
+#include "bx_host.h"
 
-hipError_t bx_lds_attr(const void* kern, size_t bytes);  // bx_engine.hip (never lowers a limit)
 
 using namespace bx;
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
 
 namespace {
 
 int op_err(int code, const char* msg) { return bx_record_error(code, msg); }
-#define OPCHK(x)                                                  \
-  do {                                                            \
-    hipError_t _e = (x);                                          \
-    if (_e != hipSuccess) return op_err(BX_ERR_HIP, hipGetErrorString(_e)); \
-  } while (0)
-
 __global__ void iou_kernel(const double* a, int na, const double* b, int nb, double* out) {
   const size_t n = (size_t)na * nb;
   for (size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x; k < n;
@@ -319,7 +312,7 @@ int bx_iou_batch(const double* a, int na, const double* b, int nb, double* out, 
   if (!na || !nb) return BX_OK;
   hipLaunchKernelGGL(iou_kernel, dim3(grid_for((size_t)na * nb)), dim3(256), 0,
                      (hipStream_t)stream, a, na, b, nb, out);
-  OPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -332,7 +325,7 @@ int bx_pairwise_cost(int kind, const double* a, int na, int lda, const double* b
   if (lda < 4 || ldb < 4) return op_err(BX_ERR_INVALID, "row stride below 4");
   hipLaunchKernelGGL(pairwise_kernel, dim3(grid_for((size_t)na * nb)), dim3(256), 0,
                      (hipStream_t)stream, kind, a, na, lda, b, nb, ldb, w, h, out);
-  OPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -343,7 +336,7 @@ int bx_aw_max_metric(const double* emb, int nr, int nc, double w_assoc, double b
   if (!nr || !nc) return BX_OK;
   hipLaunchKernelGGL(aw_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, emb, nr, nc, w_assoc,
                      bottom, out);
-  OPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -352,7 +345,7 @@ int bx_fuse_score(double* cost, int nr, int nc, const double* confs, void* strea
   if (!nr || !nc) return BX_OK;
   hipLaunchKernelGGL(fuse_kernel, dim3(grid_for((size_t)nr * nc)), dim3(256), 0,
                      (hipStream_t)stream, cost, nr, nc, confs);
-  OPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -363,7 +356,7 @@ int bx_embedding_distance(const float* trk, int nt, const float* det, int nd, in
   hipStream_t st = (hipStream_t)stream;
   void* ws = nullptr;
   const size_t bytes = (size_t)(nt + nd) * (sizeof(float) + sizeof(double)) + 64;
-  OPCHK(hipMallocAsync(&ws, bytes, st));
+  BX_HIPCHK(hipMallocAsync(&ws, bytes, st));
   float* adn = (float*)ws;
   float* bdn = adn + nt;
   double* anr = (double*)(((uintptr_t)(bdn + nd) + 15) & ~uintptr_t(15));
@@ -374,8 +367,8 @@ int bx_embedding_distance(const float* trk, int nt, const float* det, int nd, in
                      bnr);
   hipLaunchKernelGGL(cosine_kernel, dim3(grid_for((size_t)nt * nd)), dim3(256), 0, st, trk, nt,
                      det, nd, f, adn, anr, bdn, bnr, out);
-  OPCHK(hipGetLastError());
-  OPCHK(hipFreeAsync(ws, st));
+  BX_HIPCHK(hipGetLastError());
+  BX_HIPCHK(hipFreeAsync(ws, st));
   return BX_OK;
 }
 
@@ -384,7 +377,7 @@ int bx_kf_initiate(int kind, int n, const double* meas, double* mean, double* co
   if (!n) return BX_OK;
   hipLaunchKernelGGL(kf_init_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream,
                      kind, n, meas, mean, cov);
-  OPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -393,7 +386,7 @@ int bx_kf_multi_predict(int kind, int n, double* mean, double* cov, void* stream
   if (!n) return BX_OK;
   hipLaunchKernelGGL(kf_predict_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                      kind, n, mean, cov);
-  OPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -403,7 +396,7 @@ int bx_kf_update(int kind, int n, double* mean, double* cov, const double* z, co
   if (!n) return BX_OK;
   hipLaunchKernelGGL(kf_update_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                      kind, n, mean, cov, z, conf);
-  OPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -413,7 +406,7 @@ int bx_kf_gating_distance(int kind, int n, const double* mean, const double* cov
   if (!n || !nz) return BX_OK;
   hipLaunchKernelGGL(kf_gate_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, kind,
                      n, mean, cov, z, nz, out);
-  OPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -428,8 +421,8 @@ int bx_linear_assignment_ex(const double* cost, int nr, int nc, double thresh, i
     return op_err(BX_ERR_INVALID, "nr/nc out of range (0..8192)");
   hipStream_t st = (hipStream_t)stream;
   if (!nr || !nc) {
-    if (nr) OPCHK(hipMemsetAsync(x, 0xff, sizeof(int32_t) * nr, st));
-    if (nc) OPCHK(hipMemsetAsync(y, 0xff, sizeof(int32_t) * nc, st));
+    if (nr) BX_HIPCHK(hipMemsetAsync(x, 0xff, sizeof(int32_t) * nr, st));
+    if (nc) BX_HIPCHK(hipMemsetAsync(y, 0xff, sizeof(int32_t) * nc, st));
     return BX_OK;
   }
   int elds = 2048;
@@ -458,18 +451,18 @@ int bx_linear_assignment_ex(const double* cost, int nr, int nc, double thresh, i
   void* ws = nullptr;
   const size_t ne = (size_t)nr * nc;
   const size_t jvb = (jv_bytes(nr + nc) + 255) & ~size_t(255);
-  OPCHK(hipMallocAsync(&ws, jvb + 64 + ne * 10 + 64, st));
+  BX_HIPCHK(hipMallocAsync(&ws, jvb + 64 + ne * 10 + 64, st));
   unsigned char* jvs = (unsigned char*)ws;
   int32_t* tied = (int32_t*)(jvs + jvb);
   double* gcost = (double*)(jvs + jvb + 64);
   uint16_t* gcol = (uint16_t*)(gcost + ne);
   // (never lowers the limit a concurrent call on another thread or stream launches with)
-  if (lds > 65536) OPCHK(bx_lds_attr((const void*)lap_dense_kernel, lds));
+  if (lds > 65536) BX_HIPCHK(bx_lds_attr((const void*)lap_dense_kernel, lds));
   hipLaunchKernelGGL(lap_dense_kernel, dim3(1), dim3(WG), lds, st, cost, nr, nc, thresh, elds,
                      gcol, gcost, jvs, jv_lds, cls_lds, x, y, tied);
-  OPCHK(hipGetLastError());
-  if (tied_out) OPCHK(hipMemcpyAsync(tied_out, tied, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-  OPCHK(hipFreeAsync(ws, st));
+  BX_HIPCHK(hipGetLastError());
+  if (tied_out) BX_HIPCHK(hipMemcpyAsync(tied_out, tied, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  BX_HIPCHK(hipFreeAsync(ws, st));
   return BX_OK;
 }
 
@@ -480,13 +473,13 @@ int bx_legacy_lap_pair(const double* cost, int nr, int nc, int32_t* pairs_jv, in
   hipStream_t st = (hipStream_t)stream;
   if (!nr || !nc) {
     const int32_t z[3] = {0, 0, 0};
-    OPCHK(hipMemcpyAsync(info, z, sizeof(z), hipMemcpyHostToDevice, st));
+    BX_HIPCHK(hipMemcpyAsync(info, z, sizeof(z), hipMemcpyHostToDevice, st));
     return BX_OK;
   }
   const size_t lds = jv_bytes(nr > nc ? nr : nc);
   hipLaunchKernelGGL(legacy_lap_pair_kernel, dim3(1), dim3(OW), lds, st, cost, nr, nc, pairs_jv,
                      pairs_ssp, info);
-  OPCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -503,19 +496,19 @@ int bx_lapjv(const double* cost, int nr, int nc, int extend_cost, double cost_li
   if (n > 32768) return op_err(BX_ERR_INVALID, "lapjv: extended size above 32768");
   hipStream_t st = (hipStream_t)stream;
   if (!nr || !nc) {
-    if (nr) OPCHK(hipMemsetAsync(x, 0xff, sizeof(int32_t) * nr, st));
-    if (nc) OPCHK(hipMemsetAsync(y, 0xff, sizeof(int32_t) * nc, st));
+    if (nr) BX_HIPCHK(hipMemsetAsync(x, 0xff, sizeof(int32_t) * nr, st));
+    if (nc) BX_HIPCHK(hipMemsetAsync(y, 0xff, sizeof(int32_t) * nc, st));
     return BX_OK;
   }
   const size_t lds = jv_bytes(n);
   unsigned char* gst = nullptr;
-  if (lds > 160 * 1024) OPCHK(hipMallocAsync((void**)&gst, lds, st));
+  if (lds > 160 * 1024) BX_HIPCHK(hipMallocAsync((void**)&gst, lds, st));
   const size_t dyn = gst ? 0 : lds;
-  if (dyn > 65536) OPCHK(bx_lds_attr((const void*)lapjv_kernel, dyn));
+  if (dyn > 65536) BX_HIPCHK(bx_lds_attr((const void*)lapjv_kernel, dyn));
   hipLaunchKernelGGL(lapjv_kernel, dim3(1), dim3(OW), dyn, st, cost, nr, nc, mode, cost_limit,
                      gst, x, y);
-  OPCHK(hipGetLastError());
-  if (gst) OPCHK(hipFreeAsync(gst, st));
+  BX_HIPCHK(hipGetLastError());
+  if (gst) BX_HIPCHK(hipFreeAsync(gst, st));
   return BX_OK;
 }
 

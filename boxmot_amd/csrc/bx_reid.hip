@@ -20,20 +20,14 @@
 #include "../../include/bxreid.h"
 #include "bx_device.h"
 #include "bx_resize.h"
+#include "bx_host.h"
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
 
 using namespace bx;
 
 namespace {
 
 int re_err(int code, const std::string& msg) { return bx_record_error(code, msg.c_str()); }
-#define RECHK(x)                                                            \
-  do {                                                                      \
-    hipError_t _e = (x);                                                    \
-    if (_e != hipSuccess) return re_err(BX_ERR_HIP, hipGetErrorString(_e)); \
-  } while (0)
-
 constexpr int CT = 256;       // threads of a crop workgroup
 constexpr int ROW_WALK = 4;   // rows a lane walks with one set of x taps (a tile's depth)
 
@@ -249,7 +243,7 @@ int bx_reid_crops(const uint8_t* frames, int F, int H, int W, const float* boxes
   else if (half) reid_crops_kernel<_Float16, false><<<grid, block, 0, st>>>(a);
   else if (nhwc) reid_crops_kernel<float, true><<<grid, block, 0, st>>>(a);
   else reid_crops_kernel<float, false><<<grid, block, 0, st>>>(a);
-  RECHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -268,7 +262,7 @@ int bx_reid_normalize(const void* in, int in_half, int64_t in_stride, int n, int
     reid_normalize_kernel<<<grid, block, 0, st>>>((const float*)in, in_stride, n, F, (double*)out);
   else
     reid_normalize_kernel<<<grid, block, 0, st>>>((const float*)in, in_stride, n, F, (float*)out);
-  RECHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 

@@ -49,8 +49,7 @@
 
 using namespace bx;
 
-int bx_record_error(int code, const char* msg);  // bx_engine.hip (shared bx_last_error)
-hipError_t bx_lds_attr(const void* kern, size_t bytes);  // bx_engine.hip (never lowers a limit)
+#include "bx_host.h"
 
 namespace {
 
@@ -3505,53 +3504,16 @@ struct bx_ss {
   SsDev dev;
   bx_ss_config cfg;
   void* arena = nullptr;
-  double* h_dets = nullptr;
-  int* h_off = nullptr;
-  double* h_embs = nullptr;
-  double* h_warp = nullptr;
-  double* h_out = nullptr;
-  int* h_cnt = nullptr;
-  // pinned mirrors for update_host (asynchronous copies, one sync per frame) and the counters
-  // row of the last update_host sequence (bx_ss_counters_host answers from it)
-  double* p_dets = nullptr;
-  double* p_embs = nullptr;
-  double* p_warp = nullptr;
-  double* p_out = nullptr;
-  int* p_cnt = nullptr;
-  int* p_sq = nullptr;
+  // update_host staging (detections as doubles, 10-wide rows); sg.p_sq: the counters row of the
+  // last update_host sequence (bx_ss_counters_host answers from it)
+  BxStaging sg;
   int cache_seq = -1;
-  int probe_stage = -1;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  int ev_used = 0;
+  BxProbe probe;  // stages 0..8 (ss_launch)
   // crowd test + ss_pre_kernel run on `side` beside ss_nn_kernel / ss_rec_kernel (neither reads
   // what the other writes); fork after ss_prep_kernel, join before ss_cost_kernel
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
-
-#define SCHK(x)                                                                    \
-  do {                                                                             \
-    hipError_t _e = (x);                                                           \
-    if (_e != hipSuccess)                                                          \
-      return bx_record_error(BX_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
-
-static int ss_probe_begin(bx_ss* e, int stage, hipStream_t st) {
-  if (e->probe_stage != stage) return BX_OK;
-  if (e->ev_used == (int)e->ev.size()) {
-    hipEvent_t a, b;
-    SCHK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
-    SCHK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
-    e->ev.push_back({a, b});
-  }
-  SCHK(hipEventRecord(e->ev[e->ev_used].first, st));
-  return BX_OK;
-}
-static int ss_probe_end(bx_ss* e, int stage, hipStream_t st) {
-  if (e->probe_stage != stage) return BX_OK;
-  SCHK(hipEventRecord(e->ev[e->ev_used++].second, st));
-  return BX_OK;
-}
 
 static size_t ss_lds_bytes(const SsDev& d) {
   return d.ws_lds == 1 ? (size_t)d.wsd_n * 8 + (size_t)d.wsi_n * 4 : (size_t)ws_lsap_bytes(d.N);
@@ -3563,11 +3525,11 @@ static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int
   const SsDev& d = e->dev;
   int rc;
   if (!embs) return bx_record_error(BX_ERR_SHAPE, "StrongSort needs embeddings");
-  if ((rc = ss_probe_begin(e, 0, st))) return rc;
+  if ((rc = e->probe.begin(0, st))) return rc;
   hipLaunchKernelGGL(ss_prep_kernel, dim3(d.D + 1, nseq), dim3(64), 0, st, d, seq0, off, embs,
                      dets);
-  SCHK(hipGetLastError());
-  if ((rc = ss_probe_end(e, 0, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(0, st))) return rc;
   // fork: ss_pre_kernel (crowd mode, quality + sort, cascade keys; one wave per sequence) on the
   // side stream beside the gallery distance
   const size_t lds = ss_lds_bytes(d);
@@ -3578,30 +3540,30 @@ static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int
   const bool side_all = nseq >= 8;
   hipStream_t sm = side_all ? e->side : st;
   if (side_all) {
-    SCHK(hipEventRecord(e->ev_fork, st));
-    SCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
+    BX_HIPCHK(hipEventRecord(e->ev_fork, st));
+    BX_HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
   }
-  if ((rc = ss_probe_begin(e, 3, sm))) return rc;
+  if ((rc = e->probe.begin(3, sm))) return rc;
   if (d.crowd)
     hipLaunchKernelGGL(ss_crowd_kernel, dim3(crowd_blocks(nseq), nseq), dim3(256),
                        sizeof(double) * 4 * d.T, sm, d, seq0);
   hipLaunchKernelGGL(ss_motion_kernel, dim3(d.T, nseq), dim3(64), 0, sm, d, seq0, warps);
-  SCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   if (!side_all) {
-    if ((rc = ss_probe_end(e, 3, st))) return rc;
-    SCHK(hipEventRecord(e->ev_fork, st));
-    SCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-    if ((rc = ss_probe_begin(e, 3, e->side))) return rc;
+    if ((rc = e->probe.end(3, st))) return rc;
+    BX_HIPCHK(hipEventRecord(e->ev_fork, st));
+    BX_HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
+    if ((rc = e->probe.begin(3, e->side))) return rc;
   }
   hipLaunchKernelGGL(ss_pre_kernel, dim3(nseq), dim3(64), lds, e->side, d, seq0, dets, off,
                      warps);
-  SCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(ss_sort_kernel, dim3((d.D + 255) / 256, nseq), dim3(256), 0, e->side, d,
                      seq0);
-  SCHK(hipGetLastError());
-  if ((rc = ss_probe_end(e, 3, e->side))) return rc;
-  SCHK(hipEventRecord(e->ev_join, e->side));
-  if ((rc = ss_probe_begin(e, 1, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(3, e->side))) return rc;
+  BX_HIPCHK(hipEventRecord(e->ev_join, e->side));
+  if ((rc = e->probe.begin(1, st))) return rc;
   // a fixed set of waves per sequence pulls (pack, 16 NDT-detection block) items off the
   // sequence's counter (ss_nn_kernel): ~BX_SS_NN_WAVES in all (two per SIMD), at least one per
   // sequence and no more than its largest item count (packs <= listed tracks)
@@ -3628,35 +3590,35 @@ static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int
     hipLaunchKernelGGL((ss_nn_kernel<2>), dim3(gx, nseq, 1), dim3(64), 0, st, d, seq0, off);
   else
     hipLaunchKernelGGL((ss_nn_kernel<1>), dim3(gx, nseq, 1), dim3(64), 0, st, d, seq0, off);
-  SCHK(hipGetLastError());
-  if ((rc = ss_probe_end(e, 1, st))) return rc;
-  if ((rc = ss_probe_begin(e, 2, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(1, st))) return rc;
+  if ((rc = e->probe.begin(2, st))) return rc;
   hipLaunchKernelGGL(ss_rec_kernel, dim3(LOSTN, nseq), dim3(256), 0, st, d, seq0, off, embs);
-  SCHK(hipGetLastError());
-  if ((rc = ss_probe_end(e, 2, st))) return rc;
-  SCHK(hipStreamWaitEvent(st, e->ev_join, 0));  // join
-  if ((rc = ss_probe_begin(e, 4, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(2, st))) return rc;
+  BX_HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));  // join
+  if ((rc = e->probe.begin(4, st))) return rc;
   hipLaunchKernelGGL(ss_cost_kernel, dim3(d.T, nseq), dim3(64), 0, st, d, seq0);
-  SCHK(hipGetLastError());
-  if ((rc = ss_probe_end(e, 4, st))) return rc;
-  if ((rc = ss_probe_begin(e, 5, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(4, st))) return rc;
+  if ((rc = e->probe.begin(5, st))) return rc;
   hipLaunchKernelGGL(ss_match_kernel, dim3(nseq), dim3(128), lds, st, d, seq0);
-  SCHK(hipGetLastError());
-  if ((rc = ss_probe_end(e, 5, st))) return rc;
-  if ((rc = ss_probe_begin(e, 6, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(5, st))) return rc;
+  if ((rc = e->probe.begin(6, st))) return rc;
   hipLaunchKernelGGL(ss_update_kernel,
                      dim3(((d.T < d.D ? d.T : d.D) + SS_UPD_W - 1) / SS_UPD_W, nseq),
                      dim3(64 * SS_UPD_W), 0, st, d, seq0);
-  SCHK(hipGetLastError());
-  if ((rc = ss_probe_end(e, 6, st))) return rc;
-  if ((rc = ss_probe_begin(e, 7, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(6, st))) return rc;
+  if ((rc = e->probe.begin(7, st))) return rc;
   hipLaunchKernelGGL(ss_post_kernel, dim3(nseq), dim3(64), lds, st, d, seq0, off, out, cnt);
-  SCHK(hipGetLastError());
-  if ((rc = ss_probe_end(e, 7, st))) return rc;
-  if ((rc = ss_probe_begin(e, 8, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(7, st))) return rc;
+  if ((rc = e->probe.begin(8, st))) return rc;
   hipLaunchKernelGGL(ss_fit_kernel, dim3(d.T + LOSTN, nseq), dim3(64), 0, st, d, seq0);
-  SCHK(hipGetLastError());
-  if ((rc = ss_probe_end(e, 8, st))) return rc;
+  BX_HIPCHK(hipGetLastError());
+  if ((rc = e->probe.end(8, st))) return rc;
   return BX_OK;
 }
 
@@ -3674,162 +3636,154 @@ int bx_ss_create(const bx_ss_config* c, bx_ss** out) {
     return bx_record_error(BX_ERR_NO_DEVICE, "no HIP device visible");
   bx_ss* e = new bx_ss();
   e->cfg = *c;
-  SsDev& d = e->dev;
-  d.S = c->n_seq;
-  d.T = c->track_cap;
-  d.D = c->det_cap;
-  d.F = c->emb_dim;
-  d.VP = vp;
-  const int crowd_budget = c->nn_budget * 2 < 300 ? c->nn_budget * 2 : 300;
-  // partial_fit appends a track's <= MAXF features before truncating to the budget
-  d.GB = (c->nn_budget > crowd_budget ? c->nn_budget : crowd_budget) + MAXF;
-  if (d.GB > GB_MAX) {
-    delete e;
-    return bx_record_error(BX_ERR_INVALID, "nn_budget too large (gallery > 320 entries)");
-  }
-  d.N = 2 * d.T > d.D ? 2 * d.T : d.D;
-  d.min_conf = c->min_conf;
-  d.max_iou = c->max_iou_dist;
-  d.mc_lambda = c->mc_lambda;
-  d.ema_alpha = c->ema_alpha;
-  d.thi = c->conf_thresh_high;
-  d.tlo = c->conf_thresh_low;
-  d.idw = c->id_preservation_weight;
-  d.n_init = c->n_init;
-  d.crowd = c->crowd_detection != 0;
-  d.born = c->born_confirmed != 0;
-  d.wsi_n = ws_ints(d.T, d.D, d.N);
-  d.wsd_n = ws_doubles(d.T, d.D, d.N);
-  // the frame kernel's workspace in LDS when it fits beside ~3 other workgroups per CU
-  const size_t ws_bytes = (size_t)d.wsd_n * 8 + (size_t)d.wsi_n * 4;
-  // all of it in LDS when it fits beside ~3 other workgroups per CU; else the LSAP state alone
-  // (the solver's inner loops; track_cap, det_cap <= 1024 keep it within 106 KB)
-  d.ws_lds = ws_bytes <= 48 * 1024 ? 1 : 2;
-  d.lsap_fast = 1;
-  const size_t S = d.S, T = d.T, D = d.D, F = d.F, VP = d.VP, GB = d.GB;
-  size_t off = 0;
-  auto cb = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_trk = cb(S * T * sizeof(SsTrk));
-  const size_t o_gv = cb(S * T * GB * sizeof(int));
-  const size_t o_gq = cb(S * T * GB * sizeof(double));
-  const size_t o_gt = cb(S * T * GB * sizeof(int));
-  const size_t o_vec = cb(S * T * VP * F * sizeof(double));
-  const size_t o_vecn = cb(S * T * VP * F * sizeof(double));
-  const size_t o_vden = cb(S * T * VP * sizeof(double));
-  const size_t o_vwn = cb(S * T * VP * sizeof(double));
-  const size_t o_sq = cb((S + 1) * SQS * sizeof(int));
-  const size_t o_sqd = cb((S + 1) * 2 * sizeof(double));
-  const size_t o_ord = cb(S * T * sizeof(int));
-  const size_t o_lost = cb(S * LOSTN * sizeof(int));
-  const size_t o_nnl = cb(S * T * sizeof(int));
-  const size_t o_pk = cb(S * (T + 3) * sizeof(int));
-  const size_t o_nnd = cb(S * T * D * sizeof(double));
-  const size_t o_prep = cb(S * D * 4 * sizeof(double));
-  const size_t o_dn = cb(S * D * F * sizeof(double));
-  const size_t o_nf = cb(S * D * F * sizeof(double));
-  const size_t o_rec = cb(S * LOSTN * D * sizeof(double));
-  const size_t o_cost = cb(S * 4 * T * D * sizeof(double));
-  const size_t o_cfull = cb(S * T * D * sizeof(double));
-  const size_t o_cfullT = cb(S * T * D * sizeof(double));
-  const size_t o_tlist = cb(S * T * SS_TL * sizeof(int16_t));
-  const size_t o_tcnt = cb(S * T * sizeof(int));
-  const size_t o_crank = cb(S * T * sizeof(int));
-  const size_t o_ckey = cb(S * T * sizeof(double));
-  const size_t o_ctsu = cb(S * T * sizeof(int));
-  const size_t o_cpos = cb(S * T * sizeof(int));
-  const size_t o_ncf = cb(S * sizeof(int));
-  const size_t o_fdt = cb(S * D * DTW * sizeof(double));
-  const size_t o_fdord = cb(S * D * sizeof(int));
-  const size_t o_faud = cb(S * D * sizeof(int));
-  const size_t o_fmt = cb(S * 4 * (D + 2) * sizeof(int));
-  const size_t o_ffut = cb(S * 3 * T * sizeof(int));
-  const size_t o_wsi = cb(S * (size_t)d.wsi_n * sizeof(int));
-  const size_t o_wsd = cb(S * (size_t)d.wsd_n * sizeof(double));
-  const size_t o_st = cb(sizeof(int) * 4);
+  // everything that can fail runs in `fill`: a failure frees what was allocated so far
+  auto fill = [&]() -> int {
+    SsDev& d = e->dev;
+    d.S = c->n_seq;
+    d.T = c->track_cap;
+    d.D = c->det_cap;
+    d.F = c->emb_dim;
+    d.VP = vp;
+    const int crowd_budget = c->nn_budget * 2 < 300 ? c->nn_budget * 2 : 300;
+    // partial_fit appends a track's <= MAXF features before truncating to the budget
+    d.GB = (c->nn_budget > crowd_budget ? c->nn_budget : crowd_budget) + MAXF;
+    if (d.GB > GB_MAX)
+      return bx_record_error(BX_ERR_INVALID, "nn_budget too large (gallery > 320 entries)");
+    d.N = 2 * d.T > d.D ? 2 * d.T : d.D;
+    d.min_conf = c->min_conf;
+    d.max_iou = c->max_iou_dist;
+    d.mc_lambda = c->mc_lambda;
+    d.ema_alpha = c->ema_alpha;
+    d.thi = c->conf_thresh_high;
+    d.tlo = c->conf_thresh_low;
+    d.idw = c->id_preservation_weight;
+    d.n_init = c->n_init;
+    d.crowd = c->crowd_detection != 0;
+    d.born = c->born_confirmed != 0;
+    d.wsi_n = ws_ints(d.T, d.D, d.N);
+    d.wsd_n = ws_doubles(d.T, d.D, d.N);
+    // the frame kernel's workspace in LDS when it fits beside ~3 other workgroups per CU
+    const size_t ws_bytes = (size_t)d.wsd_n * 8 + (size_t)d.wsi_n * 4;
+    // all of it in LDS when it fits beside ~3 other workgroups per CU; else the LSAP state alone
+    // (the solver's inner loops; track_cap, det_cap <= 1024 keep it within 106 KB)
+    d.ws_lds = ws_bytes <= 48 * 1024 ? 1 : 2;
+    d.lsap_fast = 1;
+    const size_t S = d.S, T = d.T, D = d.D, F = d.F, VP = d.VP, GB = d.GB;
+    BxCarve cb;
+    const size_t o_trk = cb(S * T * sizeof(SsTrk));
+    const size_t o_gv = cb(S * T * GB * sizeof(int));
+    const size_t o_gq = cb(S * T * GB * sizeof(double));
+    const size_t o_gt = cb(S * T * GB * sizeof(int));
+    const size_t o_vec = cb(S * T * VP * F * sizeof(double));
+    const size_t o_vecn = cb(S * T * VP * F * sizeof(double));
+    const size_t o_vden = cb(S * T * VP * sizeof(double));
+    const size_t o_vwn = cb(S * T * VP * sizeof(double));
+    const size_t o_sq = cb((S + 1) * SQS * sizeof(int));
+    const size_t o_sqd = cb((S + 1) * 2 * sizeof(double));
+    const size_t o_ord = cb(S * T * sizeof(int));
+    const size_t o_lost = cb(S * LOSTN * sizeof(int));
+    const size_t o_nnl = cb(S * T * sizeof(int));
+    const size_t o_pk = cb(S * (T + 3) * sizeof(int));
+    const size_t o_nnd = cb(S * T * D * sizeof(double));
+    const size_t o_prep = cb(S * D * 4 * sizeof(double));
+    const size_t o_dn = cb(S * D * F * sizeof(double));
+    const size_t o_nf = cb(S * D * F * sizeof(double));
+    const size_t o_rec = cb(S * LOSTN * D * sizeof(double));
+    const size_t o_cost = cb(S * 4 * T * D * sizeof(double));
+    const size_t o_cfull = cb(S * T * D * sizeof(double));
+    const size_t o_cfullT = cb(S * T * D * sizeof(double));
+    const size_t o_tlist = cb(S * T * SS_TL * sizeof(int16_t));
+    const size_t o_tcnt = cb(S * T * sizeof(int));
+    const size_t o_crank = cb(S * T * sizeof(int));
+    const size_t o_ckey = cb(S * T * sizeof(double));
+    const size_t o_ctsu = cb(S * T * sizeof(int));
+    const size_t o_cpos = cb(S * T * sizeof(int));
+    const size_t o_ncf = cb(S * sizeof(int));
+    const size_t o_fdt = cb(S * D * DTW * sizeof(double));
+    const size_t o_fdord = cb(S * D * sizeof(int));
+    const size_t o_faud = cb(S * D * sizeof(int));
+    const size_t o_fmt = cb(S * 4 * (D + 2) * sizeof(int));
+    const size_t o_ffut = cb(S * 3 * T * sizeof(int));
+    const size_t o_wsi = cb(S * (size_t)d.wsi_n * sizeof(int));
+    const size_t o_wsd = cb(S * (size_t)d.wsd_n * sizeof(double));
+    const size_t o_st = cb(sizeof(int) * 4);
 #ifdef BX_PHASE_TIMING
-  const size_t o_dbg = cb(S * SS_DBG * sizeof(unsigned long long));
+    const size_t o_dbg = cb(S * SS_DBG * sizeof(unsigned long long));
 #endif
-  if (hipMalloc(&e->arena, off) != hipSuccess) {
-    delete e;
-    return bx_record_error(BX_ERR_HIP, "hipMalloc of the StrongSort arena failed");
-  }
-  SCHK(hipMemset(e->arena, 0, off));
-  char* base = (char*)e->arena;
-  d.trk = (SsTrk*)(base + o_trk);
-  d.gal_v = (int*)(base + o_gv);
-  d.gal_q = (double*)(base + o_gq);
-  d.gal_t = (int*)(base + o_gt);
-  d.vec = (double*)(base + o_vec);
-  d.vecn = (double*)(base + o_vecn);
-  d.vden = (double*)(base + o_vden);
-  d.vwn = (double*)(base + o_vwn);
-  d.sq = (int*)(base + o_sq);
-  d.sqd = (double*)(base + o_sqd);
-  d.order = (int*)(base + o_ord);
-  d.lost = (int*)(base + o_lost);
-  d.nnl = (int*)(base + o_nnl);
-  d.pk = (int*)(base + o_pk);
-  d.nnd = (double*)(base + o_nnd);
-  d.dprep = (double*)(base + o_prep);
-  d.dn = (double*)(base + o_dn);
-  d.nf = (double*)(base + o_nf);
-  d.recsim = (double*)(base + o_rec);
-  d.cost = (double*)(base + o_cost);
-  d.cfull = (double*)(base + o_cfull);
-  d.cfullT = (double*)(base + o_cfullT);
-  d.tlist = (int16_t*)(base + o_tlist);
-  d.tcnt = (int*)(base + o_tcnt);
-  d.crank = (int*)(base + o_crank);
-  d.ckey = (double*)(base + o_ckey);
-  d.ctsu = (int*)(base + o_ctsu);
-  d.cpos = (int*)(base + o_cpos);
-  d.ncf = (int*)(base + o_ncf);
-  d.fdt = (double*)(base + o_fdt);
-  d.fdord = (int*)(base + o_fdord);
-  d.faud = (int*)(base + o_faud);
-  d.fmt = (int*)(base + o_fmt);
-  d.ffut = (int*)(base + o_ffut);
-  d.wsi = (int*)(base + o_wsi);
-  d.wsd = (double*)(base + o_wsd);
-  d.status = (int*)(base + o_st);
+    if (hipMalloc(&e->arena, cb.off) != hipSuccess)
+      return bx_record_error(BX_ERR_HIP, "hipMalloc of the StrongSort arena failed");
+    BX_HIPCHK(hipMemset(e->arena, 0, cb.off));
+    char* base = (char*)e->arena;
+    d.trk = (SsTrk*)(base + o_trk);
+    d.gal_v = (int*)(base + o_gv);
+    d.gal_q = (double*)(base + o_gq);
+    d.gal_t = (int*)(base + o_gt);
+    d.vec = (double*)(base + o_vec);
+    d.vecn = (double*)(base + o_vecn);
+    d.vden = (double*)(base + o_vden);
+    d.vwn = (double*)(base + o_vwn);
+    d.sq = (int*)(base + o_sq);
+    d.sqd = (double*)(base + o_sqd);
+    d.order = (int*)(base + o_ord);
+    d.lost = (int*)(base + o_lost);
+    d.nnl = (int*)(base + o_nnl);
+    d.pk = (int*)(base + o_pk);
+    d.nnd = (double*)(base + o_nnd);
+    d.dprep = (double*)(base + o_prep);
+    d.dn = (double*)(base + o_dn);
+    d.nf = (double*)(base + o_nf);
+    d.recsim = (double*)(base + o_rec);
+    d.cost = (double*)(base + o_cost);
+    d.cfull = (double*)(base + o_cfull);
+    d.cfullT = (double*)(base + o_cfullT);
+    d.tlist = (int16_t*)(base + o_tlist);
+    d.tcnt = (int*)(base + o_tcnt);
+    d.crank = (int*)(base + o_crank);
+    d.ckey = (double*)(base + o_ckey);
+    d.ctsu = (int*)(base + o_ctsu);
+    d.cpos = (int*)(base + o_cpos);
+    d.ncf = (int*)(base + o_ncf);
+    d.fdt = (double*)(base + o_fdt);
+    d.fdord = (int*)(base + o_fdord);
+    d.faud = (int*)(base + o_faud);
+    d.fmt = (int*)(base + o_fmt);
+    d.ffut = (int*)(base + o_ffut);
+    d.wsi = (int*)(base + o_wsi);
+    d.wsd = (double*)(base + o_wsd);
+    d.status = (int*)(base + o_st);
 #ifdef BX_PHASE_TIMING
-  d.dbg = (unsigned long long*)(base + o_dbg);
+    d.dbg = (unsigned long long*)(base + o_dbg);
 #else
-  d.dbg = nullptr;
+    d.dbg = nullptr;
 #endif
-  // per-sequence defaults (row S holds them for bx_ss_reset): max_age, budget, threshold
-  std::vector<int> q((S + 1) * SQS, 0);
-  std::vector<double> qd((S + 1) * 2, c->max_cos_dist);
-  for (size_t k = 0; k < S; k++) {
-    q[k * SQS + Q_NEXTID] = 1;
-    q[k * SQS + Q_MAXAGE] = c->max_age;
-    q[k * SQS + Q_BUDGET] = c->nn_budget;
+    // per-sequence defaults (row S holds them for bx_ss_reset): max_age, budget, threshold
+    std::vector<int> q((S + 1) * SQS, 0);
+    std::vector<double> qd((S + 1) * 2, c->max_cos_dist);
+    for (size_t k = 0; k < S; k++) {
+      q[k * SQS + Q_NEXTID] = 1;
+      q[k * SQS + Q_MAXAGE] = c->max_age;
+      q[k * SQS + Q_BUDGET] = c->nn_budget;
+    }
+    q[S * SQS + 0] = c->max_age;
+    q[S * SQS + 1] = c->nn_budget;
+    BX_HIPCHK(hipMemcpy(d.sq, q.data(), q.size() * sizeof(int), hipMemcpyHostToDevice));
+    BX_HIPCHK(hipMemcpy(d.sqd, qd.data(), qd.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (d.ws_lds) {
+      const int lds = (int)ss_lds_bytes(d);
+      BX_HIPCHK(bx_lds_attr((const void*)ss_pre_kernel, lds));
+      BX_HIPCHK(bx_lds_attr((const void*)ss_match_kernel, lds));
+      BX_HIPCHK(bx_lds_attr((const void*)ss_post_kernel, lds));
+    }
+    BX_HIPCHK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
+    BX_HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
+    BX_HIPCHK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
+    return e->sg.alloc(sizeof(double) * 6 * D, sizeof(double) * D * F, 8, 10, d.D, SQS);
+  };
+  const int rc = fill();
+  if (rc) {
+    bx_ss_destroy(e);
+    return rc;
   }
-  q[S * SQS + 0] = c->max_age;
-  q[S * SQS + 1] = c->nn_budget;
-  SCHK(hipMemcpy(d.sq, q.data(), q.size() * sizeof(int), hipMemcpyHostToDevice));
-  SCHK(hipMemcpy(d.sqd, qd.data(), qd.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (d.ws_lds) {
-    const int lds = (int)ss_lds_bytes(d);
-    SCHK(bx_lds_attr((const void*)ss_pre_kernel, lds));
-    SCHK(bx_lds_attr((const void*)ss_match_kernel, lds));
-    SCHK(bx_lds_attr((const void*)ss_post_kernel, lds));
-  }
-  SCHK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-  SCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-  SCHK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-  SCHK(hipMalloc(&e->h_dets, sizeof(double) * 6 * D));
-  SCHK(hipMalloc(&e->h_off, sizeof(int) * 2));
-  SCHK(hipMalloc(&e->h_embs, sizeof(double) * D * F));
-  SCHK(hipMalloc(&e->h_warp, sizeof(double) * 6));
-  SCHK(hipMalloc(&e->h_out, sizeof(double) * 10 * D));
-  SCHK(hipMalloc(&e->h_cnt, sizeof(int)));
-  SCHK(hipHostMalloc(&e->p_dets, sizeof(double) * 6 * d.D));
-  SCHK(hipHostMalloc(&e->p_embs, sizeof(double) * (size_t)d.D * d.F));
-  SCHK(hipHostMalloc(&e->p_warp, sizeof(double) * 8));
-  SCHK(hipHostMalloc(&e->p_out, sizeof(double) * 10 * d.D));
-  SCHK(hipHostMalloc(&e->p_cnt, sizeof(int) * 4));
-  SCHK(hipHostMalloc(&e->p_sq, sizeof(int) * SQS));
   *out = e;
   return BX_OK;
 }
@@ -3841,7 +3795,7 @@ int bx_ss_copy_state(bx_ss* dst, bx_ss* src) {
     return bx_record_error(BX_ERR_INVALID, "bx_ss_copy_state: destination must match the "
                                            "source's sequences, features, vector pool and budget "
                                            "and have at least its capacities");
-  SCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   const size_t S = a.S, Ta = a.T, Tb = b.T, F = a.F, VP = a.VP, GB = a.GB;
   auto rows = [&](void* d, const void* s_, size_t per_slot) -> hipError_t {
     return hipMemcpy2D(d, Tb * per_slot, s_, Ta * per_slot, Ta * per_slot, S,
@@ -3849,23 +3803,23 @@ int bx_ss_copy_state(bx_ss* dst, bx_ss* src) {
   };
   // per-slot state: track records, galleries (entries, qualities, times), the vector pools and
   // their norms, the list order and the next frame's query list
-  SCHK(rows(b.trk, a.trk, sizeof(SsTrk)));
-  SCHK(rows(b.gal_v, a.gal_v, GB * sizeof(int)));
-  SCHK(rows(b.gal_q, a.gal_q, GB * sizeof(double)));
-  SCHK(rows(b.gal_t, a.gal_t, GB * sizeof(int)));
-  SCHK(rows(b.vec, a.vec, VP * F * sizeof(double)));
-  SCHK(rows(b.vecn, a.vecn, VP * F * sizeof(double)));
-  SCHK(rows(b.vden, a.vden, VP * sizeof(double)));
-  SCHK(rows(b.vwn, a.vwn, VP * sizeof(double)));
-  SCHK(rows(b.order, a.order, sizeof(int)));
-  SCHK(rows(b.nnl, a.nnl, sizeof(int)));
+  BX_HIPCHK(rows(b.trk, a.trk, sizeof(SsTrk)));
+  BX_HIPCHK(rows(b.gal_v, a.gal_v, GB * sizeof(int)));
+  BX_HIPCHK(rows(b.gal_q, a.gal_q, GB * sizeof(double)));
+  BX_HIPCHK(rows(b.gal_t, a.gal_t, GB * sizeof(int)));
+  BX_HIPCHK(rows(b.vec, a.vec, VP * F * sizeof(double)));
+  BX_HIPCHK(rows(b.vecn, a.vecn, VP * F * sizeof(double)));
+  BX_HIPCHK(rows(b.vden, a.vden, VP * sizeof(double)));
+  BX_HIPCHK(rows(b.vwn, a.vwn, VP * sizeof(double)));
+  BX_HIPCHK(rows(b.order, a.order, sizeof(int)));
+  BX_HIPCHK(rows(b.nnl, a.nnl, sizeof(int)));
   // per-sequence scalars (+ the defaults row S), the lost buffer (slot ids), status
-  SCHK(hipMemcpy(b.sq, a.sq, (S + 1) * SQS * sizeof(int), hipMemcpyDeviceToDevice));
-  SCHK(hipMemcpy(b.sqd, a.sqd, (S + 1) * 2 * sizeof(double), hipMemcpyDeviceToDevice));
-  SCHK(hipMemcpy(b.lost, a.lost, S * LOSTN * sizeof(int), hipMemcpyDeviceToDevice));
-  SCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.sq, a.sq, (S + 1) * SQS * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.sqd, a.sqd, (S + 1) * 2 * sizeof(double), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.lost, a.lost, S * LOSTN * sizeof(int), hipMemcpyDeviceToDevice));
+  BX_HIPCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
   dst->cache_seq = -1;
-  SCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   return BX_OK;
 }
 
@@ -3874,23 +3828,9 @@ int bx_ss_destroy(bx_ss* e) {
   if (e->side) (void)hipStreamDestroy(e->side);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-  for (auto& p : e->ev) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->h_dets);
-  (void)hipFree(e->h_off);
-  (void)hipFree(e->h_embs);
-  (void)hipFree(e->h_warp);
-  (void)hipFree(e->h_out);
-  (void)hipFree(e->h_cnt);
-  (void)hipHostFree(e->p_dets);
-  (void)hipHostFree(e->p_embs);
-  (void)hipHostFree(e->p_warp);
-  (void)hipHostFree(e->p_out);
-  (void)hipHostFree(e->p_cnt);
-  (void)hipHostFree(e->p_sq);
+  e->sg.free();
   delete e;
   return BX_OK;
 }
@@ -3902,7 +3842,7 @@ int bx_ss_reset(bx_ss* e, int seq0, int nseq, void* stream) {
   e->cache_seq = -1;
   hipLaunchKernelGGL(ss_reset_kernel, dim3((nseq + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      e->dev, seq0, nseq);
-  SCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
@@ -3923,33 +3863,22 @@ int bx_ss_update_host(bx_ss* e, int seq, const double* dets, int n, const double
   hipStream_t st = (hipStream_t)stream;
   // pinned mirrors: asynchronous copies in, the frame, rows (at most n) + count + status +
   // counters back, one synchronisation
-  if (n) {
-    memcpy(e->p_dets, dets, sizeof(double) * 6 * n);
-    memcpy(e->p_embs, embs, sizeof(double) * (size_t)n * e->dev.F);
-    SCHK(hipMemcpyAsync(e->h_dets, e->p_dets, sizeof(double) * 6 * n, hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(e->h_embs, e->p_embs, sizeof(double) * (size_t)n * e->dev.F,
-                        hipMemcpyHostToDevice, st));
-  }
-  if (warp) {
-    memcpy(e->p_warp, warp, sizeof(double) * 6);
-    SCHK(hipMemcpyAsync(e->h_warp, e->p_warp, sizeof(double) * 6, hipMemcpyHostToDevice, st));
-  }
-  e->p_cnt[2] = 0;
-  e->p_cnt[3] = n;
-  SCHK(hipMemcpyAsync(e->h_off, e->p_cnt + 2, sizeof(int) * 2, hipMemcpyHostToDevice, st));
+  BxStaging& sg = e->sg;
+  int rc;
+  if (n && ((rc = sg.put(sg.h_dets, sg.p_dets, dets, sizeof(double) * 6 * n, st)) ||
+            (rc = sg.put(sg.h_embs, sg.p_embs, embs, sizeof(double) * (size_t)n * e->dev.F, st))))
+    return rc;
+  if (warp && (rc = sg.put(sg.h_warp, sg.p_warp, warp, sizeof(double) * 6, st))) return rc;
+  if ((rc = sg.put_off(n, st))) return rc;
   e->cache_seq = -1;
-  int rc = ss_launch(e, seq, 1, e->h_dets, e->h_off, e->h_embs, warp ? e->h_warp : nullptr,
-                     e->h_out, e->h_cnt, st);
+  rc = ss_launch(e, seq, 1, (double*)sg.h_dets, sg.h_off, (double*)sg.h_embs,
+                 warp ? sg.h_warp : nullptr, sg.h_out, sg.h_cnt, st);
   if (rc) return rc;
-  SCHK(hipMemcpyAsync(e->p_cnt, e->h_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  SCHK(hipMemcpyAsync(e->p_cnt + 1, e->dev.status, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (n) SCHK(hipMemcpyAsync(e->p_out, e->h_out, sizeof(double) * 10 * n, hipMemcpyDeviceToHost, st));
-  SCHK(hipMemcpyAsync(e->p_sq, e->dev.sq + (size_t)seq * SQS, sizeof(int) * SQS,
-                      hipMemcpyDeviceToHost, st));
-  SCHK(hipStreamSynchronize(st));
-  const int cnt = e->p_cnt[0], status = e->p_cnt[1];
+  if ((rc = sg.take(e->dev.status, e->dev.sq + (size_t)seq * SQS, n, st))) return rc;
+  BX_HIPCHK(hipStreamSynchronize(st));
+  const int cnt = sg.p_cnt[0], status = sg.p_cnt[1];
   e->cache_seq = seq;
-  if (cnt) memcpy(out, e->p_out, sizeof(double) * 10 * cnt);
+  if (cnt) memcpy(out, sg.p_out, sizeof(double) * 10 * cnt);
   *n_out = cnt;
   if (status) return bx_record_error(status, "StrongSort engine status latched (see bx_ss_status)");
   return BX_OK;
@@ -3957,7 +3886,7 @@ int bx_ss_update_host(bx_ss* e, int seq, const double* dets, int n, const double
 
 int bx_ss_status(bx_ss* e, int* status) {
   if (!e || !status) return bx_record_error(BX_ERR_INVALID, "null argument");
-  SCHK(hipMemcpy(status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
@@ -3966,10 +3895,10 @@ int bx_ss_counters_host(bx_ss* e, int seq, int* frame_count, int* next_id, int* 
   if (!e || seq < 0 || seq >= e->dev.S) return bx_record_error(BX_ERR_INVALID, "bad sequence");
   int s[SQS];
   if (seq == e->cache_seq) {
-    memcpy(s, e->p_sq, sizeof(s));
+    memcpy(s, e->sg.p_sq, sizeof(s));
   } else {
-    SCHK(hipDeviceSynchronize());
-    SCHK(hipMemcpy(s, e->dev.sq + (size_t)seq * SQS, sizeof(s), hipMemcpyDeviceToHost));
+    BX_HIPCHK(hipDeviceSynchronize());
+    BX_HIPCHK(hipMemcpy(s, e->dev.sq + (size_t)seq * SQS, sizeof(s), hipMemcpyDeviceToHost));
   }
   if (frame_count) *frame_count = s[Q_FRAME];
   if (next_id) *next_id = s[Q_NEXTID];
@@ -3982,17 +3911,17 @@ int bx_ss_tracks_host(bx_ss* e, int seq, int cap, int32_t* ids, int32_t* state, 
                       double* cov, int* n) {
   if (!e || seq < 0 || seq >= e->dev.S || cap < 0 || !n)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ss_tracks_host");
-  SCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   int s[SQS];
-  SCHK(hipMemcpy(s, e->dev.sq + (size_t)seq * SQS, sizeof(s), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(s, e->dev.sq + (size_t)seq * SQS, sizeof(s), hipMemcpyDeviceToHost));
   const int nt = s[Q_NTR];
   std::vector<int> ord(nt);
   if (nt)
-    SCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
+    BX_HIPCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
                    hipMemcpyDeviceToHost));
   for (int k = 0; k < nt && k < cap; k++) {
     SsTrk t;
-    SCHK(hipMemcpy(&t, e->dev.trk + (size_t)seq * e->dev.T + ord[k], sizeof(SsTrk),
+    BX_HIPCHK(hipMemcpy(&t, e->dev.trk + (size_t)seq * e->dev.T + ord[k], sizeof(SsTrk),
                    hipMemcpyDeviceToHost));
     if (ids) ids[k] = t.id;
     if (state) state[k] = t.state;
@@ -4005,15 +3934,15 @@ int bx_ss_tracks_host(bx_ss* e, int seq, int cap, int32_t* ids, int32_t* state, 
 
 // the sequence's track list (slots in list order) and its track records, one copy each
 static int ss_read_list(bx_ss* e, int seq, std::vector<int>& ord, std::vector<SsTrk>& trk) {
-  SCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   int s[SQS];
-  SCHK(hipMemcpy(s, e->dev.sq + (size_t)seq * SQS, sizeof(s), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(s, e->dev.sq + (size_t)seq * SQS, sizeof(s), hipMemcpyDeviceToHost));
   ord.assign(s[Q_NTR], 0);
   if (!ord.empty())
-    SCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * ord.size(),
+    BX_HIPCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * ord.size(),
                    hipMemcpyDeviceToHost));
   trk.resize(e->dev.T);
-  SCHK(hipMemcpy(trk.data(), e->dev.trk + (size_t)seq * e->dev.T, sizeof(SsTrk) * e->dev.T,
+  BX_HIPCHK(hipMemcpy(trk.data(), e->dev.trk + (size_t)seq * e->dev.T, sizeof(SsTrk) * e->dev.T,
                  hipMemcpyDeviceToHost));
   return BX_OK;
 }
@@ -4054,9 +3983,9 @@ int bx_ss_track_attrs_set_host(bx_ss* e, int seq, int n, const int32_t* ids, con
     const int k = ss_find(ord, trk, ids[j]);
     if (k < 0) return bx_record_error(BX_ERR_INVALID, "track_attrs_set: no live track with that id");
     SsTrk* dt = e->dev.trk + (size_t)seq * e->dev.T + k;
-    if (quality) SCHK(hipMemcpy(&dt->quality, quality + j, sizeof(double), hipMemcpyHostToDevice));
-    if (conf) SCHK(hipMemcpy(&dt->conf, conf + j, sizeof(double), hipMemcpyHostToDevice));
-    if (max_age) SCHK(hipMemcpy(&dt->max_age, max_age + j, sizeof(int), hipMemcpyHostToDevice));
+    if (quality) BX_HIPCHK(hipMemcpy(&dt->quality, quality + j, sizeof(double), hipMemcpyHostToDevice));
+    if (conf) BX_HIPCHK(hipMemcpy(&dt->conf, conf + j, sizeof(double), hipMemcpyHostToDevice));
+    if (max_age) BX_HIPCHK(hipMemcpy(&dt->max_age, max_age + j, sizeof(int), hipMemcpyHostToDevice));
   }
   return BX_OK;
 }
@@ -4073,7 +4002,7 @@ int bx_ss_last_feature_host(bx_ss* e, int seq, int n, const int32_t* ids, double
     if (k < 0 || trk[k].nfeat < 1)
       return bx_record_error(BX_ERR_INVALID, "last_feature: no live track with features and that id");
     const size_t vi = ((size_t)seq * e->dev.T + k) * e->dev.VP + trk[k].feat[trk[k].nfeat - 1];
-    SCHK(hipMemcpy(feats + (size_t)j * F, e->dev.vec + vi * F, sizeof(double) * F,
+    BX_HIPCHK(hipMemcpy(feats + (size_t)j * F, e->dev.vec + vi * F, sizeof(double) * F,
                    hipMemcpyDeviceToHost));
   }
   return BX_OK;
@@ -4097,18 +4026,18 @@ int bx_ss_last_feature_set_host(bx_ss* e, int seq, int n, const int32_t* ids, co
   }
   const int F = e->dev.F;
   void* buf = nullptr;
-  SCHK(hipMalloc(&buf, sizeof(int) * n + sizeof(double) * (size_t)n * F + 256));
+  BX_HIPCHK(hipMalloc(&buf, sizeof(int) * n + sizeof(double) * (size_t)n * F + 256));
   int* d_slots = (int*)buf;
   double* d_src = (double*)((char*)buf + ((sizeof(int) * n + 255) & ~(size_t)255));
-  SCHK(hipMemcpy(d_slots, slots.data(), sizeof(int) * n, hipMemcpyHostToDevice));
-  SCHK(hipMemcpy(d_src, feats, sizeof(double) * (size_t)n * F, hipMemcpyHostToDevice));
+  BX_HIPCHK(hipMemcpy(d_slots, slots.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+  BX_HIPCHK(hipMemcpy(d_src, feats, sizeof(double) * (size_t)n * F, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(ss_feat_set_kernel, dim3(n), dim3(64), 0, 0, e->dev, seq, d_slots, d_src,
                      normalize);
-  SCHK(hipGetLastError());
-  SCHK(hipDeviceSynchronize());
-  SCHK(hipFree(buf));
+  BX_HIPCHK(hipGetLastError());
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipFree(buf));
   int status = 0;
-  SCHK(hipMemcpy(&status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(&status, e->dev.status, sizeof(int), hipMemcpyDeviceToHost));
   if (status) return bx_record_error(status, "a track's feature pool is exhausted (raise vec_cap)");
   return BX_OK;
 }
@@ -4117,26 +4046,26 @@ int bx_ss_state_set_host(bx_ss* e, int seq, int n, const int32_t* ids, const dou
                          const double* cov) {
   if (!e || seq < 0 || seq >= e->dev.S || n < 0 || (n && !ids))
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ss_state_set_host");
-  SCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   int s[SQS];
-  SCHK(hipMemcpy(s, e->dev.sq + (size_t)seq * SQS, sizeof(s), hipMemcpyDeviceToHost));
+  BX_HIPCHK(hipMemcpy(s, e->dev.sq + (size_t)seq * SQS, sizeof(s), hipMemcpyDeviceToHost));
   const int nt = s[Q_NTR];
   std::vector<int> ord(nt);
   if (nt)
-    SCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
+    BX_HIPCHK(hipMemcpy(ord.data(), e->dev.order + (size_t)seq * e->dev.T, sizeof(int) * nt,
                    hipMemcpyDeviceToHost));
   for (int j = 0; j < n; j++) {
     SsTrk* dt = nullptr;
     SsTrk t;
     for (int k = 0; k < nt && !dt; k++) {
       SsTrk* cand = e->dev.trk + (size_t)seq * e->dev.T + ord[k];
-      SCHK(hipMemcpy(&t, cand, sizeof(SsTrk), hipMemcpyDeviceToHost));
+      BX_HIPCHK(hipMemcpy(&t, cand, sizeof(SsTrk), hipMemcpyDeviceToHost));
       if (t.id == ids[j]) dt = cand;
     }
     if (!dt) return bx_record_error(BX_ERR_INVALID, "state_set: no live track with that id");
     if (mean) memcpy(t.mean, mean + 8 * j, sizeof(t.mean));
     if (cov) memcpy(t.cov, cov + 64 * j, sizeof(t.cov));
-    SCHK(hipMemcpy(dt, &t, sizeof(SsTrk), hipMemcpyHostToDevice));
+    BX_HIPCHK(hipMemcpy(dt, &t, sizeof(SsTrk), hipMemcpyHostToDevice));
   }
   return BX_OK;
 }
@@ -4146,16 +4075,16 @@ int bx_ss_lsap_op(const double* cost, int R, int CC, double max_d, int fast, int
   if (R < 1 || R > CC || CC > 1024 || !info || !status)
     return bx_record_error(BX_ERR_INVALID, "bx_ss_lsap_op: 1 <= R <= CC <= 1024");
   const size_t lds = (size_t)3 * CC * 8 + (size_t)11 * CC * 4;
-  SCHK(bx_lds_attr((const void*)ss_lsap_op_kernel, lds));
+  BX_HIPCHK(bx_lds_attr((const void*)ss_lsap_op_kernel, lds));
   hipLaunchKernelGGL(ss_lsap_op_kernel, dim3(1), dim3(64), lds, (hipStream_t)stream, cost, R, CC,
                      max_d, fast, rows, cols, info, status);
-  SCHK(hipGetLastError());
+  BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
 
 int bx_ss_set_lsap_mode(bx_ss* e, int fast) {
   if (!e || fast < 0 || fast > 1) return bx_record_error(BX_ERR_INVALID, "bad lsap mode");
-  SCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   e->dev.lsap_fast = fast;
   return BX_OK;
 }
@@ -4164,9 +4093,9 @@ int bx_ss_lsap_stats_host(bx_ss* e, int seq0, int nseq, int64_t* sums) {
   if (!e || !sums || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.S)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ss_lsap_stats_host");
   std::vector<int> s((size_t)nseq * SQS);
-  SCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   if (nseq)
-    SCHK(hipMemcpy(s.data(), e->dev.sq + (size_t)seq0 * SQS, sizeof(int) * s.size(),
+    BX_HIPCHK(hipMemcpy(s.data(), e->dev.sq + (size_t)seq0 * SQS, sizeof(int) * s.size(),
                    hipMemcpyDeviceToHost));
   for (int k = 0; k < 5; k++) sums[k] = 0;
   for (int k = 0; k < nseq; k++) {
@@ -4184,9 +4113,9 @@ int bx_ss_frame_stats_host(bx_ss* e, int seq0, int nseq, int64_t* sums) {
   if (!e || !sums || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.S)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ss_frame_stats_host");
   std::vector<int> s((size_t)nseq * SQS);
-  SCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipDeviceSynchronize());
   if (nseq)
-    SCHK(hipMemcpy(s.data(), e->dev.sq + (size_t)seq0 * SQS, sizeof(int) * s.size(),
+    BX_HIPCHK(hipMemcpy(s.data(), e->dev.sq + (size_t)seq0 * SQS, sizeof(int) * s.size(),
                    hipMemcpyDeviceToHost));
   int64_t a[7] = {0, 0, 0, 0, 0, 0, 0};
   for (int k = 0; k < nseq; k++) {
@@ -4205,33 +4134,22 @@ int bx_ss_frame_stats_host(bx_ss* e, int seq0, int nseq, int64_t* sums) {
 
 int bx_ss_probe(bx_ss* e, int stage) {
   if (!e) return bx_record_error(BX_ERR_INVALID, "null engine");
-  e->probe_stage = stage;
-  e->ev_used = 0;
+  e->probe.set(stage);
   return BX_OK;
 }
 
 // Diagnostic (timing builds only; not in the public header): copies [S][32] phase counters.
 int bx_ss_debug_host(bx_ss* e, unsigned long long* out) {
   if (!e || !out || !e->dev.dbg) return bx_record_error(BX_ERR_INVALID, "not a timing build");
-  SCHK(hipDeviceSynchronize());
-  SCHK(hipMemcpy(out, e->dev.dbg, sizeof(unsigned long long) * SS_DBG * e->dev.S,
+  BX_HIPCHK(hipDeviceSynchronize());
+  BX_HIPCHK(hipMemcpy(out, e->dev.dbg, sizeof(unsigned long long) * SS_DBG * e->dev.S,
                  hipMemcpyDeviceToHost));
   return BX_OK;
 }
 
 int bx_ss_probe_read(bx_ss* e, double* total_ms, int* count) {
   if (!e || !total_ms || !count) return bx_record_error(BX_ERR_INVALID, "null argument");
-  double s = 0.0;
-  for (int k = 0; k < e->ev_used; k++) {
-    SCHK(hipEventSynchronize(e->ev[k].second));
-    float ms = 0.f;
-    SCHK(hipEventElapsedTime(&ms, e->ev[k].first, e->ev[k].second));
-    s += ms;
-  }
-  *total_ms = s;
-  *count = e->ev_used;
-  e->ev_used = 0;
-  return BX_OK;
+  return e->probe.read(total_ms, count);
 }
 
 }  // extern "C"

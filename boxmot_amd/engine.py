@@ -36,7 +36,104 @@ class EngineParams:
     with_reid: bool = True
 
 
-class Engine:
+class _NativeHandle:
+    """A handle over a ``<prefix>_*`` family of the C ABI: its life and its status."""
+
+    _PREFIX = ""   # "bx_ocsort", ...: every entry point of the family is <prefix>_<name>
+
+    def _fn(self, name):
+        return getattr(self._L, f"{self._PREFIX}_{name}")
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._fn("destroy")(h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def status(self) -> int:
+        s = C.c_int(0)
+        N.check(self._fn("status")(self._h, C.byref(s)), f"{self._PREFIX}_status")
+        return s.value
+
+
+class _NativeEngine(_NativeHandle):
+    """What the six tracker engines share on top: create, the sequence-range / stream preamble
+    of ``step``, reset and the timing probe.  A class whose C signature or returned keys differ
+    keeps its own method."""
+
+    STAGES: list = []  # the probe's stage names, in the C stage order
+
+    def _create(self, cfg) -> None:
+        self._L = N.load()
+        h = C.c_void_p()
+        N.check(self._fn("create")(C.byref(cfg), C.byref(h)), f"{self._PREFIX}_create")
+        self._h = h
+
+    def _range(self, seq0, nseq, stream):
+        """(nseq, stream) with their defaults: every sequence from seq0, the current stream."""
+        return (self.n_seq - seq0 if nseq is None else nseq,
+                _current_stream() if stream is None else stream)
+
+    def reset(self, seq0: int = 0, nseq: int | None = None, stream=None):
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        N.check(self._fn("reset")(self._h, seq0, nseq, stream), f"{self._PREFIX}_reset")
+
+    def slots_used(self, seq: int = 0) -> int:
+        return self.counters(seq)["n_tracks"]
+
+    def probe(self, stage) -> None:
+        """Time every launch of one stage with HIP events (name from STAGES or index);
+        None/-1 = off."""
+        idx = -1 if stage is None else (self.STAGES.index(stage) if isinstance(stage, str)
+                                        else int(stage))
+        N.check(self._fn("probe")(self._h, idx), f"{self._PREFIX}_probe")
+
+    def probe_read(self):
+        """(total ms, launches) of the probed stage since the last read."""
+        t, n = C.c_double(), C.c_int()
+        N.check(self._fn("probe_read")(self._h, C.byref(t), C.byref(n)), "probe_read")
+        return t.value, n.value
+
+
+class _TrackListEngine(_NativeEngine):
+    """The engines whose counter row is (frame_count, id_count, n_tracks): OCSort's family and
+    BoostTrack."""
+
+    def counters(self, seq: int = 0) -> dict:
+        fc, idc, nt = C.c_int(), C.c_int(), C.c_int()
+        N.check(self._fn("counters_host")(self._h, seq, C.byref(fc), C.byref(idc), C.byref(nt)),
+                "counters")
+        return {"frame_count": fc.value, "id_count": idc.value, "n_tracks": nt.value}
+
+    def set_id_count(self, seq: int, value: int):
+        N.check(self._fn("set_id_count")(self._h, seq, int(value), None), "set_id_count")
+
+
+class _OcsFamilyEngine(_TrackListEngine):
+    """OCSort, DeepOCSort and HybridSort: the per-sequence frame size of the centroid mode and
+    the three-number frame statistics."""
+
+    def set_frame_size(self, seq: int, w: float, h: float):
+        N.check(self._fn("set_frame_size")(self._h, seq, float(w), float(h), None),
+                "set_frame_size")
+
+    def frame_stats(self, seq0: int = 0, nseq: int | None = None) -> dict:
+        """Last frame over sequences [seq0, seq0+nseq): live tracks, output rows, frame."""
+        nseq = self.n_seq - seq0 if nseq is None else nseq
+        a = (C.c_int64 * 3)()
+        N.check(self._fn("frame_stats_host")(self._h, seq0, nseq, a), "frame_stats")
+        return dict(zip(["tracks", "outputs", "frame"], [int(x) for x in a]))
+
+
+class Engine(_NativeEngine):
+    _PREFIX = "bx_engine"
+
     def __init__(self, kind: str, n_seq: int = 1, track_cap: int = 1024, det_cap: int = 384,
                  emb_dim: int = 0, emb_f64: bool = False, params: EngineParams | None = None):
         if kind not in KINDS:
@@ -56,25 +153,10 @@ class Engine:
             new_track_thresh=p.new_track_thresh, proximity_thresh=p.proximity_thresh,
             appearance_thresh=p.appearance_thresh,
             fuse_first_associate=int(bool(p.fuse_first_associate)), with_reid=int(self.with_reid))
-        self._L = N.load()
         self._overlap, self._inflight = False, None
-        h = C.c_void_p()
-        N.check(self._L.bx_engine_create(C.byref(cfg), C.byref(h)), "bx_engine_create")
-        self._h = h
+        self._create(cfg)
 
     # ----------------------------------------------------------------------------- lifecycle
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.bx_engine_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def reset(self, seq0: int = 0, nseq: int | None = None, stream: int | None = None):
         nseq = self.n_seq - seq0 if nseq is None else nseq
         N.check(self._L.bx_engine_reset(self._h, seq0, nseq, stream), "bx_engine_reset")
@@ -87,10 +169,8 @@ class Engine:
         dets [sum N,6] float32, det_off [nseq+1] int32, embs [sum N,F] float32/64 or None,
         warps [nseq,6] float64 or None, out [sum N,8] float64, out_count [nseq] int32.
         """
-        nseq = self.n_seq - seq0 if nseq is None else nseq
+        nseq, stream = self._range(seq0, nseq, stream)
         ptr = _ptr
-        if stream is None:
-            stream = _current_stream()
         N.check(self._L.bx_engine_step(self._h, seq0, nseq, ptr(dets), ptr(det_off), ptr(embs),
                                        ptr(warps), ptr(out), ptr(out_count), stream),
                 "bx_engine_step")
@@ -195,18 +275,8 @@ class Engine:
         return out[: m.value].copy()
 
     # ---------------------------------------------------------------------------- state I/O
-    def status(self) -> int:
-        s = C.c_int(0)
-        N.check(self._L.bx_engine_status(self._h, C.byref(s)), "bx_engine_status")
-        return s.value
-
     STAGES = ["det_features", "predict", "gate", "cosine", "assoc", "update", "cov_predict",
               "features", "finish"]  # bx_stage order (include/bxassoc.h)
-
-    def probe(self, stage) -> None:
-        """Time every launch of one pipeline stage with HIP events (None/-1 disables)."""
-        k = -1 if stage is None else (self.STAGES.index(stage) if isinstance(stage, str) else stage)
-        N.check(self._L.bx_engine_probe(self._h, k), "bx_engine_probe")
 
     def set_early_features(self, on: bool = True) -> None:
         """Start each full step's detection-feature kernel at once on a stream of its own
@@ -238,12 +308,6 @@ class Engine:
         self._overlap = bool(on)
         if not on:
             self._inflight = None
-
-    def probe_read(self):
-        """(total ms, launches) of the probed stage since the last read."""
-        t, n = C.c_double(), C.c_int()
-        N.check(self._L.bx_engine_probe_read(self._h, C.byref(t), C.byref(n)), "probe_read")
-        return t.value, n.value
 
     def frame_stats(self, seq0: int = 0, nseq: int = None) -> dict:
         """Last frame's unit counts summed over sequences (bench byte accounting)."""
@@ -366,9 +430,11 @@ class OcsortParams:
     frame_h: float = 1080.0
 
 
-class OcsortEngine:
+class OcsortEngine(_OcsFamilyEngine):
     """Handle over ``bx_ocsort_*`` (include/bxocsort.h): ``n_seq`` OCSort sequences in HBM, one
     kernel launch (one wave per sequence) per frame."""
+
+    _PREFIX = "bx_ocsort"
 
     def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
                  params: OcsortParams | None = None):
@@ -380,13 +446,7 @@ class OcsortEngine:
             q_xy_scaling=p.Q_xy_scaling, q_s_scaling=p.Q_s_scaling, max_age=int(p.max_age),
             min_hits=int(p.min_hits), delta_t=int(p.delta_t), use_byte=int(bool(p.use_byte)),
             asso_kind=_asso_kind(p.asso_func), frame_w=float(p.frame_w), frame_h=float(p.frame_h))
-        self._L = N.load()
-        h = C.c_void_p()
-        N.check(self._L.bx_ocsort_create(C.byref(cfg), C.byref(h)), "bx_ocsort_create")
-        self._h = h
-
-    def slots_used(self, seq: int = 0) -> int:
-        return self.counters(seq)["n_tracks"]
+        self._create(cfg)
 
     def grown(self, track_cap: int, det_cap: int) -> "OcsortEngine":
         """A new engine with larger capacities holding this one's state (bx_ocsort_copy_state)."""
@@ -394,28 +454,10 @@ class OcsortEngine:
         N.check(self._L.bx_ocsort_copy_state(e._h, self._h), "bx_ocsort_copy_state")
         return e
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.bx_ocsort_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, seq0: int = 0, nseq: int | None = None, stream=None):
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        N.check(self._L.bx_ocsort_reset(self._h, seq0, nseq, stream), "bx_ocsort_reset")
-
     def step(self, dets, det_off, out, out_count, seq0: int = 0, nseq: int | None = None,
              stream=None):
         """One frame for sequences [seq0, seq0+nseq) from device tensors (see bx_ocsort_step)."""
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        if stream is None:
-            stream = _current_stream()
+        nseq, stream = self._range(seq0, nseq, stream)
         N.check(self._L.bx_ocsort_step(self._h, seq0, nseq, _ptr(dets), _ptr(det_off), _ptr(out),
                                        _ptr(out_count), stream), "bx_ocsort_step")
 
@@ -441,24 +483,6 @@ class OcsortEngine:
             out.ctypes.data, C.byref(m), None), "bx_ocsort_update_classes_host")
         return out[: m.value].copy(), g.value
 
-    def status(self) -> int:
-        s = C.c_int(0)
-        N.check(self._L.bx_ocsort_status(self._h, C.byref(s)), "bx_ocsort_status")
-        return s.value
-
-    def counters(self, seq: int = 0) -> dict:
-        fc, idc, nt = C.c_int(), C.c_int(), C.c_int()
-        N.check(self._L.bx_ocsort_counters_host(self._h, seq, C.byref(fc), C.byref(idc),
-                                                C.byref(nt)), "counters")
-        return {"frame_count": fc.value, "id_count": idc.value, "n_tracks": nt.value}
-
-    def set_id_count(self, seq: int, value: int):
-        N.check(self._L.bx_ocsort_set_id_count(self._h, seq, int(value), None), "set_id_count")
-
-    def set_frame_size(self, seq: int, w: float, h: float):
-        N.check(self._L.bx_ocsort_set_frame_size(self._h, seq, float(w), float(h), None),
-                "set_frame_size")
-
     def tracks(self, seq: int = 0) -> dict:
         """Host snapshot of the track list (list order): ids, XYSR means x [7], covariances."""
         cap = self.track_cap
@@ -477,20 +501,8 @@ class OcsortEngine:
         N.check(self._L.bx_ocsort_state_set_host(self._h, seq, n, ids.ctypes.data, _p(a), _p(b)),
                 "state_set")
 
-    def frame_stats(self, seq0: int = 0, nseq: int | None = None) -> dict:
-        """Last frame over sequences [seq0, seq0+nseq): live tracks, output rows, frame."""
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        a = (C.c_int64 * 3)()
-        N.check(self._L.bx_ocsort_frame_stats_host(self._h, seq0, nseq, a), "frame_stats")
-        return dict(zip(["tracks", "outputs", "frame"], [int(x) for x in a]))
-
     def probe(self, on: bool = True) -> None:
         N.check(self._L.bx_ocsort_probe(self._h, int(bool(on))), "bx_ocsort_probe")
-
-    def probe_read(self):
-        t, n = C.c_double(), C.c_int()
-        N.check(self._L.bx_ocsort_probe_read(self._h, C.byref(t), C.byref(n)), "probe_read")
-        return t.value, n.value
 
 
 @dataclass
@@ -515,11 +527,13 @@ class DeepOcsortParams:
     frame_h: float = 1080.0
 
 
-class DeepOcsortEngine:
+class DeepOcsortEngine(_OcsFamilyEngine):
     """Handle over ``bx_deepoc_*`` (include/bxdeepocsort.h): ``n_seq`` DeepOCSort sequences in
     HBM; per frame the appearance contraction (fp64 MFMA), the frame kernel (one wave per
     sequence) and the embedding update.  Embeddings are float64, ``emb_dim`` wide (any positive
     width; unused with ``embedding_off``)."""
+
+    _PREFIX = "bx_deepoc"
 
     STAGES = ["embcost", "frame", "feature"]
 
@@ -537,13 +551,7 @@ class DeepOcsortEngine:
             max_age=int(p.max_age), min_hits=int(p.min_hits), delta_t=int(p.delta_t),
             embedding_off=int(bool(p.embedding_off)), aw_off=int(bool(p.aw_off)),
             asso_kind=_asso_kind(p.asso_func), frame_w=float(p.frame_w), frame_h=float(p.frame_h))
-        self._L = N.load()
-        h = C.c_void_p()
-        N.check(self._L.bx_deepoc_create(C.byref(cfg), C.byref(h)), "bx_deepoc_create")
-        self._h = h
-
-    def slots_used(self, seq: int = 0) -> int:
-        return self.counters(seq)["n_tracks"]
+        self._create(cfg)
 
     def grown(self, track_cap: int, det_cap: int, map_cap: int | None = None) -> "DeepOcsortEngine":
         """A new engine with larger capacities holding this one's state (bx_deepoc_copy_state);
@@ -554,29 +562,11 @@ class DeepOcsortEngine:
         N.check(self._L.bx_deepoc_copy_state(e._h, self._h), "bx_deepoc_copy_state")
         return e
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.bx_deepoc_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, seq0: int = 0, nseq: int | None = None, stream=None):
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        N.check(self._L.bx_deepoc_reset(self._h, seq0, nseq, stream), "bx_deepoc_reset")
-
     def step(self, dets, det_off, embs, warps, out, out_count, seq0: int = 0,
              nseq: int | None = None, stream=None):
         """One frame for sequences [seq0, seq0+nseq) from device tensors (see bx_deepoc_step):
         embs float64 [sum N, emb_dim] (None with embedding_off), warps [nseq, 6] or None."""
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        if stream is None:
-            stream = _current_stream()
+        nseq, stream = self._range(seq0, nseq, stream)
         N.check(self._L.bx_deepoc_step(self._h, seq0, nseq, _ptr(dets), _ptr(det_off), _ptr(embs),
                                        _ptr(warps), _ptr(out), _ptr(out_count), stream),
                 "bx_deepoc_step")
@@ -649,24 +639,6 @@ class DeepOcsortEngine:
             C.byref(g), out.ctypes.data, C.byref(m), None), "bx_deepoc_update_classes_host")
         return out[: m.value].copy(), g.value
 
-    def status(self) -> int:
-        s = C.c_int(0)
-        N.check(self._L.bx_deepoc_status(self._h, C.byref(s)), "bx_deepoc_status")
-        return s.value
-
-    def counters(self, seq: int = 0) -> dict:
-        fc, idc, nt = C.c_int(), C.c_int(), C.c_int()
-        N.check(self._L.bx_deepoc_counters_host(self._h, seq, C.byref(fc), C.byref(idc),
-                                                C.byref(nt)), "counters")
-        return {"frame_count": fc.value, "id_count": idc.value, "n_tracks": nt.value}
-
-    def set_id_count(self, seq: int, value: int):
-        N.check(self._L.bx_deepoc_set_id_count(self._h, seq, int(value), None), "set_id_count")
-
-    def set_frame_size(self, seq: int, w: float, h: float):
-        N.check(self._L.bx_deepoc_set_frame_size(self._h, seq, float(w), float(h), None),
-                "set_frame_size")
-
     def tracks(self, seq: int = 0) -> dict:
         """Host snapshot of the track list (list order): ids, XYSR means x [7], covariances
         [7, 7] and, unless embedding_off, embeddings [emb_dim]."""
@@ -693,24 +665,6 @@ class DeepOcsortEngine:
             e = np.ascontiguousarray(emb, np.float64).reshape(n, self.emb_dim)
         N.check(self._L.bx_deepoc_state_set_host(self._h, seq, n, ids.ctypes.data, _p(a), _p(b),
                                                  _p(e)), "state_set")
-
-    def frame_stats(self, seq0: int = 0, nseq: int | None = None) -> dict:
-        """Last frame over sequences [seq0, seq0+nseq): live tracks, output rows, frame."""
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        a = (C.c_int64 * 3)()
-        N.check(self._L.bx_deepoc_frame_stats_host(self._h, seq0, nseq, a), "frame_stats")
-        return dict(zip(["tracks", "outputs", "frame"], [int(x) for x in a]))
-
-    def probe(self, stage) -> None:
-        """Time one stage per step (name from STAGES or index); None = off."""
-        idx = -1 if stage is None else (self.STAGES.index(stage) if isinstance(stage, str)
-                                        else int(stage))
-        N.check(self._L.bx_deepoc_probe(self._h, idx), "bx_deepoc_probe")
-
-    def probe_read(self):
-        t, n = C.c_double(), C.c_int()
-        N.check(self._L.bx_deepoc_probe_read(self._h, C.byref(t), C.byref(n)), "probe_read")
-        return t.value, n.value
 
 
 def deepoc_embcost(dets_embs, trk_embs, out, stream=None) -> None:
@@ -742,10 +696,12 @@ class HybridsortParams:
     frame_h: float = 1080.0
 
 
-class HybridsortEngine:
+class HybridsortEngine(_OcsFamilyEngine):
     """Handle over ``bx_hybrid_*`` (include/bxhybridsort.h): ``n_seq`` HybridSort sequences in
     HBM; per frame the two cosine-distance contractions (fp64 MFMA), the frame kernel (one wave
     per sequence) and the feature update.  Embeddings are float64, ``emb_dim`` wide."""
+
+    _PREFIX = "bx_hybrid"
 
     STAGES = ["dist", "frame", "feature"]
 
@@ -761,13 +717,7 @@ class HybridsortEngine:
             tcm_first_step_weight=float(p.TCM_first_step_weight), max_age=int(p.max_age),
             min_hits=int(p.min_hits), delta_t=int(p.delta_t), asso_kind=_asso_kind(p.asso_func),
             frame_w=float(p.frame_w), frame_h=float(p.frame_h))
-        self._L = N.load()
-        h = C.c_void_p()
-        N.check(self._L.bx_hybrid_create(C.byref(cfg), C.byref(h)), "bx_hybrid_create")
-        self._h = h
-
-    def slots_used(self, seq: int = 0) -> int:
-        return self.counters(seq)["n_tracks"]
+        self._create(cfg)
 
     def grown(self, track_cap: int, det_cap: int, map_cap: int | None = None) -> "HybridsortEngine":
         """A new engine with larger capacities holding this one's state (bx_hybrid_copy_state);
@@ -778,29 +728,11 @@ class HybridsortEngine:
         N.check(self._L.bx_hybrid_copy_state(e._h, self._h), "bx_hybrid_copy_state")
         return e
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.bx_hybrid_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, seq0: int = 0, nseq: int | None = None, stream=None):
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        N.check(self._L.bx_hybrid_reset(self._h, seq0, nseq, stream), "bx_hybrid_reset")
-
     def step(self, dets, det_off, embs, out, out_count, seq0: int = 0, nseq: int | None = None,
              stream=None):
         """One frame for sequences [seq0, seq0+nseq) from device tensors (see bx_hybrid_step):
         embs float64 [sum N, emb_dim]."""
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        if stream is None:
-            stream = _current_stream()
+        nseq, stream = self._range(seq0, nseq, stream)
         N.check(self._L.bx_hybrid_step(self._h, seq0, nseq, _ptr(dets), _ptr(det_off), _ptr(embs),
                                        _ptr(out), _ptr(out_count), stream), "bx_hybrid_step")
 
@@ -867,24 +799,6 @@ class HybridsortEngine:
             out.ctypes.data, C.byref(m), None), "bx_hybrid_update_classes_host")
         return out[: m.value].copy(), g.value
 
-    def status(self) -> int:
-        s = C.c_int(0)
-        N.check(self._L.bx_hybrid_status(self._h, C.byref(s)), "bx_hybrid_status")
-        return s.value
-
-    def counters(self, seq: int = 0) -> dict:
-        fc, idc, nt = C.c_int(), C.c_int(), C.c_int()
-        N.check(self._L.bx_hybrid_counters_host(self._h, seq, C.byref(fc), C.byref(idc),
-                                                C.byref(nt)), "counters")
-        return {"frame_count": fc.value, "id_count": idc.value, "n_tracks": nt.value}
-
-    def set_id_count(self, seq: int, value: int):
-        N.check(self._L.bx_hybrid_set_id_count(self._h, seq, int(value), None), "set_id_count")
-
-    def set_frame_size(self, seq: int, w: float, h: float):
-        N.check(self._L.bx_hybrid_set_frame_size(self._h, seq, float(w), float(h), None),
-                "set_frame_size")
-
     def tracks(self, seq: int = 0) -> dict:
         """Host snapshot of the track list (list order): ids, the 9-state means x [9]
         (u, v, s, score, r and the velocities of the first four), covariances [9, 9], smoothed
@@ -916,17 +830,6 @@ class HybridsortEngine:
         """Live tracks over sequences [seq0, seq0+nseq) after the last frame."""
         nseq = self.n_seq - seq0 if nseq is None else nseq
         return {"tracks": sum(self.counters(q)["n_tracks"] for q in range(seq0, seq0 + nseq))}
-
-    def probe(self, stage) -> None:
-        """Time one stage per step (name from STAGES or index); None = off."""
-        idx = -1 if stage is None else (self.STAGES.index(stage) if isinstance(stage, str)
-                                        else int(stage))
-        N.check(self._L.bx_hybrid_probe(self._h, idx), "bx_hybrid_probe")
-
-    def probe_read(self):
-        t, n = C.c_double(), C.c_int()
-        N.check(self._L.bx_hybrid_probe_read(self._h, C.byref(t), C.byref(n)), "probe_read")
-        return t.value, n.value
 
     def state_save(self, seq: int = 0) -> np.ndarray:
         """One sequence's whole tracker state as an opaque byte array (bx_hybrid_state_save_host)."""
@@ -965,11 +868,13 @@ def hybrid_bank_mean(bank, pushed, out, stream=None) -> None:
                                          stream), "bx_hybrid_bank_mean")
 
 
-class ClassSplit:
+class ClassSplit(_NativeHandle):
     """Handle over ``bx_classes_*`` (include/bxclasses.h): per_class=True on the device for
     ``n_seq`` sequences of ``n_classes`` classes — the stable class split of a frame's rows and the
     merge of the class sequences' output rows under class-global ids.  The engines'
     ``step_classes`` own one; built directly it drives the two kernels alone."""
+
+    _PREFIX = "bx_classes"
 
     def __init__(self, n_seq: int, n_classes: int, emb_dim: int = 0, row_cap: int = 256,
                  map_cap: int = 4096, id0: int = 1):
@@ -995,12 +900,6 @@ class ClassSplit:
         if h and self._owner is None:
             self._L.bx_classes_destroy(h)
         self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def split(self, dets, det_off, embs, o_dets, o_embs, o_off, o_src, nseq: int | None = None,
               stream=None) -> None:
@@ -1029,11 +928,6 @@ class ClassSplit:
         nseq = self.n_seq - seq0 if nseq is None else nseq
         N.check(self._L.bx_classes_reset(self._h, seq0, nseq, stream), "bx_classes_reset")
 
-    def status(self) -> int:
-        s = C.c_int(0)
-        N.check(self._L.bx_classes_status(self._h, C.byref(s)), "bx_classes_status")
-        return s.value
-
     def id_count(self, seq: int = 0) -> int:
         g = C.c_int(0)
         N.check(self._L.bx_classes_id_count_host(self._h, seq, C.byref(g)), "id_count")
@@ -1051,7 +945,7 @@ class ClassSplit:
         return m[: n.value].copy()
 
 
-class SequenceFeeder:
+class SequenceFeeder(_NativeHandle):
     """Handle over ``bx_feed_*`` (include/bxfeed.h): the packed rows of many sequences resident
     in HBM, gathered per frame index into the batched arrays a ``step`` takes, and the steps'
     output rows appended on the device as MOT rows; one copy back at the end.
@@ -1062,6 +956,8 @@ class SequenceFeeder:
     buffer (default: its detection count); ``guard_rows``: extra rows behind the last buffer.
     ``schedule[t]`` lists the runs of frame index t as ``(seq0, nseq, rows, dets, det_off, embs,
     out, out_count)`` with the last five as device addresses."""
+
+    _PREFIX = "bx_feed"
 
     def __init__(self, dets, embs, tables, emb_dim: int, res_cap=None, guard_rows: int = 0):
         S = len(dets)
@@ -1110,18 +1006,6 @@ class SequenceFeeder:
                 runs.append(tuple(x.value for x in i3 + p5))
             self.schedule.append(runs)
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.bx_feed_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def gather(self, t: int, stream=None) -> None:
         """Write every run's dets / embs / det_off of frame index t (one launch)."""
         if stream is None:
@@ -1133,11 +1017,6 @@ class SequenceFeeder:
         if stream is None:
             stream = _current_stream()
         N.check(self._L.bx_feed_append(self._h, int(t), stream), "bx_feed_append")
-
-    def status(self) -> int:
-        s = C.c_int(0)
-        N.check(self._L.bx_feed_status(self._h, C.byref(s)), "bx_feed_status")
-        return s.value
 
     def raw_results(self):
         """The whole result allocation [rows, 9] (guard rows last), each sequence's first row
@@ -1202,10 +1081,12 @@ class BoostParams:
     with_reid: bool = True
 
 
-class BoostEngine:
+class BoostEngine(_TrackListEngine):
     """Handle over ``bx_boost_*`` (include/bxboost.h): ``n_seq`` BoostTrack sequences in HBM;
     per frame a ReID contraction (fp64 MFMA), the frame kernel (a 1-4 wave workgroup per
     sequence) and the embedding update."""
+
+    _PREFIX = "bx_boost"
 
     def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
                  emb_dim: int = 0, params: BoostParams | None = None):
@@ -1225,13 +1106,7 @@ class BoostEngine:
             s_sim_corr=int(bool(p.s_sim_corr)), use_rich_s=int(bool(p.use_rich_s)),
             use_sb=int(bool(p.use_sb)), use_vt=int(bool(p.use_vt)),
             with_reid=int(bool(p.with_reid)))
-        self._L = N.load()
-        h = C.c_void_p()
-        N.check(self._L.bx_boost_create(C.byref(cfg), C.byref(h)), "bx_boost_create")
-        self._h = h
-
-    def slots_used(self, seq: int = 0) -> int:
-        return self.counters(seq)["n_tracks"]
+        self._create(cfg)
 
     def grown(self, track_cap: int, det_cap: int) -> "BoostEngine":
         """A new engine with larger capacities holding this one's state (bx_boost_copy_state)."""
@@ -1239,28 +1114,10 @@ class BoostEngine:
         N.check(self._L.bx_boost_copy_state(e._h, self._h), "bx_boost_copy_state")
         return e
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.bx_boost_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, seq0: int = 0, nseq: int | None = None, stream=None):
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        N.check(self._L.bx_boost_reset(self._h, seq0, nseq, stream), "bx_boost_reset")
-
     def step(self, dets, det_off, embs, warps, out, out_count, seq0: int = 0,
              nseq: int | None = None, stream=None):
         """One frame for sequences [seq0, seq0+nseq) from device tensors (see bx_boost_step)."""
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        if stream is None:
-            stream = _current_stream()
+        nseq, stream = self._range(seq0, nseq, stream)
         N.check(self._L.bx_boost_step(self._h, seq0, nseq, _ptr(dets), _ptr(det_off), _ptr(embs),
                                       _ptr(warps), _ptr(out), _ptr(out_count), stream),
                 "bx_boost_step")
@@ -1307,20 +1164,6 @@ class BoostEngine:
             None), "bx_boost_update_classes_host")
         return out[: m.value].copy()
 
-    def status(self) -> int:
-        s = C.c_int(0)
-        N.check(self._L.bx_boost_status(self._h, C.byref(s)), "bx_boost_status")
-        return s.value
-
-    def counters(self, seq: int = 0) -> dict:
-        fc, idc, nt = C.c_int(), C.c_int(), C.c_int()
-        N.check(self._L.bx_boost_counters_host(self._h, seq, C.byref(fc), C.byref(idc),
-                                               C.byref(nt)), "counters")
-        return {"frame_count": fc.value, "id_count": idc.value, "n_tracks": nt.value}
-
-    def set_id_count(self, seq: int, value: int):
-        N.check(self._L.bx_boost_set_id_count(self._h, seq, int(value), None), "set_id_count")
-
     def tracks(self, seq: int = 0) -> dict:
         """Host snapshot of the track list (list order): ids, means x [8], covariances [8, 8],
         embeddings [F] (with_reid)."""
@@ -1354,17 +1197,6 @@ class BoostEngine:
 
     STAGES = ["embcost", "frame", "feature"]
 
-    def probe(self, stage) -> None:
-        """Time one stage per step (name from STAGES or index); None = off."""
-        idx = -1 if stage is None else (self.STAGES.index(stage) if isinstance(stage, str)
-                                        else int(stage))
-        N.check(self._L.bx_boost_probe(self._h, idx), "bx_boost_probe")
-
-    def probe_read(self):
-        t, n = C.c_double(), C.c_int()
-        N.check(self._L.bx_boost_probe_read(self._h, C.byref(t), C.byref(n)), "probe_read")
-        return t.value, n.value
-
 
 @dataclass
 class SsParams:
@@ -1385,10 +1217,12 @@ class SsParams:
     born_confirmed: bool = False
 
 
-class SsEngine:
+class SsEngine(_NativeEngine):
     """Handle over ``bx_ss_*`` (include/bxstrongsort.h): ``n_seq`` StrongSort sequences in HBM;
     per frame the detection-feature kernel, the NN-gallery distance (fp64 MFMA), the recovery
     similarities and the frame kernel (one wave per sequence)."""
+
+    _PREFIX = "bx_ss"
 
     STAGES = ["prep", "nn", "recovery", "pre", "cost", "match", "update", "post", "fit"]
 
@@ -1407,10 +1241,7 @@ class SsEngine:
             id_preservation_weight=float(p.id_preservation_weight),
             crowd_detection=int(bool(p.crowd_detection)),
             born_confirmed=int(bool(p.born_confirmed)))
-        self._L = N.load()
-        h = C.c_void_p()
-        N.check(self._L.bx_ss_create(C.byref(cfg), C.byref(h)), "bx_ss_create")
-        self._h = h
+        self._create(cfg)
         self.vec_cap = vec_cap
 
     def slots_used(self, seq: int = 0) -> int:
@@ -1424,29 +1255,11 @@ class SsEngine:
         N.check(self._L.bx_ss_copy_state(e._h, self._h), "bx_ss_copy_state")
         return e
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._L.bx_ss_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, seq0: int = 0, nseq: int | None = None, stream=None):
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        N.check(self._L.bx_ss_reset(self._h, seq0, nseq, stream), "bx_ss_reset")
-
     def step(self, dets, det_off, embs, warps, out, out_count, seq0: int = 0,
              nseq: int | None = None, stream=None):
         """One frame for sequences [seq0, seq0+nseq) from device tensors (see bx_ss_step):
         dets [sumN, 6] f64, det_off [S+1] i32, embs [sumN, F] f64, out [sumN, 10] f64."""
-        nseq = self.n_seq - seq0 if nseq is None else nseq
-        if stream is None:
-            stream = _current_stream()
+        nseq, stream = self._range(seq0, nseq, stream)
         N.check(self._L.bx_ss_step(self._h, seq0, nseq, _ptr(dets), _ptr(det_off), _ptr(embs),
                                    _ptr(warps), _ptr(out), _ptr(out_count), stream), "bx_ss_step")
 
@@ -1465,11 +1278,6 @@ class SsEngine:
             None if w is None else w.ctypes.data, out.ctypes.data, C.byref(m), None),
             "bx_ss_update_host")
         return out[: m.value].copy()
-
-    def status(self) -> int:
-        s = C.c_int(0)
-        N.check(self._L.bx_ss_status(self._h, C.byref(s)), "bx_ss_status")
-        return s.value
 
     def counters(self, seq: int = 0) -> dict:
         fc, nid, nt, nl = C.c_int(), C.c_int(), C.c_int(), C.c_int()
@@ -1554,16 +1362,6 @@ class SsEngine:
         N.check(self._L.bx_ss_lsap_stats_host(self._h, seq0, nseq, a), "lsap_stats")
         return dict(zip(["solves", "unique", "unique_up_to_rejected", "ties", "restarts"],
                         [int(x) for x in a]))
-
-    def probe(self, stage) -> None:
-        idx = -1 if stage is None else (self.STAGES.index(stage) if isinstance(stage, str)
-                                        else int(stage))
-        N.check(self._L.bx_ss_probe(self._h, idx), "bx_ss_probe")
-
-    def probe_read(self):
-        t, n = C.c_double(), C.c_int()
-        N.check(self._L.bx_ss_probe_read(self._h, C.byref(t), C.byref(n)), "probe_read")
-        return t.value, n.value
 
 
 def _ptr(x):
