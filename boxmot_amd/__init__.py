@@ -6,11 +6,12 @@ reference's ``update(dets, img, embs) -> [M, 8]`` contract.  The numerics run in
 (HIP, gfx950); ``boxmot_amd.engine.Engine`` / ``OcsortEngine`` / ``BoostEngine`` / ``SsEngine`` / ``DeepOcsortEngine`` / ``HybridsortEngine`` expose the batched many-sequence API.
 ``gsi`` / ``linear_interpolation`` / ``gaussian_smooth`` are the GSI post-processing of MOT result files.
 ``evaluate_mot`` / ``mot_summary`` are the HOTA / CLEAR / Identity evaluation of MOT result files.
-``ECC`` / ``EccBatch`` / ``get_cmc_method`` are the camera-motion compensation from images.
+``ECC`` / ``EccBatch`` / ``SOF`` / ``SofBatch`` / ``get_cmc_method`` are the camera-motion
+compensation from images.
 ``ReidFrontEnd`` / ``crop_batch`` / ``normalize_features`` are the ReID front end around the caller's network.
 """
 from .cmc import (MOTION_AFFINE, MOTION_EUCLIDEAN, MOTION_HOMOGRAPHY, MOTION_TRANSLATION, ECC,
-                  EccBatch, get_cmc_method)
+                  EccBatch, SOF, SofBatch, get_cmc_method)
 from .evaluation import evaluate_mot, mot_summary
 from .postprocessing import gaussian_smooth, gsi, linear_interpolation
 from .reid import ReidFrontEnd, crop_batch, normalize_features
@@ -22,6 +23,6 @@ __version__ = "0.1.0"
 __all__ = ["create_tracker", "get_tracker_config", "ByteTrack", "BotSort", "OcSort",
            "BoostTrack", "StrongSort", "DeepOcSort", "HybridSort", "gsi", "linear_interpolation",
            "gaussian_smooth", "DeepOcSortPerClass", "HybridSortPerClass", "evaluate_mot",
-           "mot_summary", "ECC", "EccBatch", "get_cmc_method", "MOTION_TRANSLATION",
+           "mot_summary", "ECC", "EccBatch", "SOF", "SofBatch", "get_cmc_method", "MOTION_TRANSLATION",
            "MOTION_EUCLIDEAN", "MOTION_AFFINE", "MOTION_HOMOGRAPHY", "ReidFrontEnd",
            "crop_batch", "normalize_features", "__version__"]

@@ -29,6 +29,7 @@ HEADER_CLASSES = REPO / "include" / "bxclasses.h"
 HEADER_EVAL = REPO / "include" / "bxeval.h"
 HEADER_CMC = REPO / "include" / "bxcmc.h"
 HEADER_REID = REPO / "include" / "bxreid.h"
+HEADER_SOF = REPO / "include" / "bxsof.h"
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -40,7 +41,7 @@ HIPCC_FLAGS = [
 ]
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
            "bx_strongsort.hip", "bx_deepocsort.hip", "bx_hybridsort.hip", "bx_gsi.hip", "bx_feed.hip",
-           "bx_classes.hip", "bx_eval.hip", "bx_cmc.hip", "bx_reid.hip",
+           "bx_classes.hip", "bx_eval.hip", "bx_cmc.hip", "bx_reid.hip", "bx_sof.hip",
            "bx_io.cpp"]
 
 
@@ -207,6 +208,14 @@ class BxSsConfig(C.Structure):
     ]
 
 
+class BxSofParams(C.Structure):
+    _fields_ = [
+        ("max_corners", C.c_int32), ("win_size", C.c_int32), ("max_level", C.c_int32),
+        ("max_iter", C.c_int32), ("quality_level", C.c_double), ("eps", C.c_double),
+        ("threshold", C.c_double), ("scale", C.c_double),
+    ]
+
+
 # every symbol include/*.h declares (checked by tests/test_native_abi.py)
 EXPORTS = [
     "bx_last_error", "bx_device_count", "bx_engine_create", "bx_engine_destroy",
@@ -267,6 +276,9 @@ EXPORTS = [
     "bx_ecc_create", "bx_ecc_destroy", "bx_ecc_reset", "bx_ecc_work_size", "bx_ecc_apply",
     "bx_ecc_apply_host", "bx_ecc_status", "bx_ecc_state_host",
     "bx_reid_crops", "bx_reid_normalize",
+    "bx_sof_create", "bx_sof_destroy", "bx_sof_reset", "bx_sof_levels", "bx_sof_apply",
+    "bx_sof_apply_host", "bx_sof_status", "bx_sof_pyramid_bytes", "bx_sof_state_host",
+    "bx_sof_points_host",
 ]
 
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -487,6 +499,18 @@ _SIGS = {
     "bx_reid_crops": ([_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int]
                       + [C.c_float] * 6 + [C.c_int, _vp, _vp, _vp], C.c_int),
     "bx_reid_normalize": ([_vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, C.c_int, _vp], C.c_int),
+    "bx_sof_create": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "bx_sof_destroy": ([_vp], C.c_int),
+    "bx_sof_reset": ([_vp, C.c_int, _vp], C.c_int),
+    "bx_sof_levels": ([C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip], C.c_int),
+    "bx_sof_apply": ([_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(BxSofParams),
+                      _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_sof_apply_host": ([_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                           C.POINTER(BxSofParams), _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_sof_status": ([_vp, _ip], C.c_int),
+    "bx_sof_pyramid_bytes": ([_vp, C.POINTER(C.c_size_t)], C.c_int),
+    "bx_sof_state_host": ([_vp, C.c_int, _ip, _ip, _ip, _ip, _vp, _ip, _vp, _vp], C.c_int),
+    "bx_sof_points_host": ([_vp, C.c_int, _ip, _vp, _vp, _vp, _vp, _vp, _ip], C.c_int),
 }
 
 _lib = None

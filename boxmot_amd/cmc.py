@@ -1,4 +1,5 @@
-"""Camera-motion compensation on the GPU: the ECC image alignment of ``motion/cmc/ecc.py``.
+"""Camera-motion compensation on the GPU: the ECC image alignment of ``motion/cmc/ecc.py`` and
+the sparse optical flow of ``motion/cmc/sof.py``.
 
 Reference stage replaced (``boxmot/motion/cmc/ecc.py:63-128`` with ``base_cmc.py:27-43``): grey
 conversion, the resize to ``scale`` and ``cv2.findTransformECC`` against the previous frame, on the
@@ -10,7 +11,13 @@ as the device tensor the engines' ``warps`` argument takes (no host synchronisat
 inputs are on the device).  There is no CPU fallback: without the
 library or a HIP device the calls raise ``NativeUnavailable``.
 
-Agreement with OpenCV's own ``findTransformECC`` is unmeasured.
+``SOF`` / ``SofBatch`` replace ``motion/cmc/sof.py:64-160`` the same way (``include/bxsof.h``;
+DESIGN.md 2.17 is the contract): Shi-Tomasi keypoints, pyramidal Lucas-Kanade tracking with one
+wave per keypoint and a similarity fitted by a deterministic consensus, with the pyramids and the
+keypoints of every camera resident on the device.
+
+Agreement with OpenCV's own ``findTransformECC``, ``goodFeaturesToTrack``,
+``calcOpticalFlowPyrLK`` and ``estimateAffinePartial2D`` is unmeasured.
 """
 from __future__ import annotations
 
@@ -307,12 +314,293 @@ class ECC:
         return warp.reshape(2, 3).astype(np.float32)
 
 
+# per-stream result codes of the sparse optical flow (include/bxsof.h); SOF_NO_FRAME is SofBatch's
+# own: the stream was not listed
+SOF_OK, SOF_FIRST_FRAME, SOF_TOO_FEW, SOF_NO_MODEL, SOF_NO_KEYPOINTS, SOF_NO_FRAME = 0, 1, 2, 3, 4, 5
+SOF_MAX_CORNERS, SOF_MAX_LEVELS, SOF_HYPOTHESES = 1024, 4, 256
+
+
+class _SofHandle:
+    """One ``bx_sof`` handle."""
+
+    def __init__(self, n_streams: int, max_h: int, max_w: int):
+        import torch  # (first, as everywhere in the package: one HIP runtime per process)
+
+        self._h = C.c_void_p()
+        self._L = N.load()
+        if N.device_count() == 0 or not torch.cuda.is_available():
+            raise N.NativeUnavailable("SOF needs a HIP device")
+        self.n_streams, self.max_h, self.max_w = int(n_streams), int(max_h), int(max_w)
+        N.check(self._L.bx_sof_create(self.n_streams, self.max_h, self.max_w, C.byref(self._h)),
+                "bx_sof_create")
+        nb = C.c_size_t(0)
+        N.check(self._L.bx_sof_pyramid_bytes(self._h, C.byref(nb)), "bx_sof_pyramid_bytes")
+        self.pyramid_bytes = int(nb.value)
+
+    def close(self):
+        if self._h:
+            self._L.bx_sof_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream: int = -1):
+        from .engine import _current_stream
+
+        N.check(self._L.bx_sof_reset(self._h, int(stream), _current_stream()), "bx_sof_reset")
+
+    def status(self) -> int:
+        st = C.c_int(0)
+        N.check(self._L.bx_sof_status(self._h, C.byref(st)), "bx_sof_status")
+        return st.value
+
+    def state(self, stream: int = 0):
+        """``{"has_prev", "levels": [uint8 [h_l, w_l], ...], "keypoints": float64 [n, 2] (x, y),
+        "lam": float64 [h, w]}`` of a stream: its previous pyramid, the keypoints it holds and the
+        minimum-eigenvalue plane of the last frame it was given (synchronises)."""
+        hp, nl, nk = C.c_int(0), C.c_int(0), C.c_int(0)
+        lh, lw = (C.c_int * SOF_MAX_LEVELS)(), (C.c_int * SOF_MAX_LEVELS)()
+        pyr = np.zeros(self.pyramid_bytes, np.uint8)
+        kp = np.zeros((SOF_MAX_CORNERS, 2), np.float64)
+        lam = np.zeros(self.max_h * self.max_w, np.float64)
+        N.check(self._L.bx_sof_state_host(
+            self._h, int(stream), C.byref(hp), C.byref(nl), lh, lw, pyr.ctypes.data, C.byref(nk),
+            kp.ctypes.data, lam.ctypes.data), "bx_sof_state_host")
+        out = {"has_prev": bool(hp.value), "levels": [], "keypoints": kp[: nk.value].copy(),
+               "lam": None}
+        off = 0
+        for l in range(nl.value):
+            out["levels"].append(pyr[off: off + lh[l] * lw[l]].reshape(lh[l], lw[l]).copy())
+            off += lh[l] * lw[l]
+        if out["levels"]:
+            out["lam"] = lam[: lh[0] * lw[0]].reshape(lh[0], lw[0]).copy()
+        return out
+
+    def points(self, stream: int = 0):
+        """The tracking record of a stream's last apply: ``{"prev", "next": float64 [n, 2],
+        "tracked": bool [n], "iterations": int32 [n], "inlier": bool [n], "winner": int}``
+        (synchronises)."""
+        n, win = C.c_int(0), C.c_int(0)
+        prev, nxt = np.zeros((SOF_MAX_CORNERS, 2)), np.zeros((SOF_MAX_CORNERS, 2))
+        ok, inl = np.zeros(SOF_MAX_CORNERS, np.uint8), np.zeros(SOF_MAX_CORNERS, np.uint8)
+        it = np.zeros(SOF_MAX_CORNERS, np.int32)
+        N.check(self._L.bx_sof_points_host(
+            self._h, int(stream), C.byref(n), prev.ctypes.data, nxt.ctypes.data, ok.ctypes.data,
+            it.ctypes.data, inl.ctypes.data, C.byref(win)), "bx_sof_points_host")
+        k = n.value
+        return {"prev": prev[:k].copy(), "next": nxt[:k].copy(), "tracked": ok[:k].astype(bool),
+                "iterations": it[:k].copy(), "inlier": inl[:k].astype(bool), "winner": win.value}
+
+
+class _SofSettings:
+    """The reference's feature and Lucas-Kanade parameters as attributes (``sof.py:44-58``)."""
+
+    def _init_settings(self, scale):
+        self.scale = scale
+        self.grayscale = True
+        self.max_corners = 1000
+        self.quality_level = 0.01
+        self.min_distance = 1
+        self.block_size = 3
+        self.win_size = 21
+        self.max_level = 3
+        self.criteria = (30, 0.01)  # LK: most iterations per level, the step that ends them
+        self.ransac_threshold = 3.0  # consensus threshold in working pixels
+
+    def _params(self) -> N.BxSofParams:
+        """The C parameters; the refusals need no device."""
+        if self.min_distance > 1:
+            raise NotImplementedError("min_distance above 1 is not supported (the reference "
+                                      "never uses it)")
+        if self.block_size != 3:
+            raise NotImplementedError("block_size other than 3 is not supported")
+        win = int(self.win_size)
+        if win % 2 == 0 or not 5 <= win <= 31:
+            raise ValueError(f"win_size must be odd and within 5..31, got {self.win_size!r}")
+        if not 1 <= int(self.max_corners) <= SOF_MAX_CORNERS:
+            raise ValueError(f"max_corners must be within 1..{SOF_MAX_CORNERS}")
+        if not 0 <= int(self.max_level) < SOF_MAX_LEVELS:
+            raise ValueError(f"max_level must be within 0..{SOF_MAX_LEVELS - 1}")
+        if not 0 < float(self.quality_level) <= 1:
+            raise ValueError("quality_level must be within (0, 1]")
+        max_iter, eps = self.criteria
+        if int(max_iter) < 0 or not float(eps) >= 0 or not float(self.ransac_threshold) > 0:
+            raise ValueError("criteria / ransac_threshold out of range")
+        return N.BxSofParams(int(self.max_corners), win, int(self.max_level), int(max_iter),
+                             float(self.quality_level), float(eps), float(self.ransac_threshold),
+                             _scale_arg(self.scale))
+
+
+class SofBatch(_SofSettings):
+    """Sparse optical flow for ``n_streams`` cameras: one ``apply`` tracks every listed stream's
+    keypoints from its previous frame into its new one and fits a similarity, all on the current
+    stream.  With device inputs (frames a CUDA tensor, ``streams`` ``None`` or a CUDA tensor)
+    nothing inside synchronises the host with the device.  A numpy ``frames`` array or a list of
+    ``streams`` is copied to the device first, and that copy waits for the stream.
+
+    ``max_h`` / ``max_w`` bound the working image (after the resize); left ``None`` they are taken
+    from the first frames.  The parameters are ``SOF``'s attributes."""
+
+    def __init__(self, n_streams: int, scale=0.15, max_h: int | None = None,
+                 max_w: int | None = None):
+        if n_streams < 1:
+            raise ValueError("n_streams must be at least 1")
+        self.n_streams = int(n_streams)
+        self._init_settings(scale)
+        self._cap = (max_h, max_w)
+        self._handle = None
+        self._all = None  # device arange(n_streams)
+        self._eye = None  # device [n_streams, 6] identity warps
+
+    def _ensure(self, H: int, W: int) -> _SofHandle:
+        if self._handle is None:
+            h, w = work_size(H, W, self.scale)
+            self._handle = _SofHandle(self.n_streams, self._cap[0] or h, self._cap[1] or w)
+        return self._handle
+
+    def close(self):
+        if self._handle is not None:
+            self._handle.close()
+            self._handle = None
+
+    def reset(self, stream: int = -1):
+        """Forget the previous frame of one stream (default: of all)."""
+        if self._handle is not None:
+            self._handle.reset(stream)
+
+    def status(self) -> int:
+        return 0 if self._handle is None else self._handle.status()
+
+    def state(self, stream: int = 0):
+        if self._handle is None:
+            return {"has_prev": False, "levels": [], "keypoints": np.zeros((0, 2)), "lam": None}
+        return self._handle.state(stream)
+
+    def points(self, stream: int = 0):
+        return self._handle.points(stream)
+
+    def apply(self, frames, streams=None):
+        """frames, streams: as ``EccBatch.apply`` (same checks; a CUDA ``streams`` tensor is not
+        checked: an index out of range skips that frame and latches ``status()``).
+
+        Returns CUDA tensors over all streams: warps float64 ``[n_streams, 6]`` (row-major 2x3,
+        the engines' ``warps`` argument), code int32 (``SOF_OK`` / ``SOF_FIRST_FRAME`` /
+        ``SOF_TOO_FEW`` / ``SOF_NO_MODEL`` / ``SOF_NO_KEYPOINTS``; ``SOF_NO_FRAME`` with the
+        identity warp for a stream that was not listed), n_keypoints, n_tracked, n_inliers int32
+        ``[n_streams]``."""
+        import torch
+
+        from .engine import _current_stream
+
+        params = self._params()
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8:
+                raise ValueError("frames must be uint8")
+            n, H, W, ch = _frame_dims(frames.shape, self.grayscale)
+            hd = self._ensure(H, W)
+            frames = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
+        else:
+            if frames.dtype != torch.uint8 or not frames.is_cuda:
+                raise ValueError("frames must be a numpy array or a CUDA uint8 tensor")
+            n, H, W, ch = _frame_dims(frames.shape, self.grayscale)
+            hd = self._ensure(H, W)
+            frames = frames.contiguous()
+        S = self.n_streams
+        if streams is None:
+            if n > S:
+                raise ValueError(f"capacity exceeded: {n} frames for {S} streams")
+            if self._all is None:
+                self._all = torch.arange(S, dtype=torch.int32, device="cuda")
+            sd = self._all
+        elif isinstance(streams, torch.Tensor) and streams.is_cuda:
+            sd = streams.to(torch.int32).contiguous()
+        else:
+            sh = np.asarray(streams, np.int64).reshape(-1)
+            if sh.size and (sh.min() < 0 or sh.max() >= S):
+                raise ValueError("invalid argument: stream index out of range")
+            if np.unique(sh).size != sh.size:
+                raise ValueError("invalid argument: a stream is listed twice")
+            sd = torch.from_numpy(sh.astype(np.int32)).cuda()
+        if streams is not None and sd.numel() != n:
+            raise ValueError(f"{n} frames but {sd.numel()} stream indices")
+        if self._eye is None:  # device fills only: a tensor built from host values would copy
+            self._eye = torch.zeros(S, 6, dtype=torch.float64, device="cuda")  # and synchronise
+            self._eye[:, 0] = 1.0
+            self._eye[:, 4] = 1.0
+        warps = self._eye.clone()
+        code = torch.full((S,), SOF_NO_FRAME, dtype=torch.int32, device="cuda")
+        nkp = torch.zeros(S, dtype=torch.int32, device="cuda")
+        ntrk = torch.zeros(S, dtype=torch.int32, device="cuda")
+        ninl = torch.zeros(S, dtype=torch.int32, device="cuda")
+        N.check(hd._L.bx_sof_apply(
+            hd._h, n, H, W, ch, frames.data_ptr(), sd.data_ptr(), C.byref(params),
+            warps.data_ptr(), code.data_ptr(), nkp.data_ptr(), ntrk.data_ptr(), ninl.data_ptr(),
+            _current_stream()), "bx_sof_apply")
+        self._keep = (frames, sd)  # alive until the next call: the launches are asynchronous
+        return warps, code, nkp, ntrk, ninl
+
+
+class SOF(_SofSettings):
+    """The reference's ``SOF`` (``motion/cmc/sof.py``): ``apply(img, detections)`` returns the 2x3
+    float32 warp from the previous frame to this one, the identity on the first frame and on any
+    failure.  ``detections`` is ignored, as in the reference.  One camera; the device handle is
+    built at the first frame from the image size.  The feature and Lucas-Kanade parameters are
+    attributes with the reference's values (``max_corners``, ``quality_level``, ``min_distance``,
+    ``block_size``, ``win_size``, ``max_level``, ``criteria``, ``ransac_threshold``).  ``last``
+    holds the float64 warp, the code and the numbers of keypoints, tracked points and inliers of
+    the last call."""
+
+    def __init__(self, scale=0.15):
+        self._init_settings(scale)
+        self.last = None
+        self._handle = None
+
+    def reset(self):
+        if self._handle is not None:
+            self._handle.reset(0)
+
+    def apply(self, img, detections=None):
+        params = self._params()
+        img = np.ascontiguousarray(img)
+        if img.dtype != np.uint8:
+            raise ValueError("img must be uint8")
+        if img.ndim == 2:
+            H, W, ch = img.shape[0], img.shape[1], 1
+        else:
+            _, H, W, ch = _frame_dims((1,) + img.shape, self.grayscale)
+        if self._handle is None:
+            h, w = work_size(H, W, self.scale)
+            self._handle = _SofHandle(1, h, w)
+        hd = self._handle
+        streams = np.zeros(1, np.int32)
+        warp = np.zeros((1, 6), np.float64)
+        ints = np.zeros((4, 1), np.int32)
+        from .engine import _current_stream
+
+        N.check(hd._L.bx_sof_apply_host(
+            hd._h, 1, H, W, ch, img.ctypes.data, streams.ctypes.data, C.byref(params),
+            warp.ctypes.data, ints[0].ctypes.data, ints[1].ctypes.data, ints[2].ctypes.data,
+            ints[3].ctypes.data, _current_stream()), "bx_sof_apply_host")
+        self.last = {"warp": warp.reshape(2, 3).copy(), "code": int(ints[0, 0]),
+                     "n_keypoints": int(ints[1, 0]), "n_tracked": int(ints[2, 0]),
+                     "n_inliers": int(ints[3, 0])}
+        return warp.reshape(2, 3).astype(np.float32)
+
+
 def get_cmc_method(cmc_method):
     """``motion/cmc/__init__.py``'s lookup: the class of a method name, ``None`` for an unknown
-    one.  Only ECC runs here; the feature-based methods name themselves."""
+    one.  ECC is returned as the reference does; "sof" keeps its refusal (the lookup's behaviour
+    is pinned) and points to the class that runs it; ORB and SIFT are OpenCV's."""
     if cmc_method == "ecc":
         return ECC
-    if cmc_method in ("orb", "sof", "sift"):
+    if cmc_method == "sof":
+        raise NotImplementedError("cmc method 'sof' is not returned by this lookup: assign "
+                                  "boxmot_amd.SOF() to tracker.cmc")
+    if cmc_method in ("orb", "sift"):
         raise NotImplementedError(f"cmc method '{cmc_method}' is not supported: it is feature-based "
                                   "and defined by OpenCV; assign your own object to tracker.cmc")
     return None
