@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests.golden_util import compare_outputs
+from tests.scenes import DEEPOC_TIED as TIED, scene_of
 
 pytestmark = pytest.mark.gpu
 
@@ -36,12 +37,6 @@ def native():
     return torch
 
 
-def scene_of(fx):
-    from boxmot_amd.synth import SyntheticScene
-
-    return SyntheticScene(**ast.literal_eval(str(fx["scene"])))
-
-
 def make_tracker(args, warp_seed=None, **caps):
     from boxmot_amd import DeepOcSort
     from boxmot_amd.synth import SyntheticCMC, synth_warp
@@ -52,7 +47,7 @@ def make_tracker(args, warp_seed=None, **caps):
     return tr
 
 
-def run(tr, scene, n_frames, empty_at=()):
+def run(tr, scene, n_frames, empty_at=(), snap_at=(), snaps=None):
     rows = []
     for t in range(1, n_frames + 1):
         d, e, _ = scene.frame(t)
@@ -62,20 +57,69 @@ def run(tr, scene, n_frames, empty_at=()):
             tr.cmc.t = t
         o = np.asarray(tr.update(d, IMG, e), np.float64).reshape(-1, 8)
         rows.append(np.concatenate([np.full((o.shape[0], 1), t, np.float64), o], 1))
+        if t in snap_at:
+            snaps[t] = tr.engine.tracks(0)
     return np.concatenate(rows, 0)
+
+
+def print_state_maxima(name, got, want, keys=("x", "P", "emb")):
+    """The largest |device - reference| per state array over the snapshots (before any of them
+    is asserted), where the track lists have the same length."""
+    worst = {}
+    for g, w in zip(got, want):
+        for k in keys:
+            if k in w and k in g and g[k].shape == w[k].shape and w[k].size:
+                worst[k] = max(worst.get(k, 0.0), float(np.abs(g[k] - w[k]).max()))
+    print(f"{name}: max |device - reference| " + " ".join(f"{k}={v:.3e}" for k, v in worst.items()))
+
+
+def compare_state(got, ref, where):
+    """The engine's tracks() against the reference's per-track state (list order), with the
+    bounds and the reasoning of compare_state in test_hybridsort_gpu.py.
+    ids: exact.
+    kf.x, kf.P: 1e-9 absolute, the bound the box columns carry, for entries of box magnitude, and
+      1e-11 of their size for the larger ones (areas and covariances reach 1e4..1e5; the 4x4
+      inverse and the matrix products run in another summation order than LAPACK / BLAS; a wrong
+      Q, R or P0 entry moves them by 1e-3 and more).
+    emb: unit-size entries after at most 120 moving-average steps, each a few float64 roundings
+      with the norm summed in another order: 1e-12 absolute."""
+    np.testing.assert_array_equal(got["id"], ref["id"], err_msg=where)
+    assert set(got) == set(ref), where
+    for k in ("x", "P"):
+        np.testing.assert_allclose(got[k], ref[k], rtol=1e-11, atol=1e-9, err_msg=f"{where} {k}")
+    if "emb" in ref:
+        np.testing.assert_allclose(got["emb"], ref["emb"], rtol=0, atol=1e-12,
+                                   err_msg=f"{where} emb")
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=fixture_id)
 def test_fixture_parity(native, path):
+    """Boxes within 1e-9, every other column and the row count per frame exact; and, after four
+    of the frames, every track's filter state and embedding against the reference's
+    (compare_state): output boxes are observations, so only this pins the filter, the ORU
+    replay, the affine correction of a frozen track and the embedding kernel."""
     with np.load(path) as fx:
+        for k in ast.literal_eval(str(fx["needs"])):
+            assert int(fx[k]) > 0, f"the fixture never reached {k}"
+        assert int(fx["lap_degenerate"]) == 0 or path.stem[len("deepoc_"):] in TIED
         ref = fx["outputs"]
         args = ast.literal_eval(str(fx["tracker_args"]))
         seed = int(fx["warp_seed"]) if "warp_seed" in fx.files else None
         scene, nf = scene_of(fx), int(fx["n_frames"])
+        frames, off = [int(f) for f in fx["state_frames"]], fx["state_off"]
+        state = {k[len("state_"):]: fx[k] for k in fx.files
+                 if k.startswith("state_") and k not in ("state_frames", "state_off")}
     tr = make_tracker(args, seed)
-    got = run(tr, scene, nf)
-    assert tr.engine.status() == 0
+    snaps = {}
+    got = run(tr, scene, nf, snap_at=frames, snaps=snaps)
+    assert tr.engine.status() == 0 and len(frames) == 4 and off[-1] > 0
+    np.testing.assert_array_equal(np.bincount(got[:, 0].astype(int), minlength=nf + 1),
+                                  np.bincount(ref[:, 0].astype(int), minlength=nf + 1))
     compare_outputs(got, ref, box_atol=1e-9)
+    want = [{k: v[off[j]: off[j + 1]] for k, v in state.items()} for j in range(4)]
+    print_state_maxima(path.stem, [snaps[f] for f in frames], want)
+    for j, f in enumerate(frames):
+        compare_state(snaps[f], want[j], f"frame {f}")
 
 
 @pytest.mark.parametrize("nd,nt,F", [(1, 1, 1), (16, 16, 4), (33, 65, 20), (32, 64, 16),

@@ -10,7 +10,8 @@ import boxmot_amd._native as N
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 CASES = ["grid24_f20", "crowd40_f64", "crowd40_awoff", "crowd40_emboff", "crowd32_warp",
-         "crowd96_f32", "giou_crowd40"]
+         "crowd96_f32", "giou_crowd40", "dt1_short", "dt7_warp", "params", "hmiou", "ciou", "diou",
+         "centroid", "stop76"]
 IMG = np.zeros((1080, 1920, 3), np.uint8)
 
 # the reference signature's values (trackers/deepocsort/deepocsort.py:265-287)
@@ -117,12 +118,16 @@ def test_fixture_form(name):
     assert path.stat().st_size < 1 << 20  # the repository's limit for a committed file
     keys = {"outputs", "n_frames", "kind", "scene", "tracker_args", "lap_calls", "lap_degenerate",
             "lap_frames", "fast_frames", "ocr_rematches", "oru_unfreezes", "affine_frozen",
-            "frames_gt64"}
+            "frames_gt64", "deaths", "births", "below_thresh_dets", "lookback_ge4", "ocr_big",
+            "first_big", "needs", "state_frames", "state_off", "state_id", "state_x", "state_P"}
     with np.load(path) as fx:
-        assert set(fx.files) - {"warp_seed"} == keys
-        assert ("warp_seed" in fx.files) == (name == "crowd32_warp")
+        assert set(fx.files) - {"warp_seed", "scene_kind", "state_emb"} == keys
+        assert ("warp_seed" in fx.files) == (name in ("crowd32_warp", "dt7_warp"))
+        assert ("scene_kind" in fx.files) == (name == "stop76")
+        assert ("state_emb" in fx.files) == (name != "crowd40_emboff")
         assert str(fx["kind"]) == "deepocsort" and int(fx["n_frames"]) <= 120
-        assert fx["outputs"].shape[1] == 9 and "float64" in str(fx["scene"])
+        assert fx["outputs"].shape[1] == 9
+        assert "float64" in str(fx["scene"]) or name == "stop76"  # (StopScene: always float64)
 
 
 def test_only_these_fixtures():

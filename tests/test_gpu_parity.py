@@ -905,6 +905,36 @@ def test_ocsort_large_scene_vs_oracle(torch_cuda):
     run_ocsort_batched(torch_cuda, [sc], 30, dict(OCS_ARGS, use_byte=True, det_thresh=0.5))
 
 
+def test_ocsort_stop_scene_ocr_cost_in_global_memory(torch_cuda):
+    """76 objects that all stop in frame 7 (tests/scenes.py): no prediction overlaps a detection
+    over the threshold, every detection overlaps its track's last observation, so the OCR round
+    solves 76 x 76 = 5776 > 5120 costs, more than the LDS ever holds: per frame bitwise against
+    the oracle, and the three claims checked on the oracle's own state."""
+    from tests.scenes import LDS_COST_MAX, StopScene
+
+    sc = StopScene(n_obj=76, seed=7)
+    orc = po.OracleTracker("ocsort", **OCS_ARGS)
+    for t in range(1, 7):
+        orc.update(sc.frame(t)[0])
+    st = orc.ocsort_tracks()
+    x = st["x"].copy()
+    x[:, :3] += x[:, 4:7]  # the prediction for frame 7: one step of the constant-velocity model
+    w = np.sqrt(x[:, 2] * x[:, 3])
+    h = x[:, 2] / w
+    pred = np.stack([x[:, 0] - w / 2, x[:, 1] - h / 2, x[:, 0] + w / 2, x[:, 1] + h / 2], 1)
+    d7 = sc.frame(7)[0]
+    assert st["id"].shape[0] == 76 == d7.shape[0] and 76 * 76 > LDS_COST_MAX
+    lt = np.maximum(d7[:, None, :2], pred[None, :, :2])
+    rb = np.minimum(d7[:, None, 2:4], pred[None, :, 2:4])
+    inter = np.clip(rb - lt, 0, None).prod(2)
+    area = lambda b: (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])  # noqa: E731
+    iou = inter / (area(d7)[:, None] + area(pred)[None, :] - inter)
+    assert iou.max() < OCS_ARGS["asso_threshold"]  # the first association keeps nothing
+    out7 = orc.update(d7)
+    assert sorted(out7[:, 4]) == sorted(st["id"] + 1)  # yet every track goes on: the OCR round
+    run_ocsort_batched(torch_cuda, [sc], 12, dict(OCS_ARGS))
+
+
 def test_ocsort_empty_frames_and_global_ids(torch_cuda):
     from boxmot_amd import OcSort
 
