@@ -141,8 +141,9 @@ __device__ inline double aw_weight(const double* v, int n, int stride, double bo
   *apply = cnt >= 2;
   if (cnt < 2) return 1.0;
   if (m1 == 0) return 0.0;
+  // Python's max(ex, 0): 0 only when 0 > ex, so the NaN of two infinite entries stays
   const double ex = m2 / m1 - bottom;
-  return 1 - (ex > 0 ? ex : 0.0) / (1 - bottom);
+  return 1 - (0 > ex ? 0.0 : ex) / (1 - bottom);
 }
 
 // AssociationFunction registry (utils/iou.py:79-346), numpy's operation order per mode.

@@ -825,7 +825,7 @@ static double aw_weight(const double *v, int n, int stride, double bottom, int *
     if (m1 == 0) return 0.0;
     const double ratio = m2 / m1;
     const double ex = ratio - bottom;
-    return 1 - (ex > 0 ? ex : 0.0) / (1 - bottom);
+    return 1 - (0 > ex ? 0.0 : ex) / (1 - bottom); /* Python's max(ex, 0): a NaN ex stays */
 }
 
 void bxo_aw_max_metric(const double *emb, int nr, int nc, double w_assoc, double bottom,
