@@ -3,15 +3,17 @@
 Drop-in surface: ``create_tracker``, ``get_tracker_config``, ``ByteTrack``, ``BotSort``, ``OcSort``, ``BoostTrack``, ``StrongSort``, ``DeepOcSort``, ``HybridSort`` (and their per_class forms
 ``DeepOcSortPerClass``, ``HybridSortPerClass``) with the
 reference's ``update(dets, img, embs) -> [M, 8]`` contract.  The numerics run in libbxassoc.so
-(HIP, gfx950); ``boxmot_amd.engine.Engine`` / ``OcsortEngine`` / ``BoostEngine`` / ``SsEngine`` / ``DeepOcsortEngine`` / ``HybridsortEngine`` expose the batched many-sequence API.
+(HIP, gfx950); ``boxmot_amd.engine.Engine`` / ``OcsortEngine`` (``OcsortTableEngine``: per-sequence parameters) / ``BoostEngine`` / ``SsEngine`` / ``DeepOcsortEngine`` / ``HybridsortEngine`` expose the batched many-sequence API.
 ``gsi`` / ``linear_interpolation`` / ``gaussian_smooth`` are the GSI post-processing of MOT result files.
 ``evaluate_mot`` / ``mot_summary`` are the HOTA / CLEAR / Identity evaluation of MOT result files.
 ``ECC`` / ``EccBatch`` / ``SOF`` / ``SofBatch`` / ``get_cmc_method`` are the camera-motion
 compensation from images.
+``tune.grid`` / ``tune.sweep`` run a hyper-parameter sweep (K configs x S sequences) as one batched OCSort engine.
 ``ReidFrontEnd`` / ``crop_batch`` / ``normalize_features`` are the ReID front end around the caller's network.
 """
 from .cmc import (MOTION_AFFINE, MOTION_EUCLIDEAN, MOTION_HOMOGRAPHY, MOTION_TRANSLATION, ECC,
                   EccBatch, SOF, SofBatch, get_cmc_method)
+from . import tune
 from .evaluation import evaluate_mot, mot_summary
 from .postprocessing import gaussian_smooth, gsi, linear_interpolation
 from .reid import ReidFrontEnd, crop_batch, normalize_features
@@ -25,4 +27,4 @@ __all__ = ["create_tracker", "get_tracker_config", "ByteTrack", "BotSort", "OcSo
            "gaussian_smooth", "DeepOcSortPerClass", "HybridSortPerClass", "evaluate_mot",
            "mot_summary", "ECC", "EccBatch", "SOF", "SofBatch", "get_cmc_method", "MOTION_TRANSLATION",
            "MOTION_EUCLIDEAN", "MOTION_AFFINE", "MOTION_HOMOGRAPHY", "ReidFrontEnd",
-           "crop_batch", "normalize_features", "__version__"]
+           "crop_batch", "normalize_features", "tune", "__version__"]

@@ -160,6 +160,15 @@ class BxOcsortConfig(C.Structure):
     ]
 
 
+class BxOcsortSeqParams(C.Structure):
+    _fields_ = [
+        ("min_conf", C.c_double), ("det_thresh", C.c_double), ("asso_threshold", C.c_double),
+        ("inertia", C.c_double), ("q_xy_scaling", C.c_double), ("q_s_scaling", C.c_double),
+        ("max_age", C.c_int32), ("min_hits", C.c_int32), ("delta_t", C.c_int32),
+        ("use_byte", C.c_int32), ("asso_kind", C.c_int32),
+    ]
+
+
 class BxBoostConfig(C.Structure):
     _fields_ = [
         ("n_seq", C.c_int32), ("track_cap", C.c_int32), ("det_cap", C.c_int32),
@@ -234,7 +243,8 @@ EXPORTS = [
     "bx_nn_cosine_distance", "bx_ocsort_create", "bx_ocsort_destroy", "bx_ocsort_reset", "bx_ocsort_step",
     "bx_ocsort_update_host", "bx_ocsort_status", "bx_ocsort_counters_host",
     "bx_ocsort_set_id_count", "bx_ocsort_set_frame_size", "bx_ocsort_tracks_host", "bx_ocsort_probe", "bx_ocsort_probe_read",
-    "bx_ocsort_frame_stats_host", "bx_boost_create", "bx_boost_destroy", "bx_boost_reset",
+    "bx_ocsort_frame_stats_host", "bx_ocsort_set_seq_params_host", "bx_ocsort_seq_params_host",
+    "bx_boost_create", "bx_boost_destroy", "bx_boost_reset",
     "bx_boost_step", "bx_boost_update_host", "bx_boost_status", "bx_boost_counters_host",
     "bx_boost_set_id_count", "bx_boost_tracks_host", "bx_boost_frame_stats_host",
     "bx_boost_probe", "bx_boost_probe_read", "bx_ss_create", "bx_ss_destroy", "bx_ss_reset",
@@ -348,6 +358,9 @@ _SIGS = {
     "bx_ocsort_probe": ([_vp, C.c_int], C.c_int),
     "bx_ocsort_frame_stats_host": ([_vp, C.c_int, C.c_int, C.POINTER(C.c_int64)], C.c_int),
     "bx_ocsort_probe_read": ([_vp, _dp, _ip], C.c_int),
+    "bx_ocsort_set_seq_params_host": ([_vp, C.c_int, C.c_int, C.POINTER(BxOcsortSeqParams), _vp],
+                                      C.c_int),
+    "bx_ocsort_seq_params_host": ([_vp, C.c_int, C.POINTER(BxOcsortSeqParams)], C.c_int),
     "bx_boost_create": ([C.POINTER(BxBoostConfig), C.POINTER(C.c_void_p)], C.c_int),
     "bx_boost_destroy": ([_vp], C.c_int),
     "bx_boost_reset": ([_vp, C.c_int, C.c_int, _vp], C.c_int),

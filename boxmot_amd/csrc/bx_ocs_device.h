@@ -22,6 +22,14 @@ struct OcsTrk {
   int observed, has_saved, hvalid, htail;
 };
 
+// One sequence's entry of the per-sequence parameter table: the OcsDev fields that size no
+// memory.  `set` 0: the sequence runs on the engine's own parameters.
+struct OcsSeqPar {
+  double min_conf, det_thresh, asso_threshold, inertia, q_xy, q_s;
+  int max_age, min_hits, delta_t, use_byte, asso_kind;
+  int set;
+};
+
 struct OcsDev {
   int S, T, D, N;  // N = max(T, D): largest assignment problem
   double min_conf, det_thresh, asso_threshold, inertia, q_xy, q_s;
@@ -36,7 +44,32 @@ struct OcsDev {
   double* cost_g;   // [S][D*T] or null
   int* status;
   unsigned long long* dbg;  // [S][OCS_DBG] phase stamps (diagnostic builds only, else null)
+  // [S] per-sequence parameters, or null: none was ever set (OCSort only: DeepOCSort and
+  // HybridSort leave it null).  A kernel reads it, never writes it.
+  const OcsSeqPar* seqpar = nullptr;
 };
+
+// The kernel-entry override: sequence `seq`'s entry of the table, when it is set, replaces the
+// eleven per-sequence fields in the kernel's own copy of `g` (and max_obs, which follows
+// max_age); everything downstream reads them through `g` as before.  `seq` is wave-uniform, so
+// these are scalar loads, once per workgroup.
+__device__ __forceinline__ void ocs_seq_override(OcsDev& g, int seq) {
+  if (!g.seqpar) return;
+  const OcsSeqPar* p = g.seqpar + seq;
+  if (!p->set) return;
+  g.min_conf = p->min_conf;
+  g.det_thresh = p->det_thresh;
+  g.asso_threshold = p->asso_threshold;
+  g.inertia = p->inertia;
+  g.q_xy = p->q_xy;
+  g.q_s = p->q_s;
+  g.max_age = p->max_age;
+  g.max_obs = p->max_age >= 50 ? p->max_age + 5 : 50;  // derived, as the engine's create does
+  g.min_hits = p->min_hits;
+  g.delta_t = p->delta_t;
+  g.use_byte = p->use_byte;
+  g.asso_kind = p->asso_kind;
+}
 
 // Diagnostic phase stamps and counters (build with -DBX_PHASE_TIMING; never shipped): per
 // sequence, cycles accumulated per phase over all frames [0, 16), event counters [16, 24) and

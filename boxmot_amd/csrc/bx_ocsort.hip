@@ -45,6 +45,7 @@ __global__ void __launch_bounds__(OW)
   carve(g, lds_raw, L);
   const int lane = threadIdx.x;
   const int b = blockIdx.x, seq = seq0 + b;
+  ocs_seq_override(g, seq);  // this sequence's own parameters, when the table holds some
   L.jv.dc = g.dbg ? g.dbg + (size_t)seq * OCS_DBG + 24 : nullptr;
   const int r0 = det_off[b];
   int n = det_off[b + 1] - r0;
@@ -542,7 +543,15 @@ struct bx_ocsort : OcsHost {
   int* h_ccnt = nullptr;
   int ncls_alloc = 0;
   BxProbe probe;  // the frame kernel is stage 0
+  // per-sequence parameters (bx_ocsort_set_seq_params_host): the device table dev.seqpar points
+  // to, allocated by the first set, and its host mirror
+  OcsSeqPar* d_seqpar = nullptr;
+  std::vector<OcsSeqPar> h_seqpar;
 };
+
+// the field checks bx_ocsort_create and bx_ocsort_set_seq_params_host share
+static bool bad_delta_t(int delta_t) { return delta_t < 1 || delta_t > OBS_KEEP - 1; }
+static bool bad_asso_kind(int k) { return k < ASSO_IOU || k > ASSO_CENTROID; }
 
 static int launch(bx_ocsort* e, int seq0, int nseq, const float* dets, const int* off,
                   double* out, int* cnt, hipStream_t st) {
@@ -561,12 +570,12 @@ int bx_ocsort_create(const bx_ocsort_config* c, bx_ocsort** out) {
   if (c->n_seq <= 0 || c->track_cap <= 0 || c->det_cap <= 0 || c->track_cap > 512 ||
       c->det_cap > 512)
     return bx_record_error(BX_ERR_INVALID, "n_seq/track_cap/det_cap out of range");
-  if (c->delta_t < 1 || c->delta_t > OBS_KEEP - 1)
+  if (bad_delta_t(c->delta_t))
     return bx_record_error(BX_ERR_INVALID, "delta_t must be in [1, 7]");
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0)
     return bx_record_error(BX_ERR_NO_DEVICE, "no HIP device visible");
-  if (c->asso_kind < ASSO_IOU || c->asso_kind > ASSO_CENTROID)
+  if (bad_asso_kind(c->asso_kind))
     return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
   bx_ocsort* e = new bx_ocsort();
   e->cfg = *c;
@@ -664,6 +673,7 @@ int bx_ocsort_destroy(bx_ocsort* e) {
   if (!e) return BX_OK;
   e->probe.destroy();
   (void)hipFree(e->arena);
+  (void)hipFree(e->d_seqpar);
   e->sg.free();
   (void)hipFree(e->h_coff);
   (void)hipFree(e->h_ccnt);
@@ -822,6 +832,68 @@ int bx_ocsort_set_id_count(bx_ocsort* e, int seq, int id_count, void* stream) {
 
 int bx_ocsort_set_frame_size(bx_ocsort* e, int seq, double w, double h, void* stream) {
   return ocs_set_frame_size(e, seq, w, h, stream);
+}
+
+int bx_ocsort_set_seq_params_host(bx_ocsort* e, int seq0, int nseq,
+                                  const bx_ocsort_seq_params* params_host, void* stream) {
+  if (!e || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.S)
+    return bx_record_error(BX_ERR_INVALID, "bad sequence range");
+  for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
+    if (bad_delta_t(params_host[k].delta_t))
+      return bx_record_error(BX_ERR_INVALID, "delta_t must be in [1, 7]");
+    if (bad_asso_kind(params_host[k].asso_kind))
+      return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
+  }
+  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
+  hipStream_t st = (hipStream_t)stream;
+  const size_t S = e->dev.S;
+  if (!e->d_seqpar) {
+    if (hipMalloc(&e->d_seqpar, S * sizeof(OcsSeqPar)) != hipSuccess) {
+      e->d_seqpar = nullptr;
+      return bx_record_error(BX_ERR_HIP, "hipMalloc of the OCSort parameter table failed");
+    }
+    BX_HIPCHK(hipMemset(e->d_seqpar, 0, S * sizeof(OcsSeqPar)));
+    e->h_seqpar.assign(S, OcsSeqPar{});
+    e->dev.seqpar = e->d_seqpar;
+  }
+  for (int k = 0; k < nseq; k++) {
+    OcsSeqPar& d = e->h_seqpar[seq0 + k];
+    d = OcsSeqPar{};
+    if (!params_host) continue;
+    const bx_ocsort_seq_params& p = params_host[k];
+    d.min_conf = p.min_conf;
+    d.det_thresh = p.det_thresh;
+    d.asso_threshold = p.asso_threshold;
+    d.inertia = p.inertia;
+    d.q_xy = 1.0 * p.q_xy_scaling;
+    d.q_s = 1.0 * p.q_s_scaling;
+    d.max_age = p.max_age;
+    d.min_hits = p.min_hits;
+    d.delta_t = p.delta_t;
+    d.use_byte = p.use_byte;
+    d.asso_kind = p.asso_kind;
+    d.set = 1;
+  }
+  BX_HIPCHK(hipMemcpyAsync(e->d_seqpar + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(OcsSeqPar),
+                           hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
+  return BX_OK;
+}
+
+int bx_ocsort_seq_params_host(bx_ocsort* e, int seq, bx_ocsort_seq_params* out_host) {
+  if (!e || seq < 0 || seq >= e->dev.S || !out_host)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ocsort_seq_params_host");
+  const bx_ocsort_config& c = e->cfg;
+  bx_ocsort_seq_params o = {c.min_conf, c.det_thresh, c.asso_threshold, c.inertia, c.q_xy_scaling,
+                            c.q_s_scaling, c.max_age, c.min_hits, c.delta_t, c.use_byte,
+                            c.asso_kind};
+  if (!e->h_seqpar.empty() && e->h_seqpar[seq].set) {
+    const OcsSeqPar& d = e->h_seqpar[seq];
+    o = {d.min_conf, d.det_thresh, d.asso_threshold, d.inertia, d.q_xy, d.q_s, d.max_age,
+         d.min_hits, d.delta_t, d.use_byte, d.asso_kind};
+  }
+  *out_host = o;
+  return BX_OK;
 }
 
 int bx_ocsort_tracks_host(bx_ocsort* e, int seq, int cap, int32_t* ids, double* x, double* p,

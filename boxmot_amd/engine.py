@@ -505,6 +505,66 @@ class OcsortEngine(_OcsFamilyEngine):
         N.check(self._L.bx_ocsort_probe(self._h, int(bool(on))), "bx_ocsort_probe")
 
 
+class OcsortTableEngine(OcsortEngine):
+    """An ``OcsortEngine`` whose sequences may each run on parameters of their own
+    (``bx_ocsort_set_seq_params_host``, include/bxocsort.h): the engine of a hyper-parameter
+    sweep, K configs x S sequences as K*S sequences of one handle (boxmot_amd.tune)."""
+
+    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
+                 params: OcsortParams | None = None):
+        super().__init__(n_seq, track_cap, det_cap, params)
+        self._seq_over = {}  # sequence -> its own OcsortParams, for grown()
+
+    def grown(self, track_cap: int, det_cap: int) -> "OcsortTableEngine":
+        """As OcsortEngine.grown; bx_ocsort_copy_state carries tracks only, so the table is set
+        again on the new engine."""
+        e = OcsortTableEngine(self.n_seq, track_cap, det_cap, self.params)
+        N.check(self._L.bx_ocsort_copy_state(e._h, self._h), "bx_ocsort_copy_state")
+        for k, p in sorted(self._seq_over.items()):
+            e.set_seq_params(k, [p])
+        return e
+
+    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
+        """Give sequences [seq0, seq0 + len(params)) parameters of their own
+        (bx_ocsort_set_seq_params_host): ``params`` is a list of OcsortParams, whose frame_w /
+        frame_h are not part of the table.  ``None`` clears the override of ``nseq`` sequences
+        from seq0 (default: all from seq0).  For use between sequences, at frame 0."""
+        if params is None:
+            n = self.n_seq - seq0 if nseq is None else nseq
+            arr = None
+        else:
+            n = len(params)
+            arr = (N.BxOcsortSeqParams * max(n, 1))(*[N.BxOcsortSeqParams(
+                min_conf=p.min_conf, det_thresh=p.det_thresh, asso_threshold=p.asso_threshold,
+                inertia=p.inertia, q_xy_scaling=p.Q_xy_scaling, q_s_scaling=p.Q_s_scaling,
+                max_age=int(p.max_age), min_hits=int(p.min_hits), delta_t=int(p.delta_t),
+                use_byte=int(bool(p.use_byte)), asso_kind=_asso_kind(p.asso_func))
+                for p in params])
+        N.check(self._L.bx_ocsort_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
+                "bx_ocsort_set_seq_params_host")
+        for k in range(n):
+            if params is None:
+                self._seq_over.pop(seq0 + k, None)
+            else:
+                self._seq_over[seq0 + k] = params[k]
+
+    def seq_params(self, seq: int) -> OcsortParams:
+        """The parameters sequence ``seq`` runs on (bx_ocsort_seq_params_host): its own when set,
+        else the engine's; frame_w / frame_h are the engine's."""
+        from .iou import KINDS
+
+        o = N.BxOcsortSeqParams()
+        N.check(self._L.bx_ocsort_seq_params_host(self._h, int(seq), C.byref(o)),
+                "bx_ocsort_seq_params_host")
+        name = {v: k for k, v in KINDS.items()}[o.asso_kind]
+        return OcsortParams(min_conf=o.min_conf, det_thresh=o.det_thresh, max_age=o.max_age,
+                            min_hits=o.min_hits, asso_threshold=o.asso_threshold,
+                            delta_t=o.delta_t, inertia=o.inertia, use_byte=bool(o.use_byte),
+                            Q_xy_scaling=o.q_xy_scaling, Q_s_scaling=o.q_s_scaling,
+                            asso_func=name, frame_w=self.params.frame_w,
+                            frame_h=self.params.frame_h)
+
+
 @dataclass
 class DeepOcsortParams:
     """DeepOcSort constructor parameters (deepocsort.py:265-287 names and defaults)."""

@@ -1,0 +1,169 @@
+"""Hyper-parameter sweeps on the batched engine: K configurations x S sequences as ONE engine.
+
+Reference stage replaced (``boxmot/engine/evolve.py``): its objective function runs the tracker
+over all sequences with one configuration and evaluates, once per trial.  Here the K
+configurations of a sweep run together: an ``OcsortTableEngine`` of K*S sequences is built, engine
+sequence ``k*S + s`` is sequence ``s`` under configuration ``k`` (``set_seq_params``,
+include/bxocsort.h), and every frame index is one K*S-wide launch fed from device memory
+(``engine.SequenceFeeder``, include/bxfeed.h).  The search strategy (which configurations to try)
+stays with the caller; ``grid`` builds the cartesian product of a search space.
+
+Only OCSort has per-sequence parameters; DESIGN.md 2.18 is the contract.
+"""
+from __future__ import annotations
+
+import itertools
+from pathlib import Path
+
+import numpy as np
+
+SUPPORTED = ("ocsort",)
+_CAPS = ("track_cap", "det_cap")
+
+
+def grid(space: dict) -> list:
+    """The cartesian product of ``space`` (name -> list of values; names are OcSort's constructor
+    arguments) as a list of dicts, the last name varying fastest."""
+    names = list(space)
+    return [dict(zip(names, v)) for v in itertools.product(*[list(space[n]) for n in names])]
+
+
+def _check(tracker_type: str, configs) -> list:
+    """The refusals of ``sweep`` that need no engine."""
+    if tracker_type not in SUPPORTED:
+        raise NotImplementedError(
+            f"tune.sweep drives {', '.join(SUPPORTED)} only (the engine with per-sequence "
+            f"parameters), not {tracker_type}")
+    configs = [dict(c) for c in configs]
+    if not configs:
+        raise ValueError("tune.sweep needs at least one config")
+    for k, c in enumerate(configs):
+        if "per_class" in c:
+            raise NotImplementedError(f"config {k}: per_class is not available in a sweep")
+    for cap in _CAPS:
+        if len({repr(c.get(cap)) for c in configs}) > 1:
+            raise ValueError(f"{cap} sizes the engine's memory: it must be absent from every "
+                             f"config or equal in all of them")
+    return configs
+
+
+def _resolve(cfg: dict):
+    """(OcsortParams, track_cap, det_cap) of one config, resolved as run_sequences resolves its
+    tracker_kwargs: through ``motio._batched_engine`` itself, on a one-sequence engine."""
+    from . import motio
+
+    eng = motio._batched_engine("ocsort", 1, 0, cfg)[0]
+    try:
+        return eng.params, eng.track_cap, eng.det_cap
+    finally:
+        eng.close()
+
+
+def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict | None = None,
+          benchmark: str = "MOT17", seq_lengths: dict | None = None,
+          frame_ids: dict | None = None, frame_sizes: dict | None = None) -> list:
+    """Run every config of ``configs`` over every sequence in one batched engine.
+
+    sequences / frame_ids / frame_sizes: as in ``motio.run_sequences``.  configs: K dicts of
+    tracker kwargs, each meaning what ``run_sequences("ocsort", ..., tracker_kwargs=cfg)`` makes
+    of it (an empty dict is create_tracker's YAML defaults, a non-empty one goes through the
+    drop-in's constructor as an ``evolve_param_dict`` does).  ``track_cap`` / ``det_cap`` must be
+    absent or equal across configs (``ValueError``), ``per_class`` and trackers other than ocsort
+    raise ``NotImplementedError``; all three before any engine is built.
+
+    Returns one entry per config: ``{"config": cfg, "results": {name: [n, 9] float64 MOT rows},
+    "summary": mot_summary of the config or None without gt}``.  With ``exp_dir`` the rows are
+    also written to ``exp_dir/<k as 4 digits>/<name>.txt``, byte-identical to run_sequences'
+    files.  With ``gt`` (name -> gt rows or file, ``seq_lengths`` / ``benchmark`` as in
+    ``evaluate_mot``) every config is scored: one evaluator handle, one run per config, because
+    a run's COMBINED record is formed on the device over all the sequences of the run.
+
+    The detections are uploaded once per (config, sequence): K copies of a few MB for MOT-sized
+    inputs.  A nonzero engine or feeder status raises ``RuntimeError``.
+    """
+    configs = _check(tracker_type, configs)
+    from . import motio
+    from .engine import OcsortTableEngine, SequenceFeeder
+
+    names = list(sequences)
+    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
+            for s in sequences.values()]
+    S, K = len(seqs), len(configs)
+    if not S:
+        return [{"config": c, "results": {}, "summary": None} for c in configs]
+    resolved = [_resolve(c) for c in configs]
+    params = [r[0] for r in resolved]
+    eng = OcsortTableEngine(n_seq=K * S, track_cap=resolved[0][1], det_cap=resolved[0][2],
+                       params=params[0])
+    feed = None
+    try:
+        fids = [np.asarray(frame_ids[nm]) if frame_ids and nm in frame_ids else s.frame_ids
+                for nm, s in zip(names, seqs)]
+        dets, tables = [], []
+        for s, f in zip(seqs, fids):
+            start, cnt = np.zeros(len(f), np.int64), np.zeros(len(f), np.int64)
+            for i, x in enumerate(f):
+                j = s._index.get(int(x))
+                if j is not None:
+                    start[i], cnt[i] = s.offsets[j], s.offsets[j + 1] - s.offsets[j]
+            tables.append((start, cnt, np.asarray(f, np.int64)))
+            dets.append(np.asarray(s.dets).astype(np.float32))
+        for k in range(K):
+            eng.set_seq_params(k * S, [params[k]] * S)
+            for q, nm in enumerate(names):
+                if frame_sizes and nm in frame_sizes:
+                    eng.set_frame_size(k * S + q, *frame_sizes[nm])
+        feed = SequenceFeeder(dets * K, [None] * (K * S), tables * K, 0)
+        for t in range(feed.n_frames):
+            runs = feed.schedule[t]
+            if not runs:
+                continue
+            feed.gather(t)
+            for q0, ns, _, pd, po, _, pout, pcnt in runs:
+                eng.step(pd, po, pout, pcnt, seq0=q0, nseq=ns)
+            feed.append(t)
+        if eng.status() != 0:
+            raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
+        rows = feed.results()
+    finally:
+        if feed is not None:
+            feed.close()
+        eng.close()
+    out = []
+    for k, cfg in enumerate(configs):
+        res = {nm: rows[k * S + q].copy() for q, nm in enumerate(names)}
+        if exp_dir is not None:
+            for nm, r in res.items():
+                motio.write_mot_results(Path(exp_dir) / f"{k:04d}" / f"{nm}.txt",
+                                        r if r.size else np.empty((0, 0)))
+        out.append({"config": cfg, "results": res, "summary": None})
+    if gt is not None:
+        for o, summary in zip(out, _score(gt, [o["results"] for o in out], benchmark,
+                                          seq_lengths)):
+            o["summary"] = summary
+    return out
+
+
+def _score(gt: dict, results: list, benchmark: str, seq_lengths) -> list:
+    """mot_summary of every config's results, as ``evaluate_mot(gt, results_k)`` gives it: the
+    gt is parsed once, and one evaluator handle runs once per config."""
+    from . import evaluation as E
+
+    if benchmark not in E.BENCHMARKS:
+        raise ValueError(f"benchmark must be one of {sorted(E.BENCHMARKS)}, got {benchmark!r}")
+    if "COMBINED" in gt:
+        raise ValueError("a sequence cannot be called COMBINED")
+    names, frames, gts, _ = E.prepare_inputs(gt, results[0], seq_lengths)
+    parsed = dict(zip(names, gts))
+    summaries = []
+    ev = E.MotEvaluator()
+    try:
+        for res in results:
+            trs = E.prepare_inputs(parsed, res, seq_lengths)[3]
+            rec = ev.run(frames, gts, trs, E.BENCHMARKS[benchmark])
+            full = {n: E._unpack(rec[k], E.METRICS) for k, n in enumerate(names)}
+            full["COMBINED"] = E._unpack(rec[len(names)], E.METRICS)
+            summaries.append(E.mot_summary(full))
+    finally:
+        ev.close()
+    return summaries

@@ -48,11 +48,22 @@ typedef struct {
     double frame_w, frame_h;
 } bx_ocsort_config;
 
+/* The fields of bx_ocsort_config that size no memory: the ones a sequence may have of its own
+ * (below).  n_seq, track_cap, det_cap, the frame size and the LDS carve stay engine-wide.  max_obs,
+ * which the create call derives from max_age (50, or max_age + 5 from 50 on) and which sizes no
+ * memory either, follows a sequence's own max_age by the same rule. */
+typedef struct {
+    double min_conf, det_thresh, asso_threshold, inertia, q_xy_scaling, q_s_scaling;
+    int32_t max_age, min_hits, delta_t, use_byte;
+    int32_t asso_kind;
+} bx_ocsort_seq_params;
+
 typedef struct bx_ocsort bx_ocsort;
 
 int bx_ocsort_create(const bx_ocsort_config *cfg, bx_ocsort **out);
 int bx_ocsort_destroy(bx_ocsort *e);
-/* Forget all tracks of sequences [seq0, seq0+nseq) (frame and id counters back to 0). */
+/* Forget all tracks of sequences [seq0, seq0+nseq) (frame and id counters back to 0).  Their
+ * per-sequence parameters, when set, stay. */
 int bx_ocsort_reset(bx_ocsort *e, int seq0, int nseq, void *stream);
 /* One frame for sequences [seq0, seq0+nseq) — one kernel launch.
  *   dets    [sum N][6] float32 (x1,y1,x2,y2,conf,cls)
@@ -87,10 +98,28 @@ int bx_kf_xysr_initiate(int n, const double *bbox, double *x, double *P, void *s
 int bx_kf_xysr_predict(int n, double *x, double *P, double q_xy_scaling, double q_s_scaling,
                        void *stream);
 int bx_kf_xysr_update(int n, double *x, double *P, const double *z, void *stream);
+/* Per-sequence parameters: a hyper-parameter sweep runs K configurations x S sequences as K*S
+ * sequences of ONE engine, every launch K*S workgroups wide.  params_host [nseq] gives sequences
+ * [seq0, seq0+nseq) parameters of their own; NULL clears the range, whose sequences then run on
+ * the engine's parameters again.  Every entry is validated as the create call validates the same
+ * fields (delta_t within the 8-slot observation ring, a known asso_kind); an invalid entry, or a
+ * range outside [0, n_seq), returns BX_ERR_INVALID and changes nothing.  The values live in a
+ * device table the frame kernel reads at its entry (uniform loads, once per workgroup) and never
+ * writes; until the first set there is no table and the kernel runs as it always did.  Copies on
+ * `stream`, then synchronises it.
+ * Meant for use between sequences, at frame 0 (after a reset): changing a sequence's parameters
+ * while it holds tracks is allowed, but no reference behaviour is defined for it.  A reset keeps
+ * the table; a state copy (below) carries tracks only, so the destination keeps its own table.
+ * The second entry point reads a sequence's effective parameters back (its entry, or the
+ * engine's when it has none); host memory, no device work. */
+int bx_ocsort_set_seq_params_host(bx_ocsort *e, int seq0, int nseq,
+                                  const bx_ocsort_seq_params *params_host, void *stream);
+int bx_ocsort_seq_params_host(bx_ocsort *e, int seq, bx_ocsort_seq_params *out_host);
 /* Latched device status (BX_OK, BX_ERR_TRACK_OVERFLOW or BX_ERR_CAPACITY). */
 /* Capacity growth (the reference's track list is unbounded: ocsort.py:246-439 (self.active_tracks / KalmanBoxTracker list)): copy every
  * sequence's tracker state of `src` into `dst`, a fresh engine with the same configuration and
- * sequences and track_cap / det_cap at least src's (slot ids stay valid).  Synchronous. */
+ * sequences and track_cap / det_cap at least src's (slot ids stay valid).  Synchronous.  Tracks
+ * only: the per-sequence parameter table is not copied. */
 int bx_ocsort_copy_state(bx_ocsort *dst, bx_ocsort *src);
 int bx_ocsort_status(bx_ocsort *e, int *status);
 int bx_ocsort_counters_host(bx_ocsort *e, int seq, int *frame_count, int *id_count,
