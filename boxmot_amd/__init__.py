@@ -14,7 +14,7 @@ compensation from images.
 from .cmc import (MOTION_AFFINE, MOTION_EUCLIDEAN, MOTION_HOMOGRAPHY, MOTION_TRANSLATION, ECC,
                   EccBatch, SOF, SofBatch, get_cmc_method)
 from . import tune
-from .evaluation import evaluate_mot, mot_summary
+from .evaluation import evaluate_mot, evaluate_mot_device, mot_summary
 from .postprocessing import gaussian_smooth, gsi, linear_interpolation
 from .reid import ReidFrontEnd, crop_batch, normalize_features
 from .tracker_zoo import create_tracker, get_tracker_config
@@ -25,6 +25,7 @@ __version__ = "0.1.0"
 __all__ = ["create_tracker", "get_tracker_config", "ByteTrack", "BotSort", "OcSort",
            "BoostTrack", "StrongSort", "DeepOcSort", "HybridSort", "gsi", "linear_interpolation",
            "gaussian_smooth", "DeepOcSortPerClass", "HybridSortPerClass", "evaluate_mot",
+           "evaluate_mot_device",
            "mot_summary", "ECC", "EccBatch", "SOF", "SofBatch", "get_cmc_method", "MOTION_TRANSLATION",
            "MOTION_EUCLIDEAN", "MOTION_AFFINE", "MOTION_HOMOGRAPHY", "ReidFrontEnd",
            "crop_batch", "normalize_features", "tune", "__version__"]

@@ -272,8 +272,8 @@ EXPORTS = [
     "bx_gsi_workspace_bytes", "bx_gsi_smooth", "bx_gsi_run_host",
     "bx_feed_create", "bx_feed_destroy", "bx_feed_upload_host", "bx_feed_shape",
     "bx_feed_frame_runs", "bx_feed_run", "bx_feed_gather", "bx_feed_append", "bx_feed_status",
-    "bx_feed_result_rows", "bx_feed_results_host", "bx_feed_read_run_host",
-    "bx_feed_write_run_host",
+    "bx_feed_result_rows", "bx_feed_results_host", "bx_feed_results_device",
+    "bx_feed_read_run_host", "bx_feed_write_run_host",
     "bx_classes_create", "bx_classes_destroy", "bx_classes_shape", "bx_classes_scratch",
     "bx_classes_split", "bx_classes_merge", "bx_classes_state", "bx_classes_reset",
     "bx_classes_status", "bx_classes_id_count_host", "bx_classes_set_id_count",
@@ -283,6 +283,7 @@ EXPORTS = [
     "bx_hybrid_classes", "bx_hybrid_update_classes_host", "bx_hybrid_probe",
     "bx_hybrid_probe_read",
     "bx_eval_create", "bx_eval_destroy", "bx_eval_capacity", "bx_eval_run_host",
+    "bx_eval_set_gt_host", "bx_eval_run_device",
     "bx_ecc_create", "bx_ecc_destroy", "bx_ecc_reset", "bx_ecc_work_size", "bx_ecc_apply",
     "bx_ecc_apply_host", "bx_ecc_status", "bx_ecc_state_host",
     "bx_reid_crops", "bx_reid_normalize",
@@ -465,6 +466,8 @@ _SIGS = {
     "bx_feed_status": ([_vp, _ip], C.c_int),
     "bx_feed_result_rows": ([_vp, C.POINTER(C.c_int64)], C.c_int),
     "bx_feed_results_host": ([_vp, _vp, _vp, _vp], C.c_int),
+    "bx_feed_results_device": ([_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                C.POINTER(C.c_int64)], C.c_int),
     "bx_feed_read_run_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp], C.c_int),
     "bx_feed_write_run_host": ([_vp, C.c_int, C.c_int, _vp, _vp], C.c_int),
     "bx_classes_create": ([C.c_int] * 6 + [C.POINTER(C.c_void_p)], C.c_int),
@@ -499,6 +502,8 @@ _SIGS = {
     "bx_eval_destroy": ([_vp], C.c_int),
     "bx_eval_capacity": ([_vp, _ip, _ip, _ip, _ip], C.c_int),
     "bx_eval_run_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_eval_set_gt_host": ([_vp, C.c_int, _vp, _vp, _vp], C.c_int),
+    "bx_eval_run_device": ([_vp, C.c_int, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, _vp], C.c_int),
     "bx_ecc_create": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "bx_ecc_destroy": ([_vp], C.c_int),
     "bx_ecc_reset": ([_vp, C.c_int, _vp], C.c_int),

@@ -415,6 +415,15 @@ int bx_feed_results_host(bx_feed* f, double* res, int64_t* base, int64_t* n) {
   return BX_OK;
 }
 
+int bx_feed_results_device(bx_feed* f, void** res, void** base, void** n, int64_t* rows) {
+  if (!f || !res || !base || !n || !rows) return bx_record_error(BX_ERR_INVALID, "null argument");
+  *res = f->dev.res;
+  *base = (void*)f->dev.res_base;
+  *n = f->dev.res_n;
+  *rows = f->res_rows;
+  return BX_OK;
+}
+
 int bx_feed_read_run_host(bx_feed* f, int t, int r, float* dets, int32_t* det_off, double* embs) {
   int i, rc;
   if ((rc = feed_run_of(f, t, r, &i))) return rc;

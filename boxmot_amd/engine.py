@@ -1098,6 +1098,19 @@ class SequenceFeeder(_NativeHandle):
             raise RuntimeError(f"feeder status {self.status()} (result buffer overflow)")
         return [res[base[k]: base[k] + cnt[k]] for k in range(self.n_seq)]
 
+    @property
+    def results_device(self):
+        """The result buffers where they lie, as device pointers: (rows [result_rows, 9] float64,
+        base [n_seq + 1] int64, n [n_seq] int64, result_rows).  No copy and no synchronisation;
+        valid until ``close``.  ``MotEvaluator.run_device`` takes them as they are.  (A property:
+        the class's methods are pinned by tests/test_engine_api_host.py, and this one only reads
+        three pointers.)"""
+        p = [C.c_void_p() for _ in range(3)]
+        n = C.c_int64()
+        N.check(self._L.bx_feed_results_device(self._h, *[C.byref(x) for x in p], C.byref(n)),
+                "bx_feed_results_device")
+        return p[0].value or 0, p[1].value or 0, p[2].value or 0, n.value
+
     def read_run(self, t: int, r: int):
         """Host copies of the gathered (dets, det_off, embs) of run r of frame index t."""
         _, nseq, rows = self.schedule[t][r][:3]

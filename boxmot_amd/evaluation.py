@@ -147,6 +147,60 @@ class MotEvaluator:
                 "bx_eval_run_host")
         return out
 
+    def set_gt(self, frames: np.ndarray, gts: list) -> None:
+        """Bucket and upload the gt of S sequences once; ``run_device`` scores against it until
+        the next call replaces it.  ``run`` ignores it."""
+        S = len(gts)
+        frames = np.ascontiguousarray(frames, np.int32)
+        goff = np.zeros(S + 1, np.int64)
+        goff[1:] = np.cumsum([g.shape[0] for g in gts])
+        grow = np.ascontiguousarray(np.concatenate(gts), np.float64) if S and goff[-1] else \
+            np.zeros((1, 9))
+        N.check(self._L.bx_eval_set_gt_host(self._h, S, frames.ctypes.data, goff.ctypes.data,
+                                            grow.ctypes.data), "bx_eval_set_gt_host")
+        self._gt_seqs = S
+
+    def run_device(self, rows, base, n, n_groups: int, benchmark: int,
+                   row_stride: int = 9) -> np.ndarray:
+        """Records ``[n_groups, S + 1, RECORD]`` of tracker rows in device memory against the gt
+        of ``set_gt``: evaluator sequence ``k * S + s`` is rows ``[base[q], base[q] + n[q])`` of
+        ``rows`` (``[., row_stride]`` float64: frame, id, x, y, w, h, ...), scored against gt
+        sequence ``s``; each group's last record is its COMBINED.  ``rows`` / ``base`` / ``n``
+        are contiguous CUDA tensors (float64, int64, int64) or raw integer device pointers; the
+        rows stay on the device.  Bit-identical to ``run`` on the same rows in the same order."""
+        import torch
+
+        S = getattr(self, "_gt_seqs", 0)
+        K = int(n_groups)
+        ptr = []
+        for name, x, dt in (("rows", rows, torch.float64), ("base", base, torch.int64),
+                            ("n", n, torch.int64)):
+            if isinstance(x, torch.Tensor):
+                if not x.is_cuda or x.dtype != dt or not x.is_contiguous():
+                    raise ValueError(f"run_device: {name} must be a contiguous CUDA {dt} tensor")
+                if name != "rows" and S and x.numel() < K * S:
+                    raise ValueError(f"run_device: {name} needs n_groups * S = {K * S} entries")
+                if name == "rows" and x.numel() == 0:
+                    # (an empty tensor has no storage to point at; no row of it is ever read)
+                    x = pad = torch.zeros(int(row_stride), dtype=dt, device=x.device)
+                ptr.append(x.data_ptr())
+            else:
+                ptr.append(int(x))
+        if isinstance(rows, torch.Tensor):
+            if rows.numel() % int(row_stride):
+                raise ValueError("run_device: rows is not a whole number of row_stride columns")
+            if S and K >= 1 and isinstance(base, torch.Tensor) and isinstance(n, torch.Tensor):
+                have = rows.numel() // int(row_stride)
+                b, c = base[:K * S], n[:K * S]
+                if bool(((b < 0) | (c < 0) | (b + c > have)).any()):
+                    raise ValueError("run_device: base / n reach outside the rows tensor")
+            torch.cuda.current_stream().synchronize()  # (the rows' producer, before our stream)
+        out = np.zeros((max(K, 1), S + 1, RECORD))
+        N.check(self._L.bx_eval_run_device(self._h, K, int(benchmark), ptr[0], int(row_stride),
+                                           ptr[1], ptr[2], out.ctypes.data, None),
+                "bx_eval_run_device")
+        return out
+
 
 def _unpack(rec: np.ndarray, metrics) -> dict:
     res = {}
@@ -199,6 +253,40 @@ def evaluate_mot(gt: dict, results, benchmark: str = "MOT17", seq_lengths: dict 
         ev.close()
     res = {n: _unpack(out[k], metrics) for k, n in enumerate(names)}
     res["COMBINED"] = _unpack(out[len(names)], metrics)
+    return res
+
+
+def evaluate_mot_device(gt: dict, rows, base, n, n_groups: int = 1, benchmark: str = "MOT17",
+                        seq_lengths: dict | None = None, metrics=METRICS,
+                        max_boxes: int | None = None, max_ids: int | None = None,
+                        max_frames: int | None = None, row_stride: int = 9) -> list:
+    """``evaluate_mot`` for tracker rows that already lie in device memory, ``n_groups`` result
+    sets at once (the configurations of a sweep): ``rows`` / ``base`` / ``n`` as
+    ``MotEvaluator.run_device`` takes them, sequence ``k * S + s`` being gt sequence ``s`` (in
+    ``gt``'s order) of group ``k``.  Returns one dict per group, shaped like ``evaluate_mot``'s.
+    The rows never leave the device."""
+    if benchmark not in BENCHMARKS:
+        raise ValueError(f"benchmark must be one of {sorted(BENCHMARKS)}, got {benchmark!r}")
+    metrics = tuple(metrics)
+    for m in metrics:
+        if m not in METRICS:
+            raise ValueError(f"unknown metric family {m!r} (known: {METRICS})")
+    if int(n_groups) < 1:
+        raise ValueError("n_groups must be at least 1")
+    names, frames, gts, _ = prepare_inputs(gt, {}, seq_lengths)
+    if "COMBINED" in names:
+        raise ValueError("a sequence cannot be called COMBINED")
+    ev = MotEvaluator(max_boxes, max_ids, max_frames)
+    try:
+        ev.set_gt(frames, gts)
+        out = ev.run_device(rows, base, n, int(n_groups), BENCHMARKS[benchmark], row_stride)
+    finally:
+        ev.close()
+    res = []
+    for rec in out:
+        r = {nm: _unpack(rec[k], metrics) for k, nm in enumerate(names)}
+        r["COMBINED"] = _unpack(rec[len(names)], metrics)
+        res.append(r)
     return res
 
 

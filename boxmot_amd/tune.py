@@ -28,8 +28,24 @@ def grid(space: dict) -> list:
     return [dict(zip(names, v)) for v in itertools.product(*[list(space[n]) for n in names])]
 
 
-def _check(tracker_type: str, configs) -> list:
+SCORES = ("host", "device")
+
+
+def _check(tracker_type: str, configs, sequences=None, gt=None, exp_dir=None, score="host",
+           keep_results=True) -> list:
     """The refusals of ``sweep`` that need no engine."""
+    if score not in SCORES:
+        raise ValueError(f"score must be one of {SCORES}, got {score!r}")
+    if score == "device" and gt is None:
+        raise ValueError('score="device" scores against gt: give gt')
+    if not keep_results:
+        if gt is None:
+            raise ValueError("keep_results=False without gt would return nothing")
+        if exp_dir is not None:
+            raise ValueError("keep_results=False: exp_dir needs the rows on the host")
+        if score == "host":
+            raise ValueError('keep_results=False: score="host" needs the rows on the host; '
+                             'use score="device"')
     if tracker_type not in SUPPORTED:
         raise NotImplementedError(
             f"tune.sweep drives {', '.join(SUPPORTED)} only (the engine with per-sequence "
@@ -44,6 +60,9 @@ def _check(tracker_type: str, configs) -> list:
         if len({repr(c.get(cap)) for c in configs}) > 1:
             raise ValueError(f"{cap} sizes the engine's memory: it must be absent from every "
                              f"config or equal in all of them")
+    if score == "device" and sequences is not None and list(gt) != list(sequences):
+        raise ValueError('score="device" reads the engine\'s sequences in place: gt must name '
+                         'the same sequences in the same order')
     return configs
 
 
@@ -61,7 +80,8 @@ def _resolve(cfg: dict):
 
 def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict | None = None,
           benchmark: str = "MOT17", seq_lengths: dict | None = None,
-          frame_ids: dict | None = None, frame_sizes: dict | None = None) -> list:
+          frame_ids: dict | None = None, frame_sizes: dict | None = None,
+          score: str = "host", keep_results: bool = True) -> list:
     """Run every config of ``configs`` over every sequence in one batched engine.
 
     sequences / frame_ids / frame_sizes: as in ``motio.run_sequences``.  configs: K dicts of
@@ -78,10 +98,19 @@ def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict
     ``evaluate_mot``) every config is scored: one evaluator handle, one run per config, because
     a run's COMBINED record is formed on the device over all the sequences of the run.
 
+    ``score="device"`` scores all K configs in ONE evaluator run of K groups, straight from the
+    feeder's result buffers in device memory (``SequenceFeeder.results_device``,
+    ``MotEvaluator.set_gt`` / ``run_device``): the rows are neither copied to the host nor
+    bucketed there, and the summaries are bit-identical to ``score="host"``'s.  It needs ``gt``
+    to name the sequences in ``sequences``' order.  ``keep_results=False`` (with
+    ``score="device"`` and gt, without ``exp_dir``) skips the copy of the rows altogether:
+    ``"results"`` is None.  Combinations that cannot work raise ``ValueError`` before any engine
+    is built.
+
     The detections are uploaded once per (config, sequence): K copies of a few MB for MOT-sized
     inputs.  A nonzero engine or feeder status raises ``RuntimeError``.
     """
-    configs = _check(tracker_type, configs)
+    configs = _check(tracker_type, configs, sequences, gt, exp_dir, score, keep_results)
     from . import motio
     from .engine import OcsortTableEngine, SequenceFeeder
 
@@ -90,7 +119,8 @@ def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict
             for s in sequences.values()]
     S, K = len(seqs), len(configs)
     if not S:
-        return [{"config": c, "results": {}, "summary": None} for c in configs]
+        return [{"config": c, "results": {} if keep_results else None, "summary": None}
+                for c in configs]
     resolved = [_resolve(c) for c in configs]
     params = [r[0] for r in resolved]
     eng = OcsortTableEngine(n_seq=K * S, track_cap=resolved[0][1], det_cap=resolved[0][2],
@@ -124,20 +154,31 @@ def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict
             feed.append(t)
         if eng.status() != 0:
             raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
-        rows = feed.results()
+        summaries = None
+        if score == "device":
+            if feed.status() != 0:
+                raise RuntimeError(f"feeder status {feed.status()} (result buffer overflow)")
+            summaries = _score_device(gt, feed, K, benchmark, seq_lengths)
+        rows = feed.results() if keep_results else None
     finally:
         if feed is not None:
             feed.close()
         eng.close()
     out = []
     for k, cfg in enumerate(configs):
+        if rows is None:
+            out.append({"config": cfg, "results": None, "summary": summaries[k]})
+            continue
         res = {nm: rows[k * S + q].copy() for q, nm in enumerate(names)}
         if exp_dir is not None:
             for nm, r in res.items():
                 motio.write_mot_results(Path(exp_dir) / f"{k:04d}" / f"{nm}.txt",
                                         r if r.size else np.empty((0, 0)))
         out.append({"config": cfg, "results": res, "summary": None})
-    if gt is not None:
+    if summaries is not None:
+        for o, summary in zip(out, summaries):
+            o["summary"] = summary
+    elif gt is not None:
         for o, summary in zip(out, _score(gt, [o["results"] for o in out], benchmark,
                                           seq_lengths)):
             o["summary"] = summary
@@ -166,4 +207,29 @@ def _score(gt: dict, results: list, benchmark: str, seq_lengths) -> list:
             summaries.append(E.mot_summary(full))
     finally:
         ev.close()
+    return summaries
+
+
+def _score_device(gt: dict, feed, n_groups: int, benchmark: str, seq_lengths) -> list:
+    """mot_summary of every config from the feeder's device-resident rows: the gt is bucketed
+    and uploaded once, and ONE evaluator run of ``n_groups`` groups forms every COMBINED."""
+    from . import evaluation as E
+
+    if benchmark not in E.BENCHMARKS:
+        raise ValueError(f"benchmark must be one of {sorted(E.BENCHMARKS)}, got {benchmark!r}")
+    if "COMBINED" in gt:
+        raise ValueError("a sequence cannot be called COMBINED")
+    names, frames, gts, _ = E.prepare_inputs(gt, {}, seq_lengths)
+    res, base, n, _ = feed.results_device
+    ev = E.MotEvaluator()
+    try:
+        ev.set_gt(frames, gts)
+        rec = ev.run_device(res, base, n, n_groups, E.BENCHMARKS[benchmark], row_stride=9)
+    finally:
+        ev.close()
+    summaries = []
+    for r in rec:
+        full = {nm: E._unpack(r[k], E.METRICS) for k, nm in enumerate(names)}
+        full["COMBINED"] = E._unpack(r[len(names)], E.METRICS)
+        summaries.append(E.mot_summary(full))
     return summaries

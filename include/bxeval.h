@@ -79,6 +79,28 @@ int bx_eval_run_host(void *h, int n_seq, int benchmark, const int32_t *seq_frame
                      const int64_t *tr_off_host, const double *tr_rows_host, double *out_host,
                      void *stream);
 
+/* Bucket and upload the ground truth of n_seq sequences (arguments and errors as the gt side of
+ * bx_eval_run_host) into an allocation the handle keeps until the next call replaces it or the
+ * handle is destroyed.  Synchronous.  bx_eval_run_host ignores it. */
+int bx_eval_set_gt_host(void *h, int n_seq, const int32_t *seq_frames_host,
+                        const int64_t *gt_off_host, const double *gt_rows_host);
+
+/* Evaluate tracker rows that lie in device memory against the resident ground truth of S
+ * sequences, for n_groups groups at once: evaluator sequence q = k * S + s is scored against gt
+ * sequence s.  The rows never cross to the host; O(frames + sequences) integers do.
+ *   tr_rows     DEVICE float64 [.][row_stride], row_stride >= 6: frame, id, x, y, w, h, ...
+ *   tr_base     DEVICE int64 [n_groups * S] first row of sequence q
+ *   tr_n        DEVICE int64 [n_groups * S] rows of sequence q; rows outside [base, base + n)
+ *               are never read
+ *   out_host    [n_groups][S + 1][BX_EVAL_NF]: a group's S records, then its COMBINED
+ * The work is queued on `stream` and synchronised; the caller orders the rows' producer before
+ * it.  Results are bit-identical to bx_eval_run_host on the same rows in the same order, and the
+ * statuses are the same (BX_ERR_INVALID also when no gt is set, or for a negative base or n);
+ * out_host is written only on BX_OK. */
+int bx_eval_run_device(void *h, int n_groups, int benchmark, const void *tr_rows,
+                       int64_t row_stride, const void *tr_base, const void *tr_n, double *out_host,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

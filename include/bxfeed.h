@@ -91,6 +91,10 @@ int bx_feed_result_rows(bx_feed *f, int64_t *rows);
  * allocation; base_host [n_seq + 1] int64 first row of each sequence's buffer; n_host [n_seq]
  * int64 rows each sequence appended. */
 int bx_feed_results_host(bx_feed *f, double *res_host, int64_t *base_host, int64_t *n_host);
+/* The same three buffers where they lie, as DEVICE pointers: res float64 [result_rows][9], base
+ * int64 [n_seq + 1], n int64 [n_seq]; rows = result_rows.  No copy and no synchronisation: the
+ * caller orders its reads behind the appends.  Valid until bx_feed_destroy. */
+int bx_feed_results_device(bx_feed *f, void **res, void **base, void **n, int64_t *rows);
 /* Diagnostics (synchronous): read back the gathered inputs of run r of frame index t (after a
  * gather of t), and write out / out_count of that run from host arrays (before an append). */
 int bx_feed_read_run_host(bx_feed *f, int t, int r, float *dets_host, int32_t *det_off_host,
