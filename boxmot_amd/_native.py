@@ -286,6 +286,7 @@ EXPORTS = [
     "bx_eval_set_gt_host", "bx_eval_run_device",
     "bx_ecc_create", "bx_ecc_destroy", "bx_ecc_reset", "bx_ecc_work_size", "bx_ecc_apply",
     "bx_ecc_apply_host", "bx_ecc_status", "bx_ecc_state_host",
+    "bx_ecc_chain_reserve", "bx_ecc_apply_chain", "bx_ecc_apply_chain_host",
     "bx_reid_crops", "bx_reid_normalize",
     "bx_sof_create", "bx_sof_destroy", "bx_sof_reset", "bx_sof_levels", "bx_sof_apply",
     "bx_sof_apply_host", "bx_sof_status", "bx_sof_pyramid_bytes", "bx_sof_state_host",
@@ -512,6 +513,12 @@ _SIGS = {
                       C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "bx_ecc_apply_host": ([_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_double,
                            C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_ecc_chain_reserve": ([_vp, C.c_int], C.c_int),
+    "bx_ecc_apply_chain": ([_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
+                            C.c_double, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_ecc_apply_chain_host": ([_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int,
+                                 C.c_double, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp],
+                                C.c_int),
     "bx_ecc_status": ([_vp, _ip], C.c_int),
     "bx_ecc_state_host": ([_vp, C.c_int, _ip, _ip, _ip, _vp, _vp, _vp], C.c_int),
     "bx_reid_crops": ([_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int]

@@ -8,7 +8,9 @@ is the contract): a preprocessing kernel in exact integer arithmetic and one per
 per camera that runs the whole ECC iteration in fp64.  ``ECC`` is the reference's class for one
 camera (``tracker.cmc = ECC()``); ``EccBatch`` aligns many cameras per call and returns the warps
 as the device tensor the engines' ``warps`` argument takes (no host synchronisation when its
-inputs are on the device).  There is no CPU fallback: without the
+inputs are on the device).  ``EccChain`` aligns many consecutive frames of a camera per call and
+``warp_table`` builds from it the warps of every stepped frame of a set of sequences, for the file
+flow (``motio.run_sequences``).  There is no CPU fallback: without the
 library or a HIP device the calls raise ``NativeUnavailable``.
 
 ``SOF`` / ``SofBatch`` replace ``motion/cmc/sof.py:64-160`` the same way (``include/bxsof.h``;
@@ -312,6 +314,293 @@ class ECC:
         self.last = {"warp": warp.reshape(2, 3).copy(), "rho": float(rho[0]),
                      "iterations": int(iters[0]), "code": int(code[0])}
         return warp.reshape(2, 3).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------ chained ECC
+class EccChain:
+    """ECC over many consecutive frames of a camera per call (``bx_ecc_apply_chain``; DESIGN.md
+    2.19): frame i of a call is aligned to frame i - 1 when both are of one stream, otherwise to
+    its stream's stored previous image, one workgroup per pair.  Warps, rho, iterations, codes and
+    the streams' final state are bit for bit those of ``EccBatch.apply`` called one frame at a
+    time.
+
+    ``batch`` is the ``EccBatch`` whose handle the chain shares: ``chain.batch.apply`` is the
+    plain apply on the same streams, and the two may be mixed.  ``max_frames`` bounds a call's
+    frames (``reserve`` grows it); the other arguments are ``EccBatch``'s."""
+
+    def __init__(self, n_streams: int, max_frames: int = 64, warp_mode: int = MOTION_TRANSLATION,
+                 eps: float = 1e-5, max_iter: int = 100, scale=0.15, grayscale: bool = True,
+                 max_h: int | None = None, max_w: int | None = None):
+        if max_frames < 1:
+            raise ValueError("max_frames must be at least 1")
+        self.batch = EccBatch(n_streams, warp_mode, eps, max_iter, scale, False, grayscale,
+                              max_h, max_w)
+        self.n_streams = self.batch.n_streams
+        self.max_frames = int(max_frames)
+        self._reserved = 0
+        self._keep = None
+
+    def _ensure(self, H: int, W: int) -> _Handle:
+        hd = self.batch._ensure(H, W)
+        if self._reserved < self.max_frames:
+            N.check(hd._L.bx_ecc_chain_reserve(hd._h, self.max_frames), "bx_ecc_chain_reserve")
+            self._reserved = self.max_frames
+        return hd
+
+    def reserve(self, max_frames: int):
+        """Room for ``max_frames`` frames per call (never shrinks)."""
+        self.max_frames = max(self.max_frames, int(max_frames))
+        if self.batch._handle is not None:
+            self._ensure(0, 0)
+
+    def close(self):
+        self.batch.close()
+        self._reserved = 0
+
+    def reset(self, stream: int = -1):
+        self.batch.reset(stream)
+
+    def status(self) -> int:
+        return self.batch.status()
+
+    def state(self, stream: int = 0):
+        return self.batch.state(stream)
+
+    def _frames(self, frames):
+        import torch
+
+        b = self.batch
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8:
+                raise ValueError("frames must be uint8")
+            dims = _frame_dims(frames.shape, b.grayscale)
+            return torch.from_numpy(np.ascontiguousarray(frames)).cuda(), dims
+        if frames.dtype != torch.uint8 or not frames.is_cuda:
+            raise ValueError("frames must be a numpy array or a CUDA uint8 tensor")
+        return frames.contiguous(), _frame_dims(frames.shape, b.grayscale)
+
+    def apply(self, frames, streams, dst=None, out=None):
+        """frames: numpy array or CUDA uint8 tensor ``[n, H, W, 3]`` (BGR) or ``[n, H, W]``
+        (grey); streams: the stream of each frame, the frames of one stream adjacent and in time
+        order.  A list or numpy ``streams`` is checked here (range, adjacency: ``ValueError``); a
+        CUDA tensor is not: an index out of range skips its frame and latches ``status()``, a
+        stream in two separate groups is undefined behaviour (in bounds).
+
+        Frame i writes row ``dst[i]`` (default: row i) of ``out``, the tuple ``(warps [rows, 6]
+        float64, rho [rows] float64, iterations [rows] int32, code [rows] int32)`` of CUDA
+        tensors; other rows are untouched.  Without ``out`` fresh ``[n]``-row tensors are made
+        (identity, 0, 0, ``NO_FRAME``).  Returns ``out``.  With device inputs nothing inside
+        synchronises the host with the device."""
+        import torch
+
+        from .engine import _current_stream
+
+        b = self.batch
+        mode = _check_mode(b.warp_mode)
+        scale = _scale_arg(b.scale)
+        frames, (n, H, W, ch) = self._frames(frames)
+        hd = self._ensure(H, W)
+        S = self.n_streams
+        if isinstance(streams, torch.Tensor) and streams.is_cuda:
+            sd = streams.to(torch.int32).contiguous()
+        else:
+            sh = np.asarray(streams, np.int64).reshape(-1)
+            if sh.size and (sh.min() < 0 or sh.max() >= S):
+                raise ValueError("invalid argument: stream index out of range")
+            starts = sh[np.r_[True, sh[1:] != sh[:-1]]] if sh.size else sh
+            if np.unique(starts).size != starts.size:
+                raise ValueError("invalid argument: the frames of a stream are not adjacent")
+            sd = torch.from_numpy(sh.astype(np.int32)).cuda()
+        if sd.numel() != n:
+            raise ValueError(f"{n} frames but {sd.numel()} stream indices")
+        if out is None:
+            if dst is not None:
+                raise ValueError("dst needs the out tensors it points into")
+            warps = torch.zeros(n, 6, dtype=torch.float64, device="cuda")
+            warps[:, 0] = 1.0
+            warps[:, 4] = 1.0
+            out = (warps, torch.zeros(n, dtype=torch.float64, device="cuda"),
+                   torch.zeros(n, dtype=torch.int32, device="cuda"),
+                   torch.full((n,), NO_FRAME, dtype=torch.int32, device="cuda"))
+        warps, rho, iters, code = out
+        rows = int(rho.numel())
+        want = ((warps, torch.float64, rows * 6), (rho, torch.float64, rows),
+                (iters, torch.int32, rows), (code, torch.int32, rows))
+        for t, dt, ne in want:
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == ne):
+                raise ValueError("out must be contiguous CUDA tensors: warps [rows, 6] float64, "
+                                 "rho float64, iterations int32, code int32 [rows]")
+        dd = None
+        if dst is None:
+            if n > rows:
+                raise ValueError(f"{n} frames but {rows} result rows")
+        elif isinstance(dst, torch.Tensor) and dst.is_cuda:
+            dd = dst.to(torch.int64).contiguous()
+        else:
+            dh = np.asarray(dst, np.int64).reshape(-1)
+            if dh.size and (dh.min() < 0 or dh.max() >= rows):
+                raise ValueError("invalid argument: dst row out of range")
+            dd = torch.from_numpy(dh).cuda()
+        if dd is not None and dd.numel() != n:
+            raise ValueError(f"{n} frames but {dd.numel()} dst rows")
+        N.check(hd._L.bx_ecc_apply_chain(
+            hd._h, n, H, W, ch, frames.data_ptr(), sd.data_ptr(),
+            None if dd is None else dd.data_ptr(), mode, b.eps, b.max_iter, scale,
+            warps.data_ptr(), rho.data_ptr(), iters.data_ptr(), code.data_ptr(),
+            _current_stream()), "bx_ecc_apply_chain")
+        self._keep = (frames, sd, dd)  # alive until the next call: the launches are asynchronous
+        return out
+
+    def apply_host(self, frames, streams):
+        """The host entry (``bx_ecc_apply_chain_host``): numpy ``frames`` and ``streams`` in,
+        numpy ``(warps [n, 6], rho, iterations, code)`` out, one synchronisation.  The library
+        itself refuses a stream index out of range or a stream whose frames are not adjacent
+        (``ValueError``, nothing launched)."""
+        from .engine import _current_stream
+
+        b = self.batch
+        mode = _check_mode(b.warp_mode)
+        scale = _scale_arg(b.scale)
+        frames = np.ascontiguousarray(frames)
+        if frames.dtype != np.uint8:
+            raise ValueError("frames must be uint8")
+        n, H, W, ch = _frame_dims(frames.shape, b.grayscale)
+        sh = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
+        if sh.size != n:
+            raise ValueError(f"{n} frames but {sh.size} stream indices")
+        hd = self._ensure(H, W)
+        warps, rho = np.zeros((n, 6), np.float64), np.zeros(n, np.float64)
+        iters, code = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        N.check(hd._L.bx_ecc_apply_chain_host(
+            hd._h, n, H, W, ch, frames.ctypes.data, sh.ctypes.data, mode, b.eps, b.max_iter,
+            scale, warps.ctypes.data, rho.ctypes.data, iters.ctypes.data, code.ctypes.data,
+            _current_stream()), "bx_ecc_apply_chain_host")
+        return warps, rho, iters, code
+
+
+NOT_STEPPED = -1  # a warp table's code for a frame its sequence is not stepped at
+
+
+def chain_plan(stepped, sizes, chunk: int = 64) -> list:
+    """The calls that chain every stepped frame of S sequences, a pure function of its arguments.
+
+    stepped: per sequence a bool mask over its iterated frames; sizes: per sequence its frame
+    size, any hashable (``None`` is fine for a sequence that is never stepped).  Returns a list of
+    ``(size, seq, t)`` with ``seq`` and ``t`` int64 arrays of at most ``chunk`` entries: frame
+    ``t[i]`` of sequence ``seq[i]`` is frame i of that call.  Sequences are grouped by size, in
+    order of first appearance; within a group the sequences' stepped frames are laid end to end
+    (sequence by sequence, each in time order) and cut every ``chunk`` frames, so a call never
+    mixes sizes, each sequence is one contiguous run of a call, and a sequence cut by a call's
+    end goes on at the start of the next one, from the state the first left."""
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    if len(stepped) != len(sizes):
+        raise ValueError("one size per sequence")
+    groups = {}
+    for k, m in enumerate(stepped):
+        ts = np.flatnonzero(np.asarray(m, bool).reshape(-1))
+        if ts.size:
+            groups.setdefault(sizes[k], []).append((k, ts))
+    calls = []
+    for size, members in groups.items():
+        seq = np.concatenate([np.full(ts.size, k, np.int64) for k, ts in members])
+        t = np.concatenate([ts for _, ts in members]).astype(np.int64)
+        for a in range(0, seq.size, chunk):
+            calls.append((size, seq[a: a + chunk], t[a: a + chunk]))
+    return calls
+
+
+class WarpTable:
+    """The warps of every iterated frame of S sequences in device memory, frame-major:
+    ``warps [T, S, 6]`` float64, ``rho [T, S]`` float64, ``iterations`` and ``code [T, S]`` int32
+    (CUDA tensors).  The warps of the sequences ``[seq0, seq0 + nseq)`` at frame index t are the
+    contiguous block at ``(t * S + seq0) * 6``: what every engine's ``step(..., warps, ...)``
+    takes.  A frame its sequence is not stepped at holds the identity and ``NOT_STEPPED``."""
+
+    def __init__(self, warps, rho, iterations, code):
+        self.warps, self.rho, self.iterations, self.code = warps, rho, iterations, code
+        self.n_frames, self.n_seq = int(warps.shape[0]), int(warps.shape[1])
+
+    def host(self) -> dict:
+        """Numpy copies (synchronises)."""
+        return {k: getattr(self, k).cpu().numpy() for k in ("warps", "rho", "iterations", "code")}
+
+    def close(self):
+        self.warps = self.rho = self.iterations = self.code = None
+
+
+def _empty_table(T: int, S: int) -> WarpTable:
+    import torch
+
+    warps = torch.zeros(T, S, 6, dtype=torch.float64, device="cuda")
+    warps[:, :, 0] = 1.0
+    warps[:, :, 4] = 1.0
+    return WarpTable(warps, torch.zeros(T, S, dtype=torch.float64, device="cuda"),
+                     torch.zeros(T, S, dtype=torch.int32, device="cuda"),
+                     torch.full((T, S), NOT_STEPPED, dtype=torch.int32, device="cuda"))
+
+
+def warp_table(images, stepped, *, warp_mode: int = MOTION_TRANSLATION, eps: float = 1e-5,
+               max_iter: int = 100, scale=0.15, chunk: int = 64) -> WarpTable:
+    """The ECC warp of every stepped frame of S sequences, computed by chained calls of at most
+    ``chunk`` frames (``chain_plan``) and left in device memory.
+
+    images: per sequence a uint8 array ``[frames, H, W]`` or ``[frames, H, W, 3]`` (BGR) over
+    the frames the sequence iterates, or a callable ``index -> frame`` (``[H, W]`` or ``[H, W,
+    3]``, index the position among the iterated frames); only stepped frames are read.  stepped:
+    per sequence a bool mask over its iterated frames.  The template of a stepped frame is the
+    previous stepped frame of its sequence (the reference runs its CMC inside ``update`` only);
+    a sequence's first stepped frame has code ``FIRST_FRAME``.  The defaults are ``ECC()``'s.  A
+    call stages ``chunk`` whole frames on the host and on the device."""
+    mode = _check_mode(warp_mode)
+    _scale_arg(scale)
+    S = len(images)
+    if len(stepped) != S:
+        raise ValueError(f"{S} image sources but {len(stepped)} stepped masks")
+    stepped = [np.asarray(m, bool).reshape(-1) for m in stepped]
+    first = {}  # a callable's first stepped frame, read for its size and used once
+
+    def fetch(k: int, t: int) -> np.ndarray:
+        if k in first and first[k][0] == t:
+            return first.pop(k)[1]
+        src = images[k]
+        f = np.asarray(src(int(t)) if callable(src) else src[int(t)])
+        if f.dtype != np.uint8 or f.ndim not in (2, 3) or (f.ndim == 3 and f.shape[2] != 3):
+            raise ValueError(f"sequence {k}: frames must be uint8 [H, W] or [H, W, 3]")
+        return f
+
+    sizes = []
+    for k, m in enumerate(stepped):
+        if not callable(images[k]) and len(images[k]) < m.size:
+            raise ValueError(f"sequence {k}: {len(images[k])} frames for a mask of {m.size}")
+        if not m.any():
+            sizes.append(None)
+            continue
+        t0 = int(np.flatnonzero(m)[0])
+        first[k] = (t0, fetch(k, t0))
+        sizes.append(first[k][1].shape)
+    calls = chain_plan(stepped, sizes, chunk)
+    tab = _empty_table(max([m.size for m in stepped] + [0]), S)
+    if not calls:
+        return tab
+    work = [work_size(sz[0], sz[1], scale) for sz in sizes if sz is not None]
+    ecc = EccChain(S, max_frames=max(c[1].size for c in calls), warp_mode=mode, eps=eps,
+                   max_iter=max_iter, scale=scale, max_h=max(h for h, _ in work),
+                   max_w=max(w for _, w in work))
+    try:
+        out = (tab.warps.view(-1, 6), tab.rho.view(-1), tab.iterations.view(-1),
+               tab.code.view(-1))
+        for size, seq, t in calls:
+            frames = np.stack([fetch(int(k), int(x)) for k, x in zip(seq, t)])
+            if frames.shape[1:] != tuple(size):
+                raise ValueError(f"sequence {int(seq[0])}: frames of more than one size")
+            ecc.apply(frames, seq, dst=t * S + seq, out=out)
+        st = ecc.status()  # (synchronises: the staged frames may go)
+        if st != 0:
+            raise RuntimeError(f"ecc status {st}")
+    finally:
+        ecc.close()
+    return tab
 
 
 # per-stream result codes of the sparse optical flow (include/bxsof.h); SOF_NO_FRAME is SofBatch's

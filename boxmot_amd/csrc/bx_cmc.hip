@@ -43,9 +43,22 @@ struct CmDev {
   int* status;                // latched BX_ERR_*
 };
 
+// Scratch of the chained apply (bx_ecc_chain_reserve): one slot per frame of a call, each the
+// planes a stream has for its new image, with the same cap stride.
+struct CmChain {
+  int max_frames;
+  uint8_t* grey;         // [max_frames][cap]
+  float *curf, *gx, *gy;  // [max_frames][cap]
+};
+
 struct CmHandle {
   CmDev d{};
+  CmChain c{};
   int max_h = 0, max_w = 0;
+  // staging of the chained host entry ([max_frames] each, grown with the slots)
+  int32_t* cstreams = nullptr;
+  double *cwarps = nullptr, *crho = nullptr;
+  int32_t *citers = nullptr, *ccode = nullptr;
   // staging of the host entry (grown to the largest call)
   uint8_t* sframes = nullptr;
   size_t sframes_bytes = 0;
@@ -373,7 +386,174 @@ __global__ __launch_bounds__(ET) void cmc_ecc_kernel(CmDev d, EccArgs a) {
   for (int idx = tid; idx < npix; idx += ET) P[idx] = C[idx];
 }
 
+// ------------------------------------------------------------------------------------------
+// the chained apply: n frames per call, frame i aligned to frame i - 1 of the
+// call when both are of one stream, else to the stream's stored previous image.  Three launches:
+//   cmc_chain_prep_kernel      cmc_prep_kernel writing slot i instead of the stream's planes
+//   cmc_ecc_chain_kernel       cmc_ecc_kernel reading its template from slot i - 1 or d.prev and
+//                              its image from slot i; it writes results only, never the state
+//   cmc_chain_handover_kernel  the last frame of every stream becomes that stream's state.  It
+//                              is a launch of its own because the workgroup of a stream's first
+//                              frame reads d.prev for its whole loop: no workgroup of the solve
+//                              may write it.
+__global__ __launch_bounds__(PT) void cmc_chain_prep_kernel(CmDev d, CmChain c, PrepArgs a) {
+  const int k = blockIdx.y;
+  const int s = a.streams[k];
+  if (s < 0 || s >= d.n_streams) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) atomicMax(d.status, (int)BX_ERR_INVALID);
+    return;
+  }
+  const int idx = blockIdx.x * PT + threadIdx.x;
+  if (idx >= a.h * a.w) return;
+  const int x = idx % a.w, y = idx / a.w;
+  const uint8_t* f = a.frames + (size_t)k * a.H * a.W * a.ch;
+  const unsigned g = work_pixel(a, f, x, y);
+  const int xl = reflect101(x - 1, a.w), xr = reflect101(x + 1, a.w);
+  const int yu = reflect101(y - 1, a.h), yd = reflect101(y + 1, a.h);
+  const float l = (float)work_pixel(a, f, xl, y), r = (float)work_pixel(a, f, xr, y);
+  const float u = (float)work_pixel(a, f, x, yu), dn = (float)work_pixel(a, f, x, yd);
+  const size_t o = (size_t)k * d.cap + idx;
+  c.grey[o] = (uint8_t)g;
+  c.curf[o] = (float)g;
+  c.gx[o] = 0.5f * (r - l);
+  c.gy[o] = 0.5f * (dn - u);
+}
+
+struct ChainArgs {
+  const int32_t* streams;  // [n]
+  const int64_t* dst;      // [n] result row of each frame, or null: row i
+  int h, w, max_iter;
+  double eps, scale;
+  double *warps, *rho;
+  int32_t *iters, *code;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(ET) void cmc_ecc_chain_kernel(CmDev d, CmChain ch, ChainArgs a) {
+  constexpr int K = Model<MODE>::K, NS = Model<MODE>::NS;
+  constexpr int NR = MODE == BX_ECC_AFFINE ? 6 + 3 * K : NS;  // sums of the largest pass
+  __shared__ double red[EW * NR];
+  __shared__ double tot[NS];
+  __shared__ double sm[8];  // warp (6), angle
+  __shared__ int ctl;
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x;
+  const int s = a.streams[i];
+  if (s < 0 || s >= d.n_streams) return;  // (latched by the prep kernel)
+  const bool chained = i > 0 && a.streams[i - 1] == s;
+  const int w = a.w, h = a.h;
+  const size_t base = (size_t)i * d.cap;
+  const uint8_t* T = chained ? ch.grey + (size_t)(i - 1) * d.cap : d.prev + (size_t)s * d.cap;
+  const float *I = ch.curf + base, *GX = ch.gx + base, *GY = ch.gy + base;
+
+  // thread 0's loop state
+  double rho = -1.0, last_rho = -a.eps;
+  int it = 0;
+  if (tid == 0) {
+    for (int q = 0; q < 6; q++) sm[q] = (q == 0 || q == 4) ? 1.0 : 0.0;
+    sm[6] = asin(sm[3]);
+    int c;
+    if (!chained && !d.has_prev[s]) {
+      c = CTL_FIRST;
+    } else if (!chained && (d.ph[s] != h || d.pw[s] != w)) {
+      atomicMax(d.status, (int)BX_ERR_SHAPE);
+      c = CTL_FIRST;
+    } else {
+      c = (1 <= a.max_iter && fabs(rho - last_rho) >= a.eps) ? CTL_RUN : CTL_DONE;
+    }
+    ctl = c;
+  }
+  __syncthreads();
+  int c = ctl;
+  while (c == CTL_RUN) {
+    if (MODE == BX_ECC_AFFINE) {
+      ecc_pass<MODE, 1>(T, I, GX, GY, w, h, sm, red, tot);
+      ecc_pass<MODE, 2>(T, I, GX, GY, w, h, sm, red, tot);
+    } else {
+      ecc_pass<MODE, 0>(T, I, GX, GY, w, h, sm, red, tot);
+    }
+    if (tid == 0) {
+      double S[NS], m[7];
+#pragma unroll
+      for (int q = 0; q < NS; q++) S[q] = tot[q];
+#pragma unroll
+      for (int q = 0; q < 7; q++) m[q] = sm[q];
+      last_rho = rho;
+      it++;
+      if (!ecc_finish<MODE>(S, m, &rho)) {
+        ctl = CTL_FAIL;
+      } else {
+#pragma unroll
+        for (int q = 0; q < 7; q++) sm[q] = m[q];
+        ctl = (it + 1 <= a.max_iter && fabs(rho - last_rho) >= a.eps) ? CTL_RUN : CTL_DONE;
+      }
+    }
+    __syncthreads();
+    c = ctl;
+  }
+  if (tid == 0) {
+    double o[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    if (c == CTL_DONE) {
+      for (int q = 0; q < 6; q++) o[q] = sm[q];
+      if (a.scale > 0.0 && a.scale < 1.0) {
+        o[2] = o[2] / a.scale;
+        o[5] = o[5] / a.scale;
+      }
+    }
+    const size_t r = a.dst ? (size_t)a.dst[i] : (size_t)i;
+    for (int q = 0; q < 6; q++) a.warps[r * 6 + q] = o[q];
+    a.rho[r] = c == CTL_FIRST ? 0.0 : rho;
+    a.iters[r] = it;
+    a.code[r] = c == CTL_DONE ? BX_ECC_OK : c == CTL_FIRST ? BX_ECC_FIRST_FRAME : BX_ECC_NOT_CONVERGED;
+  }
+}
+
+// The last frame of each stream's group: its grey image and gradients become the stream's, as
+// after a plain apply of that frame (d.cur / d.curf are scratch of the plain apply, rewritten by
+// its prep kernel before anything reads them).
+__global__ __launch_bounds__(PT) void cmc_chain_handover_kernel(CmDev d, CmChain c,
+                                                                const int32_t* streams, int n,
+                                                                int h, int w) {
+  const int k = blockIdx.y;
+  const int s = streams[k];
+  if (s < 0 || s >= d.n_streams) return;
+  if (k + 1 < n && streams[k + 1] == s) return;
+  const int idx = blockIdx.x * PT + threadIdx.x;
+  if (idx == 0) {
+    d.has_prev[s] = 1;
+    d.ph[s] = h;
+    d.pw[s] = w;
+  }
+  if (idx >= h * w) return;
+  const size_t from = (size_t)k * d.cap + idx, to = (size_t)s * d.cap + idx;
+  d.prev[to] = c.grey[from];
+  d.gx[to] = c.gx[from];
+  d.gy[to] = c.gy[from];
+}
+
 int round_half_even(double v) { return (int)std::nearbyint(v); }
+
+int launch_chain(CmHandle* H_, int n, int H, int W, int ch, const uint8_t* frames,
+                 const int32_t* streams, const int64_t* dst, int mode, double eps, int max_iter,
+                 double scale, int h, int w, double* warps, double* rho, int32_t* iters,
+                 int32_t* code, hipStream_t st) {
+  PrepArgs p{frames, streams, H, W, ch, h, w, (scale > 0.0 && scale < 1.0) ? 1 : 0, scale};
+  const dim3 pg((h * w + PT - 1) / PT, n);
+  hipLaunchKernelGGL(cmc_chain_prep_kernel, pg, dim3(PT), 0, st, H_->d, H_->c, p);
+  ChainArgs a{streams, dst, h, w, max_iter, eps, scale, warps, rho, iters, code};
+  if (mode == BX_ECC_TRANSLATION)
+    hipLaunchKernelGGL(cmc_ecc_chain_kernel<BX_ECC_TRANSLATION>, dim3(n), dim3(ET), 0, st, H_->d,
+                       H_->c, a);
+  else if (mode == BX_ECC_EUCLIDEAN)
+    hipLaunchKernelGGL(cmc_ecc_chain_kernel<BX_ECC_EUCLIDEAN>, dim3(n), dim3(ET), 0, st, H_->d,
+                       H_->c, a);
+  else
+    hipLaunchKernelGGL(cmc_ecc_chain_kernel<BX_ECC_AFFINE>, dim3(n), dim3(ET), 0, st, H_->d,
+                       H_->c, a);
+  hipLaunchKernelGGL(cmc_chain_handover_kernel, pg, dim3(PT), 0, st, H_->d, H_->c, streams, n, h, w);
+  BX_HIPCHK(hipGetLastError());
+  return BX_OK;
+}
 
 int launch(CmHandle* H_, int n, int H, int W, int ch, const uint8_t* frames, const int32_t* streams,
            int mode, double eps, int max_iter, double scale, int h, int w, const double* init,
@@ -411,6 +591,21 @@ int check_args(CmHandle* H_, int n, int H, int W, int ch, int mode, int max_iter
     return cm_err(BX_ERR_CAPACITY, "working image " + std::to_string(*h) + "x" + std::to_string(*w) +
                                        " exceeds the handle's " + std::to_string(H_->max_h) + "x" +
                                        std::to_string(H_->max_w));
+  return BX_OK;
+}
+
+// the same for the chained entries: a call's frames are bounded by the reserved slots, not by
+// the streams
+int check_chain_args(CmHandle* H_, int n, int H, int W, int ch, int mode, int max_iter,
+                     double scale, int* h, int* w) {
+  if (n < 0) return cm_err(BX_ERR_INVALID, "n/H/W/channels/max_iter/scale out of range");
+  int rc = check_args(H_, 0, H, W, ch, mode, max_iter, scale, h, w);
+  if (rc != BX_OK) return rc;
+  if ((long long)H * W * ch * (long long)(n > 0 ? n : 1) >= (1LL << 40))
+    return cm_err(BX_ERR_INVALID, "frames too large");
+  if (n > H_->c.max_frames)
+    return cm_err(BX_ERR_CAPACITY, "more frames than chain slots reserved (" +
+                                       std::to_string(H_->c.max_frames) + ")");
   return BX_OK;
 }
 
@@ -482,7 +677,9 @@ int bx_ecc_destroy(void* h) {
   if (!H_) return BX_OK;
   CmDev& d = H_->d;
   void* ps[] = {d.prev, d.cur, d.curf, d.gx, d.gy, d.has_prev, H_->sframes, H_->sstreams,
-                H_->sinit, H_->swarps, H_->srho, H_->siters, H_->scode};
+                H_->sinit, H_->swarps, H_->srho, H_->siters, H_->scode,
+                H_->c.grey, H_->c.curf, H_->c.gx, H_->c.gy, H_->cstreams, H_->cwarps, H_->crho,
+                H_->citers, H_->ccode};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   delete H_;
@@ -568,6 +765,102 @@ int bx_ecc_apply_host(void* h, int n, int H, int W, int channels, const uint8_t*
     iterations_host[s] = iv[s];
     code_host[s] = cv[s];
   }
+  return BX_OK;
+}
+
+int bx_ecc_chain_reserve(void* h, int max_frames) {
+  CmHandle* H_ = (CmHandle*)h;
+  if (!H_) return cm_err(BX_ERR_INVALID, "null ecc handle");
+  const size_t cap = (size_t)H_->d.cap;
+  if (max_frames < 1 || max_frames > BX_ECC_MAX_STREAMS ||
+      (long long)max_frames * (long long)cap * 14 > (1LL << 36))
+    return cm_err(BX_ERR_INVALID, "max_frames out of range");
+  if (max_frames <= H_->c.max_frames) return BX_OK;
+  // grown: the slots hold nothing between calls, so the old ones are dropped once the device
+  // has finished with them
+  BX_HIPCHK(hipDeviceSynchronize());
+  CmChain& c = H_->c;
+  void** ps[] = {(void**)&c.grey,       (void**)&c.curf,   (void**)&c.gx,
+                 (void**)&c.gy,         (void**)&H_->cstreams, (void**)&H_->cwarps,
+                 (void**)&H_->crho,     (void**)&H_->citers,   (void**)&H_->ccode};
+  for (void** p : ps) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  c.max_frames = 0;
+  const size_t m = (size_t)max_frames;
+  const size_t bytes[] = {m * cap, m * cap * 4, m * cap * 4, m * cap * 4, m * 4,
+                          m * 48,  m * 8,       m * 4,       m * 4};
+  for (int q = 0; q < 9; q++) {
+    hipError_t e = hipMalloc(ps[q], bytes[q]);
+    if (e != hipSuccess) {
+      for (void** p : ps) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+      }
+      return cm_err(BX_ERR_HIP, hipGetErrorString(e));
+    }
+  }
+  c.max_frames = max_frames;
+  return BX_OK;
+}
+
+int bx_ecc_apply_chain(void* h, int n, int H, int W, int channels, const uint8_t* frames,
+                       const int32_t* streams, const int64_t* dst, int warp_mode, double eps,
+                       int max_iter, double scale, double* warps, double* rho,
+                       int32_t* iterations, int32_t* code, void* hip_stream) {
+  CmHandle* H_ = (CmHandle*)h;
+  int hh, ww;
+  int rc = check_chain_args(H_, n, H, W, channels, warp_mode, max_iter, scale, &hh, &ww);
+  if (rc != BX_OK) return rc;
+  if (n == 0) return BX_OK;
+  if (!frames || !streams || !warps || !rho || !iterations || !code)
+    return cm_err(BX_ERR_INVALID, "null argument");
+  return launch_chain(H_, n, H, W, channels, frames, streams, dst, warp_mode, eps, max_iter,
+                      scale, hh, ww, warps, rho, iterations, code, (hipStream_t)hip_stream);
+}
+
+int bx_ecc_apply_chain_host(void* h, int n, int H, int W, int channels,
+                            const uint8_t* frames_host, const int32_t* streams_host,
+                            int warp_mode, double eps, int max_iter, double scale,
+                            double* warps_host, double* rho_host, int32_t* iterations_host,
+                            int32_t* code_host, void* hip_stream) {
+  CmHandle* H_ = (CmHandle*)h;
+  int hh, ww;
+  int rc = check_chain_args(H_, n, H, W, channels, warp_mode, max_iter, scale, &hh, &ww);
+  if (rc != BX_OK) return rc;
+  if (n == 0) return BX_OK;
+  if (!frames_host || !streams_host || !warps_host || !rho_host || !iterations_host || !code_host)
+    return cm_err(BX_ERR_INVALID, "null argument");
+  const int S = H_->d.n_streams;
+  std::vector<char> seen(S, 0);
+  for (int k = 0; k < n; k++) {
+    const int s = streams_host[k];
+    if (s < 0 || s >= S) return cm_err(BX_ERR_INVALID, "stream index out of range");
+    if (seen[s] && streams_host[k - 1] != s)
+      return cm_err(BX_ERR_INVALID, "the frames of a stream are not adjacent");
+    seen[s] = 1;
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t fb = (size_t)n * H * W * channels;
+  if (fb > H_->sframes_bytes) {
+    BX_HIPCHK(hipStreamSynchronize(st));
+    if (H_->sframes) (void)hipFree(H_->sframes);
+    H_->sframes = nullptr;
+    H_->sframes_bytes = 0;
+    BX_HIPCHK(hipMalloc(&H_->sframes, fb));
+    H_->sframes_bytes = fb;
+  }
+  BX_HIPCHK(hipMemcpyAsync(H_->sframes, frames_host, fb, hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemcpyAsync(H_->cstreams, streams_host, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  rc = launch_chain(H_, n, H, W, channels, H_->sframes, H_->cstreams, nullptr, warp_mode, eps,
+                    max_iter, scale, hh, ww, H_->cwarps, H_->crho, H_->citers, H_->ccode, st);
+  if (rc != BX_OK) return rc;
+  BX_HIPCHK(hipMemcpyAsync(warps_host, H_->cwarps, (size_t)n * 48, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(rho_host, H_->crho, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(iterations_host, H_->citers, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(code_host, H_->ccode, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   return BX_OK;
 }
 

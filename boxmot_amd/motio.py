@@ -206,9 +206,11 @@ def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs:
 RESIDENT_TRACKERS = ("deepocsort", "hybridsort")  # trackers run_sequences(resident=True) drives
 
 
-def _step(eng, tracker_type: str, dets, det_off, embs, out, out_count, seq0: int, nseq: int):
+def _step(eng, tracker_type: str, dets, det_off, embs, out, out_count, seq0: int, nseq: int,
+          warps=None):
     """One frame of sequences [seq0, seq0 + nseq) on a DeepOcsortEngine / HybridsortEngine:
-    ``step``, or ``step_classes`` on a per_class engine (HybridsortEngine.step takes no warps)."""
+    ``step``, or ``step_classes`` on a per_class engine (HybridsortEngine.step takes no warps).
+    warps: the run's [nseq, 6] block of a warp table (DeepOcsortEngine.step only)."""
     C = getattr(eng, "n_classes", 0)
     if tracker_type == "hybridsort":
         if C:
@@ -218,13 +220,14 @@ def _step(eng, tracker_type: str, dets, det_off, embs, out, out_count, seq0: int
     elif C:
         eng.step_classes(dets, det_off, embs, None, out, out_count, C, seq0=seq0, nseq=nseq)
     else:
-        eng.step(dets, det_off, embs, None, out, out_count, seq0=seq0, nseq=nseq)
+        eng.step(dets, det_off, embs, warps, out, out_count, seq0=seq0, nseq=nseq)
 
 
-def _resident_results(eng, tracker_type: str, seqs, fids, F: int, ddt) -> list:
+def _resident_results(eng, tracker_type: str, seqs, fids, F: int, ddt, warps=None) -> list:
     """The frame loop of run_sequences with the sequences resident in HBM (engine.SequenceFeeder):
     one upload, per frame index one gather launch, the steps of its runs and one append launch,
-    one copy back.  Returns each sequence's MOT rows [n, 9]."""
+    one copy back.  Returns each sequence's MOT rows [n, 9].  warps: [T, S, 6] device tensor or
+    None; a run's block goes to its step."""
     from .engine import SequenceFeeder
 
     feed_emb = F if getattr(eng, "emb_dim", 0) else 0
@@ -249,7 +252,8 @@ def _resident_results(eng, tracker_type: str, seqs, fids, F: int, ddt) -> list:
                 continue
             feed.gather(t)
             for k, ns, _, pd, po, pe, pout, pcnt in runs:
-                _step(eng, tracker_type, pd, po, pe, pout, pcnt, k, ns)
+                _step(eng, tracker_type, pd, po, pe, pout, pcnt, k, ns,
+                      None if warps is None else warps[t, k: k + ns])
             feed.append(t)
         if eng.status() != 0:
             raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
@@ -258,10 +262,100 @@ def _resident_results(eng, tracker_type: str, seqs, fids, F: int, ddt) -> list:
         feed.close()
 
 
+WARP_TRACKERS = ("botsort", "boosttrack", "strongsort", "deepocsort")  # run_sequences(warps=...)
+_ECC_KEYS = ("warp_mode", "eps", "max_iter", "scale", "chunk")
+
+
+def _check_warp_args(tracker_type: str, tracker_kwargs: dict, n_classes: int, warps, images,
+                     cmc):
+    """The refusals of run_sequences' warps / images / cmc that need no sequence, no engine and
+    no device; returns warp_table's keyword arguments (None without ``images``)."""
+    if warps is None and images is None:
+        if cmc is not None:
+            raise ValueError("cmc names how warps are computed from images: give images too")
+        return None
+    if tracker_type not in WARP_TRACKERS:
+        raise ValueError(
+            f"{tracker_type} takes no camera-motion warp (its engine has none and the "
+            f"reference's tracker runs no CMC): warps / images are for {', '.join(WARP_TRACKERS)}")
+    if n_classes or tracker_kwargs.get("per_class"):
+        raise ValueError("warps / images in a per_class run are not supported: the reference "
+                         "calls its CMC once per class call")
+    if tracker_kwargs.get("cmc_off") or tracker_kwargs.get("use_ecc") is False:
+        raise ValueError("the tracker's camera-motion compensation is switched off in "
+                         "tracker_kwargs (cmc_off / use_ecc): it would not apply the warps")
+    if images is None:
+        if cmc is not None:
+            raise ValueError("cmc goes with images; warps are taken as they are")
+        return None
+    if warps is not None:
+        raise ValueError("give images (with cmc) or warps, not both")
+    if cmc is None:
+        raise ValueError('images need cmc: "ecc" or a dict of ECC settings')
+    if cmc == "ecc":
+        return {}
+    if not isinstance(cmc, dict) or set(cmc) - set(_ECC_KEYS):
+        raise ValueError(f'cmc must be "ecc" or a dict with keys among {", ".join(_ECC_KEYS)}')
+    return dict(cmc)
+
+
+def _flow_warps(names, seqs, fids, F: int, warps, images, ecc_kw):
+    """The [T, S, 6] float64 device tensor run_sequences hands its engines, T the most iterated
+    frames of a sequence: a WarpTable's warps, plain per-sequence arrays, or the table computed
+    from images, each value rounded to float32 (what the reference's cmc.apply returns).  The
+    shapes are checked before anything touches the device."""
+    from . import cmc as M
+
+    S, T = len(seqs), max([len(f) for f in fids] + [0])
+    if images is not None:
+        missing = [nm for nm in names if nm not in images]
+        if missing:
+            raise ValueError(f"no images for {', '.join(missing)}")
+        stepped = []
+        for s, f in zip(seqs, fids):  # the flow's own stepping rule
+            m = np.zeros(len(f), bool)
+            for t, x in enumerate(f):
+                d, e = s.frame(x)
+                m[t] = bool(d.size and (e.size or not F))
+            stepped.append(m)
+        for nm, m in zip(names, stepped):
+            if not callable(images[nm]) and len(images[nm]) != m.size:
+                raise ValueError(f"{nm}: {len(images[nm])} images for {m.size} iterated frames")
+        tab = M.warp_table([images[nm] for nm in names], stepped, **ecc_kw)
+        try:
+            return tab.warps.to(dtype=_torch().float32).to(dtype=_torch().float64).contiguous()
+        finally:
+            tab.close()
+    if isinstance(warps, M.WarpTable):
+        if warps.warps is None or tuple(warps.warps.shape) != (T, S, 6):
+            raise ValueError(f"the warp table is not [{T}, {S}, 6]: it was built for other "
+                             "sequences or frames")
+        return warps.warps.to(dtype=_torch().float32).to(dtype=_torch().float64).contiguous()
+    if not hasattr(warps, "keys"):
+        raise ValueError("warps must be a cmc.WarpTable or a mapping name -> [n_frames, 6]")
+    host = np.zeros((T, S, 6), np.float64)
+    host[:, :, 0] = host[:, :, 4] = 1.0
+    for k, (nm, f) in enumerate(zip(names, fids)):
+        if nm not in warps:
+            raise ValueError(f"no warps for {nm}")
+        w = np.asarray(warps[nm], np.float64)
+        if w.shape not in ((len(f), 6), (len(f), 2, 3)):
+            raise ValueError(f"{nm}: warps of shape {w.shape} for {len(f)} iterated frames")
+        host[: len(f), k] = w.reshape(len(f), 6).astype(np.float32)
+    return _torch().from_numpy(host).cuda()
+
+
+def _torch():
+    import torch
+
+    return torch
+
+
 def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict | None = None,
                   frame_sizes: dict | None = None, tracker_kwargs: dict | None = None,
                   gsi: bool = False, gsi_interval: int = 20, gsi_tau: float = 10,
-                  resident: bool = False, n_classes: int = 0) -> dict:
+                  resident: bool = False, n_classes: int = 0, warps=None, images: dict | None = None,
+                  cmc=None) -> dict:
     """process_sequence (val.py:304-354) for every sequence at once.
 
     sequences: name -> packed file (pack_sequence) or BinSequence; frame_ids: name -> the frames
@@ -277,25 +371,43 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
     0..n_classes-1 (DeepOcSortPerClass / HybridSortPerClass per sequence; ``per_class`` in
     tracker_kwargs raises for these two, as their plain constructors do), with the class split and
     the id merge on the device, resident or not.
+    Camera-motion compensation (the reference's ``tracker.update(dets, img, embs)`` runs its CMC
+    on every stepped frame), for the trackers in WARP_TRACKERS, resident or not; left out, no
+    warp is applied, as before:
+    warps: a ``cmc.WarpTable`` over these sequences (in their order) and their iterated frames,
+    or a mapping name -> ``[n_frames, 6]`` (or ``[n_frames, 2, 3]``) array of the warp at every
+    iterated frame of that sequence (rows of frames that are not stepped are not read), e.g.
+    from ``SofBatch``.
+    images, cmc: name -> the sequence's images (``cmc.warp_table``'s array or callable), and
+    ``"ecc"`` or a dict of ECC settings (warp_mode, eps, max_iter, scale, chunk): the flow derives
+    the stepped frames, builds the table with ``cmc.warp_table``, runs and closes it.
+    Every warp reaches the engine rounded to float32, the type the reference's ``cmc.apply``
+    returns and the drop-ins pass on.  ValueError, before anything is built: a tracker outside
+    WARP_TRACKERS, a per_class run, ``images`` without ``cmc`` or with ``warps``, a table or an
+    array that does not match the sequences and their iterated frames.
     """
     if resident and tracker_type not in RESIDENT_TRACKERS:
         raise NotImplementedError(
             f"run_sequences(resident=True) is not available for {tracker_type}: the "
             f"device-resident feeder drives {', '.join(RESIDENT_TRACKERS)} only")
+    ecc_kw = _check_warp_args(tracker_type, tracker_kwargs or {}, n_classes, warps, images, cmc)
     import torch
 
     names = list(sequences)
     seqs = [s if isinstance(s, BinSequence) else BinSequence(s) for s in sequences.values()]
     S = len(seqs)
     F = max([s.emb_dim for s in seqs] + [0])
+    fids = [np.asarray(frame_ids[nm]) if frame_ids and nm in frame_ids else s.frame_ids
+            for nm, s in zip(names, seqs)]
+    table = None
+    if warps is not None or images is not None:
+        table = _flow_warps(names, seqs, fids, F, warps, images, ecc_kw)
     eng, ddt, ncol = _batched_engine(tracker_type, S, F, tracker_kwargs or {}, n_classes) \
         if n_classes else _batched_engine(tracker_type, S, F, tracker_kwargs or {})
     if tracker_type == "ocsort" and frame_sizes:
         for k, nm in enumerate(names):
             if nm in frame_sizes:
                 eng.set_frame_size(k, *frame_sizes[nm])
-    fids = [np.asarray(frame_ids[nm]) if frame_ids and nm in frame_ids else s.frame_ids
-            for nm, s in zip(names, seqs)]
     if tracker_type in ("deepocsort", "hybridsort") and frame_sizes:
         C = getattr(eng, "n_classes", 0) or 1  # (per_class: every class sequence of the sequence)
         for k, nm in enumerate(names):
@@ -304,7 +416,7 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
                     eng.set_frame_size(q, *frame_sizes[nm])
     if resident:
         exp_dir = Path(exp_dir)
-        for nm, res in zip(names, _resident_results(eng, tracker_type, seqs, fids, F, ddt)):
+        for nm, res in zip(names, _resident_results(eng, tracker_type, seqs, fids, F, ddt, table)):
             write_mot_results(exp_dir / f"{nm}.txt", res if res.size else np.empty((0, 0)))
         if gsi:
             from . import postprocessing
@@ -342,6 +454,7 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
             od = torch.from_numpy(off).to(dev)
             out = torch.empty((int(off[-1]), ncol), dtype=torch.float64, device=dev)
             cnt = torch.empty(k1 - k, dtype=torch.int32, device=dev)
+            wk = None if table is None else table[t, k: k1]  # the run's [nseq, 6] block
             if tracker_type == "ocsort":
                 eng.step(dd, od, out, cnt, seq0=k, nseq=k1 - k)
             elif tracker_type in ("deepocsort", "hybridsort"):
@@ -349,14 +462,14 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
                 if F and eng.emb_dim:
                     emb = torch.from_numpy(np.concatenate([frame[q][1] for q in range(k, k1)])
                                            .astype(np.float64)).to(dev)
-                _step(eng, tracker_type, dd, od, emb, out, cnt, k, k1 - k)
+                _step(eng, tracker_type, dd, od, emb, out, cnt, k, k1 - k, wk)
             else:
                 emb = None
                 if F and getattr(eng, "with_reid", True) and not (
                         tracker_type == "boosttrack" and not eng.emb_dim):
                     emb = torch.from_numpy(np.concatenate([frame[q][1] for q in range(k, k1)])
                                            .astype(np.float64)).to(dev)
-                eng.step(dd, od, emb, None, out, cnt, seq0=k, nseq=k1 - k)
+                eng.step(dd, od, emb, wk, out, cnt, seq0=k, nseq=k1 - k)
             o, c = out.cpu().numpy(), cnt.cpu().numpy()
             for q in range(k, k1):
                 rows = o[off[q - k]: off[q - k] + c[q - k]]

@@ -91,6 +91,49 @@ int bx_ecc_apply_host(void *h, int n, int H, int W, int channels, const uint8_t 
                       double scale, const double *init_warps_host, double *warps_host,
                       double *rho_host, int32_t *iterations_host, int32_t *code_host,
                       void *hip_stream);
+/* ---- the chained apply: many consecutive frames of a camera per call.
+ *
+ * Scratch for max_frames <= BX_ECC_MAX_STREAMS frames per call on an existing handle: per frame
+ * a slot with a grey image, its float copy and its two gradients, max_h * max_w * 14 bytes.
+ * Idempotent; a larger max_frames grows the scratch (waiting for the device first), a smaller
+ * one changes nothing.  The slots carry nothing from one call to the next.  BX_ERR_INVALID for
+ * max_frames out of range. */
+int bx_ecc_chain_reserve(void *h, int max_frames);
+
+/* n <= max_frames frames in one call, all launches on hip_stream, no host synchronisation.
+ *   frames      device [n][H][W][channels] uint8, as bx_ecc_apply
+ *   streams     device [n] int32: the stream of each frame.  A stream may repeat: its frames are
+ *               adjacent in the call and in time order, so a stream forms at most one group per
+ *               call.  A stream listed in two separate groups (0,1,0) is undefined behaviour
+ *               (the results and the state of that stream are garbage; the accesses stay in
+ *               bounds).
+ *   dst         device [n] int64 or null: the row of the four result arrays that frame i writes
+ *               (null: row i).  The caller sizes the arrays for the rows it names.
+ *   warps       device [.][6] float64; rho [.] float64; iterations, code [.] int32: row dst[i]
+ *               holds frame i's result, with the meanings of bx_ecc_apply; other rows are
+ *               untouched
+ * Frame i is aligned to frame i - 1 of the call when streams[i - 1] == streams[i], otherwise to
+ * the stored previous image of its stream: BX_ECC_FIRST_FRAME if there is none, and also (with
+ * BX_ERR_SHAPE latched) if its working size is another.  Every iteration starts at the identity
+ * (there is no init_warps).  After the call each listed stream's previous image, size and
+ * gradients are those of its last frame in the call, whatever the codes.  The results and the
+ * final state are, bit for bit, those of n successive bx_ecc_apply calls of one frame each.
+ * BX_ERR_CAPACITY (nothing launched, state unchanged): n > max_frames reserved or a working image
+ * larger than max_h x max_w.  BX_ERR_INVALID: as bx_ecc_apply.  A stream index out of range
+ * skips that frame (its row is untouched) and latches BX_ERR_INVALID in bx_ecc_status. */
+int bx_ecc_apply_chain(void *h, int n, int H, int W, int channels, const uint8_t *frames,
+                       const int32_t *streams, const int64_t *dst, int warp_mode, double eps,
+                       int max_iter, double scale, double *warps, double *rho,
+                       int32_t *iterations, int32_t *code, void *hip_stream);
+/* The same from host arrays: stages the frames, runs, copies the n result rows back (row i is
+ * frame i) and synchronises once.  Also BX_ERR_INVALID (nothing launched) for a stream index out
+ * of range or a stream whose frames are not adjacent. */
+int bx_ecc_apply_chain_host(void *h, int n, int H, int W, int channels,
+                            const uint8_t *frames_host, const int32_t *streams_host,
+                            int warp_mode, double eps, int max_iter, double scale,
+                            double *warps_host, double *rho_host, int32_t *iterations_host,
+                            int32_t *code_host, void *hip_stream);
+
 /* Latched device-side status (BX_OK, BX_ERR_INVALID or BX_ERR_SHAPE); synchronises. */
 int bx_ecc_status(void *h, int *status);
 /* A stream's state, copied to the host (synchronises): whether it has a previous image, its
