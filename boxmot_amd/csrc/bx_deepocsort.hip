@@ -11,8 +11,8 @@
 // Per frame, three launches on the caller's stream:
 //   deepoc_embcost_kernel  dets_embs @ trk_embs.T for every detection x pre-frame track of every
 //                          sequence: the fp64 MFMA tile of bx_embtile.h (shared with BoostTrack)
-//   deepoc_frame_kernel    one wave64 workgroup per sequence, grown from ocsort_frame_kernel on
-//                          the device code of bx_ocs_device.h: CMC affine correction, predict,
+//   deepoc_frame_kernel    one wave64 workgroup per sequence, the frame phases of
+//                          bx_ocs_device.h plus its own: CMC affine correction, predict,
 //                          first association (IoU + direction consistency + appearance), updates,
 //                          OCR round, births, outputs, deaths; emits embedding records
 //   deepoc_feature_kernel  wave per record: emb = a*emb + (1-a)*det, emb /= ||emb|| (wave-order
@@ -183,7 +183,9 @@ __global__ void __launch_bounds__(256)
   ec_tile_store(acc, d0, t0, nd, nt, out, nt);
 }
 
-__global__ void __launch_bounds__(OW)
+// (two waves per SIMD, as OCSort's kernel gets unasked: with every phase inlined the allocator
+// would otherwise take a few registers past 256 and halve the occupancy)
+__global__ void __launch_bounds__(OW) __attribute__((amdgpu_waves_per_eu(2)))
     deepoc_frame_kernel(DocDev gd, int seq0, const float* __restrict__ dets,
                         const int* __restrict__ det_off, const double* __restrict__ warps,
                         double* __restrict__ out, int* __restrict__ out_count) {
@@ -194,39 +196,20 @@ __global__ void __launch_bounds__(OW)
   carve(g, lds_raw, L);
   doc_carve(g, lds_raw + gd.x_off, X);
   const int lane = threadIdx.x;
-  const int b = blockIdx.x, seq = seq0 + b;
+  const int seq = seq0 + blockIdx.x;
   L.jv.dc = nullptr;
-  const int r0 = det_off[b];
-  int n = det_off[b + 1] - r0;
-  if (n > g.D) {  // the host checks det_cap; a device-side overflow is latched, never run past
-    if (threadIdx.x == 0) atomicExch(g.status, (int)BX_ERR_CAPACITY);
-    n = g.D;
-  }
-  int* sq = g.seqst + (size_t)seq * SQO;
+  const OcsFrame F = ocs_frame_begin<TB>(g, L, seq, dets, det_off);  // deepocsort.py:339
   OcsTrk* trk = g.trk + (size_t)seq * g.T;
-  int* order = g.order + (size_t)seq * g.T;
-  double* tb = g.tb + (size_t)seq * g.T * TB;
-  double* cost = g.cost_g ? g.cost_g + (size_t)seq * g.D * g.T : nullptr;
   const bool use_emb = !gd.emb_off;
   const double* ec = use_emb ? gd.ec + (size_t)seq * g.D * g.T : nullptr;
   double* em = use_emb ? gd.em + (size_t)seq * g.D * g.T : nullptr;
   int* rec = gd.rec + (size_t)seq * g.D;
   double* rec_a = gd.rec_a + (size_t)seq * g.D;
-  const int frame = sq[SO_FRAME] + 1;
-  const int id0 = sq[SO_IDS];
-  const int nt0 = sq[SO_NTR];
-  const double thr = g.asso_threshold;
-  const int ak = g.asso_kind;
-  const double fw = g.fsz[2 * seq], fh = g.fsz[2 * seq + 1];
-
-  // detections (setup_decorator's float32 rounding is the input format); deepocsort.py:339
-  for (int q = lane; q < n * 6; q += OW) L.dd[q] = (double)dets[(size_t)r0 * 6 + q];
-  for (int p = lane; p < nt0; p += OW) L.lst2[p] = order[p];
   if (use_emb)
-    for (int i = lane; i < n; i += OW) rec[i] = -1;
+    for (int i = lane; i < F.n; i += OW) rec[i] = -1;
   __syncthreads();
   const int nh = wave_compact(
-      n, [&](int i) { return L.dd[6 * i + 4] > g.det_thresh; }, [&](int i, int p) { L.hi[p] = i; });
+      F.n, [&](int i) { return L.dd[6 * i + 4] > g.det_thresh; }, [&](int i, int p) { L.hi[p] = i; });
 
   // embedding record of detection row i (deepocsort.py:357-360, :415, :446): the track slot and
   // alpha = af + (1 - af) * (1 - trust), trust = (conf - det_thresh) / (1 - det_thresh)
@@ -237,397 +220,110 @@ __global__ void __launch_bounds__(OW)
     rec_a[i] = born ? -1.0 : af + (1 - af) * (1 - trust);
     rec[i] = slot;
   };
+  const int r8 = lane & 7;
+  // update(det) of list position ti with detection row i, octet-wide, and its embedding record
+  auto update = [&](int i, int ti) {
+    const int slot = L.lst[ti];
+    const double* r = L.dd + 6 * i;
+    ocs_update_det(g, trk[slot], r8, r, r[5], i);
+    if (r8 == 0) emit(i, slot, false);
+  };
 
   // ---- CMC affine correction of every track (deepocsort.py:352-355), a lane per track -------
   if (warps) {
     double w[6];
-    for (int q = 0; q < 6; q++) w[q] = warps[(size_t)b * 6 + q];
-    for (int p = lane; p < nt0; p += OW) doc_affine(g, trk[L.lst2[p]], w);
+    for (int q = 0; q < 6; q++) w[q] = warps[(size_t)F.b * 6 + q];
+    for (int p = lane; p < F.nt0; p += OW) doc_affine(g, trk[L.lst2[p]], w);
     __syncthreads();
   }
 
-  const int oct = lane >> 3, r8 = lane & 7, rr8 = r8 < 7 ? r8 : 6;
-
-  // predict every track (an octet per track); tracks whose prediction has a NaN leave the list
-  // (deepocsort.py:367-382).  tb row per kept track: box[4], k-previous obs[5], last_obs[5],
-  // vel[2]; pp = its pre-frame list position (the column of ec)
-  int nt = 0;
-  for (int c = 0; c < nt0; c += 8) {
-    const int p = c + oct;
-    bool keep = false;
-    int slot = -1;
-    double v0 = 0.0, v1 = 0.0;  // this lane's two tb entries: [r8] and [8 + r8]
-    if (p < nt0) {
-      slot = L.lst2[p];
-      OcsTrk& t = trk[slot];
-      KfRow k;
-      row_load(t.x, t.P, rr8, k);
-      if ((osh(k.x, 6) + osh(k.x, 2)) <= 0 && rr8 == 6) k.x *= 0.0;
-      kfo_predict(g, rr8, k);
-      row_store(t.x, t.P, r8, k);
-      const int age = t.age + 1;
-      if (r8 == 0) {
-        t.age = age;
-        if (t.tsu > 0) t.hit_streak = 0;
-        t.tsu++;
-      }
-      double xs[4], bx[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) xs[q] = osh(k.x, q);
-      x_to_bbox(xs, bx);
-      keep = !(isnan(bx[0]) || isnan(bx[1]) || isnan(bx[2]) || isnan(bx[3]));
-      // k_previous_obs (deepocsort.py:17-25) with the post-predict age
-      int qq = -1;
-      const int last_age = t.last_age;
-      if (last_age >= 0) {
-        qq = obs_first(t, age - g.delta_t, g.delta_t);
-        if (qq < 0) qq = last_age & (OBS_KEEP - 1);  // observations[max(keys)]
-      }
-      auto val = [&](int e) -> double {
-        if (e < 4) return e == 0 ? bx[0] : e == 1 ? bx[1] : e == 2 ? bx[2] : bx[3];
-        if (e < 9) return qq < 0 ? -1.0 : t.obs_box[qq][e - 4];
-        if (e < 14) return t.last_obs[e - 9];
-        return t.has_vel ? t.vel[e - 14] : 0.0;
-      };
-      v0 = val(r8);
-      v1 = val(8 + r8);
-    }
-    const unsigned long long m = __ballot(keep && r8 == 0);
-    if (keep) {
-      const int q = nt + __popcll(m & ((1ull << (lane & ~7)) - 1ull));
-      if (r8 == 0) {
-        L.lst[q] = slot;
-        X.pp[q] = p;
-      }
-      double* row = tb + (size_t)q * TB;
-      row[r8] = v0;
-      row[8 + r8] = v1;
-    }
-    nt += __popcll(m);
-  }
-  __syncthreads();
+  // predict (deepocsort.py:367-382); X.pp = a kept track's pre-frame list position (the column
+  // of ec)
+  const int nt = ocs_predict_octet(g, L, F, trk, X.pp);
 
   // ---- first association: associate(dets over det_thresh, predicted tracks, emb cost) -------
-  int nm = 0, nud = 0, nut = 0;
-  if (nt == 0) {
-    for (int k = lane; k < nh; k += OW) L.ud[k] = k;
-    nud = nh;
-  } else {
-    int nmi = 0;
-    if (nh > 0) {
-      // pass 1 (lane per track, dets broadcast from LDS): IoU > threshold counts for the
-      // one-to-one test, as OCSort
-      for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = 0;
-      __syncthreads();
-      for (int c = 0; c < nt; c += OW) {
-        const int ti = c + lane;
-        if (ti < nt) {
-          const double* bq = tb + (size_t)ti * TB;
-          const double b0 = bq[0], b1 = bq[1], b2 = bq[2], b3 = bq[3];
-          const double at = (b2 - b0) * (b3 - b1);
-          int cc = 0;
-          for (int d = 0; d < nh; d++) {
-            const double* a = L.dd + 6 * L.hi[d];
-            const double xx1 = fmax(a[0], b0), yy1 = fmax(a[1], b1);
-            const double xx2 = fmin(a[2], b2), yy2 = fmin(a[3], b3);
-            const double w = fmax(0.0, xx2 - xx1), h = fmax(0.0, yy2 - yy1);
-            const double wh = w * h;
-            if (wh > 0.0 || thr < 0.0 || ak != ASSO_IOU) {
-              const double o = ak == ASSO_IOU ? wh / ((a[2] - a[0]) * (a[3] - a[1]) + at - wh)
-                                              : asso_pair(ak, a, bq, fw, fh);
-              if (o > thr) {
-                atomicAdd(&L.rowcnt[d], 1);
-                L.rowcol[d] = ti;
-                cc++;
-              }
-            }
-          }
-          L.colcnt[ti] = cc;
-        }
-      }
-      __syncthreads();
-      int mr = 0, mcx = 0;
-      for (int k = lane; k < nh; k += OW) mr = max(mr, L.rowcnt[k]);
-      for (int k = lane; k < nt; k += OW) mcx = max(mcx, L.colcnt[k]);
-      for (int o = 32; o >= 1; o >>= 1) {
-        mr = max(mr, __shfl_xor(mr, o));
-        mcx = max(mcx, __shfl_xor(mcx, o));
-      }
-      if (mr == 1 && mcx == 1) {  // one-to-one: np.stack(np.where(iou > thr), 1), row-major
-        nmi = wave_compact(
-            nh, [&](int d) { return L.rowcnt[d] == 1; },
-            [&](int d, int p) {
-              L.mi[2 * p] = d;
-              L.mi[2 * p + 1] = L.rowcol[d];
-            });
-      } else {
-        // the appearance term (association.py:464-473): emb = ec.copy(); emb[iou <= 0] = 0,
-        // then the adaptive weights of its rows and columns, or the fixed weight
-        if (use_emb) {
-          for (int c = 0; c < nt; c += OW) {
-            const int ti = c + lane;
-            if (ti < nt) {
-              const double* r = tb + (size_t)ti * TB;
-              const int col = X.pp[ti];
-              for (int d = 0; d < nh; d++) {
-                const double o = asso_pair(ak, L.dd + 6 * L.hi[d], r, fw, fh);
-                em[d * nt + ti] = o <= 0 ? 0.0 : ec[(size_t)L.hi[d] * g.T + col];
-              }
-            }
-          }
-          __syncthreads();
-          if (!gd.aw_off) {
-            for (int d = lane; d < nh; d += OW) {
-              bool ap;
-              X.rw[d] = aw_weight(em + (size_t)d * nt, nt, 1, gd.aw_param, &ap);
-              X.ra[d] = ap;
-            }
-            for (int ti = lane; ti < nt; ti += OW) {
-              bool ap;
-              X.cw[ti] = aw_weight(em + ti, nh, nt, gd.aw_param, &ap);
-              X.ca[ti] = ap;
-            }
-            __syncthreads();
-          }
-        }
-        // the full cost -((IoU + direction consistency) + appearance) and P4's legacy
-        // linear_assignment of it
-        double* C = (nh * nt <= g.cost_lds) ? L.cost : cost;
+  int nmi = 0;
+  if (nt > 0 && nh > 0) {
+    ocs_pass1_count(g, L, F, nh, nt);
+    nmi = ocs_one_to_one(L, nh, nt);
+    if (nmi < 0) {
+      // the appearance term (association.py:464-473): emb = ec.copy(); emb[iou <= 0] = 0,
+      // then the adaptive weights of its rows and columns, or the fixed weight
+      if (use_emb) {
         for (int c = 0; c < nt; c += OW) {
           const int ti = c + lane;
           if (ti < nt) {
-            const double* r = tb + (size_t)ti * TB;
-            const double* p = r + 4;
-            const double cx2 = (p[0] + p[2]) / 2.0, cy2 = (p[1] + p[3]) / 2.0;
-            const double vy = r[14], vx = r[15];
-            const double valid = p[4] < 0 ? 0.0 : 1.0;
+            const double* r = F.tb + (size_t)ti * TB;
+            const int col = X.pp[ti];
             for (int d = 0; d < nh; d++) {
-              const double* a = L.dd + 6 * L.hi[d];
-              const double o = asso_pair(ak, a, r, fw, fh);
-              // speed_direction_batch (association.py:10-20) against the k-previous obs
-              const double cx1 = (a[0] + a[2]) / 2.0, cy1 = (a[1] + a[3]) / 2.0;
-              double dx = cx1 - cx2, dy = cy1 - cy2;
-              const double norm = sqrt(dx * dx + dy * dy) + 1e-6;
-              dx = dx / norm;
-              dy = dy / norm;
-              double cth = vx * dx + vy * dy;
-              cth = cth < -1 ? -1 : (cth > 1 ? 1 : cth);
-              double ang = ocs_acos(cth);
-              ang = (3.14159265358979323846 / 2.0 - fabs(ang)) / 3.14159265358979323846;
-              const double mc = (valid * ang) * g.inertia;
-              double total = o + mc;
-              if (use_emb) {
-                const double e = em[d * nt + ti];
-                if (gd.aw_off) {
-                  total += e * gd.w_emb;
-                } else {  // compute_aw_max_metric: ((w * row) * col) * emb
-                  double w = gd.w_emb;
-                  if (X.ra[d]) w *= X.rw[d];
-                  if (X.ca[ti]) w *= X.cw[ti];
-                  total += w * e;
-                }
-              }
-              C[d * nt + ti] = -total;
+              const double o = asso_pair(F.ak, L.dd + 6 * L.hi[d], r, F.fw, F.fh);
+              em[d * nt + ti] = o <= 0 ? 0.0 : ec[(size_t)L.hi[d] * g.T + col];
             }
           }
         }
         __syncthreads();
-        nmi = ocs_lap(C, nh, nt, L.jv, L.mi);
+        if (!gd.aw_off) {
+          for (int d = lane; d < nh; d += OW) {
+            bool ap;
+            X.rw[d] = aw_weight(em + (size_t)d * nt, nt, 1, gd.aw_param, &ap);
+            X.ra[d] = ap;
+          }
+          for (int ti = lane; ti < nt; ti += OW) {
+            bool ap;
+            X.cw[ti] = aw_weight(em + ti, nh, nt, gd.aw_param, &ap);
+            X.ca[ti] = ap;
+          }
+          __syncthreads();
+        }
       }
-    }
-    // P3: unmatched = absent from the candidate pairs, ascending; then the IoU validation with
-    // rejected pairs appended in pair order (P5)
-    for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = L.colcnt[k] = 0;
-    __syncthreads();
-    for (int q = lane; q < nmi; q += OW) {
-      L.rowcnt[L.mi[2 * q]] = 1;
-      L.colcnt[L.mi[2 * q + 1]] = 1;
-    }
-    __syncthreads();
-    nud = wave_compact(nh, [&](int d) { return L.rowcnt[d] == 0; }, [&](int d, int p) { L.ud[p] = d; });
-    nut = wave_compact(nt, [&](int t) { return L.colcnt[t] == 0; }, [&](int t, int p) { L.ut[p] = t; });
-    for (int c = 0; c < nmi; c += OW) {
-      const int q = c + lane;
-      bool ok = false, rej = false;
-      int d = 0, ti = 0;
-      if (q < nmi) {
-        d = L.mi[2 * q];
-        ti = L.mi[2 * q + 1];
-        ok = asso_pair(ak, L.dd + 6 * L.hi[d], tb + (size_t)ti * TB, fw, fh) >= thr;
-        rej = !ok;
-      }
-      const unsigned long long mo = __ballot(ok), mr = __ballot(rej);
-      const unsigned long long below = (1ull << lane) - 1ull;
-      if (ok) {
-        const int p = nm + __popcll(mo & below);
-        L.mm[2 * p] = d;
-        L.mm[2 * p + 1] = ti;
-      }
-      if (rej) {
-        const int p = __popcll(mr & below);
-        L.ud[nud + p] = d;
-        L.ut[nut + p] = ti;
-      }
-      nm += __popcll(mo);
-      nud += __popcll(mr);
-      nut += __popcll(mr);
-    }
-    __syncthreads();
-  }
-  for (int c = 0; c < nm; c += 8) {
-    const int q = c + oct;
-    if (q < nm) {
-      const int i = L.hi[L.mm[2 * q]], slot = L.lst[L.mm[2 * q + 1]];
-      const double* r = L.dd + 6 * i;
-      ocs_update_det(g, trk[slot], r8, r, r[5], i);
-      if (r8 == 0) emit(i, slot, false);
+      // the full cost -((IoU + direction consistency) + appearance) and P4's legacy
+      // linear_assignment of it
+      double* C = ocs_cost_buf(g, L, F, nh, nt);
+      ocs_cost_fill(g, L, F, C, nh, nt, [&](int d, int ti, double s) {
+        double total = s;
+        if (use_emb) {
+          const double e = em[d * nt + ti];
+          if (gd.aw_off) {
+            total += e * gd.w_emb;
+          } else {  // compute_aw_max_metric: ((w * row) * col) * emb
+            double w = gd.w_emb;
+            if (X.ra[d]) w *= X.rw[d];
+            if (X.ca[ti]) w *= X.cw[ti];
+            total += w * e;
+          }
+        }
+        return total;
+      });
+      nmi = ocs_lap(C, nh, nt, L.jv, L.mi);
     }
   }
+  const OcsSplit sp = ocs_split(g, L, nh, nt, nmi, [&](int d, int ti) {
+    return asso_pair(F.ak, L.dd + 6 * L.hi[d], F.tb + (size_t)ti * TB, F.fw, F.fh) >= F.thr;
+  });
+  ocs_each<8>(sp.nm, [&](int q) { update(L.hi[L.mm[2 * q]], L.mm[2 * q + 1]); });
   __syncthreads();
 
   // ---- OCR round on the last observations (deepocsort.py:420-456) ---------------------------
-  if (nud > 0 && nut > 0) {
-    double mx = -INF;
-    for (int c = 0; c < nut; c += OW) {
-      const int k = c + lane;
-      if (k < nut) {
-        const double* bq = tb + (size_t)L.ut[k] * TB + 9;
-        for (int d = 0; d < nud; d++)
-          mx = fmax(mx, asso_pair(ak, L.dd + 6 * L.hi[L.ud[d]], bq, fw, fh));
-      }
-    }
-    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-    if (mx > thr) {
-      double* C = (nud * nut <= g.cost_lds) ? L.cost : cost;
-      for (int c = 0; c < nut; c += OW) {
-        const int k = c + lane;
-        if (k < nut) {
-          const double* bq = tb + (size_t)L.ut[k] * TB + 9;
-          for (int d = 0; d < nud; d++)
-            C[d * nut + k] = -asso_pair(ak, L.dd + 6 * L.hi[L.ud[d]], bq, fw, fh);
-        }
-      }
-      __syncthreads();
-      const int np_ = ocs_lap(C, nud, nut, L.jv, L.mi);
-      for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = L.fl[k] = 0;
-      __syncthreads();
-      for (int c = 0; c < np_; c += 8) {
-        const int q = c + oct;
-        if (q < np_) {
-          const int a = L.mi[2 * q], k = L.mi[2 * q + 1];
-          if (!(-C[a * nut + k] < thr)) {
-            const int di = L.ud[a], ti = L.ut[k];
-            const int i = L.hi[di], slot = L.lst[ti];
-            const double* r = L.dd + 6 * i;
-            ocs_update_det(g, trk[slot], r8, r, r[5], i);
-            if (r8 == 0) {
-              emit(i, slot, false);
-              L.rowcnt[di] = 2;
-              L.fl[ti] = 2;
-            }
-          }
-        }
-      }
-      __syncthreads();
-      for (int k = lane; k < nud; k += OW)
-        if (L.rowcnt[L.ud[k]] == 0) L.rowcnt[L.ud[k]] = 1;
-      for (int k = lane; k < nut; k += OW)
-        if (L.fl[L.ut[k]] == 0) L.fl[L.ut[k]] = 1;
-      __syncthreads();
-      // np.setdiff1d: ascending, unique
-      nud = wave_compact(nh, [&](int d) { return L.rowcnt[d] == 1; }, [&](int d, int p) { L.ud[p] = d; });
-      nut = wave_compact(nt, [&](int t) { return L.fl[t] == 1; }, [&](int t, int p) { L.ut[p] = t; });
-    }
-  }
-  for (int c = 0; c < nut; c += 8) {
-    const int k = c + oct;
-    if (k < nut) ocs_update_none(g, trk[L.lst[L.ut[k]]], r8);
-  }
+  const OcsRematch u = ocs_rematch<TB, 8>(g, L, F, nh, nt, sp.nud, L.hi, L.ud, sp.nut, 9,
+                                          [&](int di, int ti) { update(L.hi[di], ti); });
+  ocs_each<8>(u.nut, [&](int k) { ocs_update_none(g, trk[L.lst[L.ut[k]]], r8); });
 
   // ---- new tracks for the unmatched detections (free slots ascending) -----------------------
-  for (int s2 = lane; s2 < g.T; s2 += OW) L.fl[s2] = 0;
-  __syncthreads();
-  for (int p = lane; p < nt; p += OW) L.fl[L.lst[p]] = 1;
-  __syncthreads();
-  const int nfree = wave_compact(g.T, [&](int s2) { return L.fl[s2] == 0; }, [&](int s2, int p) { L.lst2[p] = s2; });
-  int nnew = nud;
-  if (nnew > nfree) {
-    if (lane == 0) atomicExch(g.status, (int)BX_ERR_TRACK_OVERFLOW);
-    nnew = nfree;
-  }
-  for (int c = 0; c < nnew; c += 8) {
-    const int k = c + oct;
-    if (k < nnew) {
-      const int slot = L.lst2[k];
-      const int i = L.hi[L.ud[k]];
-      const double* r = L.dd + 6 * i;
-      OcsTrk& t = trk[slot];
-      const double w = r[2] - r[0], h = r[3] - r[1];
-      const double z[4] = {r[0] + w / 2.0, r[1] + h / 2.0, w * h, w / (h + 1e-6)};
-      if (r8 < 7) {
-        t.x[r8] = r8 == 0 ? z[0] : r8 == 1 ? z[1] : r8 == 2 ? z[2] : r8 == 3 ? z[3] : 0.0;
-        const double pd = r8 < 4 ? 10.0 : 10000.0;
-#pragma unroll
-        for (int j = 0; j < 7; j++) t.P[r8 * 7 + j] = j == r8 ? pd : 0.0;
-      }
-      if (r8 == 0) {
-        t.observed = 0;
-        t.has_saved = 0;
-        t.hvalid = 0;
-        t.htail = 0;
-        t.id = id0 + k;
-        t.conf = r[4];
-        t.cls = r[5];
-        t.det_ind = i;
-        for (int q = 0; q < 5; q++) t.last_obs[q] = -1.0;
-        t.last_age = -1;
-        for (int q = 0; q < OBS_KEEP; q++) t.obs_age[q] = -1;
-        t.has_vel = 0;
-        t.vel[0] = t.vel[1] = 0.0;
-        t.tsu = t.hits = t.hit_streak = t.age = 0;
-        L.lst[nt + k] = slot;
-        emit(i, slot, true);  // emb = the detection's raw row (deepocsort.py:466)
-      }
+  const int nnew = ocs_free_slots(g, L, nt, u.nud);
+  ocs_each<8>(nnew, [&](int k) {
+    const int slot = L.lst2[k], i = L.hi[L.ud[k]];
+    ocs_born_octet(trk[slot], r8, L.dd + 6 * i, F.id0 + k, i);
+    if (r8 == 0) {
+      L.lst[nt + k] = slot;
+      emit(i, slot, true);  // emb = the detection's raw row (deepocsort.py:466)
     }
-  }
+  });
   __syncthreads();
-  const int ntr = nt + nnew;
 
-  // ---- outputs in reversed list order, then deletion of the dead (deepocsort.py:473-495) ----
-  double* orow = out + (size_t)r0 * 8;
-  const int nout = wave_compact(
-      ntr,
-      [&](int k) {
-        const OcsTrk& t = trk[L.lst[ntr - 1 - k]];
-        return t.tsu < 1 && (t.hit_streak >= g.min_hits || frame <= g.min_hits);
-      },
-      [&](int k, int p) {
-        const OcsTrk& t = trk[L.lst[ntr - 1 - k]];
-        double d[4];
-        if (sum5(t.last_obs) < 0) {
-          x_to_bbox(t.x, d);
-        } else {
-          for (int q = 0; q < 4; q++) d[q] = t.last_obs[q];
-        }
-        if (p < n) {
-          double* o = orow + (size_t)p * 8;
-          o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3];
-          o[4] = (double)t.id;  // no +1 (deepocsort.py:489): the counter starts at 1
-          o[5] = t.conf;
-          o[6] = t.cls;
-          o[7] = (double)t.det_ind;
-        }
-      });
-  const int nkeep = wave_compact(
-      ntr, [&](int k) { return trk[L.lst[k]].tsu <= g.max_age; },
-      [&](int k, int p) { order[p] = L.lst[k]; });
-  if (lane == 0) {
-    out_count[b] = nout < n ? nout : n;
-    sq[SO_FRAME] = frame;
-    sq[SO_IDS] = id0 + nnew;
-    sq[SO_NTR] = nkeep;
-    sq[SO_NOUT] = nout;
-  }
+  // ---- outputs in reversed list order, then deletion of the dead (deepocsort.py:473-495); the
+  // id without +1 (deepocsort.py:489): the counter starts at 1
+  ocs_frame_end(g, L, F, trk, out, out_count, nt + nnew, nnew, 0,
+                [](const double* x, double* d) { x_to_bbox(x, d); });
 }
 
 // update_emb (deepocsort.py:184-186) / the newborn's emb = its detection's row; wave per

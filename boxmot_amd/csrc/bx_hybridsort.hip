@@ -506,40 +506,25 @@ __global__ void __launch_bounds__(OW)
   carve(g, lds_raw, L);
   int* pp = (int*)(lds_raw + gd.x_off);  // [T] pre-frame list position of each kept track
   const int lane = threadIdx.x;
-  const int b = blockIdx.x, seq = seq0 + b;
+  const int seq = seq0 + blockIdx.x;
   L.jv.dc = nullptr;
-  const int r0 = det_off[b];
-  int n = det_off[b + 1] - r0;
-  if (n > g.D) {  // the host checks det_cap; a device-side overflow is latched, never run past
-    if (threadIdx.x == 0) atomicExch(g.status, (int)BX_ERR_CAPACITY);
-    n = g.D;
-  }
-  int* sq = g.seqst + (size_t)seq * SQO;
+  const OcsFrame F = ocs_frame_begin<HTB>(g, L, seq, dets, det_off);
   HybTrk* trk = gd.trk + (size_t)seq * g.T;
-  int* order = g.order + (size_t)seq * g.T;
-  double* tb = g.tb + (size_t)seq * g.T * HTB;
-  double* cost = g.cost_g ? g.cost_g + (size_t)seq * g.D * g.T : nullptr;
+  double* tb = F.tb;
   const double* ec0 = gd.ec + (size_t)seq * 2 * g.D * g.T;
   const double* ec1 = ec0 + (size_t)g.D * g.T;
   int* rec = gd.rec + (size_t)seq * g.D;
   int* rec_b = gd.rec_b + (size_t)seq * g.D;
-  const int frame = sq[SO_FRAME] + 1;
-  const int id0 = sq[SO_IDS];
-  const int nt0 = sq[SO_NTR];
-  const double thr = g.asso_threshold;
-  const int ak = g.asso_kind;
-  const double fw = g.fsz[2 * seq], fh = g.fsz[2 * seq + 1];
-
-  // detections (setup_decorator's float32 rounding is the input format)
-  for (int q = lane; q < n * 6; q += OW) L.dd[q] = (double)dets[(size_t)r0 * 6 + q];
-  for (int p = lane; p < nt0; p += OW) L.lst2[p] = order[p];
-  for (int i = lane; i < n; i += OW) rec[i] = -1;
+  const int nt0 = F.nt0;
+  const double thr = F.thr, fw = F.fw, fh = F.fh;
+  const int ak = F.ak;
+  for (int i = lane; i < F.n; i += OW) rec[i] = -1;
   __syncthreads();
   // remain_inds = scores > det_thresh on the float32 scores (hybridsort.py:466); the rest of the
   // frame's detections is dropped (the BYTE round that would take some of it is not built)
   const float dthr = (float)g.det_thresh;
   const int nh = wave_compact(
-      n, [&](int i) { return (float)L.dd[6 * i + 4] > dthr; }, [&](int i, int p) { L.hi[p] = i; });
+      F.n, [&](int i) { return (float)L.dd[6 * i + 4] > dthr; }, [&](int i, int p) { L.hi[p] = i; });
 
   // cls and det_ind of a kept detection are read from dets0 = [dets, scores], the UNFILTERED
   // frame, at the detection's index among the kept ones (hybridsort.py:458,467,604,709): the
@@ -587,10 +572,7 @@ __global__ void __launch_bounds__(OW)
       int qq = -1;
       const int last_age = t.last_age;
       if (last_age >= 0) {
-        for (int i = g.delta_t - 1; i >= 0; i--) {  // first hit of age-delta_t .. age-1
-          const int want = age - g.delta_t + i;
-          if (want >= 0 && t.obs_age[want & (OBS_KEEP - 1)] == want) qq = want & (OBS_KEEP - 1);
-        }
+        qq = obs_first(t, age - g.delta_t, g.delta_t);
         if (qq < 0) qq = last_age & (OBS_KEEP - 1);  // observations[max(keys)]
       }
       auto val = [&](int e) -> double {
@@ -620,261 +602,113 @@ __global__ void __launch_bounds__(OW)
   __syncthreads();
 
   // ---- first association (association.py:537-644): always the LAP ---------------------------
-  int nm = 0, nud = 0, nut = 0;
-  if (nt == 0) {
-    for (int k = lane; k < nh; k += OW) L.ud[k] = k;
-    nud = nh;
-  } else {
-    int nmi = 0;
-    if (nh > 0) {
-      double* C = (nh * nt <= g.cost_lds) ? L.cost : cost;
-      for (int c = 0; c < nt; c += OW) {
-        const int ti = c + lane;
-        if (ti < nt) {
-          const double* r = tb + (size_t)ti * HTB;
-          const double* p = r + HT_KOBS;
-          const double ks = r[HT_KS];
-          const double valid = p[4] < 0 ? 0.0 : 1.0;
-          const int col = pp[ti];
-          for (int d = 0; d < nh; d++) {
-            const int i = L.hi[d];
-            const double* a = L.dd + 6 * i;
-            const double o = asso_pair(ak, a, r, fw, fh);
-            // cost_vel of the four corners (speed_direction_batch_lt/_rt/_lb/_rb against the
-            // k-previous observation), each scaled by the detection score, summed lt+rt+lb+rb
-            double ang = 0.0;
-            for (int cn = 0; cn < 4; cn++) {
-              const int ix = cn < 2 ? 0 : 2, iy = (cn & 1) ? 3 : 1;
-              double dx = a[ix] - p[ix], dy = a[iy] - p[iy];
-              const double norm = sqrt(dx * dx + dy * dy) + 1e-6;
-              dx = dx / norm;
-              dy = dy / norm;
-              const double vy = r[HT_VEL + 2 * cn], vx = r[HT_VEL + 2 * cn + 1];
-              double cth = vx * dx + vy * dy;
-              cth = cth < -1 ? -1 : (cth > 1 ? 1 : cth);
-              double an = ocs_acos(cth);
-              an = (3.14159265358979323846 / 2.0 - fabs(an)) / 3.14159265358979323846;
-              const double mc = ((valid * an) * g.inertia) * a[4];
-              ang = cn ? ang + mc : mc;
-            }
-            const double sd = fabs(ks - a[4]);
-            ang = ang - sd * gd.tcm_w;
-            const double e0 = ec0[(size_t)i * g.T + col], e1 = ec1[(size_t)i * g.T + col];
-            C[d * nt + ti] = (1.0 * (-(o + ang)) + 1.3 * e0) + gd.lt_w * e1;
+  int nmi = 0;
+  if (nt > 0 && nh > 0) {
+    double* C = ocs_cost_buf(g, L, F, nh, nt);
+    for (int c = 0; c < nt; c += OW) {
+      const int ti = c + lane;
+      if (ti < nt) {
+        const double* r = tb + (size_t)ti * HTB;
+        const double* p = r + HT_KOBS;
+        const double ks = r[HT_KS];
+        const double valid = p[4] < 0 ? 0.0 : 1.0;
+        const int col = pp[ti];
+        for (int d = 0; d < nh; d++) {
+          const int i = L.hi[d];
+          const double* a = L.dd + 6 * i;
+          const double o = asso_pair(ak, a, r, fw, fh);
+          // cost_vel of the four corners (speed_direction_batch_lt/_rt/_lb/_rb against the
+          // k-previous observation), each scaled by the detection score, summed lt+rt+lb+rb
+          double ang = 0.0;
+          for (int cn = 0; cn < 4; cn++) {
+            const int ix = cn < 2 ? 0 : 2, iy = (cn & 1) ? 3 : 1;
+            double dx = a[ix] - p[ix], dy = a[iy] - p[iy];
+            const double norm = sqrt(dx * dx + dy * dy) + 1e-6;
+            dx = dx / norm;
+            dy = dy / norm;
+            const double vy = r[HT_VEL + 2 * cn], vx = r[HT_VEL + 2 * cn + 1];
+            double cth = vx * dx + vy * dy;
+            cth = cth < -1 ? -1 : (cth > 1 ? 1 : cth);
+            double an = ocs_acos(cth);
+            an = (3.14159265358979323846 / 2.0 - fabs(an)) / 3.14159265358979323846;
+            const double mc = ((valid * an) * g.inertia) * a[4];
+            ang = cn ? ang + mc : mc;
           }
+          const double sd = fabs(ks - a[4]);
+          ang = ang - sd * gd.tcm_w;
+          const double e0 = ec0[(size_t)i * g.T + col], e1 = ec1[(size_t)i * g.T + col];
+          C[d * nt + ti] = (1.0 * (-(o + ang)) + 1.3 * e0) + gd.lt_w * e1;
         }
       }
-      __syncthreads();
-      nmi = ocs_lap(C, nh, nt, L.jv, L.mi);
-    }
-    // unmatched = absent from the LAP's pairs, ascending; then the correction filter with the
-    // dropped pairs appended in pair order (association.py:608-637)
-    for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = L.colcnt[k] = 0;
-    __syncthreads();
-    for (int q = lane; q < nmi; q += OW) {
-      L.rowcnt[L.mi[2 * q]] = 1;
-      L.colcnt[L.mi[2 * q + 1]] = 1;
     }
     __syncthreads();
-    nud = wave_compact(nh, [&](int d) { return L.rowcnt[d] == 0; }, [&](int d, int p) { L.ud[p] = d; });
-    nut = wave_compact(nt, [&](int t) { return L.colcnt[t] == 0; }, [&](int t, int p) { L.ut[p] = t; });
-    for (int c = 0; c < nmi; c += OW) {
-      const int q = c + lane;
-      bool ok = false, rej = false;
-      int d = 0, ti = 0;
-      if (q < nmi) {
-        d = L.mi[2 * q];
-        ti = L.mi[2 * q + 1];
-        const int i = L.hi[d];
-        const double* r = tb + (size_t)ti * HTB;
-        const double o = asso_pair(ak, L.dd + 6 * i, r, fw, fh);
-        const double sd = fabs(r[HT_KS] - L.dd[6 * i + 4]);
-        const double e0 = ec0[(size_t)i * g.T + pp[ti]];
-        // dropped only if the embedding is far AND iou - score_dif is under the threshold
-        rej = e0 > 0.4 && (o - sd) < thr;
-        ok = !rej;
-      }
-      const unsigned long long mo = __ballot(ok), mr = __ballot(rej);
-      const unsigned long long below = (1ull << lane) - 1ull;
-      if (ok) {
-        const int p = nm + __popcll(mo & below);
-        L.mm[2 * p] = d;
-        L.mm[2 * p + 1] = ti;
-      }
-      if (rej) {
-        const int p = __popcll(mr & below);
-        L.ud[nud + p] = d;
-        L.ut[nut + p] = ti;
-      }
-      nm += __popcll(mo);
-      nud += __popcll(mr);
-      nut += __popcll(mr);
-    }
-    __syncthreads();
+    nmi = ocs_lap(C, nh, nt, L.jv, L.mi);
   }
-  for (int c = 0; c < nm; c += 4) {
-    const int q = c + grp;
-    if (q < nm) {
-      const int dk = L.mm[2 * q];
-      const int i = L.hi[dk], slot = L.lst[L.mm[2 * q + 1]];
-      const double* r = L.dd + 6 * i;
-      hyb_update_det(gd, trk[slot], r16, r, d0cls(dk), d0ind(dk));
-      if (r16 == 0) {
-        rec_b[i] = 0;
-        rec[i] = slot;
-      }
+  // the correction filter (association.py:608-637): a pair is dropped only if the embedding is far
+  // AND iou - score_dif is under the threshold
+  const OcsSplit sp = ocs_split(g, L, nh, nt, nmi, [&](int d, int ti) {
+    const int i = L.hi[d];
+    const double* r = tb + (size_t)ti * HTB;
+    const double o = asso_pair(ak, L.dd + 6 * i, r, fw, fh);
+    const double sd = fabs(r[HT_KS] - L.dd[6 * i + 4]);
+    const double e0 = ec0[(size_t)i * g.T + pp[ti]];
+    return !(e0 > 0.4 && (o - sd) < thr);
+  });
+  // update(det) of list position ti with the dk-th kept detection, 16 lanes wide
+  auto update = [&](int dk, int ti) {
+    hyb_update_det(gd, trk[L.lst[ti]], r16, L.dd + 6 * L.hi[dk], d0cls(dk), d0ind(dk));
+  };
+  ocs_each<16>(sp.nm, [&](int q) {
+    const int dk = L.mm[2 * q], ti = L.mm[2 * q + 1];
+    update(dk, ti);
+    if (r16 == 0) {
+      rec_b[L.hi[dk]] = 0;
+      rec[L.hi[dk]] = L.lst[ti];
     }
-  }
+  });
   __syncthreads();
 
   // ---- OCR round on the last observations (hybridsort.py:666-700); no feature update --------
-  if (nud > 0 && nut > 0) {
-    double mx = -INF;
-    for (int c = 0; c < nut; c += OW) {
-      const int k = c + lane;
-      if (k < nut) {
-        const double* bq = tb + (size_t)L.ut[k] * HTB + HT_LAST;
-        for (int d = 0; d < nud; d++)
-          mx = fmax(mx, asso_pair(ak, L.dd + 6 * L.hi[L.ud[d]], bq, fw, fh));
-      }
-    }
-    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-    if (mx > thr) {
-      double* C = (nud * nut <= g.cost_lds) ? L.cost : cost;
-      for (int c = 0; c < nut; c += OW) {
-        const int k = c + lane;
-        if (k < nut) {
-          const double* bq = tb + (size_t)L.ut[k] * HTB + HT_LAST;
-          for (int d = 0; d < nud; d++)
-            C[d * nut + k] = -asso_pair(ak, L.dd + 6 * L.hi[L.ud[d]], bq, fw, fh);
-        }
-      }
-      __syncthreads();
-      const int np_ = ocs_lap(C, nud, nut, L.jv, L.mi);
-      for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = L.fl[k] = 0;
-      __syncthreads();
-      for (int c = 0; c < np_; c += 4) {
-        const int q = c + grp;
-        if (q < np_) {
-          const int a = L.mi[2 * q], k = L.mi[2 * q + 1];
-          if (!(-C[a * nut + k] < thr)) {
-            const int di = L.ud[a], ti = L.ut[k];
-            const int i = L.hi[di], slot = L.lst[ti];
-            const double* r = L.dd + 6 * i;
-            hyb_update_det(gd, trk[slot], r16, r, d0cls(di), d0ind(di));
-            if (r16 == 0) {
-              L.rowcnt[di] = 2;
-              L.fl[ti] = 2;
-            }
-          }
-        }
-      }
-      __syncthreads();
-      for (int k = lane; k < nud; k += OW)
-        if (L.rowcnt[L.ud[k]] == 0) L.rowcnt[L.ud[k]] = 1;
-      for (int k = lane; k < nut; k += OW)
-        if (L.fl[L.ut[k]] == 0) L.fl[L.ut[k]] = 1;
-      __syncthreads();
-      // np.setdiff1d: ascending, unique
-      nud = wave_compact(nh, [&](int d) { return L.rowcnt[d] == 1; }, [&](int d, int p) { L.ud[p] = d; });
-      nut = wave_compact(nt, [&](int t) { return L.fl[t] == 1; }, [&](int t, int p) { L.ut[p] = t; });
-    }
-  }
-  for (int c = 0; c < nut; c += 4) {
-    const int k = c + grp;
-    if (k < nut) hyb_update_none(g, trk[L.lst[L.ut[k]]], r16);
-  }
+  const OcsRematch u =
+      ocs_rematch<HTB, 16>(g, L, F, nh, nt, sp.nud, L.hi, L.ud, sp.nut, HT_LAST, update);
+  ocs_each<16>(u.nut, [&](int k) { hyb_update_none(g, trk[L.lst[L.ut[k]]], r16); });
 
   // ---- new tracks for the unmatched detections (free slots ascending) -----------------------
-  for (int s2 = lane; s2 < g.T; s2 += OW) L.fl[s2] = 0;
-  __syncthreads();
-  for (int p = lane; p < nt; p += OW) L.fl[L.lst[p]] = 1;
-  __syncthreads();
-  const int nfree = wave_compact(g.T, [&](int s2) { return L.fl[s2] == 0; }, [&](int s2, int p) { L.lst2[p] = s2; });
-  int nnew = nud;
-  if (nnew > nfree) {
-    if (lane == 0) atomicExch(g.status, (int)BX_ERR_TRACK_OVERFLOW);
-    nnew = nfree;
-  }
-  for (int c = 0; c < nnew; c += 4) {
-    const int k = c + grp;
-    if (k < nnew) {
-      const int slot = L.lst2[k];
-      const int dk = L.ud[k];
-      const int i = L.hi[dk];
-      const double* r = L.dd + 6 * i;
-      HybTrk& t = trk[slot];
-      float zf[5];
-      box_to_z(r, zf);
-      if (r16 < HX) {  // kf.x[:5] = z; P = diag(10 x5, 10000 x4) (hybridsort.py:164-173)
-        t.x[r16] = r16 == 0 ? zf[0] : r16 == 1 ? zf[1] : r16 == 2 ? zf[2] : r16 == 3 ? zf[3]
-                   : r16 == 4 ? zf[4] : 0.0;
-        const double pd = r16 < 5 ? 10.0 : 10000.0;
+  const int nnew = ocs_free_slots(g, L, nt, u.nud);
+  ocs_each<16>(nnew, [&](int k) {
+    const int slot = L.lst2[k];
+    const int dk = L.ud[k];
+    const int i = L.hi[dk];
+    const double* r = L.dd + 6 * i;
+    HybTrk& t = trk[slot];
+    float zf[5];
+    box_to_z(r, zf);
+    if (r16 < HX) {  // kf.x[:5] = z; P = diag(10 x5, 10000 x4) (hybridsort.py:164-173)
+      t.x[r16] = r16 == 0 ? zf[0] : r16 == 1 ? zf[1] : r16 == 2 ? zf[2] : r16 == 3 ? zf[3]
+                 : r16 == 4 ? zf[4] : 0.0;
+      const double pd = r16 < 5 ? 10.0 : 10000.0;
 #pragma unroll
-        for (int j = 0; j < HX; j++) t.P[r16 * HX + j] = j == r16 ? pd : 0.0;
-      }
-      if (r16 == 0) {
-        t.observed = 0;
-        t.has_saved = 0;
-        t.hvalid = 0;
-        t.htail = 0;
-        t.id = id0 + k;
-        t.conf = r[4];
-        t.cls = d0cls(dk);
-        t.det_ind = d0ind(dk);
-        t.confidence = (float)r[4];
-        t.conf_pre = 0.0f;
-        t.has_pre = 0;
-        for (int q = 0; q < 5; q++) t.last_obs[q] = -1.0;
-        t.last_age = -1;
-        for (int q = 0; q < OBS_KEEP; q++) t.obs_age[q] = -1;
-        t.has_vel = 0;
-        for (int q = 0; q < 4; q++) t.vel[q][0] = t.vel[q][1] = 0.0;
-        t.tsu = t.hits = t.hit_streak = t.age = 0;
-        L.lst[nt + k] = slot;
-        rec_b[i] = 1;
-        rec[i] = slot;
-      }
+      for (int j = 0; j < HX; j++) t.P[r16 * HX + j] = j == r16 ? pd : 0.0;
     }
-  }
+    if (r16 == 0) {
+      ocs_born_common(t, F.id0 + k, r[4]);
+      t.cls = d0cls(dk);
+      t.det_ind = d0ind(dk);
+      t.confidence = (float)r[4];
+      t.conf_pre = 0.0f;
+      t.has_pre = 0;
+      for (int q = 0; q < 4; q++) t.vel[q][0] = t.vel[q][1] = 0.0;
+      L.lst[nt + k] = slot;
+      rec_b[i] = 1;
+      rec[i] = slot;
+    }
+  });
   __syncthreads();
-  const int ntr = nt + nnew;
 
-  // ---- outputs in reversed list order, then deletion of the dead (hybridsort.py:716-741) ----
-  double* orow = out + (size_t)r0 * 8;
-  const int nout = wave_compact(
-      ntr,
-      [&](int k) {
-        const HybTrk& t = trk[L.lst[ntr - 1 - k]];
-        return t.tsu < 1 && (t.hit_streak >= g.min_hits || frame <= g.min_hits);
-      },
-      [&](int k, int p) {
-        const HybTrk& t = trk[L.lst[ntr - 1 - k]];
-        double d[4];
-        if (sum5(t.last_obs) < 0) {
-          x9_to_bbox(t.x, d);
-        } else {
-          for (int q = 0; q < 4; q++) d[q] = t.last_obs[q];
-        }
-        if (p < n) {
-          double* o = orow + (size_t)p * 8;
-          o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3];
-          o[4] = (double)t.id;  // the per-sequence counter starts at 1 (count 0, id + 1)
-          o[5] = t.conf;
-          o[6] = t.cls;
-          o[7] = t.det_ind;
-        }
-      });
-  const int nkeep = wave_compact(
-      ntr, [&](int k) { return trk[L.lst[k]].tsu <= g.max_age; },
-      [&](int k, int p) { order[p] = L.lst[k]; });
-  if (lane == 0) {
-    out_count[b] = nout < n ? nout : n;
-    sq[SO_FRAME] = frame;
-    sq[SO_IDS] = id0 + nnew;
-    sq[SO_NTR] = nkeep;
-    sq[SO_NOUT] = nout;
-  }
+  // ---- outputs in reversed list order, then deletion of the dead (hybridsort.py:716-741); the
+  // id as it is: the per-sequence counter starts at 1 (count 0, id + 1)
+  ocs_frame_end(g, L, F, trk, out, out_count, nt + nnew, nnew, 0,
+                [](const double* x, double* d) { x9_to_bbox(x, d); });
 }
 
 // update_features (hybridsort.py:216-235) of the first round's matches and the newborns; wave per

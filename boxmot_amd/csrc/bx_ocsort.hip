@@ -43,442 +43,96 @@ __global__ void __launch_bounds__(OW)
   extern __shared__ __align__(16) char lds_raw[];
   OcsLds L;
   carve(g, lds_raw, L);
-  const int lane = threadIdx.x;
-  const int b = blockIdx.x, seq = seq0 + b;
+  const int seq = seq0 + blockIdx.x;
   ocs_seq_override(g, seq);  // this sequence's own parameters, when the table holds some
   L.jv.dc = g.dbg ? g.dbg + (size_t)seq * OCS_DBG + 24 : nullptr;
-  const int r0 = det_off[b];
-  int n = det_off[b + 1] - r0;
-  if (n > g.D) {  // the host checks det_cap; a device-side overflow is latched, never run past
-    if (threadIdx.x == 0) atomicExch(g.status, (int)BX_ERR_CAPACITY);
-    n = g.D;
-  }
-  int* sq = g.seqst + (size_t)seq * SQO;
-  OcsTrk* trk = g.trk + (size_t)seq * g.T;
-  int* order = g.order + (size_t)seq * g.T;
-  double* tb = g.tb + (size_t)seq * g.T * TB;
-  double* cost = g.cost_g ? g.cost_g + (size_t)seq * g.D * g.T : nullptr;
 #ifdef BX_PHASE_TIMING
   unsigned long long t_last = __builtin_amdgcn_s_memtime();
 #endif
-  const int frame = sq[SO_FRAME] + 1;
-  const int id0 = sq[SO_IDS];
-  const int nt0 = sq[SO_NTR];
-  const double thr = g.asso_threshold;
-  const int ak = g.asso_kind;
-  const double fw = g.fsz[2 * seq], fh = g.fsz[2 * seq + 1];
-
-  // detections (setup_decorator's float32 rounding is the input format) and the splits
-  for (int q = lane; q < n * 6; q += OW) L.dd[q] = (double)dets[(size_t)r0 * 6 + q];
-  for (int p = lane; p < nt0; p += OW) L.lst2[p] = order[p];
+  const OcsFrame F = ocs_frame_begin<TB>(g, L, seq, dets, det_off);
+  OcsTrk* trk = g.trk + (size_t)seq * g.T;
   __syncthreads();
+  // the splits: the BYTE round's low-confidence detections and the rest of the frame's
   const int nl = wave_compact(
-      n, [&](int i) { const double c = L.dd[6 * i + 4]; return c > g.min_conf && c < g.det_thresh; },
+      F.n, [&](int i) { const double c = L.dd[6 * i + 4]; return c > g.min_conf && c < g.det_thresh; },
       [&](int i, int p) { L.lo[p] = i; });
   const int nh = wave_compact(
-      n, [&](int i) { return L.dd[6 * i + 4] > g.det_thresh; }, [&](int i, int p) { L.hi[p] = i; });
+      F.n, [&](int i) { return L.dd[6 * i + 4] > g.det_thresh; }, [&](int i, int p) { L.hi[p] = i; });
+  const int r8 = threadIdx.x & 7;
+  // update(det) of list position ti with detection row i, octet-wide
+  auto update = [&](int i, int ti) {
+    const double* r = L.dd + 6 * i;
+    ocs_update_det(g, trk[L.lst[ti]], r8, r, r[5], i);
+  };
 
-  const int oct = lane >> 3, r8 = lane & 7, rr8 = r8 < 7 ? r8 : 6;
-
-  // predict every track (an octet per track); tracks whose prediction has a NaN leave the list
-  // (ocsort.py:278-288).  tb row per kept track: box[4], k-previous obs[5], last_obs[5], vel[2]
-  int nt = 0;
-  for (int c = 0; c < nt0; c += 8) {
-    const int p = c + oct;
-    bool keep = false;
-    int slot = -1;
-    double v0 = 0.0, v1 = 0.0;  // this lane's two tb entries: [r8] and [8 + r8]
-    if (p < nt0) {
-      slot = L.lst2[p];
-      OcsTrk& t = trk[slot];
-      KfRow k;
-      row_load(t.x, t.P, rr8, k);
-      if ((osh(k.x, 6) + osh(k.x, 2)) <= 0 && rr8 == 6) k.x *= 0.0;
-      kfo_predict(g, rr8, k);
-      row_store(t.x, t.P, r8, k);
-      const int age = t.age + 1;
-      if (r8 == 0) {
-        t.age = age;
-        if (t.tsu > 0) t.hit_streak = 0;
-        t.tsu++;
-      }
-      double xs[4], bx[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) xs[q] = osh(k.x, q);
-      x_to_bbox(xs, bx);
-      keep = !(isnan(bx[0]) || isnan(bx[1]) || isnan(bx[2]) || isnan(bx[3]));
-      // k_previous_obs (ocsort.py:17-28) with the post-predict age
-      int qq = -1;
-      const int last_age = t.last_age;
-      if (last_age >= 0) {
-        qq = obs_first(t, age - g.delta_t, g.delta_t);
-        if (qq < 0) qq = last_age & (OBS_KEEP - 1);  // observations[max(keys)]
-      }
-      auto val = [&](int e) -> double {
-        if (e < 4) return e == 0 ? bx[0] : e == 1 ? bx[1] : e == 2 ? bx[2] : bx[3];
-        if (e < 9) return qq < 0 ? -1.0 : t.obs_box[qq][e - 4];
-        if (e < 14) return t.last_obs[e - 9];
-        return t.has_vel ? t.vel[e - 14] : 0.0;
-      };
-      v0 = val(r8);
-      v1 = val(8 + r8);
-    }
-    const unsigned long long m = __ballot(keep && r8 == 0);
-    if (keep) {
-      const int q = nt + __popcll(m & ((1ull << (lane & ~7)) - 1ull));
-      if (r8 == 0) L.lst[q] = slot;
-      double* row = tb + (size_t)q * TB;
-      row[r8] = v0;
-      row[8 + r8] = v1;
-    }
-    nt += __popcll(m);
-  }
-  __syncthreads();
+  const int nt = ocs_predict_octet(g, L, F, trk, nullptr);
   OSTAMP(1);
 
   // ---- first association: enhanced_associate(high dets, predicted tracks) -----------------
-  int nm = 0, nud = 0, nut = 0;
-  if (nt == 0) {
-    for (int k = lane; k < nh; k += OW) L.ud[k] = k;
-    nud = nh;
-  } else {
-    int nmi = 0;
-    if (nh > 0) {
-      // pass 1 (lane per track, dets broadcast from LDS): IoU > threshold counts for the
-      // one-to-one test.  A pair without overlap has IoU 0/U, never above a threshold >= 0, so
-      // only overlapping pairs divide.
-      for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = 0;
-      __syncthreads();
-      for (int c = 0; c < nt; c += OW) {
-        const int ti = c + lane;
-        if (ti < nt) {
-          const double* bq = tb + (size_t)ti * TB;
-          const double b0 = bq[0], b1 = bq[1], b2 = bq[2], b3 = bq[3];
-          const double at = (b2 - b0) * (b3 - b1);
-          int cc = 0;
-          for (int d = 0; d < nh; d++) {
-            const double* a = L.dd + 6 * L.hi[d];
-            const double xx1 = fmax(a[0], b0), yy1 = fmax(a[1], b1);
-            const double xx2 = fmin(a[2], b2), yy2 = fmin(a[3], b3);
-            const double w = fmax(0.0, xx2 - xx1), h = fmax(0.0, yy2 - yy1);
-            const double wh = w * h;
-            // the other registry modes score disjoint pairs too: no shortcut for them
-            if (wh > 0.0 || thr < 0.0 || ak != ASSO_IOU) {
-              const double o = ak == ASSO_IOU ? wh / ((a[2] - a[0]) * (a[3] - a[1]) + at - wh)
-                                              : asso_pair(ak, a, bq, fw, fh);
-              if (o > thr) {
-                atomicAdd(&L.rowcnt[d], 1);
-                L.rowcol[d] = ti;
-                cc++;
-              }
-            }
-          }
-          L.colcnt[ti] = cc;
-        }
-      }
-      __syncthreads();
-      OSTAMP(2);
-      int mr = 0, mcx = 0;
-      for (int k = lane; k < nh; k += OW) mr = max(mr, L.rowcnt[k]);
-      for (int k = lane; k < nt; k += OW) mcx = max(mcx, L.colcnt[k]);
-      for (int o = 32; o >= 1; o >>= 1) {
-        mr = max(mr, __shfl_xor(mr, o));
-        mcx = max(mcx, __shfl_xor(mcx, o));
-      }
-      if (mr == 1 && mcx == 1) {  // one-to-one: np.stack(np.where(iou > thr), 1), row-major
-        nmi = wave_compact(
-            nh, [&](int d) { return L.rowcnt[d] == 1; },
-            [&](int d, int p) {
-              L.mi[2 * p] = d;
-              L.mi[2 * p + 1] = L.rowcol[d];
-            });
-      } else {
-        // pass 2: the full cost -(IoU + direction consistency) and P4's legacy
-        // linear_assignment of it
-        double* C = (nh * nt <= g.cost_lds) ? L.cost : cost;
-        for (int c = 0; c < nt; c += OW) {
-          const int ti = c + lane;
-          if (ti < nt) {
-            const double* r = tb + (size_t)ti * TB;
-            const double* p = r + 4;
-            const double cx2 = (p[0] + p[2]) / 2.0, cy2 = (p[1] + p[3]) / 2.0;
-            const double vy = r[14], vx = r[15];
-            const double valid = p[4] < 0 ? 0.0 : 1.0;
-            for (int d = 0; d < nh; d++) {
-              const double* a = L.dd + 6 * L.hi[d];
-              const double o = asso_pair(ak, a, r, fw, fh);
-              // speed_direction_batch (association.py:10-20) against the k-previous obs
-              const double cx1 = (a[0] + a[2]) / 2.0, cy1 = (a[1] + a[3]) / 2.0;
-              double dx = cx1 - cx2, dy = cy1 - cy2;
-              const double norm = sqrt(dx * dx + dy * dy) + 1e-6;
-              dx = dx / norm;
-              dy = dy / norm;
-              double cth = vx * dx + vy * dy;
-              cth = cth < -1 ? -1 : (cth > 1 ? 1 : cth);
-              double ang = ocs_acos(cth);
-              ang = (3.14159265358979323846 / 2.0 - fabs(ang)) / 3.14159265358979323846;
-              const double mc = (valid * ang) * g.inertia;
-              C[d * nt + ti] = -(o + mc);
-            }
-          }
-        }
-        __syncthreads();
-        nmi = ocs_lap(C, nh, nt, L.jv, L.mi);
-        OCOUNT(0, 1);
-        OCOUNT(1, nh > nt ? nh : nt);
-      }
-      OSTAMP(3);
+  int nmi = 0;
+  if (nt > 0 && nh > 0) {
+    ocs_pass1_count(g, L, F, nh, nt);
+    OSTAMP(2);
+    nmi = ocs_one_to_one(L, nh, nt);
+    if (nmi < 0) {
+      double* C = ocs_cost_buf(g, L, F, nh, nt);
+      ocs_cost_fill(g, L, F, C, nh, nt, [](int, int, double s) { return s; });
+      nmi = ocs_lap(C, nh, nt, L.jv, L.mi);
+      OCOUNT(0, 1);
+      OCOUNT(1, nh > nt ? nh : nt);
     }
-    // P3: unmatched = absent from the candidate pairs, ascending; then the IoU validation with
-    // rejected pairs appended in pair order (P5)
-    for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = L.colcnt[k] = 0;
-    __syncthreads();
-    for (int q = lane; q < nmi; q += OW) {
-      L.rowcnt[L.mi[2 * q]] = 1;
-      L.colcnt[L.mi[2 * q + 1]] = 1;
-    }
-    __syncthreads();
-    nud = wave_compact(nh, [&](int d) { return L.rowcnt[d] == 0; }, [&](int d, int p) { L.ud[p] = d; });
-    nut = wave_compact(nt, [&](int t) { return L.colcnt[t] == 0; }, [&](int t, int p) { L.ut[p] = t; });
-    for (int c = 0; c < nmi; c += OW) {
-      const int q = c + lane;
-      bool ok = false, rej = false;
-      int d = 0, ti = 0;
-      if (q < nmi) {
-        d = L.mi[2 * q];
-        ti = L.mi[2 * q + 1];
-        ok = asso_pair(ak, L.dd + 6 * L.hi[d], tb + (size_t)ti * TB, fw, fh) >= thr;
-        rej = !ok;
-      }
-      const unsigned long long mo = __ballot(ok), mr = __ballot(rej);
-      const unsigned long long below = (1ull << lane) - 1ull;
-      if (ok) {
-        const int p = nm + __popcll(mo & below);
-        L.mm[2 * p] = d;
-        L.mm[2 * p + 1] = ti;
-      }
-      if (rej) {
-        const int p = __popcll(mr & below);
-        L.ud[nud + p] = d;
-        L.ut[nut + p] = ti;
-      }
-      nm += __popcll(mo);
-      nud += __popcll(mr);
-      nut += __popcll(mr);
-    }
-    __syncthreads();
+    OSTAMP(3);
   }
-  for (int c = 0; c < nm; c += 8) {
-    const int q = c + oct;
-    if (q < nm) {
-      const double* r = L.dd + 6 * L.hi[L.mm[2 * q]];
-      ocs_update_det(g, trk[L.lst[L.mm[2 * q + 1]]], r8, r, r[5], L.hi[L.mm[2 * q]]);
-    }
-  }
+  const OcsSplit sp = ocs_split(g, L, nh, nt, nmi, [&](int d, int ti) {
+    return asso_pair(F.ak, L.dd + 6 * L.hi[d], F.tb + (size_t)ti * TB, F.fw, F.fh) >= F.thr;
+  });
+  int nud = sp.nud, nut = sp.nut;
+  ocs_each<8>(sp.nm, [&](int q) { update(L.hi[L.mm[2 * q]], L.mm[2 * q + 1]); });
   __syncthreads();
   OSTAMP(4);
 
-  // IoU matrix of detections (LDS rows `dsel`) x track boxes (tb rows `tsel`, offset `boff`):
-  // its maximum (overlapping pairs only divide: a threshold >= 0 never passes 0/U), and, when
-  // asked, the full matrix -IoU into C [nr][nc]
-  auto iou_max = [&](int nr, const int* dsel, const int* dmap, int nc, const int* tsel, int boff) {
-    double mx = -INF;
-    for (int c = 0; c < nc; c += OW) {
-      const int k = c + lane;
-      if (k < nc) {
-        const double* bq = tb + (size_t)tsel[k] * TB + boff;
-        const double b0 = bq[0], b1 = bq[1], b2 = bq[2], b3 = bq[3];
-        const double at = (b2 - b0) * (b3 - b1);
-        for (int d = 0; d < nr; d++) {
-          const double* a = L.dd + 6 * dsel[dmap ? dmap[d] : d];
-          const double xx1 = fmax(a[0], b0), yy1 = fmax(a[1], b1);
-          const double xx2 = fmin(a[2], b2), yy2 = fmin(a[3], b3);
-          const double w = fmax(0.0, xx2 - xx1), h = fmax(0.0, yy2 - yy1);
-          const double wh = w * h;
-          if (ak != ASSO_IOU)
-            mx = fmax(mx, asso_pair(ak, a, bq, fw, fh));
-          else if (wh > 0.0 || thr < 0.0)
-            mx = fmax(mx, wh / ((a[2] - a[0]) * (a[3] - a[1]) + at - wh));
-        }
-      }
-    }
-    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-    return mx;
-  };
-  auto iou_fill = [&](double* C, int nr, const int* dsel, const int* dmap, int nc, const int* tsel,
-                      int boff) {
-    for (int c = 0; c < nc; c += OW) {
-      const int k = c + lane;
-      if (k < nc) {
-        const double* bq = tb + (size_t)tsel[k] * TB + boff;
-        for (int d = 0; d < nr; d++)
-          C[d * nc + k] = -asso_pair(ak, L.dd + 6 * dsel[dmap ? dmap[d] : d], bq, fw, fh);
-      }
-    }
-    __syncthreads();
-  };
-
   // ---- BYTE round on the low-confidence detections (ocsort.py:330-356) ---------------------
-  if (g.use_byte && nl > 0 && nut > 0) {
-    const double mx = iou_max(nl, L.lo, nullptr, nut, L.ut, 0);
-    if (mx > thr) {
-      double* C = (nl * nut <= g.cost_lds) ? L.cost : cost;
-      iou_fill(C, nl, L.lo, nullptr, nut, L.ut, 0);
-      const int np_ = ocs_lap(C, nl, nut, L.jv, L.mi);
-      for (int k = lane; k < g.N; k += OW) L.fl[k] = 0;
-      __syncthreads();
-      for (int c = 0; c < np_; c += 8) {
-        const int q = c + oct;
-        if (q < np_) {
-          const int dl = L.mi[2 * q], k = L.mi[2 * q + 1];
-          if (!(-C[dl * nut + k] < thr)) {
-            const double* r = L.dd + 6 * L.lo[dl];
-            ocs_update_det(g, trk[L.lst[L.ut[k]]], r8, r, r[5], L.lo[dl]);
-            if (r8 == 0) L.fl[L.ut[k]] = 2;  // removed
-          }
-        }
-      }
-      __syncthreads();
-      for (int k = lane; k < nut; k += OW)
-        if (L.fl[L.ut[k]] == 0) L.fl[L.ut[k]] = 1;
-      __syncthreads();
-      // np.setdiff1d: ascending, unique
-      nut = wave_compact(nt, [&](int t) { return L.fl[t] == 1; }, [&](int t, int p) { L.ut[p] = t; });
-      OCOUNT(2, 1);
-    }
+  if (g.use_byte) {
+    const OcsRematch u = ocs_rematch<TB, 8>(g, L, F, nh, nt, nl, L.lo, nullptr, nut, 0,
+                                            [&](int dl, int ti) { update(L.lo[dl], ti); });
+    nut = u.nut;
+    OCOUNT(2, u.ran);
   }
   OSTAMP(5);
 
   // ---- OCR round on the last observations (ocsort.py:358-386) -------------------------------
   if (nud > 0 && nut > 0) {
-    const double mx = iou_max(nud, L.hi, L.ud, nut, L.ut, 9);
+    const double mx = ocs_rematch_max<TB>(L, F, nud, L.hi, L.ud, nut, 9);
     OSTAMP(6);
-    if (mx > thr) {
-      double* C = (nud * nut <= g.cost_lds) ? L.cost : cost;
-      iou_fill(C, nud, L.hi, L.ud, nut, L.ut, 9);
-      const int np_ = ocs_lap(C, nud, nut, L.jv, L.mi);
+    if (mx > F.thr) {
       OCOUNT(3, 1);
       OCOUNT(4, nud > nut ? nud : nut);
-      for (int k = lane; k < g.N; k += OW) L.rowcnt[k] = L.fl[k] = 0;
-      __syncthreads();
-      for (int c = 0; c < np_; c += 8) {
-        const int q = c + oct;
-        if (q < np_) {
-          const int a = L.mi[2 * q], k = L.mi[2 * q + 1];
-          if (!(-C[a * nut + k] < thr)) {
-            const int di = L.ud[a], ti = L.ut[k];
-            const double* r = L.dd + 6 * L.hi[di];
-            ocs_update_det(g, trk[L.lst[ti]], r8, r, r[5], L.hi[di]);
-            if (r8 == 0) {
-              L.rowcnt[di] = 2;
-              L.fl[ti] = 2;
-            }
-          }
-        }
-      }
-      __syncthreads();
-      for (int k = lane; k < nud; k += OW)
-        if (L.rowcnt[L.ud[k]] == 0) L.rowcnt[L.ud[k]] = 1;
-      for (int k = lane; k < nut; k += OW)
-        if (L.fl[L.ut[k]] == 0) L.fl[L.ut[k]] = 1;
-      __syncthreads();
-      nud = wave_compact(nh, [&](int d) { return L.rowcnt[d] == 1; }, [&](int d, int p) { L.ud[p] = d; });
-      nut = wave_compact(nt, [&](int t) { return L.fl[t] == 1; }, [&](int t, int p) { L.ut[p] = t; });
+      const OcsRematch u = ocs_rematch_solve<TB, 8>(g, L, F, nh, nt, nud, L.hi, L.ud, nut, 9,
+                                                    [&](int di, int ti) { update(L.hi[di], ti); });
+      nud = u.nud;
+      nut = u.nut;
     }
   }
   OSTAMP(7);
-  for (int c = 0; c < nut; c += 8) {
-    const int k = c + oct;
-    if (k < nut) ocs_update_none(g, trk[L.lst[L.ut[k]]], r8);
-  }
+  ocs_each<8>(nut, [&](int k) { ocs_update_none(g, trk[L.lst[L.ut[k]]], r8); });
 
   // ---- new tracks for the unmatched high detections (free slots ascending) ----------------
-  for (int s2 = lane; s2 < g.T; s2 += OW) L.fl[s2] = 0;
+  const int nnew = ocs_free_slots(g, L, nt, nud);
+  ocs_each<8>(nnew, [&](int k) {
+    const int slot = L.lst2[k], i = L.hi[L.ud[k]];
+    ocs_born_octet(trk[slot], r8, L.dd + 6 * i, F.id0 + k, i);
+    if (r8 == 0) L.lst[nt + k] = slot;
+  });
   __syncthreads();
-  for (int p = lane; p < nt; p += OW) L.fl[L.lst[p]] = 1;
-  __syncthreads();
-  const int nfree = wave_compact(g.T, [&](int s2) { return L.fl[s2] == 0; }, [&](int s2, int p) { L.lst2[p] = s2; });
-  int nnew = nud;
-  if (nnew > nfree) {
-    if (lane == 0) atomicExch(g.status, (int)BX_ERR_TRACK_OVERFLOW);
-    nnew = nfree;
-  }
-  for (int c = 0; c < nnew; c += 8) {
-    const int k = c + oct;
-    if (k < nnew) {
-      const int slot = L.lst2[k];
-      const double* r = L.dd + 6 * L.hi[L.ud[k]];
-      OcsTrk& t = trk[slot];
-      const double w = r[2] - r[0], h = r[3] - r[1];
-      const double z[4] = {r[0] + w / 2.0, r[1] + h / 2.0, w * h, w / (h + 1e-6)};
-      if (r8 < 7) {
-        t.x[r8] = r8 == 0 ? z[0] : r8 == 1 ? z[1] : r8 == 2 ? z[2] : r8 == 3 ? z[3] : 0.0;
-        const double pd = r8 < 4 ? 10.0 : 10000.0;
-#pragma unroll
-        for (int j = 0; j < 7; j++) t.P[r8 * 7 + j] = j == r8 ? pd : 0.0;
-      }
-      if (r8 == 0) {
-        t.observed = 0;
-        t.has_saved = 0;
-        t.hvalid = 0;
-        t.htail = 0;
-        t.id = id0 + k;
-        t.conf = r[4];
-        t.cls = r[5];
-        t.det_ind = L.hi[L.ud[k]];
-        for (int q = 0; q < 5; q++) t.last_obs[q] = -1.0;
-        t.last_age = -1;
-        for (int q = 0; q < OBS_KEEP; q++) t.obs_age[q] = -1;
-        t.has_vel = 0;
-        t.vel[0] = t.vel[1] = 0.0;
-        t.tsu = t.hits = t.hit_streak = t.age = 0;
-        L.lst[nt + k] = slot;
-      }
-    }
-  }
-  __syncthreads();
-  const int ntr = nt + nnew;
   OSTAMP(8);
 
   // ---- outputs in reversed list order, then deletion of the dead (ocsort.py:414-436) ---------
-  double* orow = out + (size_t)r0 * 8;
-  const int nout = wave_compact(
-      ntr,
-      [&](int k) {
-        const OcsTrk& t = trk[L.lst[ntr - 1 - k]];
-        return t.tsu < 1 && (t.hit_streak >= g.min_hits || frame <= g.min_hits);
-      },
-      [&](int k, int p) {
-        const OcsTrk& t = trk[L.lst[ntr - 1 - k]];
-        double d[4];
-        if (sum5(t.last_obs) < 0) {
-          x_to_bbox(t.x, d);
-        } else {
-          for (int q = 0; q < 4; q++) d[q] = t.last_obs[q];
-        }
-        if (p < n) {
-          double* o = orow + (size_t)p * 8;
-          o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3];
-          o[4] = (double)(t.id + 1);
-          o[5] = t.conf;
-          o[6] = t.cls;
-          o[7] = (double)t.det_ind;
-        }
-      });
-  const int nkeep = wave_compact(
-      ntr, [&](int k) { return trk[L.lst[k]].tsu <= g.max_age; },
-      [&](int k, int p) { order[p] = L.lst[k]; });
+  ocs_frame_end(g, L, F, trk, out, out_count, nt + nnew, nnew, 1,
+                [](const double* x, double* d) { x_to_bbox(x, d); });
   OSTAMP(9);
   OCOUNT(5, nt);
   OCOUNT(6, nh);
   OCOUNT(7, 1);
-  if (lane == 0) {
-    out_count[b] = nout < n ? nout : n;
-    sq[SO_FRAME] = frame;
-    sq[SO_IDS] = id0 + nnew;
-    sq[SO_NTR] = nkeep;
-    sq[SO_NOUT] = nout;
-  }
 }
 
 __global__ void ocsort_reset_kernel(OcsDev g, int seq0, int nseq) {
