@@ -205,6 +205,25 @@ class BxHybridConfig(C.Structure):
     ]
 
 
+class BxDeepocSeqParams(C.Structure):
+    _fields_ = [
+        ("det_thresh", C.c_double), ("iou_threshold", C.c_double), ("inertia", C.c_double),
+        ("q_xy_scaling", C.c_double), ("q_s_scaling", C.c_double),
+        ("w_association_emb", C.c_double), ("alpha_fixed_emb", C.c_double),
+        ("aw_param", C.c_double), ("max_age", C.c_int32), ("min_hits", C.c_int32),
+        ("delta_t", C.c_int32), ("aw_off", C.c_int32), ("asso_kind", C.c_int32),
+    ]
+
+
+class BxHybridSeqParams(C.Structure):
+    _fields_ = [
+        ("det_thresh", C.c_double), ("iou_threshold", C.c_double), ("inertia", C.c_double),
+        ("longterm_reid_weight", C.c_double), ("tcm_first_step_weight", C.c_double),
+        ("max_age", C.c_int32), ("min_hits", C.c_int32), ("delta_t", C.c_int32),
+        ("asso_kind", C.c_int32),
+    ]
+
+
 class BxSsConfig(C.Structure):
     _fields_ = [
         ("n_seq", C.c_int32), ("track_cap", C.c_int32), ("det_cap", C.c_int32),
@@ -262,6 +281,9 @@ EXPORTS = [
     "bx_deepoc_counters_host", "bx_deepoc_set_id_count", "bx_deepoc_set_frame_size",
     "bx_deepoc_tracks_host", "bx_deepoc_state_set_host", "bx_deepoc_frame_stats_host",
     "bx_deepoc_probe", "bx_deepoc_probe_read", "bx_deepoc_embcost",
+    "bx_deepoc_set_seq_params_host", "bx_deepoc_seq_params_host",
+    "bx_hybrid_set_seq_params_host", "bx_hybrid_seq_params_host",
+    "bx_feed_create_shared", "bx_feed_device_bytes",
     "bx_hybrid_create", "bx_hybrid_destroy", "bx_hybrid_reset", "bx_hybrid_step",
     "bx_hybrid_update_host", "bx_hybrid_copy_state", "bx_hybrid_status",
     "bx_hybrid_counters_host", "bx_hybrid_set_id_count", "bx_hybrid_set_frame_size",
@@ -427,6 +449,12 @@ _SIGS = {
     "bx_deepoc_probe": ([_vp, C.c_int], C.c_int),
     "bx_deepoc_probe_read": ([_vp, _dp, _ip], C.c_int),
     "bx_deepoc_embcost": ([C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_deepoc_set_seq_params_host": ([_vp, C.c_int, C.c_int, C.POINTER(BxDeepocSeqParams), _vp],
+                                      C.c_int),
+    "bx_deepoc_seq_params_host": ([_vp, C.c_int, C.POINTER(BxDeepocSeqParams)], C.c_int),
+    "bx_hybrid_set_seq_params_host": ([_vp, C.c_int, C.c_int, C.POINTER(BxHybridSeqParams), _vp],
+                                      C.c_int),
+    "bx_hybrid_seq_params_host": ([_vp, C.c_int, C.POINTER(BxHybridSeqParams)], C.c_int),
     "bx_hybrid_create": ([C.POINTER(BxHybridConfig), C.POINTER(C.c_void_p)], C.c_int),
     "bx_hybrid_destroy": ([_vp], C.c_int),
     "bx_hybrid_reset": ([_vp, C.c_int, C.c_int, _vp], C.c_int),
@@ -457,6 +485,9 @@ _SIGS = {
                          C.POINTER(C.c_int64), _vp], C.c_int),
     "bx_feed_create": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
                         C.POINTER(C.c_void_p)], C.c_int),
+    "bx_feed_create_shared": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp,
+                               C.POINTER(C.c_void_p)], C.c_int),
+    "bx_feed_device_bytes": ([_vp, C.POINTER(C.c_int64)], C.c_int),
     "bx_feed_destroy": ([_vp], C.c_int),
     "bx_feed_upload_host": ([_vp, C.c_int, _vp, _vp], C.c_int),
     "bx_feed_shape": ([_vp, _ip, _ip], C.c_int),

@@ -41,6 +41,15 @@ namespace {
 
 // OCSort's device record (o.min_conf unused, o.use_byte 0) plus the appearance state.  Per
 // sequence, seqst[SO_IDS] starts at 1 (KalmanBoxTracker.count = 1, deepocsort.py:305).
+// One sequence's entry of DeepOCSort's per-sequence parameter table: OCSort's entry (min_conf and
+// use_byte stay 0, as in the engine's own OcsDev) plus the appearance parameters.  o.set 0: the
+// sequence runs on the engine's own parameters.
+struct DocSeqPar {
+  OcsSeqPar o;
+  double w_emb, alpha_fixed, aw_param;
+  int aw_off, pad_;
+};
+
 struct DocDev {
   OcsDev o;
   int F;               // embedding width (0 with embedding_off)
@@ -52,7 +61,27 @@ struct DocDev {
   double* em;          // [S][D*T] the masked emb cost of the first association, [nh][nt]
   int* rec;            // [S][D] per detection of the frame: the slot its embedding goes to, or -1
   double* rec_a;       // [S][D] EMA weight alpha, < 0: newborn copy
+  // [S] per-sequence parameters (bx_deepoc_set_seq_params_host), or null: none was ever set.  The
+  // frame kernel reads it, never writes it; no other kernel reads a per-sequence field
+  // (alpha_fixed reaches deepoc_feature_kernel through rec_a).
+  const DocSeqPar* seqpar = nullptr;
 };
+
+// The kernel-entry override (bx_ocs_device.h ocs_seq_apply) for DocDev: sequence `seq`'s entry,
+// when there is a table and the entry is set, replaces the per-sequence fields of the kernel's own
+// copy of `gd`.  Wave-uniform scalar loads, all before the first store.
+__device__ __forceinline__ void doc_seq_override(DocDev& gd, int seq) {
+  if (!gd.seqpar) return;
+  const DocSeqPar* p = gd.seqpar + seq;
+  if (!p->o.set) return;
+  const double w_emb = p->w_emb, alpha_fixed = p->alpha_fixed, aw_param = p->aw_param;
+  const int aw_off = p->aw_off;
+  ocs_seq_apply(gd.o, &p->o);
+  gd.w_emb = w_emb;
+  gd.alpha_fixed = alpha_fixed;
+  gd.aw_param = aw_param;
+  gd.aw_off = aw_off;
+}
 
 // LDS past the shared carve: pre-frame list position of each kept track, AW weights and flags
 struct DocLds {
@@ -190,13 +219,14 @@ __global__ void __launch_bounds__(OW) __attribute__((amdgpu_waves_per_eu(2)))
                         const int* __restrict__ det_off, const double* __restrict__ warps,
                         double* __restrict__ out, int* __restrict__ out_count) {
   extern __shared__ __align__(16) char lds_raw[];
+  const int seq = seq0 + blockIdx.x;
+  doc_seq_override(gd, seq);  // this sequence's own parameters, when the table holds some
   const OcsDev& g = gd.o;
   OcsLds L;
   DocLds X;
   carve(g, lds_raw, L);
   doc_carve(g, lds_raw + gd.x_off, X);
   const int lane = threadIdx.x;
-  const int seq = seq0 + blockIdx.x;
   L.jv.dc = nullptr;
   const OcsFrame F = ocs_frame_begin<TB>(g, L, seq, dets, det_off);  // deepocsort.py:339
   OcsTrk* trk = g.trk + (size_t)seq * g.T;
@@ -378,7 +408,15 @@ struct bx_deepoc : OcsHost {
   double* h_cwarp = nullptr;
   double* p_cwarp = nullptr;
   BxProbe probe;  // stages: 0 embcost, 1 frame, 2 feature
+  // per-sequence parameters (bx_deepoc_set_seq_params_host): the device table dev.seqpar points
+  // to, allocated by the first set, and its host mirror
+  DocSeqPar* d_seqpar = nullptr;
+  std::vector<DocSeqPar> h_seqpar;
 };
+
+// the field checks bx_deepoc_create and bx_deepoc_set_seq_params_host share
+static bool bad_delta_t(int delta_t) { return delta_t < 1 || delta_t > OBS_KEEP - 1; }
+static bool bad_asso_kind(int k) { return k < ASSO_IOU || k > ASSO_CENTROID; }
 
 static int launch(bx_deepoc* e, int seq0, int nseq, const float* dets, const int* off,
                   const double* embs, const double* warps, double* out, int* cnt, hipStream_t st) {
@@ -415,11 +453,11 @@ int bx_deepoc_create(const bx_deepoc_config* c, bx_deepoc** out) {
   if (c->n_seq <= 0 || c->track_cap <= 0 || c->det_cap <= 0 || c->track_cap > 512 ||
       c->det_cap > 512)
     return bx_record_error(BX_ERR_INVALID, "n_seq/track_cap/det_cap out of range");
-  if (c->delta_t < 1 || c->delta_t > OBS_KEEP - 1)
+  if (bad_delta_t(c->delta_t))
     return bx_record_error(BX_ERR_INVALID, "delta_t must be in [1, 7]");
   if (!c->embedding_off && c->emb_dim <= 0)
     return bx_record_error(BX_ERR_INVALID, "emb_dim must be positive unless embedding_off");
-  if (c->asso_kind < ASSO_IOU || c->asso_kind > ASSO_CENTROID)
+  if (bad_asso_kind(c->asso_kind))
     return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0)
@@ -531,6 +569,7 @@ int bx_deepoc_destroy(bx_deepoc* e) {
   if (!e) return BX_OK;
   e->probe.destroy();
   (void)hipFree(e->arena);
+  (void)hipFree(e->d_seqpar);
   e->sg.free();
   cls_glue_free(e->pc);
   (void)hipFree(e->h_cwarp);
@@ -664,6 +703,73 @@ int bx_deepoc_set_id_count(bx_deepoc* e, int seq, int id_count, void* stream) {
 
 int bx_deepoc_set_frame_size(bx_deepoc* e, int seq, double w, double h, void* stream) {
   return ocs_set_frame_size(e, seq, w, h, stream);
+}
+
+int bx_deepoc_set_seq_params_host(bx_deepoc* e, int seq0, int nseq,
+                                  const bx_deepoc_seq_params* params_host, void* stream) {
+  if (!e || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.o.S)
+    return bx_record_error(BX_ERR_INVALID, "bad sequence range");
+  for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
+    if (bad_delta_t(params_host[k].delta_t))
+      return bx_record_error(BX_ERR_INVALID, "delta_t must be in [1, 7]");
+    if (bad_asso_kind(params_host[k].asso_kind))
+      return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
+  }
+  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
+  hipStream_t st = (hipStream_t)stream;
+  const size_t S = e->dev.o.S;
+  if (!e->d_seqpar) {
+    if (hipMalloc(&e->d_seqpar, S * sizeof(DocSeqPar)) != hipSuccess) {
+      e->d_seqpar = nullptr;
+      return bx_record_error(BX_ERR_HIP, "hipMalloc of the DeepOCSort parameter table failed");
+    }
+    BX_HIPCHK(hipMemset(e->d_seqpar, 0, S * sizeof(DocSeqPar)));
+    e->h_seqpar.assign(S, DocSeqPar{});
+    e->dev.seqpar = e->d_seqpar;
+  }
+  for (int k = 0; k < nseq; k++) {
+    DocSeqPar& d = e->h_seqpar[seq0 + k];
+    d = DocSeqPar{};
+    if (!params_host) continue;
+    const bx_deepoc_seq_params& p = params_host[k];
+    d.o.min_conf = 0.0;
+    d.o.det_thresh = p.det_thresh;
+    d.o.asso_threshold = p.iou_threshold;
+    d.o.inertia = p.inertia;
+    d.o.q_xy = 1.0 * p.q_xy_scaling;
+    d.o.q_s = 1.0 * p.q_s_scaling;
+    d.o.max_age = p.max_age;
+    d.o.min_hits = p.min_hits;
+    d.o.delta_t = p.delta_t;
+    d.o.use_byte = 0;
+    d.o.asso_kind = p.asso_kind;
+    d.o.set = 1;
+    d.w_emb = p.w_association_emb;
+    d.alpha_fixed = p.alpha_fixed_emb;
+    d.aw_param = p.aw_param;
+    d.aw_off = p.aw_off != 0;
+  }
+  BX_HIPCHK(hipMemcpyAsync(e->d_seqpar + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(DocSeqPar),
+                           hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
+  return BX_OK;
+}
+
+int bx_deepoc_seq_params_host(bx_deepoc* e, int seq, bx_deepoc_seq_params* out_host) {
+  if (!e || seq < 0 || seq >= e->dev.o.S || !out_host)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_deepoc_seq_params_host");
+  const bx_deepoc_config& c = e->cfg;
+  bx_deepoc_seq_params o = {c.det_thresh, c.iou_threshold, c.inertia, c.q_xy_scaling,
+                            c.q_s_scaling, c.w_association_emb, c.alpha_fixed_emb, c.aw_param,
+                            c.max_age, c.min_hits, c.delta_t, c.aw_off != 0, c.asso_kind};
+  if (!e->h_seqpar.empty() && e->h_seqpar[seq].o.set) {
+    const DocSeqPar& d = e->h_seqpar[seq];
+    o = {d.o.det_thresh, d.o.asso_threshold, d.o.inertia, d.o.q_xy, d.o.q_s, d.w_emb,
+         d.alpha_fixed, d.aw_param, d.o.max_age, d.o.min_hits, d.o.delta_t, d.aw_off,
+         d.o.asso_kind};
+  }
+  *out_host = o;
+  return BX_OK;
 }
 
 int bx_deepoc_tracks_host(bx_deepoc* e, int seq, int cap, int32_t* ids, double* x, double* p,

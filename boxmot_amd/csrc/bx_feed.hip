@@ -40,6 +40,8 @@ struct Run {
 struct FeedDev {
   int S, F;
   const long long* seq_row0;   // [S + 1] first packed row of each sequence in dets / embs
+  const int* src;              // [S] the sequence whose packed rows sequence k gathers from
+                               // (bx_feed_create_shared), or null: its own
   const long long* tab_off;    // [S + 1]
   const long long* row_start;  // [entries] within the sequence
   const int* row_cnt;          // [entries]
@@ -120,7 +122,7 @@ feed_gather_kernel(FeedDev d, int t, int run_first, int n_runs) {
     d.g_off[run.off0 + (k - run.k0)] = before;
     if (k == run.k1 - 1) d.g_off[run.off0 + (run.k1 - run.k0)] = before + n;
   }
-  const long long src = d.seq_row0[k] + d.row_start[entry];
+  const long long src = d.seq_row0[d.src ? d.src[k] : k] + d.row_start[entry];
   const long long dst = (long long)run.row0 + before;
   feed_copy<float, f2>(d.g_dets + dst * 6, d.dets + src * 6, (long long)n * 6, tid);
   if (d.F) feed_copy<double, d2>(d.g_embs + dst * d.F, d.embs + src * d.F, (long long)n * d.F, tid);
@@ -170,6 +172,8 @@ struct bx_feed {
   FeedDev dev{};
   int S = 0, F = 0, T = 0, max_runs = 0;
   std::vector<long long> seq_row0, tab_off, res_base;
+  std::vector<int> src;       // bx_feed_create_shared's map (empty: every sequence its own source)
+  size_t device_bytes = 0;
   std::vector<Run> runs;
   std::vector<int> run_off;   // [T + 1] into runs
   std::vector<int> run_rows;  // detections of each run
@@ -191,19 +195,25 @@ static int feed_run_of(bx_feed* f, int t, int r, int* idx) {
   return BX_OK;
 }
 
-extern "C" {
-
-int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_t* tab_off,
-                   const int64_t* row_start, const int32_t* row_cnt, const int32_t* frame_id,
-                   const int64_t* res_cap, int guard_rows, bx_feed** out) {
+// bx_feed_create (src_map null: every sequence owns its rows) and bx_feed_create_shared
+static int feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_t* tab_off,
+                       const int64_t* row_start, const int32_t* row_cnt, const int32_t* frame_id,
+                       const int64_t* res_cap, int guard_rows, const int32_t* src_map,
+                       bx_feed** out) {
   if (!out || !seq_rows || !tab_off) return bx_record_error(BX_ERR_INVALID, "null argument");
   if (n_seq <= 0 || emb_dim < 0 || guard_rows < 0)
     return bx_record_error(BX_ERR_INVALID, "n_seq/emb_dim/guard_rows out of range");
   const int S = n_seq;
   if (tab_off[0] != 0) return bx_record_error(BX_ERR_INVALID, "tab_off must start at 0");
   long long T = 0;
-  for (int k = 0; k < S; k++) {
-    if (tab_off[k + 1] < tab_off[k] || seq_rows[k] < 0)
+  for (int k = 0; src_map && k < S; k++) {
+    const int q = src_map[k];
+    if (q < 0 || q > k || src_map[q] != q)
+      return bx_record_error(BX_ERR_INVALID, "src must satisfy src[k] <= k and src[src[k]] == src[k]");
+  }
+  for (int k = 0; k < S; k++) {  // (seq_rows of a sequence that reads another's rows is not read)
+    const bool own = !src_map || src_map[k] == k;
+    if (tab_off[k + 1] < tab_off[k] || (own && seq_rows[k] < 0))
       return bx_record_error(BX_ERR_INVALID, "tab_off must ascend and seq_rows be non-negative");
     if (tab_off[k + 1] - tab_off[k] > T) T = tab_off[k + 1] - tab_off[k];
   }
@@ -221,12 +231,15 @@ int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_
   f->seq_row0.assign(S + 1, 0);
   f->tab_off.assign(tab_off, tab_off + S + 1);
   f->res_base.assign(S + 1, 0);
+  if (src_map) f->src.assign(src_map, src_map + S);
   auto fill = [&]() -> int {
     for (int k = 0; k < S; k++) {
-      f->seq_row0[k + 1] = f->seq_row0[k] + seq_rows[k];
+      // only a source sequence owns packed rows; the others read their source's
+      const int q = src_map ? src_map[k] : k;
+      f->seq_row0[k + 1] = f->seq_row0[k] + (q == k ? seq_rows[k] : 0);
       long long total = 0;
       for (long long e = tab_off[k]; e < tab_off[k + 1]; e++) {
-        if (row_cnt[e] < 0 || row_start[e] < 0 || row_start[e] + row_cnt[e] > seq_rows[k])
+        if (row_cnt[e] < 0 || row_start[e] < 0 || row_start[e] + row_cnt[e] > seq_rows[q])
           return bx_record_error(BX_ERR_INVALID, "a frame table entry reaches outside its sequence");
         total += row_cnt[e];
       }
@@ -275,6 +288,7 @@ int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_
       *p = nullptr;
       BX_HIPCHK(hipMalloc(p, bytes ? bytes : 256));
       f->allocs.push_back(*p);
+      f->device_bytes += bytes ? bytes : 256;
       return BX_OK;
     };
     auto dev_put = [&](const void** p, const void* src, size_t bytes) -> int {
@@ -288,6 +302,7 @@ int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_
     int rc;
     const long long R = f->seq_row0[S];
     if ((rc = dev_put((const void**)&d.seq_row0, f->seq_row0.data(), sizeof(long long) * (S + 1)))) return rc;
+    if (src_map && (rc = dev_put((const void**)&d.src, src_map, sizeof(int) * S))) return rc;
     if ((rc = dev_put((const void**)&d.tab_off, tab_off, sizeof(long long) * (S + 1)))) return rc;
     if ((rc = dev_put((const void**)&d.row_start, row_start, sizeof(long long) * E))) return rc;
     if ((rc = dev_put((const void**)&d.row_cnt, row_cnt, sizeof(int) * E))) return rc;
@@ -320,6 +335,30 @@ int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_
   return BX_OK;
 }
 
+extern "C" {
+
+int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_t* tab_off,
+                   const int64_t* row_start, const int32_t* row_cnt, const int32_t* frame_id,
+                   const int64_t* res_cap, int guard_rows, bx_feed** out) {
+  return feed_create(n_seq, emb_dim, seq_rows, tab_off, row_start, row_cnt, frame_id, res_cap,
+                     guard_rows, nullptr, out);
+}
+
+int bx_feed_create_shared(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_t* tab_off,
+                          const int64_t* row_start, const int32_t* row_cnt,
+                          const int32_t* frame_id, const int64_t* res_cap, int guard_rows,
+                          const int32_t* src, bx_feed** out) {
+  if (!src || n_seq <= 0) return bx_record_error(BX_ERR_INVALID, "null argument");
+  return feed_create(n_seq, emb_dim, seq_rows, tab_off, row_start, row_cnt, frame_id, res_cap,
+                     guard_rows, src, out);
+}
+
+int bx_feed_device_bytes(bx_feed* f, int64_t* bytes) {
+  if (!f || !bytes) return bx_record_error(BX_ERR_INVALID, "null argument");
+  *bytes = (int64_t)f->device_bytes;
+  return BX_OK;
+}
+
 int bx_feed_destroy(bx_feed* f) {
   if (f) feed_free(f);
   return BX_OK;
@@ -327,6 +366,8 @@ int bx_feed_destroy(bx_feed* f) {
 
 int bx_feed_upload_host(bx_feed* f, int seq, const float* dets, const double* embs) {
   if (!f || seq < 0 || seq >= f->S) return bx_record_error(BX_ERR_INVALID, "bad feeder or sequence");
+  if (!f->src.empty() && f->src[seq] != seq)
+    return bx_record_error(BX_ERR_INVALID, "the sequence reads another sequence's rows: upload to its source");
   const long long r0 = f->seq_row0[seq], n = f->seq_row0[seq + 1] - r0;
   if (n == 0) return BX_OK;
   if (!dets || (f->F && !embs)) return bx_record_error(BX_ERR_INVALID, "null rows");

@@ -66,6 +66,14 @@ struct HybTrk {
   int observed, has_saved, hvalid, htail;
 };
 
+// One sequence's entry of HybridSort's per-sequence parameter table: OCSort's entry (min_conf,
+// q_xy, q_s and use_byte stay 0, as in the engine's own OcsDev) plus the two appearance weights.
+// o.set 0: the sequence runs on the engine's own parameters.
+struct HybSeqPar {
+  OcsSeqPar o;
+  double tcm_w, lt_w;
+};
+
 struct HybDev {
   OcsDev o;            // shared geometry, thresholds, lists and scratch; o.trk is unused (null)
   int F;               // embedding width
@@ -80,7 +88,24 @@ struct HybDev {
   double* ec;          // [S][2][D][T] distances by (detection of the frame, pre-frame position)
   int* rec;            // [S][D] per detection of the frame: the slot its feature goes to, or -1
   int* rec_b;          // [S][D] 1: the slot is a newborn's
+  // [S] per-sequence parameters (bx_hybrid_set_seq_params_host), or null: none was ever set.  The
+  // frame kernel reads it, never writes it; hyb_dist_kernel and hyb_feature_kernel read no
+  // per-sequence field.
+  const HybSeqPar* seqpar = nullptr;
 };
+
+// The kernel-entry override (bx_ocs_device.h ocs_seq_apply) for HybDev: sequence `seq`'s entry,
+// when there is a table and the entry is set, replaces the per-sequence fields of the kernel's own
+// copy of `gd`.  Wave-uniform scalar loads, all before the first store.
+__device__ __forceinline__ void hyb_seq_override(HybDev& gd, int seq) {
+  if (!gd.seqpar) return;
+  const HybSeqPar* p = gd.seqpar + seq;
+  if (!p->o.set) return;
+  const double tcm_w = p->tcm_w, lt_w = p->lt_w;
+  ocs_seq_apply(gd.o, &p->o);
+  gd.tcm_w = tcm_w;
+  gd.lt_w = lt_w;
+}
 
 // ------------------------------------------------------------------------------------------
 // The 9/5 filter on 16 lanes per track: lane r owns row rr = min(r, 8) (lanes 9..15 mirror row 8
@@ -501,12 +526,13 @@ __global__ void __launch_bounds__(OW)
                      const int* __restrict__ det_off, double* __restrict__ out,
                      int* __restrict__ out_count) {
   extern __shared__ __align__(16) char lds_raw[];
+  const int seq = seq0 + blockIdx.x;
+  hyb_seq_override(gd, seq);  // this sequence's own parameters, when the table holds some
   const OcsDev& g = gd.o;
   OcsLds L;
   carve(g, lds_raw, L);
   int* pp = (int*)(lds_raw + gd.x_off);  // [T] pre-frame list position of each kept track
   const int lane = threadIdx.x;
-  const int seq = seq0 + blockIdx.x;
   L.jv.dc = nullptr;
   const OcsFrame F = ocs_frame_begin<HTB>(g, L, seq, dets, det_off);
   HybTrk* trk = gd.trk + (size_t)seq * g.T;
@@ -775,7 +801,15 @@ struct bx_hybrid : OcsHost {
   size_t lds = 0;
   ClsGlue pc;     // per_class=True: the class state
   BxProbe probe;  // stages: 0 distances, 1 frame, 2 feature
+  // per-sequence parameters (bx_hybrid_set_seq_params_host): the device table dev.seqpar points
+  // to, allocated by the first set, and its host mirror
+  HybSeqPar* d_seqpar = nullptr;
+  std::vector<HybSeqPar> h_seqpar;
 };
+
+// the field checks bx_hybrid_create and bx_hybrid_set_seq_params_host share
+static bool bad_delta_t(int delta_t) { return delta_t < 1 || delta_t > OBS_KEEP - 1; }
+static bool bad_asso_kind(int k) { return k < ASSO_IOU || k > ASSO_CENTROID; }
 
 static int launch(bx_hybrid* e, int seq0, int nseq, const float* dets, const int* off,
                   const double* embs, double* out, int* cnt, hipStream_t st) {
@@ -814,11 +848,11 @@ int bx_hybrid_create(const bx_hybrid_config* c, bx_hybrid** out) {
   if (c->n_seq <= 0 || c->track_cap <= 0 || c->det_cap <= 0 || c->track_cap > 512 ||
       c->det_cap > 512)
     return bx_record_error(BX_ERR_INVALID, "n_seq/track_cap/det_cap out of range");
-  if (c->delta_t < 1 || c->delta_t > OBS_KEEP - 1)
+  if (bad_delta_t(c->delta_t))
     return bx_record_error(BX_ERR_INVALID, "delta_t must be in [1, 7]");
   if (c->emb_dim <= 0) return bx_record_error(BX_ERR_INVALID, "emb_dim must be positive");
   if (c->det_thresh < 0.0) return bx_record_error(BX_ERR_INVALID, "det_thresh must be >= 0");
-  if (c->asso_kind < ASSO_IOU || c->asso_kind > ASSO_CENTROID)
+  if (bad_asso_kind(c->asso_kind))
     return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0)
@@ -944,6 +978,7 @@ int bx_hybrid_destroy(bx_hybrid* e) {
   if (!e) return BX_OK;
   e->probe.destroy();
   (void)hipFree(e->arena);
+  (void)hipFree(e->d_seqpar);
   e->sg.free();
   cls_glue_free(e->pc);
   delete e;
@@ -987,6 +1022,68 @@ int bx_hybrid_update_host(bx_hybrid* e, int seq, const float* dets, int n, const
                       sg.h_cnt, st);
       },
       OcsStreamSync{st});
+}
+
+int bx_hybrid_set_seq_params_host(bx_hybrid* e, int seq0, int nseq,
+                                  const bx_hybrid_seq_params* params_host, void* stream) {
+  if (!e || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.o.S)
+    return bx_record_error(BX_ERR_INVALID, "bad sequence range");
+  for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
+    if (bad_delta_t(params_host[k].delta_t))
+      return bx_record_error(BX_ERR_INVALID, "delta_t must be in [1, 7]");
+    if (!(params_host[k].det_thresh >= 0.0))
+      return bx_record_error(BX_ERR_INVALID, "det_thresh must be >= 0");
+    if (bad_asso_kind(params_host[k].asso_kind))
+      return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
+  }
+  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
+  hipStream_t st = (hipStream_t)stream;
+  const size_t S = e->dev.o.S;
+  if (!e->d_seqpar) {
+    if (hipMalloc(&e->d_seqpar, S * sizeof(HybSeqPar)) != hipSuccess) {
+      e->d_seqpar = nullptr;
+      return bx_record_error(BX_ERR_HIP, "hipMalloc of the HybridSort parameter table failed");
+    }
+    BX_HIPCHK(hipMemset(e->d_seqpar, 0, S * sizeof(HybSeqPar)));
+    e->h_seqpar.assign(S, HybSeqPar{});
+    e->dev.seqpar = e->d_seqpar;
+  }
+  for (int k = 0; k < nseq; k++) {
+    HybSeqPar& d = e->h_seqpar[seq0 + k];
+    d = HybSeqPar{};
+    if (!params_host) continue;
+    const bx_hybrid_seq_params& p = params_host[k];
+    d.o.det_thresh = p.det_thresh;
+    d.o.asso_threshold = p.iou_threshold;
+    d.o.inertia = p.inertia;
+    d.o.max_age = p.max_age;
+    d.o.min_hits = p.min_hits;
+    d.o.delta_t = p.delta_t;
+    d.o.asso_kind = p.asso_kind;
+    d.o.set = 1;
+    d.tcm_w = p.tcm_first_step_weight;
+    d.lt_w = p.longterm_reid_weight;
+  }
+  BX_HIPCHK(hipMemcpyAsync(e->d_seqpar + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(HybSeqPar),
+                           hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
+  return BX_OK;
+}
+
+int bx_hybrid_seq_params_host(bx_hybrid* e, int seq, bx_hybrid_seq_params* out_host) {
+  if (!e || seq < 0 || seq >= e->dev.o.S || !out_host)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_seq_params_host");
+  const bx_hybrid_config& c = e->cfg;
+  bx_hybrid_seq_params o = {c.det_thresh, c.iou_threshold, c.inertia, c.longterm_reid_weight,
+                            c.tcm_first_step_weight, c.max_age, c.min_hits, c.delta_t,
+                            c.asso_kind};
+  if (!e->h_seqpar.empty() && e->h_seqpar[seq].o.set) {
+    const HybSeqPar& d = e->h_seqpar[seq];
+    o = {d.o.det_thresh, d.o.asso_threshold, d.o.inertia, d.lt_w, d.tcm_w, d.o.max_age,
+         d.o.min_hits, d.o.delta_t, d.o.asso_kind};
+  }
+  *out_host = o;
+  return BX_OK;
 }
 
 int bx_hybrid_probe(bx_hybrid* e, int stage) {

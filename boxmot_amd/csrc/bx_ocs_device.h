@@ -64,31 +64,44 @@ struct OcsDev {
   double* cost_g;   // [S][D*T] or null
   int* status;
   unsigned long long* dbg;  // [S][OCS_DBG] phase stamps (diagnostic builds only, else null)
-  // [S] per-sequence parameters, or null: none was ever set (OCSort only: DeepOCSort and
-  // HybridSort leave it null).  A kernel reads it, never writes it.
+  // [S] per-sequence parameters, or null: none was ever set (OCSort's table: DeepOCSort and
+  // HybridSort leave it null and keep a table of their own entry struct in DocDev / HybDev).  A
+  // kernel reads it, never writes it.
   const OcsSeqPar* seqpar = nullptr;
 };
 
-// The kernel-entry override: sequence `seq`'s entry of the table, when it is set, replaces the
-// eleven per-sequence fields in the kernel's own copy of `g` (and max_obs, which follows
-// max_age); everything downstream reads them through `g` as before.  `seq` is wave-uniform, so
-// these are scalar loads, once per workgroup.
+// The kernel-entry override, in two parts.  ocs_seq_apply puts the eleven shared per-sequence
+// fields of one table entry into a kernel's own copy of its OcsDev (and max_obs, which follows
+// max_age); everything downstream reads them through `g` as before.  All three frame kernels use
+// it: OCSort on an OcsSeqPar entry (ocs_seq_override), DeepOCSort and HybridSort on the OcsSeqPar
+// their own entry structs begin with.  `seq` is wave-uniform, so the loads are scalar loads, once
+// per workgroup, and all of them come before the first store into `g`.
+__device__ __forceinline__ void ocs_seq_apply(OcsDev& g, const OcsSeqPar* p) {
+  const double min_conf = p->min_conf, det_thresh = p->det_thresh;
+  const double asso_threshold = p->asso_threshold, inertia = p->inertia;
+  const double q_xy = p->q_xy, q_s = p->q_s;
+  const int max_age = p->max_age, min_hits = p->min_hits, delta_t = p->delta_t;
+  const int use_byte = p->use_byte, asso_kind = p->asso_kind;
+  g.min_conf = min_conf;
+  g.det_thresh = det_thresh;
+  g.asso_threshold = asso_threshold;
+  g.inertia = inertia;
+  g.q_xy = q_xy;
+  g.q_s = q_s;
+  g.max_age = max_age;
+  g.max_obs = max_age >= 50 ? max_age + 5 : 50;  // derived, as the engine's create does
+  g.min_hits = min_hits;
+  g.delta_t = delta_t;
+  g.use_byte = use_byte;
+  g.asso_kind = asso_kind;
+}
+
+// OCSort's: sequence `seq`'s entry of g.seqpar, when there is a table and the entry is set.
 __device__ __forceinline__ void ocs_seq_override(OcsDev& g, int seq) {
   if (!g.seqpar) return;
   const OcsSeqPar* p = g.seqpar + seq;
   if (!p->set) return;
-  g.min_conf = p->min_conf;
-  g.det_thresh = p->det_thresh;
-  g.asso_threshold = p->asso_threshold;
-  g.inertia = p->inertia;
-  g.q_xy = p->q_xy;
-  g.q_s = p->q_s;
-  g.max_age = p->max_age;
-  g.max_obs = p->max_age >= 50 ? p->max_age + 5 : 50;  // derived, as the engine's create does
-  g.min_hits = p->min_hits;
-  g.delta_t = p->delta_t;
-  g.use_byte = p->use_byte;
-  g.asso_kind = p->asso_kind;
+  ocs_seq_apply(g, p);
 }
 
 // Diagnostic phase stamps and counters (build with -DBX_PHASE_TIMING; never shipped): per

@@ -727,6 +727,78 @@ class DeepOcsortEngine(_OcsFamilyEngine):
                                                  _p(e)), "state_set")
 
 
+class DeepOcsortTableEngine(DeepOcsortEngine):
+    """A ``DeepOcsortEngine`` whose sequences may each run on parameters of their own
+    (``bx_deepoc_set_seq_params_host``, include/bxdeepocsort.h): the engine of a hyper-parameter
+    sweep, K configs x S sequences as K*S sequences of one handle (boxmot_amd.tune.sweep_reid).
+    ``embedding_off`` stays the engine's: it decides the embedding width and two of the three
+    launches."""
+
+    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
+                 emb_dim: int = 512, params: DeepOcsortParams | None = None):
+        super().__init__(n_seq, track_cap, det_cap, emb_dim, params)
+        self._seq_over = {}  # sequence -> its own DeepOcsortParams, for grown()
+
+    def grown(self, track_cap: int, det_cap: int,
+              map_cap: int | None = None) -> "DeepOcsortTableEngine":
+        """As DeepOcsortEngine.grown; bx_deepoc_copy_state carries tracks only, so the table is
+        set again on the new engine."""
+        e = DeepOcsortTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim or 1, self.params)
+        if map_cap is not None:
+            e.classes_config(self.classes().n_classes, map_cap)
+        N.check(self._L.bx_deepoc_copy_state(e._h, self._h), "bx_deepoc_copy_state")
+        for k, p in sorted(self._seq_over.items()):
+            e.set_seq_params(k, [p])
+        return e
+
+    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
+        """Give sequences [seq0, seq0 + len(params)) parameters of their own
+        (bx_deepoc_set_seq_params_host): ``params`` is a list of DeepOcsortParams, whose
+        embedding_off must be the engine's and whose frame_w / frame_h are not part of the table.
+        ``None`` clears the override of ``nseq`` sequences from seq0 (default: all from seq0).
+        For use between sequences, at frame 0."""
+        if params is None:
+            n = self.n_seq - seq0 if nseq is None else nseq
+            arr = None
+        else:
+            n = len(params)
+            for p in params:
+                if bool(p.embedding_off) != bool(self.params.embedding_off):
+                    raise ValueError("embedding_off is engine-wide: a sequence cannot have its own")
+            arr = (N.BxDeepocSeqParams * max(n, 1))(*[N.BxDeepocSeqParams(
+                det_thresh=float(p.det_thresh), iou_threshold=float(p.iou_threshold),
+                inertia=float(p.inertia), q_xy_scaling=float(p.Q_xy_scaling),
+                q_s_scaling=float(p.Q_s_scaling), w_association_emb=float(p.w_association_emb),
+                alpha_fixed_emb=float(p.alpha_fixed_emb), aw_param=float(p.aw_param),
+                max_age=int(p.max_age), min_hits=int(p.min_hits), delta_t=int(p.delta_t),
+                aw_off=int(bool(p.aw_off)), asso_kind=_asso_kind(p.asso_func))
+                for p in params])
+        N.check(self._L.bx_deepoc_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
+                "bx_deepoc_set_seq_params_host")
+        for k in range(n):
+            if params is None:
+                self._seq_over.pop(seq0 + k, None)
+            else:
+                self._seq_over[seq0 + k] = params[k]
+
+    def seq_params(self, seq: int) -> DeepOcsortParams:
+        """The parameters sequence ``seq`` runs on (bx_deepoc_seq_params_host): its own when set,
+        else the engine's; embedding_off, frame_w and frame_h are the engine's."""
+        from .iou import KINDS
+
+        o = N.BxDeepocSeqParams()
+        N.check(self._L.bx_deepoc_seq_params_host(self._h, int(seq), C.byref(o)),
+                "bx_deepoc_seq_params_host")
+        name = {v: k for k, v in KINDS.items()}[o.asso_kind]
+        return DeepOcsortParams(
+            det_thresh=o.det_thresh, max_age=o.max_age, min_hits=o.min_hits,
+            iou_threshold=o.iou_threshold, delta_t=o.delta_t, asso_func=name, inertia=o.inertia,
+            w_association_emb=o.w_association_emb, alpha_fixed_emb=o.alpha_fixed_emb,
+            aw_param=o.aw_param, embedding_off=self.params.embedding_off, aw_off=bool(o.aw_off),
+            Q_xy_scaling=o.q_xy_scaling, Q_s_scaling=o.q_s_scaling,
+            frame_w=self.params.frame_w, frame_h=self.params.frame_h)
+
+
 def deepoc_embcost(dets_embs, trk_embs, out, stream=None) -> None:
     """out [nd, nt] = dets_embs [nd, F] @ trk_embs [nt, F].T on device float64 tensors, by the
     tracker's own MFMA tile (bx_deepoc_embcost)."""
@@ -928,6 +1000,69 @@ def hybrid_bank_mean(bank, pushed, out, stream=None) -> None:
                                          stream), "bx_hybrid_bank_mean")
 
 
+class HybridsortTableEngine(HybridsortEngine):
+    """A ``HybridsortEngine`` whose sequences may each run on parameters of their own
+    (``bx_hybrid_set_seq_params_host``, include/bxhybridsort.h): the engine of a hyper-parameter
+    sweep, K configs x S sequences as K*S sequences of one handle (boxmot_amd.tune.sweep_reid)."""
+
+    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
+                 emb_dim: int = 512, params: HybridsortParams | None = None):
+        super().__init__(n_seq, track_cap, det_cap, emb_dim, params)
+        self._seq_over = {}  # sequence -> its own HybridsortParams, for grown()
+
+    def grown(self, track_cap: int, det_cap: int,
+              map_cap: int | None = None) -> "HybridsortTableEngine":
+        """As HybridsortEngine.grown; bx_hybrid_copy_state carries tracks only, so the table is
+        set again on the new engine."""
+        e = HybridsortTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim, self.params)
+        if map_cap is not None:
+            e.classes_config(self.classes().n_classes, map_cap)
+        N.check(self._L.bx_hybrid_copy_state(e._h, self._h), "bx_hybrid_copy_state")
+        for k, p in sorted(self._seq_over.items()):
+            e.set_seq_params(k, [p])
+        return e
+
+    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
+        """Give sequences [seq0, seq0 + len(params)) parameters of their own
+        (bx_hybrid_set_seq_params_host): ``params`` is a list of HybridsortParams, whose frame_w /
+        frame_h are not part of the table.  ``None`` clears the override of ``nseq`` sequences
+        from seq0 (default: all from seq0).  For use between sequences, at frame 0."""
+        if params is None:
+            n = self.n_seq - seq0 if nseq is None else nseq
+            arr = None
+        else:
+            n = len(params)
+            arr = (N.BxHybridSeqParams * max(n, 1))(*[N.BxHybridSeqParams(
+                det_thresh=float(p.det_thresh), iou_threshold=float(p.iou_threshold),
+                inertia=float(p.inertia), longterm_reid_weight=float(p.longterm_reid_weight),
+                tcm_first_step_weight=float(p.TCM_first_step_weight), max_age=int(p.max_age),
+                min_hits=int(p.min_hits), delta_t=int(p.delta_t),
+                asso_kind=_asso_kind(p.asso_func)) for p in params])
+        N.check(self._L.bx_hybrid_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
+                "bx_hybrid_set_seq_params_host")
+        for k in range(n):
+            if params is None:
+                self._seq_over.pop(seq0 + k, None)
+            else:
+                self._seq_over[seq0 + k] = params[k]
+
+    def seq_params(self, seq: int) -> HybridsortParams:
+        """The parameters sequence ``seq`` runs on (bx_hybrid_seq_params_host): its own when set,
+        else the engine's; frame_w / frame_h are the engine's."""
+        from .iou import KINDS
+
+        o = N.BxHybridSeqParams()
+        N.check(self._L.bx_hybrid_seq_params_host(self._h, int(seq), C.byref(o)),
+                "bx_hybrid_seq_params_host")
+        name = {v: k for k, v in KINDS.items()}[o.asso_kind]
+        return HybridsortParams(
+            det_thresh=o.det_thresh, max_age=o.max_age, min_hits=o.min_hits,
+            iou_threshold=o.iou_threshold, delta_t=o.delta_t, asso_func=name, inertia=o.inertia,
+            longterm_reid_weight=o.longterm_reid_weight,
+            TCM_first_step_weight=o.tcm_first_step_weight, frame_w=self.params.frame_w,
+            frame_h=self.params.frame_h)
+
+
 class ClassSplit(_NativeHandle):
     """Handle over ``bx_classes_*`` (include/bxclasses.h): per_class=True on the device for
     ``n_seq`` sequences of ``n_classes`` classes — the stable class split of a frame's rows and the
@@ -1020,9 +1155,17 @@ class SequenceFeeder(_NativeHandle):
     _PREFIX = "bx_feed"
 
     def __init__(self, dets, embs, tables, emb_dim: int, res_cap=None, guard_rows: int = 0):
+        self._build(dets, embs, tables, emb_dim, res_cap, guard_rows, None)
+
+    def _build(self, dets, embs, tables, emb_dim, res_cap, guard_rows, source) -> None:
+        """Create, upload and read the schedule.  ``source``: None, or SharedSequenceFeeder's
+        map (only a source's rows are read and uploaded)."""
         S = len(dets)
         self.n_seq, self.emb_dim = S, int(emb_dim)
-        rows = np.array([int(np.shape(d)[0]) for d in dets], np.int64)
+        src = None if source is None else np.ascontiguousarray(source, np.int32).reshape(S)
+        own = [src is None or int(src[k]) == k for k in range(S)]
+        rows = np.array([int(np.shape(d)[0]) if own[k] else 0 for k, d in enumerate(dets)],
+                        np.int64)
         tab_off = np.zeros(S + 1, np.int64)
         tab_off[1:] = np.cumsum([len(t[1]) for t in tables])
 
@@ -1034,9 +1177,15 @@ class SequenceFeeder(_NativeHandle):
         cap = None if res_cap is None else np.ascontiguousarray(res_cap, np.int64).reshape(S)
         self._L = N.load()
         h = C.c_void_p()
-        N.check(self._L.bx_feed_create(S, self.emb_dim, rows.ctypes.data, tab_off.ctypes.data,
-                                       start.ctypes.data, cnt.ctypes.data, fid.ctypes.data,
-                                       _p(cap), int(guard_rows), C.byref(h)), "bx_feed_create")
+        if src is None:
+            N.check(self._L.bx_feed_create(S, self.emb_dim, rows.ctypes.data, tab_off.ctypes.data,
+                                           start.ctypes.data, cnt.ctypes.data, fid.ctypes.data,
+                                           _p(cap), int(guard_rows), C.byref(h)), "bx_feed_create")
+        else:
+            N.check(self._L.bx_feed_create_shared(
+                S, self.emb_dim, rows.ctypes.data, tab_off.ctypes.data, start.ctypes.data,
+                cnt.ctypes.data, fid.ctypes.data, _p(cap), int(guard_rows), src.ctypes.data,
+                C.byref(h)), "bx_feed_create_shared")
         self._h = h
         for k in range(S):
             if not rows[k]:
@@ -1128,6 +1277,29 @@ class SequenceFeeder(_NativeHandle):
         c = np.ascontiguousarray(out_count, np.int32).reshape(nseq)
         N.check(self._L.bx_feed_write_run_host(self._h, int(t), int(r), o.ctypes.data,
                                                c.ctypes.data), "bx_feed_write_run_host")
+
+    @property
+    def device_bytes(self) -> int:
+        """Bytes of device memory the feeder allocated (bx_feed_device_bytes).  (A property, as
+        ``results_device``: it reads one number.)"""
+        n = C.c_int64()
+        N.check(self._L.bx_feed_device_bytes(self._h, C.byref(n)), "bx_feed_device_bytes")
+        return n.value
+
+
+class SharedSequenceFeeder(SequenceFeeder):
+    """A ``SequenceFeeder`` whose sequences share packed rows (``bx_feed_create_shared``,
+    include/bxfeed.h): sequence k gathers from the rows of sequence ``source[k]``
+    (``source[k] <= k``, a source is its own source).  Only the sources' ``dets`` / ``embs`` are
+    read and uploaded; the entries of the other sequences may be None.  Tables, runs, gathered
+    arrays and results stay per sequence.  ``source=None`` is a plain SequenceFeeder.  (A class
+    of its own because SequenceFeeder's constructor signature is pinned by
+    tests/test_engine_api_host.py.)"""
+
+    def __init__(self, dets, embs, tables, emb_dim: int, res_cap=None, guard_rows: int = 0,
+                 source=None):
+        self.source = None if source is None else [int(q) for q in source]
+        self._build(dets, embs, tables, emb_dim, res_cap, guard_rows, source)
 
 
 @dataclass

@@ -8,7 +8,10 @@ include/bxocsort.h), and every frame index is one K*S-wide launch fed from devic
 (``engine.SequenceFeeder``, include/bxfeed.h).  The search strategy (which configurations to try)
 stays with the caller; ``grid`` builds the cartesian product of a search space.
 
-Only OCSort has per-sequence parameters; DESIGN.md 2.18 is the contract.
+Three engines have per-sequence parameters: OCSort (``sweep``; DESIGN.md 2.18 is the contract) and
+the two appearance trackers of its family, DeepOCSort and HybridSort (``sweep_reid``; DESIGN.md
+2.20), whose K*S sequences read each sequence's detections and embeddings from ONE copy in device
+memory (``engine.SharedSequenceFeeder``).
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ from pathlib import Path
 import numpy as np
 
 SUPPORTED = ("ocsort",)
+SUPPORTED_REID = ("deepocsort", "hybridsort")  # sweep_reid's trackers
 _CAPS = ("track_cap", "det_cap")
 
 
@@ -32,8 +36,9 @@ SCORES = ("host", "device")
 
 
 def _check(tracker_type: str, configs, sequences=None, gt=None, exp_dir=None, score="host",
-           keep_results=True) -> list:
-    """The refusals of ``sweep`` that need no engine."""
+           keep_results=True, supported=SUPPORTED, what="tune.sweep") -> list:
+    """The refusals of ``sweep`` (and, with its own trackers, ``sweep_reid``) that need no
+    engine."""
     if score not in SCORES:
         raise ValueError(f"score must be one of {SCORES}, got {score!r}")
     if score == "device" and gt is None:
@@ -46,13 +51,13 @@ def _check(tracker_type: str, configs, sequences=None, gt=None, exp_dir=None, sc
         if score == "host":
             raise ValueError('keep_results=False: score="host" needs the rows on the host; '
                              'use score="device"')
-    if tracker_type not in SUPPORTED:
+    if tracker_type not in supported:
         raise NotImplementedError(
-            f"tune.sweep drives {', '.join(SUPPORTED)} only (the engine with per-sequence "
+            f"{what} drives {', '.join(supported)} only (the engine with per-sequence "
             f"parameters), not {tracker_type}")
     configs = [dict(c) for c in configs]
     if not configs:
-        raise ValueError("tune.sweep needs at least one config")
+        raise ValueError(f"{what} needs at least one config")
     for k, c in enumerate(configs):
         if "per_class" in c:
             raise NotImplementedError(f"config {k}: per_class is not available in a sweep")
@@ -127,43 +132,72 @@ def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict
                        params=params[0])
     feed = None
     try:
-        fids = [np.asarray(frame_ids[nm]) if frame_ids and nm in frame_ids else s.frame_ids
-                for nm, s in zip(names, seqs)]
-        dets, tables = [], []
-        for s, f in zip(seqs, fids):
-            start, cnt = np.zeros(len(f), np.int64), np.zeros(len(f), np.int64)
-            for i, x in enumerate(f):
-                j = s._index.get(int(x))
-                if j is not None:
-                    start[i], cnt[i] = s.offsets[j], s.offsets[j + 1] - s.offsets[j]
-            tables.append((start, cnt, np.asarray(f, np.int64)))
-            dets.append(np.asarray(s.dets).astype(np.float32))
+        fids, tables = _frame_tables(names, seqs, frame_ids)
+        dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
         for k in range(K):
             eng.set_seq_params(k * S, [params[k]] * S)
             for q, nm in enumerate(names):
                 if frame_sizes and nm in frame_sizes:
                     eng.set_frame_size(k * S + q, *frame_sizes[nm])
         feed = SequenceFeeder(dets * K, [None] * (K * S), tables * K, 0)
-        for t in range(feed.n_frames):
-            runs = feed.schedule[t]
-            if not runs:
-                continue
-            feed.gather(t)
-            for q0, ns, _, pd, po, _, pout, pcnt in runs:
-                eng.step(pd, po, pout, pcnt, seq0=q0, nseq=ns)
-            feed.append(t)
-        if eng.status() != 0:
-            raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
-        summaries = None
-        if score == "device":
-            if feed.status() != 0:
-                raise RuntimeError(f"feeder status {feed.status()} (result buffer overflow)")
-            summaries = _score_device(gt, feed, K, benchmark, seq_lengths)
-        rows = feed.results() if keep_results else None
+
+        def step(t, run):
+            q0, ns, _, pd, po, _, pout, pcnt = run
+            eng.step(pd, po, pout, pcnt, seq0=q0, nseq=ns)
+
+        rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
+                                 keep_results)
     finally:
         if feed is not None:
             feed.close()
         eng.close()
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
+
+
+def _frame_tables(names, seqs, frame_ids) -> tuple:
+    """Per sequence the frame ids it iterates and its feeder table ``(row_start, row_cnt,
+    frame_id)``."""
+    fids = [np.asarray(frame_ids[nm]) if frame_ids and nm in frame_ids else s.frame_ids
+            for nm, s in zip(names, seqs)]
+    tables = []
+    for s, f in zip(seqs, fids):
+        start, cnt = np.zeros(len(f), np.int64), np.zeros(len(f), np.int64)
+        for i, x in enumerate(f):
+            j = s._index.get(int(x))
+            if j is not None:
+                start[i], cnt[i] = s.offsets[j], s.offsets[j + 1] - s.offsets[j]
+        tables.append((start, cnt, np.asarray(f, np.int64)))
+    return fids, tables
+
+
+def _drive(eng, feed, step, K: int, gt, benchmark, seq_lengths, score, keep_results) -> tuple:
+    """The frame loop both sweeps share: per frame index one gather, ``step(t, run)`` for each of
+    its runs and one append; then the status checks, the device-side scores and the one copy of
+    the rows.  Returns (rows per engine sequence or None, summaries per config or None)."""
+    for t in range(feed.n_frames):
+        runs = feed.schedule[t]
+        if not runs:
+            continue
+        feed.gather(t)
+        for run in runs:
+            step(t, run)
+        feed.append(t)
+    if eng.status() != 0:
+        raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
+    summaries = None
+    if score == "device":
+        if feed.status() != 0:
+            raise RuntimeError(f"feeder status {feed.status()} (result buffer overflow)")
+        summaries = _score_device(gt, feed, K, benchmark, seq_lengths)
+    return (feed.results() if keep_results else None), summaries
+
+
+def _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths) -> list:
+    """One entry per config from the rows of engine sequences ``k*S + s``: the files under
+    ``exp_dir``, and the host-side scores when the device did not score."""
+    from . import motio
+
+    S = len(names)
     out = []
     for k, cfg in enumerate(configs):
         if rows is None:
@@ -183,6 +217,118 @@ def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict
                                           seq_lengths)):
             o["summary"] = summary
     return out
+
+
+def _check_reid(tracker_type: str, configs, sequences, gt, exp_dir, score, keep_results,
+                warps) -> list:
+    """The refusals of ``sweep_reid`` that need no engine and no device."""
+    from . import motio
+
+    configs = _check(tracker_type, configs, sequences, gt, exp_dir, score, keep_results,
+                     supported=SUPPORTED_REID, what="tune.sweep_reid")
+    if len({bool(c.get("embedding_off", False)) for c in configs}) > 1:
+        raise ValueError("embedding_off decides the engine's embedding width and launches: it "
+                         "must be the same in every config")
+    for k, c in enumerate(configs):
+        if tracker_type == "hybridsort" and c.get("use_byte"):
+            raise NotImplementedError(
+                f"config {k}: HybridSort(use_byte=True) is not built: the reference's BYTE round "
+                "calls KalmanBoxTracker.update with the wrong arguments, so it defines no "
+                "behaviour")
+        if warps is not None:  # (hybridsort, cmc_off / use_ecc against warps)
+            motio._check_warp_args(tracker_type, c, 0, warps, None, None)
+    return configs
+
+
+def _resolve_reid(tracker_type: str, F: int, cfg: dict):
+    """(params, track_cap, det_cap) of one config, resolved as run_sequences resolves its
+    tracker_kwargs: through ``motio._batched_engine`` itself, on a one-sequence engine."""
+    from . import motio
+
+    eng = motio._batched_engine(tracker_type, 1, F, cfg)[0]
+    try:
+        return eng.params, eng.track_cap, eng.det_cap
+    finally:
+        eng.close()
+
+
+def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
+               gt: dict | None = None, benchmark: str = "MOT17", seq_lengths: dict | None = None,
+               frame_ids: dict | None = None, frame_sizes: dict | None = None,
+               score: str = "host", keep_results: bool = True, warps=None) -> list:
+    """``sweep`` for the appearance trackers ``"deepocsort"`` and ``"hybridsort"``: every config of
+    ``configs`` over every sequence in one ``DeepOcsortTableEngine`` / ``HybridsortTableEngine``
+    of K*S sequences, engine sequence ``k*S + s`` being sequence ``s`` under config ``k``.
+
+    Arguments, return value, scoring and ``keep_results`` as in ``sweep``; each config means what
+    ``run_sequences(tracker_type, ..., tracker_kwargs=cfg, resident=True)`` makes of it, and the
+    files under ``exp_dir/<k as 4 digits>/`` are byte-identical to that run's.  The sequences are
+    fed by one ``SharedSequenceFeeder`` with ``source[k*S + s] = s``: detections and embeddings
+    are uploaded and held once per sequence, not once per config.
+
+    ``warps`` (deepocsort only): what ``run_sequences(warps=...)`` takes, a ``cmc.WarpTable`` over
+    these sequences or a mapping name -> ``[n_frames, 6]``; rounded to float32 as there, and every
+    config's copy of a sequence gets that sequence's warp (the ``[T, K*S, 6]`` table is built once
+    on the device).
+
+    Raised before any engine is built: ``NotImplementedError`` for another tracker, ``per_class``
+    in a config or HybridSort's ``use_byte=True``; ``ValueError`` for caps or ``embedding_off``
+    that differ across configs, ``warps`` with hybridsort or with a config that switches the
+    camera-motion compensation off (``cmc_off`` / ``use_ecc``), sequences whose embedding widths
+    differ, and the ``score`` / ``keep_results`` combinations ``sweep`` refuses.
+    """
+    configs = _check_reid(tracker_type, configs, sequences, gt, exp_dir, score, keep_results,
+                          warps)
+    from . import motio
+    from . import engine as E
+
+    names = list(sequences)
+    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
+            for s in sequences.values()]
+    S, K = len(seqs), len(configs)
+    if not S:
+        return [{"config": c, "results": {} if keep_results else None, "summary": None}
+                for c in configs]
+    widths = sorted({int(s.emb_dim) for s in seqs})
+    if len(widths) > 1:
+        raise ValueError(f"the sequences' embedding widths differ ({widths}): one engine has one "
+                         "emb_dim")
+    F = widths[0]
+    fids, tables = _frame_tables(names, seqs, frame_ids)
+    table = None
+    if warps is not None:  # [T, S, 6] as run_sequences builds it, then every config's copy
+        table = motio._flow_warps(names, seqs, fids, F, warps, None, None).repeat(1, K, 1)
+    resolved = [_resolve_reid(tracker_type, F, c) for c in configs]
+    params = [r[0] for r in resolved]
+    cls = E.DeepOcsortTableEngine if tracker_type == "deepocsort" else E.HybridsortTableEngine
+    eng = cls(n_seq=K * S, track_cap=resolved[0][1], det_cap=resolved[0][2], emb_dim=F or 1,
+              params=params[0])
+    feed = None
+    try:
+        feed_emb = F if eng.emb_dim else 0
+        dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
+        embs = [s.embs if feed_emb else None for s in seqs]
+        for k in range(K):
+            eng.set_seq_params(k * S, [params[k]] * S)
+            for q, nm in enumerate(names):
+                if frame_sizes and nm in frame_sizes:
+                    eng.set_frame_size(k * S + q, *frame_sizes[nm])
+        none = [None] * ((K - 1) * S)
+        feed = E.SharedSequenceFeeder(dets + none, embs + none, tables * K, feed_emb,
+                                      source=list(range(S)) * K)
+
+        def step(t, run):
+            q0, ns, _, pd, po, pe, pout, pcnt = run
+            motio._step(eng, tracker_type, pd, po, pe, pout, pcnt, q0, ns,
+                        None if table is None else table[t, q0: q0 + ns])
+
+        rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
+                                 keep_results)
+    finally:
+        if feed is not None:
+            feed.close()
+        eng.close()
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
 
 
 def _score(gt: dict, results: list, benchmark: str, seq_lengths) -> list:

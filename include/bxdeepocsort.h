@@ -61,12 +61,26 @@ typedef struct {
     double frame_w, frame_h;
 } bx_deepoc_config;
 
+/* The fields of bx_deepoc_config that size no memory and decide no launch: the ones a sequence
+ * may have of its own (bx_deepoc_set_seq_params_host below).  embedding_off stays engine-wide (it
+ * decides emb_dim, the contraction launch and the feature launch), as do n_seq, the caps, emb_dim
+ * and the frame size.  max_obs, which the create call derives from max_age (50, or max_age + 5
+ * from 50 on), follows a sequence's own max_age by the same rule. */
+typedef struct {
+    double det_thresh, iou_threshold, inertia, q_xy_scaling, q_s_scaling;
+    double w_association_emb, alpha_fixed_emb, aw_param;
+    int32_t max_age, min_hits, delta_t;
+    int32_t aw_off;
+    int32_t asso_kind;
+} bx_deepoc_seq_params;
+
 typedef struct bx_deepoc bx_deepoc;
 
 int bx_deepoc_create(const bx_deepoc_config *cfg, bx_deepoc **out);
 int bx_deepoc_destroy(bx_deepoc *e);
 /* Forget all tracks of sequences [seq0, seq0+nseq): frame counter 0, id counter back to 1
- * (KalmanBoxTracker.count = 1, deepocsort.py:305). */
+ * (KalmanBoxTracker.count = 1, deepocsort.py:305).  Their per-sequence parameters, when set,
+ * stay. */
 int bx_deepoc_reset(bx_deepoc *e, int seq0, int nseq, void *stream);
 /* One frame for sequences [seq0, seq0+nseq) — three launches (two with embedding_off).
  *   dets    [sum N][6] float32 (x1,y1,x2,y2,conf,cls)
@@ -109,8 +123,29 @@ int bx_deepoc_update_classes_host(bx_deepoc *e, int seq, int n_classes, const fl
                                   int *id_count_host, double *out_host, int *n_out, void *stream);
 /* Capacity growth (the reference's track list is unbounded): copy every sequence's tracker
  * state of `src` into `dst`, a fresh engine with the same configuration and sequences and
- * track_cap / det_cap at least src's (slot ids stay valid).  Synchronous. */
+ * track_cap / det_cap at least src's (slot ids stay valid).  Synchronous.  Tracks only: the
+ * per-sequence parameter table is not copied. */
 int bx_deepoc_copy_state(bx_deepoc *dst, bx_deepoc *src);
+/* Per-sequence parameters, the contract of bx_ocsort_set_seq_params_host (bxocsort.h): a sweep
+ * runs K configurations x S sequences as K*S sequences of ONE engine.  params_host [nseq] gives
+ * sequences [seq0, seq0+nseq) parameters of their own; NULL clears the range, whose sequences then
+ * run on the engine's parameters again.  Every entry is validated as the create call validates
+ * the same fields (delta_t within the 8-slot observation ring, a known asso_kind); an invalid
+ * entry, or a range outside [0, n_seq), returns BX_ERR_INVALID and changes nothing.  The values
+ * live in a device table the frame kernel reads at its entry (uniform loads, once per workgroup)
+ * and never writes; the other kernels of a step read none of them (alpha_fixed_emb reaches the
+ * feature kernel through the records the frame kernel writes).  Until the first set there is no
+ * table and the kernel runs as it always did.  Copies on `stream`, then synchronises it.
+ * The table is indexed by engine sequence: for a bx_deepoc_step_classes engine that is the class
+ * sequence s * n_classes + c, and nothing more is promised there.
+ * Meant for use between sequences, at frame 0 (after a reset): changing a sequence's parameters
+ * while it holds tracks is allowed, but no reference behaviour is defined for it.  A reset keeps
+ * the table; a state copy carries tracks only, so the destination keeps its own table.
+ * The second entry point reads a sequence's effective parameters back (its entry, or the
+ * engine's when it has none); host memory, no device work. */
+int bx_deepoc_set_seq_params_host(bx_deepoc *e, int seq0, int nseq,
+                                  const bx_deepoc_seq_params *params_host, void *stream);
+int bx_deepoc_seq_params_host(bx_deepoc *e, int seq, bx_deepoc_seq_params *out_host);
 /* Latched device status (BX_OK, BX_ERR_TRACK_OVERFLOW or BX_ERR_CAPACITY). */
 int bx_deepoc_status(bx_deepoc *e, int *status);
 int bx_deepoc_counters_host(bx_deepoc *e, int seq, int *frame_count, int *id_count,

@@ -61,7 +61,25 @@ int bx_feed_create(int n_seq, int emb_dim, const int64_t *seq_rows_host,
                    const int64_t *tab_off_host, const int64_t *row_start_host,
                    const int32_t *row_cnt_host, const int32_t *frame_id_host,
                    const int64_t *res_cap_host, int guard_rows, bx_feed **out);
+/* bx_feed_create for sequences that share packed rows: sequence k gathers from the packed rows
+ * of sequence src_host[k] ([n_seq] int32).  A hyper-parameter sweep runs K configurations x S
+ * sequences as K*S sequences whose detections and embeddings are K copies of the same S arrays;
+ * with src[k*S + s] = s they are stored and uploaded once.
+ *   - src[k] <= k and src[src[k]] == src[k] (a source is its own source), and every frame table
+ *     entry of sequence k lies inside the rows of src[k]; otherwise BX_ERR_INVALID;
+ *   - only a source owns storage and accepts bx_feed_upload_host (BX_ERR_INVALID for another);
+ *     seq_rows_host of a sequence that is not a source is ignored;
+ *   - frame tables, runs, the gathered per-frame arrays, result buffers and appends stay per
+ *     sequence, so every step is fed exactly as from bx_feed_create.
+ * bx_feed_create is the identity map, with unchanged behaviour and layout. */
+int bx_feed_create_shared(int n_seq, int emb_dim, const int64_t *seq_rows_host,
+                          const int64_t *tab_off_host, const int64_t *row_start_host,
+                          const int32_t *row_cnt_host, const int32_t *frame_id_host,
+                          const int64_t *res_cap_host, int guard_rows, const int32_t *src_host,
+                          bx_feed **out);
 int bx_feed_destroy(bx_feed *f);
+/* Bytes of device memory the feeder allocated at creation (host, no device work). */
+int bx_feed_device_bytes(bx_feed *f, int64_t *bytes);
 /* Upload sequence seq's packed rows (synchronous): dets_host float32 [rows][6], embs_host
  * float64 [rows][emb_dim] (ignored when emb_dim is 0).  Either may be NULL for 0 rows. */
 int bx_feed_upload_host(bx_feed *f, int seq, const float *dets_host, const double *embs_host);

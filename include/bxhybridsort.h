@@ -57,11 +57,24 @@ typedef struct {
     double frame_w, frame_h;
 } bx_hybrid_config;
 
+/* The fields of bx_hybrid_config that size no memory and decide no launch: the ones a sequence
+ * may have of its own (bx_hybrid_set_seq_params_host below).  n_seq, the caps, emb_dim and the
+ * frame size stay engine-wide.  max_obs, which the create call derives from max_age (50, or
+ * max_age + 5 from 50 on), follows a sequence's own max_age by the same rule; it is the only
+ * field the create call derives from one of these (the filter's Q is constant). */
+typedef struct {
+    double det_thresh, iou_threshold, inertia;
+    double longterm_reid_weight, tcm_first_step_weight;
+    int32_t max_age, min_hits, delta_t;
+    int32_t asso_kind;
+} bx_hybrid_seq_params;
+
 typedef struct bx_hybrid bx_hybrid;
 
 int bx_hybrid_create(const bx_hybrid_config *cfg, bx_hybrid **out);
 int bx_hybrid_destroy(bx_hybrid *e);
-/* Forget all tracks of sequences [seq0, seq0+nseq): frame counter 0, id counter back to 1. */
+/* Forget all tracks of sequences [seq0, seq0+nseq): frame counter 0, id counter back to 1.  Their
+ * per-sequence parameters, when set, stay. */
 int bx_hybrid_reset(bx_hybrid *e, int seq0, int nseq, void *stream);
 /* One frame for sequences [seq0, seq0+nseq) — three launches.
  *   dets    [sum N][6] float32 (x1,y1,x2,y2,conf,cls)
@@ -107,8 +120,30 @@ int bx_hybrid_probe(bx_hybrid *e, int stage);
 int bx_hybrid_probe_read(bx_hybrid *e, double *total_ms, int *count);
 /* Capacity growth (the reference's track list is unbounded): copy every sequence's tracker
  * state of `src` into `dst`, a fresh engine with the same configuration and sequences and
- * track_cap / det_cap at least src's (slot ids stay valid).  Synchronous. */
+ * track_cap / det_cap at least src's (slot ids stay valid).  Synchronous.  Tracks only: the
+ * per-sequence parameter table is not copied. */
 int bx_hybrid_copy_state(bx_hybrid *dst, bx_hybrid *src);
+/* Per-sequence parameters, the contract of bx_ocsort_set_seq_params_host (bxocsort.h): a sweep
+ * runs K configurations x S sequences as K*S sequences of ONE engine.  params_host [nseq] gives
+ * sequences [seq0, seq0+nseq) parameters of their own; NULL clears the range, whose sequences then
+ * run on the engine's parameters again.  Every entry is validated as the create call validates
+ * the same fields (delta_t within the 8-slot observation ring, a known asso_kind, det_thresh >=
+ * 0); an invalid entry, or a range outside [0, n_seq), returns BX_ERR_INVALID and changes
+ * nothing.  The values live in a device table the frame kernel reads at its entry (uniform loads,
+ * once per workgroup) and never writes; the distance and feature kernels read none of them.
+ * Until the first set there is no table and the kernel runs as it always did.  Copies on
+ * `stream`, then synchronises it.
+ * The table is indexed by engine sequence: for a bx_hybrid_step_classes engine that is the class
+ * sequence s * n_classes + c, and nothing more is promised there.
+ * Meant for use between sequences, at frame 0 (after a reset): changing a sequence's parameters
+ * while it holds tracks is allowed, but no reference behaviour is defined for it.  A reset keeps
+ * the table; a state copy carries tracks only, so the destination keeps its own table (the
+ * state blob of bx_hybrid_state_save_host carries tracks only too).
+ * The second entry point reads a sequence's effective parameters back (its entry, or the
+ * engine's when it has none); host memory, no device work. */
+int bx_hybrid_set_seq_params_host(bx_hybrid *e, int seq0, int nseq,
+                                  const bx_hybrid_seq_params *params_host, void *stream);
+int bx_hybrid_seq_params_host(bx_hybrid *e, int seq, bx_hybrid_seq_params *out_host);
 /* Latched device status (BX_OK, BX_ERR_TRACK_OVERFLOW or BX_ERR_CAPACITY). */
 int bx_hybrid_status(bx_hybrid *e, int *status);
 int bx_hybrid_counters_host(bx_hybrid *e, int seq, int *frame_count, int *id_count,
