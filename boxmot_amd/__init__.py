@@ -7,13 +7,15 @@ reference's ``update(dets, img, embs) -> [M, 8]`` contract.  The numerics run in
 ``gsi`` / ``linear_interpolation`` / ``gaussian_smooth`` are the GSI post-processing of MOT result files.
 ``evaluate_mot`` / ``mot_summary`` are the HOTA / CLEAR / Identity evaluation of MOT result files.
 ``ECC`` / ``EccBatch`` / ``SOF`` / ``SofBatch`` / ``get_cmc_method`` are the camera-motion
-compensation from images; ``EccChain`` / ``warp_table`` align many consecutive frames of a camera
-per call, for the many-sequence file flow (``motio.run_sequences(images=..., cmc=...)``).
+compensation from images; ``EccChain`` / ``warp_table`` and ``SofChain`` / ``sof_warp_table`` run
+many consecutive frames of a camera per call, for the many-sequence file flow
+(``motio.run_sequences(images=..., cmc=...)``).
 ``tune.grid`` / ``tune.sweep`` run a hyper-parameter sweep (K configs x S sequences) as one batched OCSort engine.
 ``ReidFrontEnd`` / ``crop_batch`` / ``normalize_features`` are the ReID front end around the caller's network.
 """
 from .cmc import (MOTION_AFFINE, MOTION_EUCLIDEAN, MOTION_HOMOGRAPHY, MOTION_TRANSLATION, ECC,
-                  EccBatch, EccChain, SOF, SofBatch, get_cmc_method, warp_table)
+                  EccBatch, EccChain, SOF, SofBatch, SofChain, get_cmc_method, sof_warp_table,
+                  warp_table)
 from . import tune
 from .evaluation import evaluate_mot, evaluate_mot_device, mot_summary
 from .postprocessing import gaussian_smooth, gsi, linear_interpolation
@@ -27,6 +29,7 @@ __all__ = ["create_tracker", "get_tracker_config", "ByteTrack", "BotSort", "OcSo
            "BoostTrack", "StrongSort", "DeepOcSort", "HybridSort", "gsi", "linear_interpolation",
            "gaussian_smooth", "DeepOcSortPerClass", "HybridSortPerClass", "evaluate_mot",
            "evaluate_mot_device",
-           "mot_summary", "ECC", "EccBatch", "EccChain", "warp_table", "SOF", "SofBatch", "get_cmc_method", "MOTION_TRANSLATION",
+           "mot_summary", "ECC", "EccBatch", "EccChain", "warp_table", "SOF", "SofBatch", "SofChain",
+           "sof_warp_table", "get_cmc_method", "MOTION_TRANSLATION",
            "MOTION_EUCLIDEAN", "MOTION_AFFINE", "MOTION_HOMOGRAPHY", "ReidFrontEnd",
            "crop_batch", "normalize_features", "tune", "__version__"]

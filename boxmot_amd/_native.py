@@ -313,6 +313,7 @@ EXPORTS = [
     "bx_sof_create", "bx_sof_destroy", "bx_sof_reset", "bx_sof_levels", "bx_sof_apply",
     "bx_sof_apply_host", "bx_sof_status", "bx_sof_pyramid_bytes", "bx_sof_state_host",
     "bx_sof_points_host",
+    "bx_sof_chain_reserve", "bx_sof_apply_chain", "bx_sof_apply_chain_host",
 ]
 
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -567,6 +568,11 @@ _SIGS = {
     "bx_sof_pyramid_bytes": ([_vp, C.POINTER(C.c_size_t)], C.c_int),
     "bx_sof_state_host": ([_vp, C.c_int, _ip, _ip, _ip, _ip, _vp, _ip, _vp, _vp], C.c_int),
     "bx_sof_points_host": ([_vp, C.c_int, _ip, _vp, _vp, _vp, _vp, _vp, _ip], C.c_int),
+    "bx_sof_chain_reserve": ([_vp, C.c_int], C.c_int),
+    "bx_sof_apply_chain": ([_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp,
+                            C.POINTER(BxSofParams), _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_sof_apply_chain_host": ([_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                 C.POINTER(BxSofParams), _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
 }
 
 _lib = None

@@ -16,7 +16,8 @@ library or a HIP device the calls raise ``NativeUnavailable``.
 ``SOF`` / ``SofBatch`` replace ``motion/cmc/sof.py:64-160`` the same way (``include/bxsof.h``;
 DESIGN.md 2.17 is the contract): Shi-Tomasi keypoints, pyramidal Lucas-Kanade tracking with one
 wave per keypoint and a similarity fitted by a deterministic consensus, with the pyramids and the
-keypoints of every camera resident on the device.
+keypoints of every camera resident on the device.  ``SofChain`` runs many consecutive frames of
+a camera per call and ``sof_warp_table`` builds the file flow's warps from it.
 
 Agreement with OpenCV's own ``findTransformECC``, ``goodFeaturesToTrack``,
 ``calcOpticalFlowPyrLK`` and ``estimateAffinePartial2D`` is unmeasured.
@@ -555,30 +556,7 @@ def warp_table(images, stepped, *, warp_mode: int = MOTION_TRANSLATION, eps: flo
     mode = _check_mode(warp_mode)
     _scale_arg(scale)
     S = len(images)
-    if len(stepped) != S:
-        raise ValueError(f"{S} image sources but {len(stepped)} stepped masks")
-    stepped = [np.asarray(m, bool).reshape(-1) for m in stepped]
-    first = {}  # a callable's first stepped frame, read for its size and used once
-
-    def fetch(k: int, t: int) -> np.ndarray:
-        if k in first and first[k][0] == t:
-            return first.pop(k)[1]
-        src = images[k]
-        f = np.asarray(src(int(t)) if callable(src) else src[int(t)])
-        if f.dtype != np.uint8 or f.ndim not in (2, 3) or (f.ndim == 3 and f.shape[2] != 3):
-            raise ValueError(f"sequence {k}: frames must be uint8 [H, W] or [H, W, 3]")
-        return f
-
-    sizes = []
-    for k, m in enumerate(stepped):
-        if not callable(images[k]) and len(images[k]) < m.size:
-            raise ValueError(f"sequence {k}: {len(images[k])} frames for a mask of {m.size}")
-        if not m.any():
-            sizes.append(None)
-            continue
-        t0 = int(np.flatnonzero(m)[0])
-        first[k] = (t0, fetch(k, t0))
-        sizes.append(first[k][1].shape)
+    stepped, fetch, sizes = _table_frames(images, stepped)
     calls = chain_plan(stepped, sizes, chunk)
     tab = _empty_table(max([m.size for m in stepped] + [0]), S)
     if not calls:
@@ -878,6 +856,273 @@ class SOF(_SofSettings):
                      "n_keypoints": int(ints[1, 0]), "n_tracked": int(ints[2, 0]),
                      "n_inliers": int(ints[3, 0])}
         return warp.reshape(2, 3).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------ chained SOF
+_SOF_SETTINGS = ("max_corners", "quality_level", "min_distance", "block_size", "win_size",
+                 "max_level", "criteria", "ransac_threshold")
+
+
+class SofChain(_SofSettings):
+    """Sparse optical flow over many consecutive frames of a camera per call
+    (``bx_sof_apply_chain``): frame i of a call is tracked from frame i - 1 when
+    both are of one stream, otherwise from its stream's stored state.  Warps, codes, the three
+    counts and the streams' final state are bit for bit those of ``SofBatch.apply`` called one
+    frame at a time.
+
+    ``batch`` is the ``SofBatch`` whose handle the chain shares: ``chain.batch.apply`` is the
+    plain apply on the same streams with the chain's settings, and the two may be mixed.  The
+    parameters are ``SOF``'s attributes, read from the chain at every call (``scale`` is fixed at
+    construction).  ``max_frames`` bounds a call's frames
+    (``reserve`` grows it); the other arguments are ``SofBatch``'s."""
+
+    def __init__(self, n_streams: int, max_frames: int = 64, scale=0.15,
+                 max_h: int | None = None, max_w: int | None = None):
+        if max_frames < 1:
+            raise ValueError("max_frames must be at least 1")
+        self._batch = SofBatch(n_streams, scale, max_h, max_w)
+        self.n_streams = self._batch.n_streams
+        self._init_settings(scale)
+        self.max_frames = int(max_frames)
+        self._reserved = 0
+        self._keep = None
+
+    @property
+    def batch(self) -> SofBatch:
+        for k in _SOF_SETTINGS:  # the chain's attributes are the settings of both
+            setattr(self._batch, k, getattr(self, k))
+        return self._batch
+
+    def _ensure(self, H: int, W: int) -> _SofHandle:
+        hd = self._batch._ensure(H, W)
+        if self._reserved < self.max_frames:
+            N.check(hd._L.bx_sof_chain_reserve(hd._h, self.max_frames), "bx_sof_chain_reserve")
+            self._reserved = self.max_frames
+        return hd
+
+    def reserve(self, max_frames: int):
+        """Room for ``max_frames`` frames per call (never shrinks)."""
+        self.max_frames = max(self.max_frames, int(max_frames))
+        if self._batch._handle is not None:
+            self._ensure(0, 0)
+
+    def close(self):
+        self._batch.close()
+        self._reserved = 0
+
+    def reset(self, stream: int = -1):
+        self._batch.reset(stream)
+
+    def status(self) -> int:
+        return self._batch.status()
+
+    def state(self, stream: int = 0):
+        return self._batch.state(stream)
+
+    def points(self, stream: int = 0):
+        return self._batch.points(stream)
+
+    def _frames(self, frames):
+        import torch
+
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8:
+                raise ValueError("frames must be uint8")
+            dims = _frame_dims(frames.shape, self.grayscale)
+            return torch.from_numpy(np.ascontiguousarray(frames)).cuda(), dims
+        if frames.dtype != torch.uint8 or not frames.is_cuda:
+            raise ValueError("frames must be a numpy array or a CUDA uint8 tensor")
+        return frames.contiguous(), _frame_dims(frames.shape, self.grayscale)
+
+    def apply(self, frames, streams, dst=None, out=None):
+        """frames, streams, dst: as ``EccChain.apply`` (same checks).
+
+        Frame i writes row ``dst[i]`` (default: row i) of ``out``, the tuple ``(warps [rows, 6]
+        float64, code, n_keypoints, n_tracked, n_inliers [rows] int32)`` of CUDA tensors; other
+        rows are untouched.  Without ``out`` fresh ``[n]``-row tensors are made (identity,
+        ``SOF_NO_FRAME``, 0, 0, 0).  Returns ``out``.  With device inputs nothing inside
+        synchronises the host with the device."""
+        import torch
+
+        from .engine import _current_stream
+
+        params = self._params()
+        frames, (n, H, W, ch) = self._frames(frames)
+        hd = self._ensure(H, W)
+        S = self.n_streams
+        if isinstance(streams, torch.Tensor) and streams.is_cuda:
+            sd = streams.to(torch.int32).contiguous()
+        else:
+            sh = np.asarray(streams, np.int64).reshape(-1)
+            if sh.size and (sh.min() < 0 or sh.max() >= S):
+                raise ValueError("invalid argument: stream index out of range")
+            starts = sh[np.r_[True, sh[1:] != sh[:-1]]] if sh.size else sh
+            if np.unique(starts).size != starts.size:
+                raise ValueError("invalid argument: the frames of a stream are not adjacent")
+            sd = torch.from_numpy(sh.astype(np.int32)).cuda()
+        if sd.numel() != n:
+            raise ValueError(f"{n} frames but {sd.numel()} stream indices")
+        if out is None:
+            if dst is not None:
+                raise ValueError("dst needs the out tensors it points into")
+            warps = torch.zeros(n, 6, dtype=torch.float64, device="cuda")
+            warps[:, 0] = 1.0
+            warps[:, 4] = 1.0
+            out = (warps, torch.full((n,), SOF_NO_FRAME, dtype=torch.int32, device="cuda"),
+                   torch.zeros(n, dtype=torch.int32, device="cuda"),
+                   torch.zeros(n, dtype=torch.int32, device="cuda"),
+                   torch.zeros(n, dtype=torch.int32, device="cuda"))
+        warps, code, nkp, ntrk, ninl = out
+        rows = int(code.numel())
+        want = ((warps, torch.float64, rows * 6), (code, torch.int32, rows),
+                (nkp, torch.int32, rows), (ntrk, torch.int32, rows), (ninl, torch.int32, rows))
+        for t, dt, ne in want:
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == ne):
+                raise ValueError("out must be contiguous CUDA tensors: warps [rows, 6] float64, "
+                                 "code, n_keypoints, n_tracked, n_inliers int32 [rows]")
+        dd = None
+        if dst is None:
+            if n > rows:
+                raise ValueError(f"{n} frames but {rows} result rows")
+        elif isinstance(dst, torch.Tensor) and dst.is_cuda:
+            dd = dst.to(torch.int64).contiguous()
+        else:
+            dh = np.asarray(dst, np.int64).reshape(-1)
+            if dh.size and (dh.min() < 0 or dh.max() >= rows):
+                raise ValueError("invalid argument: dst row out of range")
+            dd = torch.from_numpy(dh).cuda()
+        if dd is not None and dd.numel() != n:
+            raise ValueError(f"{n} frames but {dd.numel()} dst rows")
+        N.check(hd._L.bx_sof_apply_chain(
+            hd._h, n, H, W, ch, frames.data_ptr(), sd.data_ptr(),
+            None if dd is None else dd.data_ptr(), C.byref(params), warps.data_ptr(),
+            code.data_ptr(), nkp.data_ptr(), ntrk.data_ptr(), ninl.data_ptr(),
+            _current_stream()), "bx_sof_apply_chain")
+        self._keep = (frames, sd, dd)  # alive until the next call: the launches are asynchronous
+        return out
+
+    def apply_host(self, frames, streams):
+        """The host entry (``bx_sof_apply_chain_host``): numpy ``frames`` and ``streams`` in,
+        numpy ``(warps [n, 6], code, n_keypoints, n_tracked, n_inliers)`` out, one
+        synchronisation.  The library itself refuses a stream index out of range or a stream whose
+        frames are not adjacent (``ValueError``, nothing launched)."""
+        from .engine import _current_stream
+
+        params = self._params()
+        frames = np.ascontiguousarray(frames)
+        if frames.dtype != np.uint8:
+            raise ValueError("frames must be uint8")
+        n, H, W, ch = _frame_dims(frames.shape, self.grayscale)
+        sh = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
+        if sh.size != n:
+            raise ValueError(f"{n} frames but {sh.size} stream indices")
+        hd = self._ensure(H, W)
+        warps = np.zeros((n, 6), np.float64)
+        ints = np.zeros((4, n), np.int32)
+        N.check(hd._L.bx_sof_apply_chain_host(
+            hd._h, n, H, W, ch, frames.ctypes.data, sh.ctypes.data, C.byref(params),
+            warps.ctypes.data, ints[0].ctypes.data, ints[1].ctypes.data, ints[2].ctypes.data,
+            ints[3].ctypes.data, _current_stream()), "bx_sof_apply_chain_host")
+        return warps, ints[0], ints[1], ints[2], ints[3]
+
+
+class SofWarpTable(WarpTable):
+    """A ``WarpTable`` of sparse-optical-flow warps: ``code`` holds ``SOF_*`` values
+    (``NOT_STEPPED`` for a frame its sequence is not stepped at), and ``n_keypoints``,
+    ``n_tracked``, ``n_inliers`` ``[T, S]`` int32 are the counts of every stepped frame.  ``rho``
+    and ``iterations`` are the zeros of an empty table: sparse optical flow has neither."""
+
+    def __init__(self, warps, rho, iterations, code, n_keypoints, n_tracked, n_inliers):
+        super().__init__(warps, rho, iterations, code)
+        self.n_keypoints, self.n_tracked, self.n_inliers = n_keypoints, n_tracked, n_inliers
+
+    def host(self) -> dict:
+        out = super().host()
+        for k in ("n_keypoints", "n_tracked", "n_inliers"):
+            out[k] = getattr(self, k).cpu().numpy()
+        return out
+
+    def close(self):
+        super().close()
+        self.n_keypoints = self.n_tracked = self.n_inliers = None
+
+
+def _table_frames(images, stepped):
+    """warp_table's frame fetching: the masks as bool arrays, ``fetch(k, t)`` and every
+    sequence's frame size (``None`` for one that is never stepped)."""
+    S = len(images)
+    if len(stepped) != S:
+        raise ValueError(f"{S} image sources but {len(stepped)} stepped masks")
+    stepped = [np.asarray(m, bool).reshape(-1) for m in stepped]
+    first = {}  # a callable's first stepped frame, read for its size and used once
+
+    def fetch(k: int, t: int) -> np.ndarray:
+        if k in first and first[k][0] == t:
+            return first.pop(k)[1]
+        src = images[k]
+        f = np.asarray(src(int(t)) if callable(src) else src[int(t)])
+        if f.dtype != np.uint8 or f.ndim not in (2, 3) or (f.ndim == 3 and f.shape[2] != 3):
+            raise ValueError(f"sequence {k}: frames must be uint8 [H, W] or [H, W, 3]")
+        return f
+
+    sizes = []
+    for k, m in enumerate(stepped):
+        if not callable(images[k]) and len(images[k]) < m.size:
+            raise ValueError(f"sequence {k}: {len(images[k])} frames for a mask of {m.size}")
+        if not m.any():
+            sizes.append(None)
+            continue
+        t0 = int(np.flatnonzero(m)[0])
+        first[k] = (t0, fetch(k, t0))
+        sizes.append(first[k][1].shape)
+    return stepped, fetch, sizes
+
+
+def sof_warp_table(images, stepped, *, sof=None, chunk: int = 64) -> SofWarpTable:
+    """The sparse-optical-flow warp of every stepped frame of S sequences, computed by chained
+    calls of at most ``chunk`` frames (``chain_plan``) and left in device memory.
+
+    images, stepped: as ``warp_table``.  sof: an object that carries ``SOF``'s settings as
+    attributes (a ``SOF``, ``SofBatch`` or ``SofChain``; only ``scale`` and the settings are read,
+    the object is neither run nor changed); ``None`` means ``SOF()``'s defaults.  The template of a
+    stepped frame is the previous stepped frame of its sequence; a sequence's first stepped frame
+    has code ``SOF_FIRST_FRAME`` (``SOF_NO_KEYPOINTS`` without a corner).  ``rho`` and
+    ``iterations`` of the table are unused (zeros)."""
+    import torch
+
+    src = SOF() if sof is None else sof
+    carrier = SOF(scale=src.scale)
+    for k in _SOF_SETTINGS:
+        setattr(carrier, k, getattr(src, k))
+    carrier._params()  # the refusals, before anything is built
+    stepped, fetch, sizes = _table_frames(images, stepped)
+    S = len(images)
+    calls = chain_plan(stepped, sizes, chunk)
+    T = max([m.size for m in stepped] + [0])
+    base = _empty_table(T, S)
+    tab = SofWarpTable(base.warps, base.rho, base.iterations, base.code,
+                       *(torch.zeros(T, S, dtype=torch.int32, device="cuda") for _ in range(3)))
+    if not calls:
+        return tab
+    work = [work_size(sz[0], sz[1], carrier.scale) for sz in sizes if sz is not None]
+    ch = SofChain(S, max_frames=max(c[1].size for c in calls), scale=carrier.scale,
+                  max_h=max(h for h, _ in work), max_w=max(w for _, w in work))
+    for k in _SOF_SETTINGS:
+        setattr(ch, k, getattr(carrier, k))
+    try:
+        out = (tab.warps.view(-1, 6), tab.code.view(-1), tab.n_keypoints.view(-1),
+               tab.n_tracked.view(-1), tab.n_inliers.view(-1))
+        for size, seq, t in calls:
+            frames = np.stack([fetch(int(k), int(x)) for k, x in zip(seq, t)])
+            if frames.shape[1:] != tuple(size):
+                raise ValueError(f"sequence {int(seq[0])}: frames of more than one size")
+            ch.apply(frames, seq, dst=t * S + seq, out=out)
+        st = ch.status()  # (synchronises: the staged frames may go)
+        if st != 0:
+            raise RuntimeError(f"sof status {st}")
+    finally:
+        ch.close()
+    return tab
 
 
 def get_cmc_method(cmc_method):

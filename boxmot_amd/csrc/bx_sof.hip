@@ -21,6 +21,9 @@
 //                      max_corners-th largest lambda found by a radix pass over its bits, the
 //                      survivors ranked in LDS; then the stream's state is switched
 // No device-wide barrier, no host round trip.
+//
+// The chained apply runs n consecutive frames per call from the same __device__
+// bodies, each frame in a slot of its own; its launches are listed above sof_chain_prep_kernel.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -68,15 +71,50 @@ struct SofDev {
   int* status;               // latched BX_ERR_*
 };
 
+// Scratch of the chained apply (bx_sof_chain_reserve): one slot per frame of a call, each what a
+// stream holds for one frame; nothing is carried from one call to the next.
+struct SofChain {
+  int max_frames;
+  uint8_t* pyr;                    // [max_frames][pcap]
+  double* lam;                     // [max_frames][cap]
+  unsigned long long *lmax, *ckey;  // [max_frames], [max_frames][cap]
+  int* cidx;                       // [max_frames][cap]
+  double *kp, *rprev, *rnext;      // [max_frames][MAXC][2]
+  int* riter;                      // [max_frames][MAXC]
+  uint8_t *rok, *rinl;             // [max_frames][MAXC]
+  int *nkp, *rn, *rwin;            // [max_frames]
+  int *plan, *topar;               // [max_frames] PL_* of a frame; a group's final par[]
+};
+
 struct SofHandle {
   SofDev d{};
+  SofChain c{};
   int max_h = 0, max_w = 0;
   uint8_t* sframes = nullptr;
   size_t sframes_bytes = 0;
   int32_t* sstreams = nullptr;
   double* swarps = nullptr;
   int32_t* sints = nullptr;  // [4][n_streams]: code, n_keypoints, n_tracked, n_inliers
+  // staging of the chained host entry, grown with the slots
+  int32_t* cstreams = nullptr;  // [max_frames]
+  double* cwarps = nullptr;     // [max_frames][6]
+  int32_t* cints = nullptr;     // [4][max_frames]
 };
+
+// a tracking record: the arrays of one stream or of one slot
+struct Rec {
+  double *prev, *next;
+  int* iter;
+  uint8_t *ok, *inl;
+};
+__device__ __forceinline__ Rec rec_of(const SofDev& d, int s) {
+  const size_t o = (size_t)s * BX_SOF_MAX_CORNERS;
+  return Rec{d.rprev + 2 * o, d.rnext + 2 * o, d.riter + o, d.rok + o, d.rinl + o};
+}
+__device__ __forceinline__ Rec rec_of(const SofChain& c, int i) {
+  const size_t o = (size_t)i * BX_SOF_MAX_CORNERS;
+  return Rec{c.rprev + 2 * o, c.rnext + 2 * o, c.riter + o, c.rok + o, c.rinl + o};
+}
 
 __device__ __forceinline__ bool bad_stream(const SofDev& d, int s) {
   return s < 0 || s >= d.n_streams;
@@ -123,14 +161,11 @@ struct PyrArgs {
   Lv lv;
   int l;
 };
-__global__ __launch_bounds__(PT) void sof_pyr_kernel(SofDev d, PyrArgs a) {
-  const int s = a.streams[blockIdx.y];
-  if (bad_stream(d, s)) return;
+// pixel idx of level l of the pyramid at base
+__device__ __forceinline__ void pyr_pixel(uint8_t* base, const PyrArgs& a, int idx) {
   const int l = a.l, w = a.lv.w[l], h = a.lv.h[l], sw = a.lv.w[l - 1], sh = a.lv.h[l - 1];
-  const int idx = blockIdx.x * PT + threadIdx.x;
   if (idx >= h * w) return;
   const int x = idx % w, y = idx / w;
-  uint8_t* base = pyr_of(d, s, d.par[s] ^ 1);
   const uint8_t* src = base + a.lv.off[l - 1];
   const int kq[5] = {1, 4, 6, 4, 1};
   int xs[5];
@@ -146,6 +181,11 @@ __global__ __launch_bounds__(PT) void sof_pyr_kernel(SofDev d, PyrArgs a) {
     sum += kq[i] * r;
   }
   base[a.lv.off[l] + idx] = (uint8_t)((sum + 128) >> 8);
+}
+__global__ __launch_bounds__(PT) void sof_pyr_kernel(SofDev d, PyrArgs a) {
+  const int s = a.streams[blockIdx.y];
+  if (bad_stream(d, s)) return;
+  pyr_pixel(pyr_of(d, s, d.par[s] ^ 1), a, blockIdx.x * PT + threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -168,15 +208,13 @@ struct RespArgs {
   const int32_t* streams;
   Lv lv;
 };
-__global__ __launch_bounds__(PT) void sof_resp_kernel(SofDev d, RespArgs a) {
-  const int s = a.streams[blockIdx.y];
-  if (bad_stream(d, s)) return;
-  const int w = a.lv.w[0], h = a.lv.h[0];
-  const int idx = blockIdx.x * PT + threadIdx.x;
+// pixel idx of the w x h level 0 at I: its lambda into L, the plane's maximum into *lmax.  Called
+// by whole waves.
+__device__ __forceinline__ void resp_pixel(const uint8_t* I, int w, int h, int idx, double* L,
+                                           unsigned long long* lmax) {
   unsigned long long bits = 0ull;
   if (idx < h * w) {
     const int x = idx % w, y = idx / w;
-    const uint8_t* I = pyr_of(d, s, d.par[s] ^ 1);
     int sa = 0, sb = 0, sc = 0;
 #pragma unroll
     for (int i = -1; i <= 1; i++)
@@ -189,7 +227,7 @@ __global__ __launch_bounds__(PT) void sof_resp_kernel(SofDev d, RespArgs a) {
         sc += dy * dy;
       }
     const double lam = min_eig((double)sa, (double)sb, (double)sc);
-    d.lam[(size_t)s * d.cap + idx] = lam;
+    L[idx] = lam;
     if (lam > 0.0) bits = (unsigned long long)__double_as_longlong(lam);
   }
   // the wave's maximum, then one atomic per wave (non-negative doubles order like their bits)
@@ -198,7 +236,13 @@ __global__ __launch_bounds__(PT) void sof_resp_kernel(SofDev d, RespArgs a) {
     const unsigned long long o = __shfl_xor(bits, dd);
     bits = o > bits ? o : bits;
   }
-  if ((threadIdx.x & 63) == 0 && bits) atomicMax(d.lmax + s, bits);
+  if ((threadIdx.x & 63) == 0 && bits) atomicMax(lmax, bits);
+}
+__global__ __launch_bounds__(PT) void sof_resp_kernel(SofDev d, RespArgs a) {
+  const int s = a.streams[blockIdx.y];
+  if (bad_stream(d, s)) return;
+  resp_pixel(pyr_of(d, s, d.par[s] ^ 1), a.lv.w[0], a.lv.h[0], blockIdx.x * PT + threadIdx.x,
+             d.lam + (size_t)s * d.cap, d.lmax + s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -230,22 +274,20 @@ __device__ __forceinline__ int scan1024(bool f, int* tmp, int& total) {
   return off + pre;
 }
 
-__global__ __launch_bounds__(ST) void sof_select_kernel(SofDev d, SelArgs a) {
+// The corners of the w x h lambda plane L (maximum's bits: lmax) ranked into kp; ck / ci: the
+// plane's candidate scratch; tmp: SW ints of LDS.  Returns their number.  By the ST threads of a
+// workgroup.
+__device__ __forceinline__ int select_corners(const double* L, unsigned long long lmax,
+                                              unsigned long long* ck, int* ci, double* kp, int w,
+                                              int h, int K, double quality, int* tmp) {
   __shared__ unsigned long long skey[MAXC];
   __shared__ int sidx[MAXC];
   __shared__ int hist[256];
-  __shared__ int tmp[SW];
   __shared__ unsigned long long sh_prefix;
   __shared__ int sh_need;
   const int tid = threadIdx.x;
-  const int s = a.streams[blockIdx.x];
-  if (bad_stream(d, s)) return;
-  const int w = a.w, h = a.h, npix = h * w;
-  const bool first = is_first(d, s, h, w, a.nl);
-  const double* L = d.lam + (size_t)s * d.cap;
-  unsigned long long* ck = d.ckey + (size_t)s * d.cap;
-  int* ci = d.cidx + (size_t)s * d.cap;
-  const double floor_lam = a.quality * __longlong_as_double((long long)d.lmax[s]);
+  const int npix = h * w;
+  const double floor_lam = quality * __longlong_as_double((long long)lmax);
 
   // candidates, compacted in pixel order
   int nc = 0;
@@ -278,7 +320,6 @@ __global__ __launch_bounds__(ST) void sof_select_kernel(SofDev d, SelArgs a) {
   __syncthreads();  // (the candidates are read by other threads below)
 
   // the K-th largest key by a radix pass from the top byte; need: how many equal to it survive
-  const int K = a.max_corners;
   unsigned long long thr = 0ull;  // survivors: key > thr, and the first `need` with key == thr
   int need = 0;
   if (nc > K) {
@@ -337,7 +378,6 @@ __global__ __launch_bounds__(ST) void sof_select_kernel(SofDev d, SelArgs a) {
   __syncthreads();
 
   // rank: lambda descending, pixel index ascending
-  double* kp = d.kp + (size_t)s * MAXC * 2;
   if (tid < ns) {
     const unsigned long long key = skey[tid];
     const int idx = sidx[tid];
@@ -349,6 +389,20 @@ __global__ __launch_bounds__(ST) void sof_select_kernel(SofDev d, SelArgs a) {
     kp[2 * rank] = (double)(idx % w);
     kp[2 * rank + 1] = (double)(idx / w);
   }
+  return ns;
+}
+
+__global__ __launch_bounds__(ST) void sof_select_kernel(SofDev d, SelArgs a) {
+  __shared__ int tmp[SW];
+  const int tid = threadIdx.x;
+  const int s = a.streams[blockIdx.x];
+  if (bad_stream(d, s)) return;
+  const int w = a.w, h = a.h;
+  const bool first = is_first(d, s, h, w, a.nl);
+  double* kp = d.kp + (size_t)s * MAXC * 2;
+  const int ns = select_corners(d.lam + (size_t)s * d.cap, d.lmax[s], d.ckey + (size_t)s * d.cap,
+                                d.cidx + (size_t)s * d.cap, kp, w, h, a.max_corners, a.quality,
+                                tmp);
   int nk = ns;
   if (ns == 0 && !first) {
     // no corner on this frame: the tracked points are kept, in order
@@ -415,27 +469,15 @@ __device__ __forceinline__ double blend(const Win& o, double v00, double v01, do
   return ((o.w00 * v00 + o.w01 * v01) + o.w10 * v10) + o.w11 * v11;
 }
 
-__global__ __launch_bounds__(TW * WAVE) void sof_track_kernel(SofDev d, TrackArgs a) {
-  extern __shared__ double tl[];  // [TW][3][win * win]: template I, Ix, Iy of the wave's point
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int s = a.streams[blockIdx.y];
-  if (bad_stream(d, s)) return;
-  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-  if (is_first(d, s, a.lv)) {
-    if (lead) d.rn[s] = 0;
-    return;
-  }
-  const int n = d.nkp[s];
-  if (lead) d.rn[s] = n;
-  const int pt = blockIdx.x * TW + wv;
-  if (pt >= n) return;
+// One wave tracks keypoint pt of kp from the pyramid P into the pyramid C and writes entry pt of
+// the record r; TI: the wave's LDS slab of 3 * win * win doubles.
+__device__ __forceinline__ void track_point(const uint8_t* P, const uint8_t* C, const double* kp,
+                                            int pt, const TrackArgs& a, double* TI, const Rec& r) {
+  const int lane = threadIdx.x & 63;
   const int win = a.win, nw = win * win;
   const double half = (double)((win - 1) / 2);
-  double *TI = tl + (size_t)wv * 3 * nw, *TX = TI + nw, *TY = TX + nw;
-  const int par = d.par[s];
-  const uint8_t *P = pyr_of(d, s, par), *C = pyr_of(d, s, par ^ 1);
-  const size_t rec = (size_t)s * MAXC + pt;
-  const double px = d.kp[2 * rec], py = d.kp[2 * rec + 1];
+  double *TX = TI + nw, *TY = TX + nw;
+  const double px = kp[2 * pt], py = kp[2 * pt + 1];
   const double eps2 = a.eps * a.eps;
   double qx = 0.0, qy = 0.0;
   int iters = 0;
@@ -540,14 +582,33 @@ __global__ __launch_bounds__(TW * WAVE) void sof_track_kernel(SofDev d, TrackArg
                  qy <= (double)(a.lv.h[0] - 1)))
     lost = true;
   if (lane == 0) {
-    d.rprev[2 * rec] = px;
-    d.rprev[2 * rec + 1] = py;
-    d.rnext[2 * rec] = qx;
-    d.rnext[2 * rec + 1] = qy;
-    d.rok[rec] = lost ? 0 : 1;
-    d.rinl[rec] = 0;
-    d.riter[rec] = iters;
+    r.prev[2 * pt] = px;
+    r.prev[2 * pt + 1] = py;
+    r.next[2 * pt] = qx;
+    r.next[2 * pt + 1] = qy;
+    r.ok[pt] = lost ? 0 : 1;
+    r.inl[pt] = 0;
+    r.iter[pt] = iters;
   }
+}
+
+__global__ __launch_bounds__(TW * WAVE) void sof_track_kernel(SofDev d, TrackArgs a) {
+  extern __shared__ double tl[];  // [TW][3][win * win]: template I, Ix, Iy of the wave's point
+  const int wv = threadIdx.x >> 6;
+  const int s = a.streams[blockIdx.y];
+  if (bad_stream(d, s)) return;
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+  if (is_first(d, s, a.lv)) {
+    if (lead) d.rn[s] = 0;
+    return;
+  }
+  const int n = d.nkp[s];
+  if (lead) d.rn[s] = n;
+  const int pt = blockIdx.x * TW + wv;
+  if (pt >= n) return;
+  const int par = d.par[s];
+  track_point(pyr_of(d, s, par), pyr_of(d, s, par ^ 1), d.kp + (size_t)s * MAXC * 2, pt, a,
+              tl + (size_t)wv * 3 * a.win * a.win, rec_of(d, s));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -579,52 +640,73 @@ __device__ __forceinline__ bool sim_inlier(const Sim& m, double px, double py, d
   return rx * rx + ry * ry <= thr2;
 }
 
-__global__ __launch_bounds__(FT) void sof_fit_kernel(SofDev d, FitArgs a) {
-  __shared__ double PX[MAXC], PY[MAXC], QX[MAXC], QY[MAXC];
-  __shared__ short CI[MAXC];
-  __shared__ int tmp[4];
-  __shared__ unsigned long long best[FW];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int s = a.streams[blockIdx.x];
-  if (bad_stream(d, s)) return;
-  double* W = a.warps + (size_t)s * 6;
-  auto finish = [&](int code, int ntrk, int ninl, int winner, const Sim* m) {
-    if (tid != 0) return;
-    double o[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
-    if (m) {
-      o[0] = m->a;
-      o[1] = -m->b;
-      o[2] = m->tx;
-      o[3] = m->b;
-      o[4] = m->a;
-      o[5] = m->ty;
-      if (a.scale > 0.0 && a.scale < 1.0) {
-        o[2] = o[2] / a.scale;
-        o[5] = o[5] / a.scale;
-      }
+// the fit's LDS, FIT_LDS bytes: the tracked pairs, their record indices and the reductions
+constexpr size_t FIT_LDS = (size_t)MAXC * (4 * 8 + 2) + 4 * 4 + FW * 8;
+struct FitLds {
+  double *PX, *PY, *QX, *QY;  // [MAXC] each
+  unsigned long long* best;   // [FW]
+  int* tmp;                   // [4]
+  short* CI;                  // [MAXC]
+};
+__device__ __forceinline__ FitLds fit_lds(void* base) {
+  FitLds f;
+  f.PX = (double*)base;
+  f.PY = f.PX + MAXC;
+  f.QX = f.PY + MAXC;
+  f.QY = f.QX + MAXC;
+  f.best = (unsigned long long*)(f.QY + MAXC);
+  f.tmp = (int*)(f.best + FW);
+  f.CI = (short*)(f.tmp + 4);
+  return f;
+}
+
+// One result row (thread 0 writes): the warp of the similarity m (the identity without one), the
+// code, the counts, and the winner into *rwin.
+__device__ __forceinline__ void fit_finish(const FitArgs& a, size_t row, int* rwin, int code,
+                                           int ntrk, int ninl, int winner, const Sim* m) {
+  if (threadIdx.x != 0) return;
+  double* W = a.warps + row * 6;
+  double o[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+  if (m) {
+    o[0] = m->a;
+    o[1] = -m->b;
+    o[2] = m->tx;
+    o[3] = m->b;
+    o[4] = m->a;
+    o[5] = m->ty;
+    if (a.scale > 0.0 && a.scale < 1.0) {
+      o[2] = o[2] / a.scale;
+      o[5] = o[5] / a.scale;
     }
-    for (int q = 0; q < 6; q++) W[q] = o[q];
-    a.code[s] = code;
-    a.n_tracked[s] = ntrk;
-    a.n_inliers[s] = ninl;
-    d.rwin[s] = winner;
-  };
-  if (is_first(d, s, a.h, a.w, a.nl)) {
-    finish(BX_SOF_FIRST_FRAME, 0, 0, -1, nullptr);
-    return;
   }
-  const int n = d.rn[s];
-  const size_t rb = (size_t)s * MAXC;
+  for (int q = 0; q < 6; q++) W[q] = o[q];
+  a.code[row] = code;
+  a.n_tracked[row] = ntrk;
+  a.n_inliers[row] = ninl;
+  *rwin = winner;
+}
+
+// The consensus fit over the n entries of the record r, by the FT threads of a workgroup; the
+// result goes to row `row`.  Every thread returns; the LDS may be reused after a barrier.
+__device__ __forceinline__ void fit_pairs(const Rec& r, int n, const FitArgs& a, size_t row,
+                                          int* rwin, const FitLds& F) {
+  double *PX = F.PX, *PY = F.PY, *QX = F.QX, *QY = F.QY;
+  short* CI = F.CI;
+  unsigned long long* best = F.best;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  auto finish = [&](int code, int ntrk, int ninl, int winner, const Sim* m) {
+    fit_finish(a, row, rwin, code, ntrk, ninl, winner, m);
+  };
   const int m = block_compact(
-      n, [&](int k) { return d.rok[rb + k] != 0; },
+      n, [&](int k) { return r.ok[k] != 0; },
       [&](int k, int pos) {
-        PX[pos] = d.rprev[2 * (rb + k)];
-        PY[pos] = d.rprev[2 * (rb + k) + 1];
-        QX[pos] = d.rnext[2 * (rb + k)];
-        QY[pos] = d.rnext[2 * (rb + k) + 1];
+        PX[pos] = r.prev[2 * k];
+        PY[pos] = r.prev[2 * k + 1];
+        QX[pos] = r.next[2 * k];
+        QY[pos] = r.next[2 * k + 1];
         CI[pos] = (short)k;
       },
-      tmp);
+      F.tmp);
   if (m < 4) {
     finish(BX_SOF_TOO_FEW, m, 0, -1, nullptr);
     return;
@@ -674,7 +756,7 @@ __global__ __launch_bounds__(FT) void sof_fit_kernel(SofDev d, FitArgs a) {
   int cnt = 0;
   for (int q = lane; q < m; q += WAVE) {
     if (!sim_inlier(hm, PX[q], PY[q], QX[q], QY[q], a.thr2)) continue;
-    d.rinl[rb + CI[q]] = 1;
+    r.inl[CI[q]] = 1;
     cnt++;
     sp += PX[q];
     sq += PY[q];
@@ -704,12 +786,300 @@ __global__ __launch_bounds__(FT) void sof_fit_kernel(SofDev d, FitArgs a) {
     finish(BX_SOF_NO_MODEL, m, 0, -1, nullptr);
     return;
   }
-  Sim r;
-  r.a = spq / spp;
-  r.b = sxq / spp;
-  r.tx = mqx - (r.a * mpx - r.b * mpy);
-  r.ty = mqy - (r.b * mpx + r.a * mpy);
-  finish(BX_SOF_OK, m, cnt, winner, &r);
+  Sim ls;
+  ls.a = spq / spp;
+  ls.b = sxq / spp;
+  ls.tx = mqx - (ls.a * mpx - ls.b * mpy);
+  ls.ty = mqy - (ls.b * mpx + ls.a * mpy);
+  finish(BX_SOF_OK, m, cnt, winner, &ls);
+}
+
+__global__ __launch_bounds__(FT) void sof_fit_kernel(SofDev d, FitArgs a) {
+  __shared__ double fl[FIT_LDS / 8];
+  static_assert(FIT_LDS % 8 == 0, "the fit's LDS is carved from doubles");
+  const int s = a.streams[blockIdx.x];
+  if (bad_stream(d, s)) return;
+  if (is_first(d, s, a.h, a.w, a.nl)) {
+    fit_finish(a, (size_t)s, d.rwin + s, BX_SOF_FIRST_FRAME, 0, 0, -1, nullptr);
+    return;
+  }
+  fit_pairs(rec_of(d, s), d.rn[s], a, (size_t)s, d.rwin + s, fit_lds(fl));
+}
+
+// ------------------------------------------------------------------------------------------
+// The chained apply: n frames per call, frame i in slot i.  Frame i is tracked
+// from frame i - 1 of the call when both are of one stream, else from the stream's stored state.
+// A group is a stream's run of adjacent frames.  Launches, all on the caller's stream:
+//   sof_chain_prep_kernel      level 0 of every slot's pyramid
+//   sof_chain_pyr_kernel       (nl - 1 launches) the higher levels
+//   sof_chain_resp_kernel      every slot's lambda plane and its maximum
+//   sof_chain_select_kernel    every slot's corners into the slot's keypoints; no stream state
+//   sof_chain_plan_kernel      one thread per group walks it: which frames are first frames (a
+//                              prefix: the stored state is first and no frame so far had a corner),
+//                              which keep the tracked points (no corner, not first), which pairs
+//                              are deferred (their template frame keeps tracked points)
+//   sof_chain_track_kernel     sof_track_kernel's body for every pair that is not deferred
+//   sof_chain_fit_kernel       sof_fit_kernel's body for the same pairs; first frames' rows
+//   sof_chain_tail_kernel      one workgroup per group walks its frames in order: a deferred pair
+//                              is tracked (a wave per keypoint, looped) and fitted, a frame that
+//                              keeps the tracked points compacts them into its slot.  Without such
+//                              a frame it reads one flag per frame
+//   sof_chain_handover_kernel  the last slot of every group becomes its stream's state.  A launch
+//                              of its own: the workgroups of a group's first pair read the stream's
+//                              stored pyramid and keypoints, so nothing before may write them
+// No workgroup waits for another, no host round trip.
+constexpr int PL_FIRST = 1, PL_NOKP = 2, PL_KEEP = 4, PL_DEFER = 8;
+
+struct ChainArgs {
+  const int32_t* streams;  // [n]
+  const int64_t* dst;      // [n] result row of each frame, or null: row i
+  int n;
+  Lv lv;
+};
+__device__ __forceinline__ size_t row_of(const ChainArgs& a, int i) {
+  return a.dst ? (size_t)a.dst[i] : (size_t)i;
+}
+__device__ __forceinline__ uint8_t* slot_pyr(const SofDev& d, const SofChain& c, int i) {
+  return c.pyr + (size_t)i * d.pcap;
+}
+__device__ __forceinline__ bool chained(const ChainArgs& a, int i) {
+  return i > 0 && a.streams[i - 1] == a.streams[i];
+}
+
+__global__ __launch_bounds__(PT) void sof_chain_prep_kernel(SofDev d, SofChain c, PrepArgs a) {
+  const int i = blockIdx.y;
+  const int s = a.streams[i];
+  if (bad_stream(d, s)) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) atomicMax(d.status, (int)BX_ERR_INVALID);
+    return;
+  }
+  if (threadIdx.x == 0 && blockIdx.x == 0) c.lmax[i] = 0ull;  // (read two launches later)
+  const int idx = blockIdx.x * PT + threadIdx.x;
+  if (idx >= a.h * a.w) return;
+  const int x = idx % a.w, y = idx / a.w;
+  const uint8_t* f = a.frames + (size_t)i * a.H * a.W * a.ch;
+  slot_pyr(d, c, i)[idx] = (uint8_t)work_pixel(a, f, x, y);
+}
+
+__global__ __launch_bounds__(PT) void sof_chain_pyr_kernel(SofDev d, SofChain c, PyrArgs a) {
+  const int i = blockIdx.y;
+  if (bad_stream(d, a.streams[i])) return;
+  pyr_pixel(slot_pyr(d, c, i), a, blockIdx.x * PT + threadIdx.x);
+}
+
+__global__ __launch_bounds__(PT) void sof_chain_resp_kernel(SofDev d, SofChain c, RespArgs a) {
+  const int i = blockIdx.y;
+  if (bad_stream(d, a.streams[i])) return;
+  resp_pixel(slot_pyr(d, c, i), a.lv.w[0], a.lv.h[0], blockIdx.x * PT + threadIdx.x,
+             c.lam + (size_t)i * d.cap, c.lmax + i);
+}
+
+// a.n_keypoints: the rows by frame; a.code is not used
+__global__ __launch_bounds__(ST) void sof_chain_select_kernel(SofDev d, SofChain c, SelArgs a,
+                                                              const int64_t* dst) {
+  __shared__ int tmp[SW];
+  const int i = blockIdx.x;
+  if (bad_stream(d, a.streams[i])) return;
+  const int ns = select_corners(c.lam + (size_t)i * d.cap, c.lmax[i], c.ckey + (size_t)i * d.cap,
+                                c.cidx + (size_t)i * d.cap, c.kp + (size_t)i * MAXC * 2, a.w, a.h,
+                                a.max_corners, a.quality, tmp);
+  if (threadIdx.x == 0) {
+    c.nkp[i] = ns;  // (a frame that keeps the tracked points gets its count from the tail)
+    a.n_keypoints[dst ? (size_t)dst[i] : (size_t)i] = ns;
+  }
+}
+
+__global__ __launch_bounds__(PT) void sof_chain_plan_kernel(SofDev d, SofChain c, ChainArgs a) {
+  const int g = blockIdx.x * PT + threadIdx.x;
+  if (g >= a.n) return;
+  const int s = a.streams[g];
+  if (bad_stream(d, s) || chained(a, g)) return;  // (one thread per group: its first frame)
+  bool first = is_first(d, s, a.lv);
+  if (first && d.has_prev[s]) atomicMax(d.status, (int)BX_ERR_SHAPE);
+  int flips = 0, i = g;
+  bool kept = false;  // the frame before keeps tracked points as its keypoints
+  for (; i < a.n && a.streams[i] == s; i++) {
+    const bool corners = c.nkp[i] > 0;
+    int p = 0;
+    if (first) p = corners ? PL_FIRST : PL_FIRST | PL_NOKP;
+    else p = (corners ? 0 : PL_KEEP) | (kept ? PL_DEFER : 0);
+    c.plan[i] = p;
+    kept = (p & PL_KEEP) != 0;
+    if (!(p & PL_NOKP)) flips++;
+    first = first && !corners;
+  }
+  c.topar[i - 1] = d.par[s] ^ (flips & 1);  // as many switches as the plain applies make
+}
+
+struct ChainTrackArgs {
+  ChainArgs ch;
+  TrackArgs t;  // (t.streams is not used)
+};
+// the pair of frame i: where its keypoints and its previous pyramid are
+__device__ __forceinline__ void pair_source(const SofDev& d, const SofChain& c, const ChainArgs& a,
+                                            int i, const uint8_t*& P, const double*& kp, int& n) {
+  if (chained(a, i)) {
+    P = slot_pyr(d, c, i - 1);
+    kp = c.kp + (size_t)(i - 1) * MAXC * 2;
+    n = c.nkp[i - 1];
+  } else {
+    const int s = a.streams[i];
+    P = pyr_of(d, s, d.par[s]);
+    kp = d.kp + (size_t)s * MAXC * 2;
+    n = d.nkp[s];
+  }
+}
+
+__global__ __launch_bounds__(TW * WAVE) void sof_chain_track_kernel(SofDev d, SofChain c,
+                                                                     ChainTrackArgs a) {
+  extern __shared__ double tl[];  // [TW][3][win * win]
+  const int wv = threadIdx.x >> 6;
+  const int i = blockIdx.y;
+  if (bad_stream(d, a.ch.streams[i])) return;
+  const int p = c.plan[i];
+  if (p & PL_DEFER) return;
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+  if (p & PL_FIRST) {
+    if (lead) c.rn[i] = 0;
+    return;
+  }
+  const uint8_t* P;
+  const double* kp;
+  int n;
+  pair_source(d, c, a.ch, i, P, kp, n);
+  if (lead) c.rn[i] = n;
+  const int pt = blockIdx.x * TW + wv;
+  if (pt >= n) return;
+  track_point(P, slot_pyr(d, c, i), kp, pt, a.t, tl + (size_t)wv * 3 * a.t.win * a.t.win,
+              rec_of(c, i));
+}
+
+struct ChainFitArgs {
+  ChainArgs ch;
+  FitArgs f;  // (f.streams is not used; its rows are by frame)
+};
+__global__ __launch_bounds__(FT) void sof_chain_fit_kernel(SofDev d, SofChain c, ChainFitArgs a) {
+  __shared__ double fl[FIT_LDS / 8];
+  const int i = blockIdx.x;
+  if (bad_stream(d, a.ch.streams[i])) return;
+  const int p = c.plan[i];
+  if (p & PL_DEFER) return;
+  const size_t row = row_of(a.ch, i);
+  if (p & PL_FIRST) {
+    fit_finish(a.f, row, c.rwin + i, (p & PL_NOKP) ? BX_SOF_NO_KEYPOINTS : BX_SOF_FIRST_FRAME, 0, 0,
+               -1, nullptr);
+    return;
+  }
+  fit_pairs(rec_of(c, i), c.rn[i], a.f, row, c.rwin + i, fit_lds(fl));
+}
+
+struct ChainTailArgs {
+  ChainArgs ch;
+  TrackArgs t;
+  FitArgs f;
+  int tw;  // waves that track: tw slabs fit the dynamic LDS
+  int32_t* n_keypoints;
+};
+__global__ __launch_bounds__(FT) void sof_chain_tail_kernel(SofDev d, SofChain c,
+                                                            ChainTailArgs a) {
+  extern __shared__ double tl[];  // max(tw track slabs, FIT_LDS), one after the other in time
+  const int wv = threadIdx.x >> 6;
+  const int g = blockIdx.x;
+  const int s = a.ch.streams[g];
+  if (bad_stream(d, s) || chained(a.ch, g)) return;  // (one workgroup per group)
+  for (int i = g; i < a.ch.n && a.ch.streams[i] == s; i++) {  // (uniform)
+    const int p = c.plan[i];
+    if (!(p & (PL_DEFER | PL_KEEP))) continue;
+    const Rec r = rec_of(c, i);
+    const size_t row = row_of(a.ch, i);
+    if (p & PL_DEFER) {
+      // the template frame's keypoints are the tracked points compacted one turn earlier
+      const double* kp = c.kp + (size_t)(i - 1) * MAXC * 2;
+      const int n = c.nkp[i - 1];
+      if (threadIdx.x == 0) c.rn[i] = n;
+      if (wv < a.tw)
+        for (int pt = wv; pt < n; pt += a.tw)
+          track_point(slot_pyr(d, c, i - 1), slot_pyr(d, c, i), kp, pt, a.t,
+                      tl + (size_t)wv * 3 * a.t.win * a.t.win, r);
+      __syncthreads();  // the record is read by every thread; the slabs become the fit's arrays
+      fit_pairs(r, n, a.f, row, c.rwin + i, fit_lds(tl));
+      __syncthreads();
+    }
+    if (p & PL_KEEP) {
+      // no corner on this frame: the tracked points are kept, in order
+      double* kp = c.kp + (size_t)i * MAXC * 2;
+      const int nk = block_compact(
+          c.rn[i], [&](int k) { return r.ok[k] != 0; },
+          [&](int k, int pos) {
+            kp[2 * pos] = r.next[2 * k];
+            kp[2 * pos + 1] = r.next[2 * k + 1];
+          },
+          (int*)tl);
+      if (threadIdx.x == 0) {
+        c.nkp[i] = nk;
+        a.n_keypoints[row] = nk;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// The last frame of each group: its slot becomes the stream's state, as after a plain apply of
+// every frame of the group.  Rows of the keypoints and of the record beyond the last frame's
+// counts are those of the latest frame of the group that wrote them, as the plain applies leave
+// them.
+__global__ __launch_bounds__(PT) void sof_chain_handover_kernel(SofDev d, SofChain c,
+                                                                ChainArgs a) {
+  const int k = blockIdx.y;
+  const int s = a.streams[k];
+  if (bad_stream(d, s)) return;
+  if (k + 1 < a.n && a.streams[k + 1] == s) return;
+  const int idx = blockIdx.x * PT + threadIdx.x;
+  const int h = a.lv.h[0], w = a.lv.w[0], nl = a.lv.nl;
+  const int p = c.plan[k];
+  const bool none = (p & PL_NOKP) != 0;  // every frame of the group was a first one without a corner
+  if (idx == 0) {
+    d.has_prev[s] = none ? 0 : 1;
+    if (!none) {
+      d.ph[s] = h;
+      d.pw[s] = w;
+      d.pnl[s] = nl;
+    }
+    d.nkp[s] = c.nkp[k];
+    d.rn[s] = c.rn[k];
+    d.rwin[s] = c.rwin[k];
+    d.lmax[s] = c.lmax[k];
+    d.par[s] = c.topar[k];  // (no thread of this launch reads par[])
+  }
+  const int to = c.topar[k];
+  if (!none) {
+    const int bytes = a.lv.off[nl - 1] + a.lv.h[nl - 1] * a.lv.w[nl - 1];
+    if (idx < bytes) pyr_of(d, s, to)[idx] = slot_pyr(d, c, k)[idx];
+  }
+  if (idx < h * w) d.lam[(size_t)s * d.cap + idx] = c.lam[(size_t)k * d.cap + idx];
+  if (idx < MAXC) {
+    const Rec rs = rec_of(d, s);
+    bool kdone = false, rdone = false;
+    for (int i = k; i >= 0 && a.streams[i] == s && !(kdone && rdone); i--) {
+      if (!kdone && idx < c.nkp[i]) {
+        const double* kp = c.kp + (size_t)i * MAXC * 2;
+        d.kp[((size_t)s * MAXC + idx) * 2] = kp[2 * idx];
+        d.kp[((size_t)s * MAXC + idx) * 2 + 1] = kp[2 * idx + 1];
+        kdone = true;
+      }
+      if (!rdone && idx < c.rn[i]) {
+        const Rec ri = rec_of(c, i);
+        rs.prev[2 * idx] = ri.prev[2 * idx];
+        rs.prev[2 * idx + 1] = ri.prev[2 * idx + 1];
+        rs.next[2 * idx] = ri.next[2 * idx];
+        rs.next[2 * idx + 1] = ri.next[2 * idx + 1];
+        rs.iter[idx] = ri.iter[idx];
+        rs.ok[idx] = ri.ok[idx];
+        rs.inl[idx] = ri.inl[idx];
+        rdone = true;
+      }
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -789,6 +1159,74 @@ int launch(SofHandle* H_, int n, int H, int W, int ch, const uint8_t* frames,
   hipLaunchKernelGGL(sof_select_kernel, dim3(n), dim3(ST), 0, st, d, sa);
   BX_HIPCHK(hipGetLastError());
   return BX_OK;
+}
+
+// the chained entries' checks: a call's frames are bounded by the reserved slots, not by the
+// streams
+int check_chain_args(SofHandle* H_, int n, int H, int W, int ch, const bx_sof_params* p, Lv* lv) {
+  if (n < 0) return sf_err(BX_ERR_INVALID, "n/H/W/channels out of range");
+  int rc = check_args(H_, 0, H, W, ch, p, lv);
+  if (rc != BX_OK) return rc;
+  if ((long long)H * W * ch * (long long)(n > 0 ? n : 1) >= (1LL << 40))
+    return sf_err(BX_ERR_INVALID, "frames too large");
+  if (n > H_->c.max_frames)
+    return sf_err(BX_ERR_CAPACITY, "more frames than chain slots reserved (" +
+                                       std::to_string(H_->c.max_frames) + ")");
+  return BX_OK;
+}
+
+int launch_chain(SofHandle* H_, int n, int H, int W, int ch, const uint8_t* frames,
+                 const int32_t* streams, const int64_t* dst, const bx_sof_params& p, const Lv& lv,
+                 double* warps, int32_t* code, int32_t* nkp, int32_t* ntrk, int32_t* ninl,
+                 hipStream_t st) {
+  const SofDev& d = H_->d;
+  const SofChain& c = H_->c;
+  const int h = lv.h[0], w = lv.w[0];
+  const dim3 pg((h * w + PT - 1) / PT, n);
+  PrepArgs pa{frames, streams, H, W, ch, h, w, (p.scale > 0.0 && p.scale < 1.0) ? 1 : 0, p.scale};
+  hipLaunchKernelGGL(sof_chain_prep_kernel, pg, dim3(PT), 0, st, d, c, pa);
+  for (int l = 1; l < lv.nl; l++) {
+    PyrArgs ya{streams, lv, l};
+    hipLaunchKernelGGL(sof_chain_pyr_kernel, dim3((lv.h[l] * lv.w[l] + PT - 1) / PT, n), dim3(PT),
+                       0, st, d, c, ya);
+  }
+  RespArgs ra{streams, lv};
+  hipLaunchKernelGGL(sof_chain_resp_kernel, pg, dim3(PT), 0, st, d, c, ra);
+  SelArgs sa{streams, h, w, lv.nl, p.max_corners, p.quality_level, code, nkp};
+  hipLaunchKernelGGL(sof_chain_select_kernel, dim3(n), dim3(ST), 0, st, d, c, sa, dst);
+  ChainArgs ca{streams, dst, n, lv};
+  hipLaunchKernelGGL(sof_chain_plan_kernel, dim3((n + PT - 1) / PT), dim3(PT), 0, st, d, c, ca);
+  TrackArgs ta{streams, lv, p.win_size, p.max_iter, p.eps};
+  const size_t slab = (size_t)3 * p.win_size * p.win_size * sizeof(double);
+  hipLaunchKernelGGL(sof_chain_track_kernel, dim3(MAXC / TW, n), dim3(TW * WAVE), TW * slab, st, d,
+                     c, ChainTrackArgs{ca, ta});
+  FitArgs fa{streams, h, w, lv.nl, p.threshold * p.threshold, p.scale, warps, code, ntrk, ninl};
+  hipLaunchKernelGGL(sof_chain_fit_kernel, dim3(n), dim3(FT), 0, st, d, c, ChainFitArgs{ca, fa});
+  // the tail's LDS: the larger of its track slabs and the fit's arrays (at most 48 KiB)
+  const int tw = FW * slab <= 48 * 1024 ? FW : TW;
+  const size_t tail_lds = tw * slab > FIT_LDS ? tw * slab : FIT_LDS;
+  hipLaunchKernelGGL(sof_chain_tail_kernel, dim3(n), dim3(FT), tail_lds, st, d, c,
+                     ChainTailArgs{ca, ta, fa, tw, nkp});
+  const int bytes = lv.off[lv.nl - 1] + lv.h[lv.nl - 1] * lv.w[lv.nl - 1];
+  const int most = bytes > MAXC ? bytes : MAXC;
+  hipLaunchKernelGGL(sof_chain_handover_kernel, dim3((most + PT - 1) / PT, n), dim3(PT), 0, st, d,
+                     c, ca);
+  BX_HIPCHK(hipGetLastError());
+  return BX_OK;
+}
+
+void free_chain(SofHandle* H_) {
+  SofChain& c = H_->c;
+  void** ps[] = {(void**)&c.pyr,   (void**)&c.lam,   (void**)&c.lmax,  (void**)&c.ckey,
+                 (void**)&c.cidx,  (void**)&c.kp,    (void**)&c.rprev, (void**)&c.rnext,
+                 (void**)&c.riter, (void**)&c.rok,   (void**)&c.rinl,  (void**)&c.nkp,
+                 (void**)&H_->cstreams, (void**)&H_->cwarps, (void**)&H_->cints};
+  for (void** p : ps) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  c.rn = c.rwin = c.plan = c.topar = nullptr;  // (parts of nkp's allocation)
+  c.max_frames = 0;
 }
 
 }  // namespace
@@ -871,6 +1309,7 @@ int bx_sof_destroy(void* h) {
                 d.rinl, d.has_prev, H_->sframes, H_->sstreams, H_->swarps, H_->sints};
   for (void* p : ps)
     if (p) (void)hipFree(p);
+  free_chain(H_);
   delete H_;
   return BX_OK;
 }
@@ -951,6 +1390,107 @@ int bx_sof_apply_host(void* h, int n, int H, int W, int channels, const uint8_t*
     n_tracked_host[s] = iv[(size_t)2 * S + s];
     n_inliers_host[s] = iv[(size_t)3 * S + s];
   }
+  return BX_OK;
+}
+
+int bx_sof_chain_reserve(void* h, int max_frames) {
+  SofHandle* H_ = (SofHandle*)h;
+  if (!H_) return sf_err(BX_ERR_INVALID, "null sof handle");
+  const SofDev& d = H_->d;
+  const size_t cap = (size_t)d.cap, pcap = (size_t)d.pcap;
+  if (max_frames < 1 || max_frames > BX_SOF_MAX_STREAMS ||
+      (long long)max_frames * (long long)(pcap + cap * 20) > (1LL << 36))
+    return sf_err(BX_ERR_INVALID, "max_frames out of range");
+  if (max_frames <= H_->c.max_frames) return BX_OK;
+  // grown: the slots hold nothing between calls, so the old ones are dropped once the device
+  // has finished with them
+  BX_HIPCHK(hipDeviceSynchronize());
+  free_chain(H_);
+  SofChain& c = H_->c;
+  const size_t m = (size_t)max_frames;
+  void** ps[] = {(void**)&c.pyr,   (void**)&c.lam,   (void**)&c.lmax,  (void**)&c.ckey,
+                 (void**)&c.cidx,  (void**)&c.kp,    (void**)&c.rprev, (void**)&c.rnext,
+                 (void**)&c.riter, (void**)&c.rok,   (void**)&c.rinl,  (void**)&c.nkp,
+                 (void**)&H_->cstreams, (void**)&H_->cwarps, (void**)&H_->cints};
+  const size_t bytes[] = {m * pcap,      m * cap * 8,   m * 8,         m * cap * 8,
+                          m * cap * 4,   m * MAXC * 16, m * MAXC * 16, m * MAXC * 16,
+                          m * MAXC * 4,  m * MAXC,      m * MAXC,      m * 5 * 4,
+                          m * 4,         m * 48,        m * 16};
+  for (int q = 0; q < 15; q++) {
+    hipError_t e = hipMalloc(ps[q], bytes[q]);
+    if (e != hipSuccess) {
+      free_chain(H_);
+      return sf_err(BX_ERR_HIP, hipGetErrorString(e));
+    }
+  }
+  c.rn = c.nkp + m;
+  c.rwin = c.rn + m;
+  c.plan = c.rwin + m;
+  c.topar = c.plan + m;
+  c.max_frames = max_frames;
+  return BX_OK;
+}
+
+int bx_sof_apply_chain(void* h, int n, int H, int W, int channels, const uint8_t* frames,
+                       const int32_t* streams, const int64_t* dst, const bx_sof_params* params,
+                       double* warps, int32_t* code, int32_t* n_keypoints, int32_t* n_tracked,
+                       int32_t* n_inliers, void* hip_stream) {
+  SofHandle* H_ = (SofHandle*)h;
+  Lv lv;
+  int rc = check_chain_args(H_, n, H, W, channels, params, &lv);
+  if (rc != BX_OK) return rc;
+  if (n == 0) return BX_OK;
+  if (!frames || !streams || !warps || !code || !n_keypoints || !n_tracked || !n_inliers)
+    return sf_err(BX_ERR_INVALID, "null argument");
+  return launch_chain(H_, n, H, W, channels, frames, streams, dst, *params, lv, warps, code,
+                      n_keypoints, n_tracked, n_inliers, (hipStream_t)hip_stream);
+}
+
+int bx_sof_apply_chain_host(void* h, int n, int H, int W, int channels,
+                            const uint8_t* frames_host, const int32_t* streams_host,
+                            const bx_sof_params* params, double* warps_host, int32_t* code_host,
+                            int32_t* n_keypoints_host, int32_t* n_tracked_host,
+                            int32_t* n_inliers_host, void* hip_stream) {
+  SofHandle* H_ = (SofHandle*)h;
+  Lv lv;
+  int rc = check_chain_args(H_, n, H, W, channels, params, &lv);
+  if (rc != BX_OK) return rc;
+  if (n == 0) return BX_OK;
+  if (!frames_host || !streams_host || !warps_host || !code_host || !n_keypoints_host ||
+      !n_tracked_host || !n_inliers_host)
+    return sf_err(BX_ERR_INVALID, "null argument");
+  const int S = H_->d.n_streams;
+  std::vector<char> seen(S, 0);
+  for (int k = 0; k < n; k++) {
+    const int s = streams_host[k];
+    if (s < 0 || s >= S) return sf_err(BX_ERR_INVALID, "stream index out of range");
+    if (seen[s] && streams_host[k - 1] != s)
+      return sf_err(BX_ERR_INVALID, "the frames of a stream are not adjacent");
+    seen[s] = 1;
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t fb = (size_t)n * H * W * channels;
+  if (fb > H_->sframes_bytes) {
+    BX_HIPCHK(hipStreamSynchronize(st));
+    if (H_->sframes) (void)hipFree(H_->sframes);
+    H_->sframes = nullptr;
+    H_->sframes_bytes = 0;
+    BX_HIPCHK(hipMalloc(&H_->sframes, fb));
+    H_->sframes_bytes = fb;
+  }
+  BX_HIPCHK(hipMemcpyAsync(H_->sframes, frames_host, fb, hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemcpyAsync(H_->cstreams, streams_host, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  const size_t m = (size_t)H_->c.max_frames;
+  int32_t* ci = H_->cints;
+  rc = launch_chain(H_, n, H, W, channels, H_->sframes, H_->cstreams, nullptr, *params, lv,
+                    H_->cwarps, ci, ci + m, ci + 2 * m, ci + 3 * m, st);
+  if (rc != BX_OK) return rc;
+  BX_HIPCHK(hipMemcpyAsync(warps_host, H_->cwarps, (size_t)n * 48, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(code_host, ci, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(n_keypoints_host, ci + m, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(n_tracked_host, ci + 2 * m, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipMemcpyAsync(n_inliers_host, ci + 3 * m, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
   return BX_OK;
 }
 

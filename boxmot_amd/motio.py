@@ -269,7 +269,8 @@ _ECC_KEYS = ("warp_mode", "eps", "max_iter", "scale", "chunk")
 def _check_warp_args(tracker_type: str, tracker_kwargs: dict, n_classes: int, warps, images,
                      cmc):
     """The refusals of run_sequences' warps / images / cmc that need no sequence, no engine and
-    no device; returns warp_table's keyword arguments (None without ``images``)."""
+    no device; returns warp_table's keyword arguments, or ``{"sof": instance}`` for a SOF
+    instance (None without ``images``)."""
     if warps is None and images is None:
         if cmc is not None:
             raise ValueError("cmc names how warps are computed from images: give images too")
@@ -291,11 +292,17 @@ def _check_warp_args(tracker_type: str, tracker_kwargs: dict, n_classes: int, wa
     if warps is not None:
         raise ValueError("give images (with cmc) or warps, not both")
     if cmc is None:
-        raise ValueError('images need cmc: "ecc" or a dict of ECC settings')
-    if cmc == "ecc":
+        raise ValueError('images need cmc: "ecc", a dict of ECC settings or a SOF instance')
+    from . import cmc as M
+
+    if isinstance(cmc, M.SOF):
+        cmc._params()  # SOF's own refusals (min_distance, block_size, ranges)
+        return {"sof": cmc}
+    if isinstance(cmc, str) and cmc == "ecc":
         return {}
     if not isinstance(cmc, dict) or set(cmc) - set(_ECC_KEYS):
-        raise ValueError(f'cmc must be "ecc" or a dict with keys among {", ".join(_ECC_KEYS)}')
+        raise ValueError(f'cmc must be "ecc", a dict with keys among {", ".join(_ECC_KEYS)} or '
+                         "a boxmot_amd.SOF instance")
     return dict(cmc)
 
 
@@ -321,7 +328,10 @@ def _flow_warps(names, seqs, fids, F: int, warps, images, ecc_kw):
         for nm, m in zip(names, stepped):
             if not callable(images[nm]) and len(images[nm]) != m.size:
                 raise ValueError(f"{nm}: {len(images[nm])} images for {m.size} iterated frames")
-        tab = M.warp_table([images[nm] for nm in names], stepped, **ecc_kw)
+        if "sof" in ecc_kw:
+            tab = M.sof_warp_table([images[nm] for nm in names], stepped, sof=ecc_kw["sof"])
+        else:
+            tab = M.warp_table([images[nm] for nm in names], stepped, **ecc_kw)
         try:
             return tab.warps.to(dtype=_torch().float32).to(dtype=_torch().float64).contiguous()
         finally:
@@ -380,7 +390,12 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
     from ``SofBatch``.
     images, cmc: name -> the sequence's images (``cmc.warp_table``'s array or callable), and
     ``"ecc"`` or a dict of ECC settings (warp_mode, eps, max_iter, scale, chunk): the flow derives
-    the stepped frames, builds the table with ``cmc.warp_table``, runs and closes it.
+    the stepped frames, builds the table with ``cmc.warp_table``, runs and closes it.  A
+    ``boxmot_amd.SOF`` instance as ``cmc`` means what a drop-in with ``tracker.cmc = SOF(...)``
+    does (the reference's DeepOCSort default): the table comes from ``cmc.sof_warp_table`` with
+    the instance's settings; the instance itself is neither run nor changed, and its own refusals
+    (``min_distance`` above 1, ``block_size`` other than 3, ranges) are raised first.  The string
+    ``"sof"`` is not accepted.
     Every warp reaches the engine rounded to float32, the type the reference's ``cmc.apply``
     returns and the drop-ins pass on.  ValueError, before anything is built: a tracker outside
     WARP_TRACKERS, a per_class run, ``images`` without ``cmc`` or with ``warps``, a table or an

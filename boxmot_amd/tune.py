@@ -269,7 +269,9 @@ def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
     ``warps`` (deepocsort only): what ``run_sequences(warps=...)`` takes, a ``cmc.WarpTable`` over
     these sequences or a mapping name -> ``[n_frames, 6]``; rounded to float32 as there, and every
     config's copy of a sequence gets that sequence's warp (the ``[T, K*S, 6]`` table is built once
-    on the device).
+    on the device).  ``cmc.sof_warp_table(images, stepped, sof=SOF(...))`` returns such a table:
+    with it the sweep runs the reference's default DeepOCSort, whose camera-motion estimator is
+    sparse optical flow.
 
     Raised before any engine is built: ``NotImplementedError`` for another tracker, ``per_class``
     in a config or HybridSort's ``use_byte=True``; ``ValueError`` for caps or ``embedding_off``

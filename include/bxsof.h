@@ -136,6 +136,55 @@ int bx_sof_apply_host(void *h, int n, int H, int W, int channels, const uint8_t 
                       const int32_t *streams_host, const bx_sof_params *params,
                       double *warps_host, int32_t *code_host, int32_t *n_keypoints_host,
                       int32_t *n_tracked_host, int32_t *n_inliers_host, void *hip_stream);
+/* ---- the chained apply: many consecutive frames of a camera per call.
+ *
+ * Scratch for max_frames <= BX_SOF_MAX_STREAMS frames per call on an existing handle: per frame a
+ * slot with what a stream holds while one frame is in flight: a pyramid (bx_sof_pyramid_bytes,
+ * about 4/3 max_h * max_w), the lambda plane and the candidate scratch (max_h * max_w * 20 bytes),
+ * the keypoints with their count and a tracking record (BX_SOF_MAX_CORNERS * 54 bytes), 28 bytes
+ * of scalars: max_h * max_w * 21.4 + 55 324 bytes per slot, and 68 bytes of staging for the host
+ * entry.  Idempotent; a larger max_frames grows the scratch (waiting for the device first), a
+ * smaller one changes nothing.  The slots carry nothing from one call to the next.
+ * BX_ERR_INVALID for max_frames out of range. */
+int bx_sof_chain_reserve(void *h, int max_frames);
+
+/* n <= max_frames frames of one H x W in one call, all launches on hip_stream, no host
+ * synchronisation.
+ *   frames      device [n][H][W][channels] uint8, as bx_sof_apply
+ *   streams     device [n] int32: the stream of each frame.  A stream may repeat: its frames are
+ *               adjacent in the call and in time order, so a stream forms at most one group per
+ *               call.  A stream listed in two separate groups (0,1,0) is undefined behaviour (the
+ *               results and the state of that stream are garbage; the accesses stay in bounds).
+ *   dst         device [n] int64 or null: the row of the five result arrays that frame i writes
+ *               (null: row i).  The caller sizes the arrays for the rows it names.
+ *   warps       device [.][6] float64; code, n_keypoints, n_tracked, n_inliers [.] int32: row
+ *               dst[i] holds frame i's result, with the meanings of bx_sof_apply; other rows are
+ *               untouched
+ * Frame i is tracked from frame i - 1 of the call when streams[i - 1] == streams[i], otherwise
+ * from the stored state of its stream: a first frame if there is none, and also (with BX_ERR_SHAPE
+ * latched) if its working size or level count is another, with bx_sof_apply's codes.  After the
+ * call each listed stream's state (previous pyramid, size, level count, keypoints, lambda plane,
+ * tracking record, whether it has a previous frame) is that of its last frame in the call.  The
+ * five results and the final state, as bx_sof_state_host and bx_sof_points_host show it, are bit
+ * for bit those of n successive bx_sof_apply calls of one frame each; this includes a frame
+ * without a corner that keeps the tracked points, a first frame without a corner, and runs of
+ * them anywhere in a call.
+ * BX_ERR_CAPACITY (nothing launched, state unchanged): n > max_frames reserved or a working image
+ * larger than max_h x max_w.  BX_ERR_INVALID: as bx_sof_apply.  A stream index out of range
+ * skips that frame (its rows are untouched) and latches BX_ERR_INVALID in bx_sof_status. */
+int bx_sof_apply_chain(void *h, int n, int H, int W, int channels, const uint8_t *frames,
+                       const int32_t *streams, const int64_t *dst, const bx_sof_params *params,
+                       double *warps, int32_t *code, int32_t *n_keypoints, int32_t *n_tracked,
+                       int32_t *n_inliers, void *hip_stream);
+/* The same from host arrays: stages the frames, runs, copies the n result rows back (row i is
+ * frame i) and synchronises once.  Also BX_ERR_INVALID (nothing launched) for a stream index out
+ * of range or a stream whose frames are not adjacent. */
+int bx_sof_apply_chain_host(void *h, int n, int H, int W, int channels,
+                            const uint8_t *frames_host, const int32_t *streams_host,
+                            const bx_sof_params *params, double *warps_host, int32_t *code_host,
+                            int32_t *n_keypoints_host, int32_t *n_tracked_host,
+                            int32_t *n_inliers_host, void *hip_stream);
+
 /* Latched device-side status (BX_OK, BX_ERR_INVALID or BX_ERR_SHAPE); synchronises. */
 int bx_sof_status(void *h, int *status);
 /* Bytes of one stream's pyramid buffer (the levels one after another, level 0 first). */
