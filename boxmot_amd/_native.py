@@ -169,6 +169,16 @@ class BxOcsortSeqParams(C.Structure):
     ]
 
 
+class BxEngineSeqParams(C.Structure):
+    _fields_ = [
+        ("min_conf", C.c_double), ("track_thresh", C.c_double),
+        ("track_high_thresh", C.c_double), ("track_low_thresh", C.c_double),
+        ("new_track_thresh", C.c_double), ("proximity_thresh", C.c_double),
+        ("appearance_thresh", C.c_double), ("fuse_first_associate", C.c_int32),
+        ("match_thresh", C.c_double), ("track_buffer", C.c_int32), ("frame_rate", C.c_int32),
+    ]
+
+
 class BxBoostConfig(C.Structure):
     _fields_ = [
         ("n_seq", C.c_int32), ("track_cap", C.c_int32), ("det_cap", C.c_int32),
@@ -258,6 +268,7 @@ EXPORTS = [
     "bx_engine_force_assoc_build", "bx_legacy_lap_pair", "bx_engine_set_early_features",
     "bx_engine_inputs_released", "bx_engine_set_cosine_mode", "bx_engine_embdist_host",
     "bx_engine_copy_state", "bx_engine_slots_used_host", "bx_ocsort_copy_state",
+    "bx_engine_set_seq_params_host", "bx_engine_seq_params_host",
     "bx_boost_copy_state", "bx_ss_copy_state",
     "bx_nn_cosine_distance", "bx_ocsort_create", "bx_ocsort_destroy", "bx_ocsort_reset", "bx_ocsort_step",
     "bx_ocsort_update_host", "bx_ocsort_status", "bx_ocsort_counters_host",
@@ -363,6 +374,9 @@ _SIGS = {
     "bx_engine_set_cosine_mode": ([_vp, C.c_int], C.c_int),
     "bx_engine_embdist_host": ([_vp, C.c_int, C.c_int, _vp, _vp, _ip], C.c_int),
     "bx_engine_copy_state": ([_vp, _vp], C.c_int),
+    "bx_engine_set_seq_params_host": ([_vp, C.c_int, C.c_int, C.POINTER(BxEngineSeqParams), _vp],
+                                      C.c_int),
+    "bx_engine_seq_params_host": ([_vp, C.c_int, C.POINTER(BxEngineSeqParams)], C.c_int),
     "bx_ocsort_copy_state": ([_vp, _vp], C.c_int),
     "bx_boost_copy_state": ([_vp, _vp], C.c_int),
     "bx_ss_copy_state": ([_vp, _vp], C.c_int),

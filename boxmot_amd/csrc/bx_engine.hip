@@ -178,6 +178,13 @@ int set_err(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+// One sequence's parameters, resolved as bx_engine_create resolves bx_config into Dev.
+struct SeqPar {
+  double low, high, new_thresh, match_thresh, prox, app;
+  int fuse_first, max_time_lost;
+  int set, pad_;  // set: this sequence runs on its own values, else on the engine's
+};
+static_assert(sizeof(SeqPar) == 64, "one table entry is one 64-byte line");
 // Device-side view of an engine (passed by value to every kernel).
 struct Dev {
   int S, T, D, F, kind, emb_f64, with_reid, fuse_first, max_time_lost, elds;
@@ -218,7 +225,24 @@ struct Dev {
   void* fscr;         // [S][D][F] frame scratch for F > REG_F only: twice-normalised det rows
   int* status;        // [1] latched engine status
   unsigned long long* dbg;  // [S][32] phase stamps (diagnostic builds only, else null)
+  const SeqPar* seqpar;  // [S] per-sequence parameters (bx_engine_set_seq_params_host),
+                                // null until the first set
 };
+// Kernel entry of the table builds (TAB; launch_frame picks them only for an engine with a table):
+// sequence s's own values over the kernel's copy of P.  s is block-uniform and the kernels never
+// write the table, so these are scalar loads, once per workgroup.  Without TAB nothing is emitted.
+template <bool TAB>
+__device__ __forceinline__ void seq_override(Dev& P, int s) {
+  if constexpr (TAB) {
+    const SeqPar* __restrict__ t = P.seqpar;
+    if (t && t[s].set) {
+      const SeqPar q = t[s];
+      P.low = q.low; P.high = q.high; P.new_thresh = q.new_thresh;
+      P.match_thresh = q.match_thresh; P.prox = q.prox; P.app = q.app;
+      P.fuse_first = q.fuse_first; P.max_time_lost = q.max_time_lost;
+    }
+  }
+}
 
 // Diagnostic phase stamps (build with -DBX_PHASE_TIMING; never in the shipped library).
 constexpr int BX_DBG_STRIDE = 64;  // stamps + counters per sequence
@@ -371,13 +395,14 @@ __device__ __forceinline__ void det_measurement(const float* r, double* meas) {
 constexpr int K1_DETS = BX_K1_DETS;
 // FC: the feature width when it is a compile-time constant (REG_F: bounds tests and per-element
 // addressing fold away, measured ~1/3 of the row's VALU instructions), else 0 (P.F).
-template <typename FT, bool NPF, int FC>
+template <typename FT, bool NPF, int FC, bool TAB>
 __global__ __launch_bounds__(WG) void det_feature_kernel(Dev P, int seq0,
                                                          const float* __restrict__ dets,
                                                          const int* __restrict__ det_off,
                                                          const FT* __restrict__ embs) {
   __shared__ __align__(16) float s_w[NWAVE * REG_FP];
   const int b = blockIdx.x, s = seq0 + b, w = wave_id(), lane = lane_id();
+  seq_override<TAB>(P, s);  // high
   const int F = FC ? FC : P.F, D = P.D;
   const int d0 = det_off[b], N = min(det_off[b + 1] - d0, D);
   const int k0 = blockIdx.y * K1_DETS, k1 = min(k0 + K1_DETS, N);
@@ -445,11 +470,12 @@ __global__ __launch_bounds__(WG) void det_feature_kernel(Dev P, int seq0,
 #endif
 constexpr int GATE_BLOCKS = BX_GATE_BLOCKS;
 constexpr int GATE_SPLIT = BX_GATE_SPLIT;  // threads per track, each over every SPLIT-th detection
-template <int KIND>
+template <int KIND, bool TAB>
 __global__ __launch_bounds__(WG) void gate_kernel(Dev P, int seq0, const float* __restrict__ dets,
                                                   const int* __restrict__ det_off) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int b = blockIdx.x, s = seq0 + b, T = P.T, D = P.D;
+  seq_override<TAB>(P, s);  // high, prox
   double* s_db = (double*)smem;                             // [D][4]
   float4* s_fb = (float4*)(smem + sizeof(double) * 4 * D);  // [D], x1 = NaN if not high
   const int d0 = det_off[b], N = min(det_off[b + 1] - d0, D);
@@ -546,10 +572,11 @@ __device__ __forceinline__ void load4(const FT* p, FT* v) {
 // RegRow::div's test of one product: RN32(p) is the correctly rounded quotient
 __device__ __forceinline__ bool div32_fast(double p) { return fabs(p) >= 0x1p-125 || p == 0.0; }
 // float32 rows.  Registers for 4 waves per SIMD (114 VGPRs, no scratch), as before.
-template <int FC>
+template <int FC, bool TAB>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void cosine_kernel(Dev P, int seq0, const int* __restrict__ det_off, const float* __restrict__ embs) {
   using FT = float;
+  seq_override<TAB>(P, seq0 + blockIdx.x);  // app (cos_finish)
   constexpr int KR = COS_P / 8;  // row pieces per lane on each side (A: tracks, B: detections)
   __shared__ __attribute__((aligned(16))) float s_ab[NWAVE][2][2][COS_PS];  // [wave][A|B][parity]
   const int b = blockIdx.x, s = seq0 + b, T = P.T, D = P.D, F = FC ? FC : P.F, w = wave_id(),
@@ -679,9 +706,10 @@ void cosine_kernel(Dev P, int seq0, const int* __restrict__ det_off, const float
 // on every element, the chains on the lower 32 lanes reading the interleaved image dword by
 // dword.  122 VGPRs, no scratch, 4 waves per SIMD; the chunk-verdict kernel above needs 128 + spills
 // for fp64 rows, and no benchmark covers them, so they stay here.
-template <typename FT, int FC>
+template <typename FT, int FC, bool TAB>
 __global__ __launch_bounds__(WG) void cosine_kernel_f64(Dev P, int seq0, const int* __restrict__ det_off,
                                                     const FT* __restrict__ embs) {
+  seq_override<TAB>(P, seq0 + blockIdx.x);  // app (cos_finish)
   constexpr int KR = COS_P / 8;  // row pieces per lane on each side (A: tracks, B: detections)
   // row stride COS_CH + 2: the 32 chain lanes (pair p, parity) read banks 2p + parity
   static_assert(sizeof(FT) == 8, "float32 rows take cosine_kernel");
@@ -757,17 +785,18 @@ __global__ __launch_bounds__(WG) void cosine_kernel_f64(Dev P, int seq0, const i
   }
 }
 
-template <typename FT, int FC>
+template <typename FT, int FC, bool TAB>
 constexpr auto cosine_rows_kernel() {
-  if constexpr (sizeof(FT) == 4) return &cosine_kernel<FC>;
-  else return &cosine_kernel_f64<FT, FC>;
+  if constexpr (sizeof(FT) == 4) return &cosine_kernel<FC, TAB>;
+  else return &cosine_kernel_f64<FT, FC, TAB>;
 }
 
 // any F: thread per pair, element by element (same arithmetic as above)
-template <typename FT>
+template <typename FT, bool TAB>
 __global__ __launch_bounds__(WG) void cosine_kernel_any(Dev P, int seq0,
                                                         const int* __restrict__ det_off,
                                                         const FT* __restrict__ embs) {
+  seq_override<TAB>(P, seq0 + blockIdx.x);  // app (cos_finish)
   const int b = blockIdx.x, s = seq0 + b, T = P.T, D = P.D, F = P.F;
   const int np = P.npair[s];
   const uint32_t* pairs = P.pairs + (size_t)s * T * D;
@@ -970,10 +999,11 @@ __global__ __launch_bounds__(WG) void materialize_kernel(Dev P, int s) {
 // HELP: the LAP's wave solver on the helper waves 1..3 (crowded scenes); without it the
 // components for the wave solver run on wave 0 after its lanes (the host picks the build from the
 // LAPs' marks, DESIGN §2.3: the helper machinery costs an uncrowded frame ~2.5 us of K3)
-template <int KIND, bool HELP>
+template <int KIND, bool HELP, bool TAB>
 __global__ __launch_bounds__(WG) void assoc_kernel(Dev P, int seq0, const float* __restrict__ dets,
                                                    const int* __restrict__ det_off) {
   extern __shared__ __align__(16) unsigned char smem[];
+  seq_override<TAB>(P, seq0 + blockIdx.x);  // every parameter field
   const int T = P.T, D = P.D;
   const LdsA Lo(T, D, P.elds);
   uint16_t* s_act = (uint16_t*)(smem + Lo.o_act);
@@ -1991,6 +2021,11 @@ struct bx_engine {
   int* h_coff = nullptr;
   int* h_ccnt = nullptr;
   double* h_cwarp = nullptr;  // [C][6] the class calls' warps
+  // per-sequence parameters (bx_engine_set_seq_params_host): the device table dev.seqpar points
+  // to, allocated by the first set, and its host mirror with the values as they were given
+  SeqPar* d_seqpar = nullptr;
+  std::vector<SeqPar> h_seqpar;
+  std::vector<bx_engine_seq_params> h_seqgiven;
 };
 
 namespace {
@@ -2016,7 +2051,9 @@ size_t park_npark_off(const bx_engine* e) {
 }
 
 // One frame of sequences [seq0, seq0+nseq): the K1..K6 pipeline on stream st.
-template <int KIND, typename FT, bool NPF>
+// TAB: the kernels that read tracker parameters in their table build (seq_override), picked by
+// launch_frame_sel iff the engine has a table.
+template <int KIND, typename FT, bool NPF, bool TAB>
 int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int* det_off,
                  const void* embs, const double* warps, double* out, int* out_count,
                  hipStream_t st) {
@@ -2089,13 +2126,14 @@ int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int*
   const bool fc5 = NPF && d.F == REG_F && (BX_FC_MASK & 2);
   if (reid && fc)
     BX_PROBED_ON(BX_STAGE_DET_FEATURES, k1st,
-                 hipLaunchKernelGGL((det_feature_kernel<FT, NPF, (NPF ? REG_F : 0)>),
+                 hipLaunchKernelGGL((det_feature_kernel<FT, NPF, (NPF ? REG_F : 0), TAB>),
                                     dim3(nseq, gy_det64), dim3(WG), 0, k1st, d, seq0, dets,
                                     det_off, (const FT*)embs));
   else if (reid)
     BX_PROBED_ON(BX_STAGE_DET_FEATURES, k1st,
-                 hipLaunchKernelGGL((det_feature_kernel<FT, NPF, 0>), dim3(nseq, gy_det64),
-                                    dim3(WG), 0, k1st, d, seq0, dets, det_off, (const FT*)embs));
+                 hipLaunchKernelGGL((det_feature_kernel<FT, NPF, 0, TAB>), dim3(nseq, gy_det64),
+                                    dim3(WG), 0, k1st, d, seq0, dets, det_off,
+                                    (const FT*)embs));
   if (early) BX_HIPCHK(hipEventRecord(e->ev_k1, e->k1s));
   if (gmc)
     BX_PROBED(BX_STAGE_PREDICT,
@@ -2108,28 +2146,28 @@ int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int*
   if (reid) {
     const size_t glds = (sizeof(double) * 4 + sizeof(float4)) * d.D;  // det boxes in LDS
     BX_PROBED(BX_STAGE_GATE,
-              hipLaunchKernelGGL(gate_kernel<KIND>, dim3(nseq, GATE_BLOCKS), dim3(WG), glds, st,
-                                 d, seq0, dets, det_off));
+              hipLaunchKernelGGL((gate_kernel<KIND, TAB>), dim3(nseq, GATE_BLOCKS), dim3(WG), glds,
+                                 st, d, seq0, dets, det_off));
     // K1c reads K1's norms and the smooth features the last K5 wrote (overlap mode: unjoined)
     if (early) BX_HIPCHK(hipStreamWaitEvent(st, e->ev_k1, 0));
     if (!early || e->side_pending)
       if (int rc = join(0)) return rc;
     if (e->cos_mode == 1)
       BX_PROBED(BX_STAGE_COSINE,
-                hipLaunchKernelGGL(cosine_kernel_any<FT>, dim3(nseq, COS_BLOCKS), dim3(WG), 0, st,
-                                   d, seq0, det_off, (const FT*)embs));
+                hipLaunchKernelGGL((cosine_kernel_any<FT, TAB>), dim3(nseq, COS_BLOCKS), dim3(WG), 0,
+                                   st, d, seq0, det_off, (const FT*)embs));
     else if (d.F == REG_F && (BX_FC_MASK & 4))
       BX_PROBED(BX_STAGE_COSINE,
-                hipLaunchKernelGGL((cosine_rows_kernel<FT, REG_F>()), dim3(nseq, COS_BLOCKS), dim3(WG),
+                hipLaunchKernelGGL((cosine_rows_kernel<FT, REG_F, TAB>()), dim3(nseq, COS_BLOCKS), dim3(WG),
                                    0, st, d, seq0, det_off, (const FT*)embs));
     else if (d.F % COS_CH == 0)
       BX_PROBED(BX_STAGE_COSINE,
-                hipLaunchKernelGGL((cosine_rows_kernel<FT, 0>()), dim3(nseq, COS_BLOCKS), dim3(WG), 0,
+                hipLaunchKernelGGL((cosine_rows_kernel<FT, 0, TAB>()), dim3(nseq, COS_BLOCKS), dim3(WG), 0,
                                    st, d, seq0, det_off, (const FT*)embs));
     else
       BX_PROBED(BX_STAGE_COSINE,
-                hipLaunchKernelGGL(cosine_kernel_any<FT>, dim3(nseq, COS_BLOCKS), dim3(WG), 0, st,
-                                   d, seq0, det_off, (const FT*)embs));
+                hipLaunchKernelGGL((cosine_kernel_any<FT, TAB>), dim3(nseq, COS_BLOCKS), dim3(WG), 0,
+                                   st, d, seq0, det_off, (const FT*)embs));
   }
   // the helper-wave build while LAPs that want it were seen in the last BX_HELP_WINDOW launches
 #ifndef BX_HELP_WINDOW
@@ -2140,7 +2178,7 @@ int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int*
                         ? e->force_help != 0
                         : e->h_lapmark && (uint32_t)(e->nlaunch - (uint32_t)*(volatile int*)
                                                          e->h_lapmark) <= BX_HELP_WINDOW;
-  auto assoc = help ? assoc_kernel<KIND, true> : assoc_kernel<KIND, false>;
+  auto assoc = help ? assoc_kernel<KIND, true, TAB> : assoc_kernel<KIND, false, TAB>;
   if (int rc = lds_attr((const void*)assoc, e->lds_assoc)) return rc;
   BX_PROBED(BX_STAGE_ASSOC, hipLaunchKernelGGL(assoc, dim3(nseq), dim3(WG), e->lds_assoc, st, d,
                                                seq0, dets, det_off));
@@ -2184,6 +2222,16 @@ int launch_frame(bx_engine* e, int seq0, int nseq, const float* dets, const int*
 #undef BX_PROBED
 #undef BX_PROBED_ON
   return BX_OK;
+}
+
+template <int KIND, typename FT, bool NPF>
+int launch_frame_sel(bx_engine* e, int seq0, int nseq, const float* dets, const int* det_off,
+                     const void* embs, const double* warps, double* out, int* out_count,
+                     hipStream_t st) {
+  return e->dev.seqpar ? launch_frame<KIND, FT, NPF, true>(e, seq0, nseq, dets, det_off, embs,
+                                                           warps, out, out_count, st)
+                       : launch_frame<KIND, FT, NPF, false>(e, seq0, nseq, dets, det_off, embs,
+                                                            warps, out, out_count, st);
 }
 
 }  // namespace
@@ -2323,6 +2371,7 @@ int bx_engine_create(const bx_config* cfg, bx_engine** out) {
       return set_err(BX_ERR_HIP, "hipMalloc of the engine arena failed");
     layout((char*)e->arena);
     d.dbg = nullptr;
+    d.seqpar = nullptr;
 #ifdef BX_PHASE_TIMING
     BX_HIPCHK(hipMalloc(&d.dbg, sizeof(unsigned long long) * BX_DBG_STRIDE * S));
     BX_HIPCHK(hipMemset(d.dbg, 0, sizeof(unsigned long long) * BX_DBG_STRIDE * S));
@@ -2382,6 +2431,7 @@ int bx_engine_destroy(bx_engine* e) {
   (void)hipFree(e->h_coff);
   (void)hipFree(e->h_ccnt);
   (void)hipFree(e->h_cwarp);
+  (void)hipFree(e->d_seqpar);
   delete e;
   return BX_OK;
 }
@@ -2413,17 +2463,17 @@ int bx_engine_step(bx_engine* e, int seq0, int nseq, const float* dets, const in
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   e->cache_seq = -1;
   if (e->dev.kind == BX_BYTETRACK)
-    return launch_frame<KIND_BYTE, float, true>(e, seq0, nseq, dets, det_off, embs, warps, out,
+    return launch_frame_sel<KIND_BYTE, float, true>(e, seq0, nseq, dets, det_off, embs, warps, out,
                                                 out_count, st);
   const bool npf = np_wave_exact(e->dev.F);
   if (e->dev.emb_f64)
-    return npf ? launch_frame<KIND_BOT, double, true>(e, seq0, nseq, dets, det_off, embs, warps,
+    return npf ? launch_frame_sel<KIND_BOT, double, true>(e, seq0, nseq, dets, det_off, embs, warps,
                                                       out, out_count, st)
-               : launch_frame<KIND_BOT, double, false>(e, seq0, nseq, dets, det_off, embs, warps,
+               : launch_frame_sel<KIND_BOT, double, false>(e, seq0, nseq, dets, det_off, embs, warps,
                                                        out, out_count, st);
-  return npf ? launch_frame<KIND_BOT, float, true>(e, seq0, nseq, dets, det_off, embs, warps, out,
+  return npf ? launch_frame_sel<KIND_BOT, float, true>(e, seq0, nseq, dets, det_off, embs, warps, out,
                                                    out_count, st)
-             : launch_frame<KIND_BOT, float, false>(e, seq0, nseq, dets, det_off, embs, warps,
+             : launch_frame_sel<KIND_BOT, float, false>(e, seq0, nseq, dets, det_off, embs, warps,
                                                     out, out_count, st);
 }
 
@@ -2869,6 +2919,78 @@ int bx_engine_embdist_host(bx_engine* e, int seq, int cap, uint32_t* pairs_out, 
       return set_err(BX_ERR_INVALID, "bx_engine_embdist_host: pair word out of range");
     dist_out[i] = tab[slot * d.D + dk];
   }
+  return BX_OK;
+}
+
+int bx_engine_set_seq_params_host(bx_engine* e, int seq0, int nseq,
+                                  const bx_engine_seq_params* params_host, void* stream) {
+  if (!e || seq0 < 0 || nseq < 0 || seq0 > e->dev.S - nseq)
+    return set_err(BX_ERR_INVALID, "bad sequence range");
+  for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
+    if (params_host[k].track_buffer < 0)
+      return set_err(BX_ERR_INVALID, "track_buffer must not be negative");
+    if (params_host[k].frame_rate <= 0)
+      return set_err(BX_ERR_INVALID, "frame_rate must be positive");
+  }
+  if (int rc = settle(e)) return rc;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (e->k1s) BX_HIPCHK(hipStreamSynchronize(e->k1s));
+  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
+  hipStream_t st = (hipStream_t)stream;
+  const size_t S = e->dev.S;
+  if (!e->d_seqpar) {
+    if (hipMalloc(&e->d_seqpar, S * sizeof(SeqPar)) != hipSuccess) {
+      e->d_seqpar = nullptr;
+      return set_err(BX_ERR_HIP, "hipMalloc of the engine's parameter table failed");
+    }
+    BX_HIPCHK(hipMemset(e->d_seqpar, 0, S * sizeof(SeqPar)));
+    e->h_seqpar.assign(S, SeqPar{});
+    e->h_seqgiven.assign(S, bx_engine_seq_params{});
+    e->dev.seqpar = e->d_seqpar;
+  }
+  const bool byte = e->dev.kind == BX_BYTETRACK;
+  for (int k = 0; k < nseq; k++) {
+    SeqPar& d = e->h_seqpar[seq0 + k];
+    d = SeqPar{};
+    if (!params_host) continue;
+    const bx_engine_seq_params& p = params_host[k];
+    e->h_seqgiven[seq0 + k] = p;
+    // as bx_engine_create resolves bx_config
+    d.match_thresh = p.match_thresh;
+    d.max_time_lost = (int)(p.frame_rate / 30.0 * p.track_buffer);
+    if (byte) {
+      d.low = p.min_conf; d.high = p.track_thresh; d.new_thresh = p.track_thresh;
+    } else {
+      d.low = p.track_low_thresh; d.high = p.track_high_thresh;
+      d.new_thresh = p.new_track_thresh;
+    }
+    d.prox = p.proximity_thresh;
+    d.app = p.appearance_thresh;
+    d.fuse_first = p.fuse_first_associate;
+    d.set = 1;
+  }
+  BX_HIPCHK(hipMemcpyAsync(e->d_seqpar + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(SeqPar),
+                           hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
+  return BX_OK;
+}
+
+int bx_engine_seq_params_host(bx_engine* e, int seq, bx_engine_seq_params* out_host) {
+  if (!e || seq < 0 || seq >= e->dev.S || !out_host)
+    return set_err(BX_ERR_INVALID, "bad arguments to bx_engine_seq_params_host");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!e->h_seqpar.empty() && e->h_seqpar[seq].set) {
+    *out_host = e->h_seqgiven[seq];
+    return BX_OK;
+  }
+  const bx_config& c = e->cfg;
+  bx_engine_seq_params o;
+  o.min_conf = c.min_conf; o.track_thresh = c.track_thresh;
+  o.track_high_thresh = c.track_high_thresh; o.track_low_thresh = c.track_low_thresh;
+  o.new_track_thresh = c.new_track_thresh; o.proximity_thresh = c.proximity_thresh;
+  o.appearance_thresh = c.appearance_thresh; o.fuse_first_associate = c.fuse_first_associate;
+  o.match_thresh = c.match_thresh; o.track_buffer = c.track_buffer; o.frame_rate = c.frame_rate;
+  *out_host = o;
   return BX_OK;
 }
 

@@ -380,6 +380,76 @@ class Engine(_NativeEngine):
 
 
 
+class TableEngine(Engine):
+    """An ``Engine`` whose sequences may each run on parameters of their own
+    (``bx_engine_set_seq_params_host``, include/bxassoc.h): the engine of a ByteTrack / BoT-SORT
+    hyper-parameter sweep, K configs x S sequences as K*S sequences of one handle
+    (boxmot_amd.tune.sweep_bot).  ``with_reid``, the capacities and the embedding width stay the
+    engine's."""
+
+    def __init__(self, kind: str, n_seq: int = 1, track_cap: int = 1024, det_cap: int = 384,
+                 emb_dim: int = 0, emb_f64: bool = False, params: EngineParams | None = None):
+        super().__init__(kind, n_seq, track_cap, det_cap, emb_dim, emb_f64, params)
+        self._seq_over = {}  # sequence -> its own EngineParams, for grown()
+
+    def grown(self, track_cap: int, det_cap: int) -> "TableEngine":
+        """As Engine.grown; bx_engine_copy_state carries tracks only, so the table is set again
+        on the new engine."""
+        e = TableEngine(self.kind, self.n_seq, track_cap, det_cap, self.emb_dim, self.emb_f64,
+                        self.params)
+        N.check(self._L.bx_engine_copy_state(e._h, self._h), "bx_engine_copy_state")
+        if self._overlap:
+            e.set_overlap(True)
+        for k, p in sorted(self._seq_over.items()):
+            e.set_seq_params(k, [p])
+        return e
+
+    def _seq_struct(self, p: EngineParams):
+        tb = p.track_buffer
+        if tb is None:  # the tracker's own default, as Engine.__init__ resolves it
+            tb = 25 if self.kind == "bytetrack" else 30
+        return N.BxEngineSeqParams(
+            min_conf=p.min_conf, track_thresh=p.track_thresh,
+            track_high_thresh=p.track_high_thresh, track_low_thresh=p.track_low_thresh,
+            new_track_thresh=p.new_track_thresh, proximity_thresh=p.proximity_thresh,
+            appearance_thresh=p.appearance_thresh,
+            fuse_first_associate=int(bool(p.fuse_first_associate)),
+            match_thresh=p.match_thresh, track_buffer=int(tb), frame_rate=int(p.frame_rate))
+
+    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
+        """Give sequences [seq0, seq0 + len(params)) parameters of their own
+        (bx_engine_set_seq_params_host): ``params`` is a list of EngineParams, whose ``with_reid``
+        is not part of the table.  ``None`` clears the override of ``nseq`` sequences from seq0
+        (default: all from seq0).  For use between sequences, at frame 0."""
+        if params is None:
+            n = self.n_seq - seq0 if nseq is None else nseq
+            arr = None
+        else:
+            n = len(params)
+            arr = (N.BxEngineSeqParams * max(n, 1))(*[self._seq_struct(p) for p in params])
+        N.check(self._L.bx_engine_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
+                "bx_engine_set_seq_params_host")
+        for k in range(n):
+            if params is None:
+                self._seq_over.pop(seq0 + k, None)
+            else:
+                self._seq_over[seq0 + k] = params[k]
+
+    def seq_params(self, seq: int) -> EngineParams:
+        """The parameters sequence ``seq`` runs on (bx_engine_seq_params_host): its own when set,
+        else the engine's; ``with_reid`` is the engine's."""
+        o = N.BxEngineSeqParams()
+        N.check(self._L.bx_engine_seq_params_host(self._h, int(seq), C.byref(o)),
+                "bx_engine_seq_params_host")
+        return EngineParams(
+            min_conf=o.min_conf, track_thresh=o.track_thresh, match_thresh=o.match_thresh,
+            track_buffer=o.track_buffer, frame_rate=o.frame_rate,
+            track_high_thresh=o.track_high_thresh, track_low_thresh=o.track_low_thresh,
+            new_track_thresh=o.new_track_thresh, proximity_thresh=o.proximity_thresh,
+            appearance_thresh=o.appearance_thresh,
+            fuse_first_associate=bool(o.fuse_first_associate), with_reid=self.params.with_reid)
+
+
 def _class_warps(warp, n_classes: int):
     """Per-class-call warps as the C ABI takes them: [n_classes][6] float64 or None."""
     if warp is None:

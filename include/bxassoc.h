@@ -186,6 +186,35 @@ int bx_engine_set_cosine_mode(bx_engine *e, int mode);
 int bx_engine_embdist_host(bx_engine *e, int seq, int cap, uint32_t *pairs_out, double *dist_out,
                            int *n_out);
 
+/* Per-sequence parameters (a hyper-parameter sweep: K configs x S sequences as K*S sequences of
+ * one engine; boxmot_amd.tune.sweep_bot).  The names and meaning of bx_config's. */
+typedef struct {
+    /* ByteTrack engines read these */
+    double min_conf, track_thresh;
+    /* BoT-SORT engines read these */
+    double track_high_thresh, track_low_thresh, new_track_thresh;
+    double proximity_thresh, appearance_thresh;
+    int32_t fuse_first_associate;
+    /* both */
+    double match_thresh;
+    int32_t track_buffer, frame_rate;
+} bx_engine_seq_params;
+/* Give sequences [seq0, seq0+nseq) parameters of their own: params_host [nseq], mapped by the
+ * engine's kind exactly as bx_engine_create maps bx_config (ByteTrack: low = min_conf, high = new
+ * = track_thresh; BoT-SORT: the three thresholds, proximity, appearance, fuse_first_associate;
+ * both: match_thresh and max_time_lost = (int)(frame_rate / 30.0 * track_buffer), derived per
+ * sequence).  NULL clears the range: those sequences run on the engine's values again.  A
+ * negative track_buffer, a frame_rate <= 0 or a bad range is BX_ERR_INVALID and changes nothing
+ * (bx_engine_create refuses nothing else about these fields either).  kind, n_seq, the capacities, emb_dim, emb_f64 and with_reid stay engine-wide.
+ * The first set allocates the device table; an engine on which none was ever set launches the
+ * kernels built without the table.  bx_engine_reset keeps the table, bx_engine_copy_state does
+ * not copy it.  Settles overlap mode and synchronises the engine's streams and `stream`. */
+int bx_engine_set_seq_params_host(bx_engine *e, int seq0, int nseq,
+                                  const bx_engine_seq_params *params_host, void *stream);
+/* The parameters sequence `seq` runs on (host mirror, no device work): its own when set, else the
+ * engine's. */
+int bx_engine_seq_params_host(bx_engine *e, int seq, bx_engine_seq_params *out_host);
+
 /* Capacity growth (the reference's track lists are unbounded: bytetrack.py:272-346): copy every
  * sequence's tracker state of `src` into `dst`, a fresh engine with the same kind, sequences and
  * features and track_cap / det_cap at least src's (slot ids stay valid; per_class parked lists
