@@ -42,7 +42,7 @@ HIPCC_FLAGS = [
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
            "bx_strongsort.hip", "bx_deepocsort.hip", "bx_hybridsort.hip", "bx_gsi.hip", "bx_feed.hip",
            "bx_classes.hip", "bx_eval.hip", "bx_cmc.hip", "bx_reid.hip", "bx_sof.hip",
-           "bx_io.cpp"]
+           "bx_io.cpp", "bx_boost_tab.hip"]
 
 
 class NativeUnavailable(RuntimeError):
@@ -192,6 +192,18 @@ class BxBoostConfig(C.Structure):
     ]
 
 
+class BxBoostSeqParams(C.Structure):
+    _fields_ = [
+        ("max_age", C.c_int32), ("min_hits", C.c_int32),
+        ("det_thresh", C.c_double), ("iou_threshold", C.c_double), ("min_box_area", C.c_double),
+        ("aspect_ratio_thresh", C.c_double), ("lambda_iou", C.c_double),
+        ("lambda_mhd", C.c_double), ("lambda_shape", C.c_double), ("dlo_boost_coef", C.c_double),
+        ("use_ecc", C.c_int32), ("use_dlo_boost", C.c_int32), ("use_duo_boost", C.c_int32),
+        ("s_sim_corr", C.c_int32), ("use_rich_s", C.c_int32), ("use_sb", C.c_int32),
+        ("use_vt", C.c_int32),
+    ]
+
+
 class BxDeepocConfig(C.Structure):
     _fields_ = [
         ("n_seq", C.c_int32), ("track_cap", C.c_int32), ("det_cap", C.c_int32),
@@ -270,6 +282,7 @@ EXPORTS = [
     "bx_engine_copy_state", "bx_engine_slots_used_host", "bx_ocsort_copy_state",
     "bx_engine_set_seq_params_host", "bx_engine_seq_params_host",
     "bx_boost_copy_state", "bx_ss_copy_state",
+    "bx_boost_set_seq_params_host", "bx_boost_seq_params_host",
     "bx_nn_cosine_distance", "bx_ocsort_create", "bx_ocsort_destroy", "bx_ocsort_reset", "bx_ocsort_step",
     "bx_ocsort_update_host", "bx_ocsort_status", "bx_ocsort_counters_host",
     "bx_ocsort_set_id_count", "bx_ocsort_set_frame_size", "bx_ocsort_tracks_host", "bx_ocsort_probe", "bx_ocsort_probe_read",
@@ -379,6 +392,9 @@ _SIGS = {
     "bx_engine_seq_params_host": ([_vp, C.c_int, C.POINTER(BxEngineSeqParams)], C.c_int),
     "bx_ocsort_copy_state": ([_vp, _vp], C.c_int),
     "bx_boost_copy_state": ([_vp, _vp], C.c_int),
+    "bx_boost_set_seq_params_host": ([_vp, C.c_int, C.c_int, C.POINTER(BxBoostSeqParams), _vp],
+                                     C.c_int),
+    "bx_boost_seq_params_host": ([_vp, C.c_int, C.POINTER(BxBoostSeqParams)], C.c_int),
     "bx_ss_copy_state": ([_vp, _vp], C.c_int),
     "bx_engine_slots_used_host": ([_vp, C.c_int, _ip], C.c_int),
     "bx_lapjv": ([_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp], C.c_int),

@@ -35,6 +35,13 @@
 
 using namespace bx;
 
+// the table build's entry points (bx_boost_tab.hip)
+int bx_boost_tab_lds_attr(size_t lds);
+void bx_boost_tab_launch(const void* dev, int nseq, int threads, size_t lds, hipStream_t st,
+                         int seq0, const float* dets, const int* off, const double* warps,
+                         double* out, int* cnt);
+
+
 
 namespace {
 
@@ -51,6 +58,16 @@ struct BstTrk {
   double conf, cls, det_ind;
   int id, tsu, hit_streak, age;
 };
+
+// One sequence's parameters (bx_boost_set_seq_params_host), as bx_boost_create resolves
+// bx_boost_config into BstDev.
+struct BstSeqPar {
+  double det_thresh, iou_thr, min_box_area, ar_thresh, l_iou, l_mhd, l_shape, dlo_coef;
+  int max_age, min_hits, use_ecc, use_dlo, use_duo, s_sim_corr, rich_s, use_sb, use_vt;
+  int set;  // this sequence runs on its own values, else on the engine's
+  int pad_[6];
+};
+static_assert(sizeof(BstSeqPar) == 128, "one table entry is two 64-byte lines");
 
 struct BstDev {
   int S, T, D, N, F;
@@ -71,7 +88,27 @@ struct BstDev {
   const double* conf_tab; // [ntab] 0.9 ** k (get_confidence)
   int* status;
   unsigned long long* dbg;  // [S][BST_DBG] phase stamps (diagnostic builds only, else null)
+  const BstSeqPar* seqpar;  // [S] per-sequence parameters, null until the first set
 };
+// Entry of the frame kernel's table build (TAB; launch picks it only for an engine with a table):
+// sequence s's own values over the kernel's copy of g.  s is block-uniform, the loads come before
+// any store and the kernel never writes the table, so these are scalar loads, once per workgroup.
+// Without TAB nothing is emitted.  cost_lds, tb_lds and the capacities are never overridden, and
+// ntab / conf_tab are the engine's (the host keeps ntab >= max(max_age) + 8 over all entries).
+template <bool TAB>
+__device__ __forceinline__ void seq_override(BstDev& g, int s) {
+  if constexpr (TAB) {
+    const BstSeqPar* __restrict__ t = g.seqpar;
+    if (t && t[s].set) {
+      const BstSeqPar q = t[s];
+      g.det_thresh = q.det_thresh; g.iou_thr = q.iou_thr; g.min_box_area = q.min_box_area;
+      g.ar_thresh = q.ar_thresh; g.l_iou = q.l_iou; g.l_mhd = q.l_mhd; g.l_shape = q.l_shape;
+      g.dlo_coef = q.dlo_coef; g.max_age = q.max_age; g.min_hits = q.min_hits;
+      g.use_ecc = q.use_ecc; g.use_dlo = q.use_dlo; g.use_duo = q.use_duo;
+      g.s_sim_corr = q.s_sim_corr; g.rich_s = q.rich_s; g.use_sb = q.use_sb; g.use_vt = q.use_vt;
+    }
+  }
+}
 
 // Diagnostic phase stamps and counters (build with -DBX_PHASE_TIMING; never shipped): per
 // sequence, cycles accumulated per phase over all frames [0, 16), event counters [16, 24) and
@@ -394,11 +431,15 @@ __host__ __device__ constexpr int frame_threads(int nseq) {
 }
 constexpr int COST_KR = 4;  // cost entries per thread per chunk (registers held across a barrier)
 
+// TAB: the build for an engine with a per-sequence parameter table (seq_override); every use of a
+// parameter below reads g after the override, so the flags are block-uniform branches.
+template <bool TAB>
 __global__ void __launch_bounds__(BW)
     boost_frame_kernel(BstDev g, int seq0, const float* __restrict__ dets,
                        const int* __restrict__ det_off, const double* __restrict__ warps,
                        double* __restrict__ out, int* __restrict__ out_count) {
   extern __shared__ __align__(16) char lds_raw[];
+  seq_override<TAB>(g, seq0 + (int)blockIdx.x);
   BstLds L;
   carve(g, lds_raw, L);
   const int tid = threadIdx.x, lane = tid & 63, nth = blockDim.x;
@@ -918,6 +959,27 @@ __global__ void __launch_bounds__(BW)
   }
 }
 
+// The table build lives in a translation unit of its own (bx_boost_tab.hip, which includes this
+// file with BX_BOOST_TAB_UNIT defined and compiles it up to here): this unit's code object then
+// holds the kernels it held before the table build existed, at the same sizes, and an engine
+// without a table runs code whose placement does not depend on the table build (DESIGN 2.23 has
+// the bench.py figures of the layouts tried).
+#ifdef BX_BOOST_TAB_UNIT
+}  // namespace
+
+int bx_boost_tab_lds_attr(size_t lds) {
+  return (int)bx_lds_attr((const void*)boost_frame_kernel<true>, lds);
+}
+void bx_boost_tab_launch(const void* dev, int nseq, int threads, size_t lds, hipStream_t st,
+                         int seq0, const float* dets, const int* off, const double* warps,
+                         double* out, int* cnt) {
+  hipLaunchKernelGGL(boost_frame_kernel<true>, dim3(nseq), dim3(threads), lds, st,
+                     *(const BstDev*)dev, seq0, dets, off, warps, out, cnt);
+}
+#else
+template __global__ void boost_frame_kernel<false>(BstDev, int, const float*, const int*,
+                                                   const double*, double*, int*);
+
 // ------------------------------------------------------------------------------------------
 // dets_embs @ trk_embs.T (boosttrack.py:274-281) for every detection x live track of a
 // sequence, on the fp64 matrix cores: the tile of bx_embtile.h (shared with DeepOCSort), grid
@@ -1077,6 +1139,14 @@ struct bx_boost {
   int* h_hold = nullptr;
   double* h_cwarp = nullptr;  // [C][6] the class calls' warps
   BxProbe probe;  // stages: 0 embcost, 1 frame, 2 feature
+  // per-sequence parameters (bx_boost_set_seq_params_host): the device table dev.seqpar points
+  // to, allocated by the first set, and its host mirror with the values as they were given
+  BstSeqPar* d_seqpar = nullptr;
+  std::vector<BstSeqPar> h_seqpar;
+  std::vector<bx_boost_seq_params> h_seqgiven;
+  double* d_tab = nullptr;  // get_confidence's table once an entry's max_age outgrew the arena's
+  double* d_eg = nullptr;   // the DLO numerators' spill when only a table entry needs it
+  bool need_g = false;      // D * T entries do not fit cost_lds (the HBM workspace layout)
 };
 
 static int launch(bx_boost* e, int seq0, int nseq, const float* dets, const int* off,
@@ -1092,7 +1162,13 @@ static int launch(bx_boost* e, int seq0, int nseq, const float* dets, const int*
     if ((rc = e->probe.end(0, st))) return rc;
   }
   if ((rc = e->probe.begin(1, st))) return rc;
-  hipLaunchKernelGGL(boost_frame_kernel, dim3(nseq), dim3(frame_threads(nseq)), e->lds, st, d, seq0, dets, off,
+  // the table build for an engine with a table: a sequence's own use_ecc decides there, so the
+  // warps go in whatever the engine's is
+  if (d.seqpar)
+    bx_boost_tab_launch(&d, nseq, frame_threads(nseq), e->lds, st, seq0, dets, off, warps, out,
+                        cnt);
+  else
+    hipLaunchKernelGGL(boost_frame_kernel<false>, dim3(nseq), dim3(frame_threads(nseq)), e->lds, st, d, seq0, dets, off,
                      d.use_ecc ? warps : nullptr, out, cnt);
   BX_HIPCHK(hipGetLastError());
   if ((rc = e->probe.end(1, st))) return rc;
@@ -1214,7 +1290,10 @@ int bx_boost_create(const bx_boost_config* c, bx_boost** out) {
     d.dbg = nullptr;
 #endif
     BX_HIPCHK(hipMemcpy(base + o_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-    BX_HIPCHK(bx_lds_attr((const void*)boost_frame_kernel, e->lds));
+    d.seqpar = nullptr;
+    e->need_g = need_g;
+    BX_HIPCHK(bx_lds_attr((const void*)boost_frame_kernel<false>, e->lds));
+    BX_HIPCHK((hipError_t)bx_boost_tab_lds_attr(e->lds));
     return e->sg.alloc(sizeof(float) * 6 * D, sizeof(double) * D * F, 8, 8, d.D, SQB);
   };
   const int rc = fill();
@@ -1249,6 +1328,143 @@ int bx_boost_copy_state(bx_boost* dst, bx_boost* src) {
   return BX_OK;
 }
 
+int bx_boost_set_seq_params_host(bx_boost* e, int seq0, int nseq,
+                                 const bx_boost_seq_params* params_host, void* stream) {
+  if (!e || seq0 < 0 || nseq < 0 || seq0 > e->dev.S - nseq)
+    return bx_record_error(BX_ERR_INVALID, "bad sequence range");
+  int top_age = 0;
+  bool want_eg = false;
+  for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
+    const bx_boost_seq_params& p = params_host[k];
+    if (p.max_age < 0 || p.max_age > 100000)  // (bx_boost_create's limit)
+      return bx_record_error(BX_ERR_INVALID, "max_age out of range");
+    if (p.min_hits < 0) return bx_record_error(BX_ERR_INVALID, "min_hits must not be negative");
+    top_age = p.max_age > top_age ? p.max_age : top_age;
+    want_eg = want_eg || (p.use_dlo_boost != 0 && p.use_rich_s != 0);
+  }
+  // frames in flight on any stream read the table, get_confidence's table and BstDev by value
+  BX_HIPCHK(hipDeviceSynchronize());
+  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
+  hipStream_t st = (hipStream_t)stream;
+  BstDev& d = e->dev;
+  const size_t S = d.S;
+  // everything that can fail before anything becomes visible
+  double* tab_new = nullptr;
+  const int ntab_new = top_age + 8;
+  if (params_host && ntab_new > d.ntab) {
+    // get_confidence reads conf_tab[min(k, ntab - 1)], k up to max_age: a longer table, from the
+    // same host pow as bx_boost_create's so that the shared indices hold the same bits
+    std::vector<double> tab(ntab_new);
+    for (int k = 0; k < ntab_new; k++) tab[k] = std::pow(0.9, (double)k);
+    if (hipMalloc(&tab_new, tab.size() * sizeof(double)) != hipSuccess)
+      return bx_record_error(BX_ERR_HIP, "hipMalloc of the confidence table failed");
+    if (hipMemcpy(tab_new, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) !=
+        hipSuccess) {
+      (void)hipFree(tab_new);
+      return bx_record_error(BX_ERR_HIP, "copy of the confidence table failed");
+    }
+  }
+  // the DLO numerators spill to e_g when D * T entries do not fit LDS; bx_boost_create allocates
+  // it only for an engine whose own use_dlo_boost and use_rich_s are on
+  double* eg_new = nullptr;
+  if (want_eg && e->need_g && !d.e_g) {
+    const size_t bytes = S * d.D * d.T * sizeof(double);
+    if (hipMalloc(&eg_new, bytes) != hipSuccess || hipMemset(eg_new, 0, bytes) != hipSuccess) {
+      (void)hipFree(eg_new);
+      (void)hipFree(tab_new);
+      return bx_record_error(BX_ERR_HIP, "hipMalloc of the DLO workspace failed");
+    }
+  }
+  // the entries, as bx_boost_create resolves bx_boost_config, staged beside the mirror
+  std::vector<BstSeqPar> stage(nseq, BstSeqPar{});
+  for (int k = 0; params_host && k < nseq; k++) {
+    const bx_boost_seq_params& p = params_host[k];
+    BstSeqPar& q = stage[k];
+    q.det_thresh = p.det_thresh;
+    q.iou_thr = p.iou_threshold;
+    q.min_box_area = p.min_box_area;
+    q.ar_thresh = p.aspect_ratio_thresh;
+    q.l_iou = p.lambda_iou;
+    q.l_mhd = p.lambda_mhd;
+    q.l_shape = p.lambda_shape;
+    q.dlo_coef = p.dlo_boost_coef;
+    q.max_age = p.max_age;
+    q.min_hits = p.min_hits;
+    q.use_ecc = p.use_ecc != 0;
+    q.use_dlo = p.use_dlo_boost != 0;
+    q.use_duo = p.use_duo_boost != 0;
+    q.s_sim_corr = p.s_sim_corr != 0;
+    q.rich_s = p.use_rich_s != 0;
+    q.use_sb = p.use_sb != 0;
+    q.use_vt = p.use_vt != 0;
+    q.set = 1;
+  }
+  BstSeqPar* tbl = e->d_seqpar;
+  const bool first = !tbl;
+  bool ok = true;
+  if (first)
+    ok = hipMalloc(&tbl, S * sizeof(BstSeqPar)) == hipSuccess &&
+         hipMemset(tbl, 0, S * sizeof(BstSeqPar)) == hipSuccess;
+  ok = ok && hipMemcpyAsync(tbl + seq0, stage.data(), nseq * sizeof(BstSeqPar),
+                            hipMemcpyHostToDevice, st) == hipSuccess &&
+       hipStreamSynchronize(st) == hipSuccess;
+  if (!ok) {
+    // nothing was committed: the mirror, BstDev and the launches' build are as they were; an
+    // existing table gets the mirror's entries back
+    if (first)
+      (void)hipFree(tbl);
+    else
+      (void)hipMemcpy(tbl + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(BstSeqPar),
+                      hipMemcpyHostToDevice);
+    (void)hipFree(eg_new);
+    (void)hipFree(tab_new);
+    return bx_record_error(BX_ERR_HIP, "allocation or copy of the parameter table failed");
+  }
+  // commit: the device holds the entries
+  if (first) {
+    e->d_seqpar = tbl;
+    e->h_seqpar.assign(S, BstSeqPar{});
+    e->h_seqgiven.assign(S, bx_boost_seq_params{});
+  }
+  for (int k = 0; k < nseq; k++) {
+    e->h_seqpar[seq0 + k] = stage[k];
+    if (params_host) e->h_seqgiven[seq0 + k] = params_host[k];
+  }
+  if (tab_new) {
+    (void)hipFree(e->d_tab);  // (the device is idle)
+    e->d_tab = tab_new;
+    d.conf_tab = tab_new;
+    d.ntab = ntab_new;
+  }
+  if (eg_new) {
+    e->d_eg = eg_new;
+    d.e_g = eg_new;
+  }
+  d.seqpar = e->d_seqpar;
+  return BX_OK;
+}
+
+int bx_boost_seq_params_host(bx_boost* e, int seq, bx_boost_seq_params* out_host) {
+  if (!e || seq < 0 || seq >= e->dev.S || !out_host)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_boost_seq_params_host");
+  if (!e->h_seqpar.empty() && e->h_seqpar[seq].set) {
+    *out_host = e->h_seqgiven[seq];
+    return BX_OK;
+  }
+  const bx_boost_config& c = e->cfg;
+  bx_boost_seq_params o;
+  o.max_age = c.max_age; o.min_hits = c.min_hits;
+  o.det_thresh = c.det_thresh; o.iou_threshold = c.iou_threshold;
+  o.min_box_area = c.min_box_area; o.aspect_ratio_thresh = c.aspect_ratio_thresh;
+  o.lambda_iou = c.lambda_iou; o.lambda_mhd = c.lambda_mhd; o.lambda_shape = c.lambda_shape;
+  o.dlo_boost_coef = c.dlo_boost_coef;
+  o.use_ecc = c.use_ecc; o.use_dlo_boost = c.use_dlo_boost; o.use_duo_boost = c.use_duo_boost;
+  o.s_sim_corr = c.s_sim_corr; o.use_rich_s = c.use_rich_s; o.use_sb = c.use_sb;
+  o.use_vt = c.use_vt;
+  *out_host = o;
+  return BX_OK;
+}
+
 int bx_boost_destroy(bx_boost* e) {
   if (!e) return BX_OK;
   e->probe.destroy();
@@ -1258,6 +1474,9 @@ int bx_boost_destroy(bx_boost* e) {
   (void)hipFree(e->h_ccnt);
   (void)hipFree(e->h_hold);
   (void)hipFree(e->h_cwarp);
+  (void)hipFree(e->d_seqpar);
+  (void)hipFree(e->d_tab);
+  (void)hipFree(e->d_eg);
   delete e;
   return BX_OK;
 }
@@ -1563,3 +1782,5 @@ int bx_boost_probe_read(bx_boost* e, double* total_ms, int* count) {
 }
 
 }  // extern "C"
+
+#endif  // BX_BOOST_TAB_UNIT

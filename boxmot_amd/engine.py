@@ -1513,6 +1513,77 @@ class BoostEngine(_TrackListEngine):
     STAGES = ["embcost", "frame", "feature"]
 
 
+class BoostTableEngine(BoostEngine):
+    """A ``BoostEngine`` whose sequences may each run on parameters of their own
+    (``bx_boost_set_seq_params_host``, include/bxboost.h): the engine of a BoostTrack
+    hyper-parameter sweep, K configs x S sequences as K*S sequences of one handle
+    (boxmot_amd.tune.sweep_boost), or of cameras with thresholds and track lifetimes of their
+    own.  ``with_reid``, the capacities and the embedding width stay the engine's.  (A class of
+    its own because BoostEngine's method set is pinned by tests/test_engine_api_host.py.)"""
+
+    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
+                 emb_dim: int = 0, params: BoostParams | None = None):
+        super().__init__(n_seq, track_cap, det_cap, emb_dim, params)
+        self._seq_over = {}  # sequence -> its own BoostParams, for grown()
+
+    def grown(self, track_cap: int, det_cap: int) -> "BoostTableEngine":
+        """As BoostEngine.grown; bx_boost_copy_state carries tracks only, so the table is set
+        again on the new engine."""
+        e = BoostTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim or 0, self.params)
+        N.check(self._L.bx_boost_copy_state(e._h, self._h), "bx_boost_copy_state")
+        for k, p in sorted(self._seq_over.items()):
+            e.set_seq_params(k, [p])
+        return e
+
+    def _seq_struct(self, p: BoostParams):
+        if bool(p.with_reid) != bool(self.params.with_reid):
+            raise ValueError("with_reid is engine-wide: a sequence cannot have its own")
+        return N.BxBoostSeqParams(
+            max_age=int(p.max_age), min_hits=int(p.min_hits), det_thresh=float(p.det_thresh),
+            iou_threshold=float(p.iou_threshold), min_box_area=float(p.min_box_area),
+            aspect_ratio_thresh=float(p.aspect_ratio_thresh), lambda_iou=float(p.lambda_iou),
+            lambda_mhd=float(p.lambda_mhd), lambda_shape=float(p.lambda_shape),
+            dlo_boost_coef=float(p.dlo_boost_coef), use_ecc=int(bool(p.use_ecc)),
+            use_dlo_boost=int(bool(p.use_dlo_boost)), use_duo_boost=int(bool(p.use_duo_boost)),
+            s_sim_corr=int(bool(p.s_sim_corr)), use_rich_s=int(bool(p.use_rich_s)),
+            use_sb=int(bool(p.use_sb)), use_vt=int(bool(p.use_vt)))
+
+    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
+        """Give sequences [seq0, seq0 + len(params)) parameters of their own
+        (bx_boost_set_seq_params_host): ``params`` is a list of BoostParams, whose ``with_reid``
+        must be the engine's (``ValueError``).  ``None`` clears the override of ``nseq`` sequences
+        from seq0 (default: all from seq0).  For use between sequences, at frame 0."""
+        if params is None:
+            n = self.n_seq - seq0 if nseq is None else nseq
+            arr = None
+        else:
+            n = len(params)
+            arr = (N.BxBoostSeqParams * max(n, 1))(*[self._seq_struct(p) for p in params])
+        N.check(self._L.bx_boost_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
+                "bx_boost_set_seq_params_host")
+        for k in range(n):
+            if params is None:
+                self._seq_over.pop(seq0 + k, None)
+            else:
+                self._seq_over[seq0 + k] = params[k]
+
+    def seq_params(self, seq: int) -> BoostParams:
+        """The parameters sequence ``seq`` runs on (bx_boost_seq_params_host): its own when set,
+        else the engine's; ``with_reid`` is the engine's."""
+        o = N.BxBoostSeqParams()
+        N.check(self._L.bx_boost_seq_params_host(self._h, int(seq), C.byref(o)),
+                "bx_boost_seq_params_host")
+        return BoostParams(
+            max_age=o.max_age, min_hits=o.min_hits, det_thresh=o.det_thresh,
+            iou_threshold=o.iou_threshold, use_ecc=bool(o.use_ecc), min_box_area=o.min_box_area,
+            aspect_ratio_thresh=o.aspect_ratio_thresh, lambda_iou=o.lambda_iou,
+            lambda_mhd=o.lambda_mhd, lambda_shape=o.lambda_shape,
+            use_dlo_boost=bool(o.use_dlo_boost), use_duo_boost=bool(o.use_duo_boost),
+            dlo_boost_coef=o.dlo_boost_coef, s_sim_corr=bool(o.s_sim_corr),
+            use_rich_s=bool(o.use_rich_s), use_sb=bool(o.use_sb), use_vt=bool(o.use_vt),
+            with_reid=bool(self.params.with_reid))
+
+
 @dataclass
 class SsParams:
     """StrongSort constructor parameters (strongsort.py:45-66 names and defaults)."""

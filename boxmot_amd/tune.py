@@ -12,7 +12,8 @@ Three engines have per-sequence parameters: OCSort (``sweep``; DESIGN.md 2.18 is
 the two appearance trackers of its family, DeepOCSort and HybridSort (``sweep_reid``; DESIGN.md
 2.20), whose K*S sequences read each sequence's detections and embeddings from ONE copy in device
 memory (``engine.SharedSequenceFeeder``).  ByteTrack and BoT-SORT, which share ``bx_engine``, have
-them too (``sweep_bot``), fed the same way.
+them too (``sweep_bot``), fed the same way, and so has BoostTrack
+(``sweep_boost``), whose variants differ in constructor flags only.
 """
 from __future__ import annotations
 
@@ -24,6 +25,7 @@ import numpy as np
 SUPPORTED = ("ocsort",)
 SUPPORTED_REID = ("deepocsort", "hybridsort")  # sweep_reid's trackers
 SUPPORTED_BOT = ("bytetrack", "botsort")       # sweep_bot's trackers
+SUPPORTED_BOOST = ("boosttrack",)              # sweep_boost's tracker
 _CAPS = ("track_cap", "det_cap")
 
 
@@ -402,6 +404,107 @@ def sweep_bot(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
     feed_emb = F if reid else 0
     eng = E.TableEngine(tracker_type, n_seq=K * S, track_cap=resolved[0][1],
                         det_cap=resolved[0][2], emb_dim=feed_emb, emb_f64=True, params=params[0])
+    feed = None
+    try:
+        dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
+        embs = [s.embs if feed_emb else None for s in seqs]
+        for k in range(K):
+            eng.set_seq_params(k * S, [params[k]] * S)
+        none = [None] * ((K - 1) * S)
+        feed = E.SharedSequenceFeeder(dets + none, embs + none, tables * K, feed_emb,
+                                      source=list(range(S)) * K)
+
+        def step(t, run):
+            q0, ns, _, pd, po, pe, pout, pcnt = run
+            eng.step(pd, po, pe if feed_emb else None,
+                     None if table is None else table[t, q0: q0 + ns], pout, pcnt,
+                     seq0=q0, nseq=ns)
+
+        rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
+                                 keep_results)
+    finally:
+        if feed is not None:
+            feed.close()
+        eng.close()
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
+
+
+def _boost_reid(cfg: dict) -> bool:
+    """with_reid as run_sequences("boosttrack", tracker_kwargs=cfg) resolves it: the YAML default
+    (on) for an empty cfg, else the constructor's (off) under cfg."""
+    return bool(cfg.get("with_reid", False)) if cfg else True
+
+
+def _check_boost(configs, sequences, gt, exp_dir, score, keep_results, warps) -> list:
+    """The refusals of ``sweep_boost`` that need no engine and no device."""
+    from . import motio
+
+    configs = _check("boosttrack", configs, sequences, gt, exp_dir, score, keep_results,
+                     supported=SUPPORTED_BOOST, what="tune.sweep_boost")
+    if len({_boost_reid(c) for c in configs}) > 1:
+        raise ValueError("with_reid decides the engine's embedding width and launches: it must "
+                         "resolve to the same value in every config")
+    if warps is not None:
+        for c in configs:  # (use_ecc=False against warps)
+            motio._check_warp_args("boosttrack", c, 0, warps, None, None)
+    return configs
+
+
+def sweep_boost(sequences: dict, configs, *, exp_dir=None, gt: dict | None = None,
+                benchmark: str = "MOT17", seq_lengths: dict | None = None,
+                frame_ids: dict | None = None, score: str = "host", keep_results: bool = True,
+                warps=None) -> list:
+    """``sweep`` for BoostTrack: every config of ``configs`` over every sequence in one
+    ``engine.BoostTableEngine`` of K*S sequences, engine sequence ``k*S + s`` being sequence ``s``
+    under config ``k``.  The variants of the BoostTrack paper (BoostTrack, BoostTrack+,
+    BoostTrack++) are configs: they differ in ``use_rich_s``, ``use_sb``, ``use_vt``,
+    ``use_dlo_boost``, ``use_duo_boost`` and ``s_sim_corr`` only.
+
+    Arguments, return value, scoring and ``keep_results`` as in ``sweep``; each config means what
+    ``run_sequences("boosttrack", ..., tracker_kwargs=cfg)`` makes of it (an empty dict is the
+    YAML's BoostTrack++ with ReID, a non-empty one goes through the drop-in's constructor), and
+    the files under ``exp_dir/<k as 4 digits>/`` are byte-identical to that run's.  The sequences
+    are fed by one ``SharedSequenceFeeder`` with ``source[k*S + s] = s``: detections and (with
+    ReID) float64 embeddings are uploaded and held once per sequence, not once per config.
+
+    ``warps``: what ``run_sequences(warps=...)`` takes, a ``cmc.WarpTable`` over these sequences
+    (``cmc.warp_table`` / ``cmc.sof_warp_table`` return one) or a mapping name ->
+    ``[n_frames, 6]``; rounded to float32 as there, and every config's copy of a sequence gets
+    that sequence's warp.
+
+    Raised before any engine is built: ``NotImplementedError`` for ``per_class`` in a config;
+    ``ValueError`` for caps or ``with_reid`` that differ across configs, ``warps`` with a config
+    that switches ``use_ecc`` off, sequences whose embedding widths differ, and the ``score`` /
+    ``gt`` / ``keep_results`` combinations ``sweep`` refuses.
+    """
+    configs = _check_boost(configs, sequences, gt, exp_dir, score, keep_results, warps)
+    from . import motio
+    from . import engine as E
+
+    names = list(sequences)
+    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
+            for s in sequences.values()]
+    S, K = len(seqs), len(configs)
+    if not S:
+        return [{"config": c, "results": {} if keep_results else None, "summary": None}
+                for c in configs]
+    widths = sorted({int(s.emb_dim) for s in seqs})
+    if len(widths) > 1:
+        raise ValueError(f"the sequences' embedding widths differ ({widths}): one engine has one "
+                         "emb_dim")
+    F = widths[0]
+    fids, tables = _frame_tables(names, seqs, frame_ids)
+    table = None
+    if warps is not None:  # [T, S, 6] as run_sequences builds it, then every config's copy
+        table = motio._flow_warps(names, seqs, fids, F, warps, None, None).repeat(1, K, 1)
+    resolved = [_resolve_reid("boosttrack", F, c) for c in configs]
+    params = [r[0] for r in resolved]
+    if len({bool(p.with_reid) for p in params}) > 1:  # (what _check_boost's reading missed)
+        raise ValueError("with_reid resolves differently across the configs: "
+                         f"{[bool(p.with_reid) for p in params]}")
+    feed_emb = F if params[0].with_reid else 0
+    eng = E.BoostTableEngine(n_seq=K * S, track_cap=resolved[0][1], det_cap=resolved[0][2],
+                             emb_dim=feed_emb, params=params[0])
     feed = None
     try:
         dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]

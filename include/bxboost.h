@@ -101,6 +101,32 @@ int bx_kf_boost_mh_dist(int nd, const double *dets, int nt, const double *x, con
  * sequence's tracker state of `src` into `dst`, a fresh engine with the same configuration and
  * sequences and track_cap / det_cap at least src's (slot ids stay valid).  Synchronous. */
 int bx_boost_copy_state(bx_boost *dst, bx_boost *src);
+/* Per-sequence parameters (a hyper-parameter sweep: K configs x S sequences as K*S sequences of
+ * one engine; boxmot_amd.tune.sweep_boost).  The names and meaning of
+ * bx_boost_config's: every field of it that sizes no memory and picks no launch. */
+typedef struct {
+    int32_t max_age, min_hits;
+    double det_thresh, iou_threshold, min_box_area, aspect_ratio_thresh;
+    double lambda_iou, lambda_mhd, lambda_shape, dlo_boost_coef;
+    int32_t use_ecc, use_dlo_boost, use_duo_boost, s_sim_corr, use_rich_s, use_sb, use_vt;
+} bx_boost_seq_params;
+/* Give sequences [seq0, seq0+nseq) parameters of their own: params_host [nseq], read as
+ * bx_boost_create reads the configuration, the flags as != 0.  NULL clears the range: those
+ * sequences run on the engine's values again.  A bad range, a negative min_hits or a max_age
+ * outside [0, 100000] (bx_boost_create's own limit) is BX_ERR_INVALID and changes nothing.
+ * n_seq, track_cap, det_cap, emb_dim and with_reid stay engine-wide.  The entry of a sequence
+ * applies to bx_boost_step, bx_boost_update_host and every class call of
+ * bx_boost_update_classes_host alike; warps reach a sequence whose own use_ecc is on whatever the
+ * engine's is.  An entry whose max_age is above every earlier one's lengthens get_confidence's
+ * table of 0.9 ** k (max_age + 8 entries) before it becomes visible.  The first set allocates the
+ * device table; an engine on which none was ever set launches the frame kernel built without it.
+ * bx_boost_reset keeps the table, bx_boost_copy_state does not copy it.  Synchronises the device
+ * before the table changes and `stream` after. */
+int bx_boost_set_seq_params_host(bx_boost *e, int seq0, int nseq,
+                                 const bx_boost_seq_params *params_host, void *stream);
+/* The parameters sequence `seq` runs on (host mirror, no device work): its own when set, else the
+ * engine's. */
+int bx_boost_seq_params_host(bx_boost *e, int seq, bx_boost_seq_params *out_host);
 int bx_boost_status(bx_boost *e, int *status);
 int bx_boost_counters_host(bx_boost *e, int seq, int *frame_count, int *id_count, int *n_tracks);
 /* KalmanBoxTracker.count is class-global in the reference (boosttrack.py:50,53-56, never reset
