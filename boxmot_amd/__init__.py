@@ -3,14 +3,14 @@
 Drop-in surface: ``create_tracker``, ``get_tracker_config``, ``ByteTrack``, ``BotSort``, ``OcSort``, ``BoostTrack``, ``StrongSort``, ``DeepOcSort``, ``HybridSort`` (and their per_class forms
 ``DeepOcSortPerClass``, ``HybridSortPerClass``) with the
 reference's ``update(dets, img, embs) -> [M, 8]`` contract.  The numerics run in libbxassoc.so
-(HIP, gfx950); ``boxmot_amd.engine.Engine`` (``TableEngine``: per-sequence parameters) / ``OcsortEngine`` (``OcsortTableEngine``: per-sequence parameters) / ``BoostEngine`` (``BoostTableEngine``: per-sequence parameters) / ``SsEngine`` / ``DeepOcsortEngine`` / ``HybridsortEngine`` expose the batched many-sequence API.
+(HIP, gfx950); ``boxmot_amd.engine.Engine`` (``TableEngine``: per-sequence parameters) / ``OcsortEngine`` (``OcsortTableEngine``: per-sequence parameters) / ``BoostEngine`` (``BoostTableEngine``: per-sequence parameters) / ``SsEngine`` (``SsTableEngine``: per-sequence parameters) / ``DeepOcsortEngine`` / ``HybridsortEngine`` expose the batched many-sequence API.
 ``gsi`` / ``linear_interpolation`` / ``gaussian_smooth`` are the GSI post-processing of MOT result files.
 ``evaluate_mot`` / ``mot_summary`` are the HOTA / CLEAR / Identity evaluation of MOT result files.
 ``ECC`` / ``EccBatch`` / ``SOF`` / ``SofBatch`` / ``get_cmc_method`` are the camera-motion
 compensation from images; ``EccChain`` / ``warp_table`` and ``SofChain`` / ``sof_warp_table`` run
 many consecutive frames of a camera per call, for the many-sequence file flow
 (``motio.run_sequences(images=..., cmc=...)``).
-``tune.grid`` / ``tune.sweep`` run a hyper-parameter sweep (K configs x S sequences) as one batched OCSort engine; ``tune.sweep_reid`` does it for DeepOCSort / HybridSort, ``tune.sweep_bot`` for ByteTrack / BoT-SORT and ``tune.sweep_boost`` for BoostTrack.
+``tune.grid`` / ``tune.sweep`` run a hyper-parameter sweep (K configs x S sequences) as one batched OCSort engine; ``tune.sweep_reid`` does it for DeepOCSort / HybridSort, ``tune.sweep_bot`` for ByteTrack / BoT-SORT, ``tune.sweep_boost`` for BoostTrack and ``tune.sweep_strong`` for StrongSort.
 ``ReidFrontEnd`` / ``crop_batch`` / ``normalize_features`` are the ReID front end around the caller's network.
 """
 from .cmc import (MOTION_AFFINE, MOTION_EUCLIDEAN, MOTION_HOMOGRAPHY, MOTION_TRANSLATION, ECC,

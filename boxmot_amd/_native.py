@@ -42,7 +42,7 @@ HIPCC_FLAGS = [
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
            "bx_strongsort.hip", "bx_deepocsort.hip", "bx_hybridsort.hip", "bx_gsi.hip", "bx_feed.hip",
            "bx_classes.hip", "bx_eval.hip", "bx_cmc.hip", "bx_reid.hip", "bx_sof.hip",
-           "bx_io.cpp", "bx_boost_tab.hip"]
+           "bx_io.cpp", "bx_boost_tab.hip", "bx_strongsort_tab.hip"]
 
 
 class NativeUnavailable(RuntimeError):
@@ -258,6 +258,16 @@ class BxSsConfig(C.Structure):
     ]
 
 
+class BxSsSeqParams(C.Structure):
+    _fields_ = [
+        ("min_conf", C.c_double), ("max_cos_dist", C.c_double), ("max_iou_dist", C.c_double),
+        ("max_age", C.c_int32), ("n_init", C.c_int32), ("nn_budget", C.c_int32),
+        ("mc_lambda", C.c_double), ("ema_alpha", C.c_double), ("conf_thresh_high", C.c_double),
+        ("conf_thresh_low", C.c_double), ("id_preservation_weight", C.c_double),
+        ("crowd_detection", C.c_int32), ("born_confirmed", C.c_int32),
+    ]
+
+
 class BxSofParams(C.Structure):
     _fields_ = [
         ("max_corners", C.c_int32), ("win_size", C.c_int32), ("max_level", C.c_int32),
@@ -283,6 +293,7 @@ EXPORTS = [
     "bx_engine_set_seq_params_host", "bx_engine_seq_params_host",
     "bx_boost_copy_state", "bx_ss_copy_state",
     "bx_boost_set_seq_params_host", "bx_boost_seq_params_host",
+    "bx_ss_set_seq_params_host", "bx_ss_seq_params_host",
     "bx_nn_cosine_distance", "bx_ocsort_create", "bx_ocsort_destroy", "bx_ocsort_reset", "bx_ocsort_step",
     "bx_ocsort_update_host", "bx_ocsort_status", "bx_ocsort_counters_host",
     "bx_ocsort_set_id_count", "bx_ocsort_set_frame_size", "bx_ocsort_tracks_host", "bx_ocsort_probe", "bx_ocsort_probe_read",
@@ -307,7 +318,7 @@ EXPORTS = [
     "bx_deepoc_probe", "bx_deepoc_probe_read", "bx_deepoc_embcost",
     "bx_deepoc_set_seq_params_host", "bx_deepoc_seq_params_host",
     "bx_hybrid_set_seq_params_host", "bx_hybrid_seq_params_host",
-    "bx_feed_create_shared", "bx_feed_device_bytes",
+    "bx_feed_create_shared", "bx_feed_create_shared_fmt", "bx_feed_device_bytes",
     "bx_hybrid_create", "bx_hybrid_destroy", "bx_hybrid_reset", "bx_hybrid_step",
     "bx_hybrid_update_host", "bx_hybrid_copy_state", "bx_hybrid_status",
     "bx_hybrid_counters_host", "bx_hybrid_set_id_count", "bx_hybrid_set_frame_size",
@@ -396,6 +407,8 @@ _SIGS = {
                                      C.c_int),
     "bx_boost_seq_params_host": ([_vp, C.c_int, C.POINTER(BxBoostSeqParams)], C.c_int),
     "bx_ss_copy_state": ([_vp, _vp], C.c_int),
+    "bx_ss_set_seq_params_host": ([_vp, C.c_int, C.c_int, C.POINTER(BxSsSeqParams), _vp], C.c_int),
+    "bx_ss_seq_params_host": ([_vp, C.c_int, C.POINTER(BxSsSeqParams)], C.c_int),
     "bx_engine_slots_used_host": ([_vp, C.c_int, _ip], C.c_int),
     "bx_lapjv": ([_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp], C.c_int),
     "bx_nn_cosine_distance": ([_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp,
@@ -518,6 +531,8 @@ _SIGS = {
                         C.POINTER(C.c_void_p)], C.c_int),
     "bx_feed_create_shared": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp,
                                C.POINTER(C.c_void_p)], C.c_int),
+    "bx_feed_create_shared_fmt": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp,
+                                   C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "bx_feed_device_bytes": ([_vp, C.POINTER(C.c_int64)], C.c_int),
     "bx_feed_destroy": ([_vp], C.c_int),
     "bx_feed_upload_host": ([_vp, C.c_int, _vp, _vp], C.c_int),

@@ -27,6 +27,8 @@
 namespace {
 
 constexpr int FW = 256;  // threads per workgroup of both kernels (4 waves)
+static_assert(BX_FEED_ROW_ALIGN * 48 % 256 == 0 && BX_FEED_ROW_ALIGN * 80 % 256 == 0,
+              "float64 dets and 10-column out rows keep the run regions 256-byte aligned");
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -58,6 +60,7 @@ struct FeedDev {
   const long long* res_base;   // [S + 1]
   long long* res_n;            // [S]
   int* status;
+  double* g_dets64;            // gathered [stage_rows][6] of the float64 mode (g_dets is null)
 };
 
 // detections of sequence k at frame index t (0 past its last frame) and the table entry
@@ -99,6 +102,9 @@ __device__ __forceinline__ void feed_copy(T* __restrict__ dst, const T* __restri
   if (tid == 0 && done < n) dst[done] = src[done];
 }
 
+// F64 (bx_feed_create_shared_fmt's det_f64): the run's dets are written as float64, each value
+// the exact widening of the packed float32 (what numpy's astype(float64) gives)
+template <bool F64>
 __global__ void __launch_bounds__(FW)
 feed_gather_kernel(FeedDev d, int t, int run_first, int n_runs) {
   const int k = blockIdx.x, tid = threadIdx.x;
@@ -124,10 +130,26 @@ feed_gather_kernel(FeedDev d, int t, int run_first, int n_runs) {
   }
   const long long src = d.seq_row0[d.src ? d.src[k] : k] + d.row_start[entry];
   const long long dst = (long long)run.row0 + before;
-  feed_copy<float, f2>(d.g_dets + dst * 6, d.dets + src * 6, (long long)n * 6, tid);
+  if constexpr (F64) {
+    // both sides 8-byte aligned (6 floats a row, 6 doubles a row): a float pair in, a double
+    // pair out
+    const f2* s2 = (const f2*)(d.dets + src * 6);
+    d2* o2 = (d2*)(d.g_dets64 + dst * 6);
+    for (long long i = tid; i < (long long)n * 3; i += FW) {
+      const f2 v = s2[i];
+      d2 w;
+      w.x = (double)v.x;
+      w.y = (double)v.y;
+      o2[i] = w;
+    }
+  } else {
+    feed_copy<float, f2>(d.g_dets + dst * 6, d.dets + src * 6, (long long)n * 6, tid);
+  }
   if (d.F) feed_copy<double, d2>(d.g_embs + dst * d.F, d.embs + src * d.F, (long long)n * d.F, tid);
 }
 
+// OC: columns of the steps' out rows (8, or 10 for StrongSort's, whose first 8 are the same)
+template <int OC>
 __global__ void __launch_bounds__(FW)
 feed_append_kernel(FeedDev d, int t, int run_first, int n_runs) {
   const int k = blockIdx.x, tid = threadIdx.x;
@@ -144,11 +166,11 @@ feed_append_kernel(FeedDev d, int t, int run_first, int n_runs) {
     if (tid == 0) atomicMax(d.status, (int)BX_ERR_CAPACITY);
     return;
   }
-  const double* out = d.g_out + ((long long)run.row0 + d.g_off[run.off0 + (k - run.k0)]) * 8;
+  const double* out = d.g_out + ((long long)run.row0 + d.g_off[run.off0 + (k - run.k0)]) * OC;
   double* res = d.res + (d.res_base[k] + have) * 9;
   const double fid = (double)d.frame_id[entry];
   for (int i = tid; i < c; i += FW) {
-    const double* r8 = out + (long long)i * 8;
+    const double* r8 = out + (long long)i * OC;
     // ops.xyxy2ltwh: [x1, y1, x2 - x1, y2 - y1]; .round() half-to-even; astype(int32)
     const double l = r8[0], tp = r8[1], w = r8[2] - r8[0], h = r8[3] - r8[1];
     double* o = res + (long long)i * 9;
@@ -179,6 +201,7 @@ struct bx_feed {
   std::vector<int> run_rows;  // detections of each run
   long long res_rows = 0;
   std::vector<void*> allocs;
+  int det_f64 = 0, out_cols = 8;  // bx_feed_create_shared_fmt's mode
 };
 
 static void feed_free(bx_feed* f) {
@@ -199,8 +222,10 @@ static int feed_run_of(bx_feed* f, int t, int r, int* idx) {
 static int feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_t* tab_off,
                        const int64_t* row_start, const int32_t* row_cnt, const int32_t* frame_id,
                        const int64_t* res_cap, int guard_rows, const int32_t* src_map,
-                       bx_feed** out) {
+                       int det_f64, int out_cols, bx_feed** out) {
   if (!out || !seq_rows || !tab_off) return bx_record_error(BX_ERR_INVALID, "null argument");
+  if ((det_f64 != 0 && det_f64 != 1) || (out_cols != 8 && out_cols != 10))
+    return bx_record_error(BX_ERR_INVALID, "det_f64 must be 0 or 1 and out_cols 8 or 10");
   if (n_seq <= 0 || emb_dim < 0 || guard_rows < 0)
     return bx_record_error(BX_ERR_INVALID, "n_seq/emb_dim/guard_rows out of range");
   const int S = n_seq;
@@ -232,6 +257,8 @@ static int feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const in
   f->tab_off.assign(tab_off, tab_off + S + 1);
   f->res_base.assign(S + 1, 0);
   if (src_map) f->src.assign(src_map, src_map + S);
+  f->det_f64 = det_f64;
+  f->out_cols = out_cols;
   auto fill = [&]() -> int {
     for (int k = 0; k < S; k++) {
       // only a source sequence owns packed rows; the others read their source's
@@ -311,10 +338,14 @@ static int feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const in
     if ((rc = dev_put((const void**)&d.res_base, f->res_base.data(), sizeof(long long) * (S + 1)))) return rc;
     if ((rc = dev_alloc((void**)&d.dets, sizeof(float) * 6 * R))) return rc;
     if ((rc = dev_alloc((void**)&d.embs, sizeof(double) * emb_dim * R))) return rc;
-    if ((rc = dev_alloc((void**)&d.g_dets, sizeof(float) * 6 * stage_rows))) return rc;
+    if (det_f64) {
+      if ((rc = dev_alloc((void**)&d.g_dets64, sizeof(double) * 6 * stage_rows))) return rc;
+    } else {
+      if ((rc = dev_alloc((void**)&d.g_dets, sizeof(float) * 6 * stage_rows))) return rc;
+    }
     if ((rc = dev_alloc((void**)&d.g_embs, sizeof(double) * emb_dim * stage_rows))) return rc;
     if ((rc = dev_alloc((void**)&d.g_off, sizeof(int) * off_cap))) return rc;
-    if ((rc = dev_alloc((void**)&d.g_out, sizeof(double) * 8 * stage_rows))) return rc;
+    if ((rc = dev_alloc((void**)&d.g_out, sizeof(double) * out_cols * stage_rows))) return rc;
     if ((rc = dev_alloc((void**)&d.g_cnt, sizeof(int) * S))) return rc;
     if ((rc = dev_alloc((void**)&d.res, sizeof(double) * 9 * f->res_rows))) return rc;
     if ((rc = dev_alloc((void**)&d.res_n, sizeof(long long) * S))) return rc;
@@ -341,7 +372,7 @@ int bx_feed_create(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_
                    const int64_t* row_start, const int32_t* row_cnt, const int32_t* frame_id,
                    const int64_t* res_cap, int guard_rows, bx_feed** out) {
   return feed_create(n_seq, emb_dim, seq_rows, tab_off, row_start, row_cnt, frame_id, res_cap,
-                     guard_rows, nullptr, out);
+                     guard_rows, nullptr, 0, 8, out);
 }
 
 int bx_feed_create_shared(int n_seq, int emb_dim, const int64_t* seq_rows, const int64_t* tab_off,
@@ -350,7 +381,17 @@ int bx_feed_create_shared(int n_seq, int emb_dim, const int64_t* seq_rows, const
                           const int32_t* src, bx_feed** out) {
   if (!src || n_seq <= 0) return bx_record_error(BX_ERR_INVALID, "null argument");
   return feed_create(n_seq, emb_dim, seq_rows, tab_off, row_start, row_cnt, frame_id, res_cap,
-                     guard_rows, src, out);
+                     guard_rows, src, 0, 8, out);
+}
+
+int bx_feed_create_shared_fmt(int n_seq, int emb_dim, const int64_t* seq_rows,
+                              const int64_t* tab_off, const int64_t* row_start,
+                              const int32_t* row_cnt, const int32_t* frame_id,
+                              const int64_t* res_cap, int guard_rows, const int32_t* src,
+                              int det_f64, int out_cols, bx_feed** out) {
+  if (!src || n_seq <= 0) return bx_record_error(BX_ERR_INVALID, "null argument");
+  return feed_create(n_seq, emb_dim, seq_rows, tab_off, row_start, row_cnt, frame_id, res_cap,
+                     guard_rows, src, det_f64, out_cols, out);
 }
 
 int bx_feed_device_bytes(bx_feed* f, int64_t* bytes) {
@@ -401,10 +442,12 @@ int bx_feed_run(bx_feed* f, int t, int r, int* seq0, int* nseq, int* rows, void*
   if (seq0) *seq0 = u.k0;
   if (nseq) *nseq = u.k1 - u.k0;
   if (rows) *rows = f->run_rows[i];
-  if (dets) *dets = d.g_dets + (size_t)u.row0 * 6;
+  if (dets)
+    *dets = f->det_f64 ? (void*)(d.g_dets64 + (size_t)u.row0 * 6)
+                       : (void*)(d.g_dets + (size_t)u.row0 * 6);
   if (det_off) *det_off = d.g_off + u.off0;
   if (embs) *embs = f->F ? d.g_embs + (size_t)u.row0 * f->F : nullptr;
-  if (out) *out = d.g_out + (size_t)u.row0 * 8;
+  if (out) *out = d.g_out + (size_t)u.row0 * f->out_cols;
   if (out_count) *out_count = d.g_cnt + u.k0;
   return BX_OK;
 }
@@ -414,7 +457,11 @@ int bx_feed_gather(bx_feed* f, int t, void* stream) {
   if (t < 0 || t >= f->T) return bx_record_error(BX_ERR_INVALID, "frame index out of range");
   const int nr = f->run_off[t + 1] - f->run_off[t];
   if (nr == 0) return BX_OK;
-  hipLaunchKernelGGL(feed_gather_kernel, dim3(f->S), dim3(FW), 0, (hipStream_t)stream, f->dev, t,
+  if (f->det_f64)
+    hipLaunchKernelGGL(feed_gather_kernel<true>, dim3(f->S), dim3(FW), 0, (hipStream_t)stream,
+                       f->dev, t, f->run_off[t], nr);
+  else
+    hipLaunchKernelGGL(feed_gather_kernel<false>, dim3(f->S), dim3(FW), 0, (hipStream_t)stream, f->dev, t,
                      f->run_off[t], nr);
   BX_HIPCHK(hipGetLastError());
   return BX_OK;
@@ -425,7 +472,11 @@ int bx_feed_append(bx_feed* f, int t, void* stream) {
   if (t < 0 || t >= f->T) return bx_record_error(BX_ERR_INVALID, "frame index out of range");
   const int nr = f->run_off[t + 1] - f->run_off[t];
   if (nr == 0) return BX_OK;
-  hipLaunchKernelGGL(feed_append_kernel, dim3(f->S), dim3(FW), 0, (hipStream_t)stream, f->dev, t,
+  if (f->out_cols == 10)
+    hipLaunchKernelGGL(feed_append_kernel<10>, dim3(f->S), dim3(FW), 0, (hipStream_t)stream,
+                       f->dev, t, f->run_off[t], nr);
+  else
+    hipLaunchKernelGGL(feed_append_kernel<8>, dim3(f->S), dim3(FW), 0, (hipStream_t)stream, f->dev, t,
                      f->run_off[t], nr);
   BX_HIPCHK(hipGetLastError());
   return BX_OK;
@@ -465,14 +516,17 @@ int bx_feed_results_device(bx_feed* f, void** res, void** base, void** n, int64_
   return BX_OK;
 }
 
-int bx_feed_read_run_host(bx_feed* f, int t, int r, float* dets, int32_t* det_off, double* embs) {
+int bx_feed_read_run_host(bx_feed* f, int t, int r, void* dets, int32_t* det_off, double* embs) {
   int i, rc;
   if ((rc = feed_run_of(f, t, r, &i))) return rc;
   const Run& u = f->runs[i];
   const FeedDev& d = f->dev;
   const size_t rows = (size_t)f->run_rows[i];
   BX_HIPCHK(hipDeviceSynchronize());
-  if (dets)
+  if (dets && f->det_f64)
+    BX_HIPCHK(hipMemcpy(dets, d.g_dets64 + (size_t)u.row0 * 6, sizeof(double) * 6 * rows,
+                        hipMemcpyDeviceToHost));
+  else if (dets)
     BX_HIPCHK(hipMemcpy(dets, d.g_dets + (size_t)u.row0 * 6, sizeof(float) * 6 * rows,
                    hipMemcpyDeviceToHost));
   if (det_off)
@@ -491,7 +545,8 @@ int bx_feed_write_run_host(bx_feed* f, int t, int r, const double* out, const in
   const Run& u = f->runs[i];
   const FeedDev& d = f->dev;
   BX_HIPCHK(hipDeviceSynchronize());
-  BX_HIPCHK(hipMemcpy(d.g_out + (size_t)u.row0 * 8, out, sizeof(double) * 8 * (size_t)f->run_rows[i],
+  const size_t oc = (size_t)f->out_cols;
+  BX_HIPCHK(hipMemcpy(d.g_out + (size_t)u.row0 * oc, out, sizeof(double) * oc * (size_t)f->run_rows[i],
                  hipMemcpyHostToDevice));
   BX_HIPCHK(hipMemcpy(d.g_cnt + u.k0, out_count, sizeof(int) * (u.k1 - u.k0), hipMemcpyHostToDevice));
   return BX_OK;

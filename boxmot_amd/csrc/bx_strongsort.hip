@@ -51,6 +51,19 @@ using namespace bx;
 
 #include "bx_host.h"
 
+// the table builds' entry points (bx_strongsort_tab.hip): `dev` is the engine's SsDev
+int bx_ss_tab_lds_attr(size_t lds);
+void bx_ss_tab_prep(const void* dev, dim3 grid, hipStream_t st, int seq0, const int* off,
+                    const double* embs, const double* dets);
+void bx_ss_tab_crowd(const void* dev, dim3 grid, size_t lds, hipStream_t st, int seq0);
+void bx_ss_tab_pre(const void* dev, dim3 grid, size_t lds, hipStream_t st, int seq0,
+                   const double* dets, const int* off, const double* warps);
+void bx_ss_tab_cost(const void* dev, dim3 grid, hipStream_t st, int seq0);
+void bx_ss_tab_match(const void* dev, dim3 grid, size_t lds, hipStream_t st, int seq0);
+void bx_ss_tab_post(const void* dev, dim3 grid, size_t lds, hipStream_t st, int seq0,
+                    const int* off, double* out, int* cnt);
+void bx_ss_tab_reset(const void* dev, dim3 grid, hipStream_t st, int seq0, int nseq);
+
 namespace {
 
 #include "bx_jv.h"
@@ -86,6 +99,18 @@ enum {
   Q_NNCTR,  // ss_nn_kernel's work counters, one per XCD (zeroed by ss_prep_kernel's pack block)
   SQS = Q_NNCTR + 8
 };
+
+// One sequence's parameters (bx_ss_set_seq_params_host), as bx_ss_create resolves bx_ss_config
+// into SsDev.  max_age, budget and max_cos are seeds of the sequence's adapted state (Q_MAXAGE,
+// Q_BUDGET, sqd): the set call and ss_reset_kernel write them there, the frame kernels never read
+// them from here.
+struct SsSeqPar {
+  double min_conf, max_iou, mc_lambda, ema_alpha, thi, tlo, idw, max_cos;
+  int n_init, crowd, born, max_age, budget;
+  int set;  // this sequence runs on its own values, else on the engine's
+  int pad_[10];
+};
+static_assert(sizeof(SsSeqPar) == 128, "one table entry is two 64-byte lines");
 
 struct SsDev {
   int S, T, D, F, VP, GB, N;
@@ -133,7 +158,25 @@ struct SsDev {
   int lsap_fast;  // 1: LSAPs solved then certified (scipy's order only on a tie); 0: scipy's order
   int* status;
   unsigned long long* dbg;  // [S][SS_DBG] phase stamps (diagnostic builds only, else null)
+  const SsSeqPar* seqpar;   // [S] per-sequence parameters, null until the first set
 };
+// Entry of a kernel's table build (TAB; ss_launch picks it only for an engine with a table):
+// sequence s's own values over the kernel's copy of g.  s is workgroup-uniform, the loads come
+// before any store and no kernel writes the table, so these are scalar loads, once per workgroup.
+// Without TAB nothing is emitted.  Capacities, pointers and the LSAP mode are never overridden;
+// max_age, nn_budget and max_cos_dist live in the sequence's adapted state, not in g.
+template <bool TAB>
+__device__ __forceinline__ void seq_override(SsDev& g, int s) {
+  if constexpr (TAB) {
+    const SsSeqPar* __restrict__ t = g.seqpar;
+    if (t && t[s].set) {
+      const SsSeqPar q = t[s];
+      g.min_conf = q.min_conf; g.max_iou = q.max_iou; g.mc_lambda = q.mc_lambda;
+      g.ema_alpha = q.ema_alpha; g.thi = q.thi; g.tlo = q.tlo; g.idw = q.idw;
+      g.n_init = q.n_init; g.crowd = q.crowd; g.born = q.born;
+    }
+  }
+}
 
 // Diagnostic phase stamps and counters (build with -DBX_PHASE_TIMING; never shipped): per
 // sequence, cycles accumulated per phase [0, 16), sub-phase cycles / counters [16, 32).
@@ -677,9 +720,12 @@ __device__ __forceinline__ bool in_list(const int* a, int n, int v) {
 // ------------------------------------------------------------------------------------------
 // Detection features (wave per input detection, 64-thread blocks): prep [wave norm of feat,
 // pairwise norm of feat, wave norm of nf, pairwise norm of nf + 1e-8], dn, nf
+// (TAB: the build for an engine with a per-sequence parameter table, seq_override)
+template <bool TAB>
 __global__ void __launch_bounds__(64)
     ss_prep_kernel(SsDev g, int seq0, const int* __restrict__ det_off,
                    const double* __restrict__ embs, const double* __restrict__ dets) {
+  seq_override<TAB>(g, seq0 + (int)blockIdx.y);
   __shared__ int lo[PW_MAXLEAF], ln[PW_MAXLEAF];
   __shared__ double leaf[PW_MAXLEAF];
   const int b = blockIdx.y, seq = seq0 + b, k = blockIdx.x;
@@ -2012,7 +2058,9 @@ __device__ __forceinline__ double enhance_clamp(const SsTrk& t, const double* d,
 // INFTY past time_since_update 1) with _enhance_cost_matrix, unclamped.  Both only depend on the
 // predicted tracks and the detections, so ss_match_kernel's solver reads them in place (by
 // cascade rank / list position and sorted detection, in both orientations).
+template <bool TAB>
 __global__ void __launch_bounds__(64) ss_cost_kernel(SsDev g, int seq0) {
+  seq_override<TAB>(g, seq0 + (int)blockIdx.y);
   __shared__ double sh[32];
   const int b = blockIdx.y, seq = seq0 + b, k = blockIdx.x, lane = threadIdx.x;
   const int* sq = g.sq + (size_t)seq * SQS;
@@ -2692,7 +2740,9 @@ constexpr int CROWD_BLOCKS = 16;
 __host__ __device__ constexpr int crowd_blocks(int nseq) {
   return nseq >= 64 ? BX_CROWD_BLOCKS_MANY : CROWD_BLOCKS;
 }
+template <bool TAB>
 __global__ void __launch_bounds__(256) ss_crowd_kernel(SsDev g, int seq0) {
+  seq_override<TAB>(g, seq0 + (int)blockIdx.y);
   extern __shared__ __align__(16) double box[];  // [4 * T]
   const int b = blockIdx.y, seq = seq0 + b;
   int* sq = g.sq + (size_t)seq * SQS;
@@ -2771,9 +2821,11 @@ __global__ void __launch_bounds__(64)
   }
 }
 
+template <bool TAB>
 __global__ void __launch_bounds__(64)
     ss_pre_kernel(SsDev g, int seq0, const double* __restrict__ dets,
                   const int* __restrict__ det_off, const double* __restrict__ warps) {
+  seq_override<TAB>(g, seq0 + (int)blockIdx.x);
   extern __shared__ __align__(16) char ss_lds[];
   __shared__ double sbox[4 * 1024];  // crowd test: track boxes; then the detection sort keys
   const int lane = threadIdx.x, b = blockIdx.x, seq = seq0 + b;
@@ -2915,8 +2967,10 @@ __global__ void __launch_bounds__(256) ss_sort_kernel(SsDev g, int seq0) {
 // the cascade and posts each LSAP (LsapJob) to wave 1, the solver, which keeps its own register
 // context.  Hands the matches (fmt), the unmatched tracks (ffut) and detections (faud) to the next
 // launches.
+template <bool TAB>
 __global__ void __launch_bounds__(128) SS_MATCH_ATTR
     ss_match_kernel(SsDev g, int seq0) {
+  seq_override<TAB>(g, seq0 + (int)blockIdx.x);
   extern __shared__ __align__(16) char ss_lds[];
   __shared__ int srank[1024], sgpos[1024], sinset[1024];
   __shared__ int flt[2048], fld[1024];  // solver column indices; sorted-detection membership
@@ -3105,9 +3159,11 @@ __global__ void __launch_bounds__(64 * SS_UPD_W) ss_update_kernel(SsDev g, int s
 }
 
 // ss_post_kernel (one wave per sequence): ID recovery, births, the lost buffer, the output rows.
+template <bool TAB>
 __global__ void __launch_bounds__(64)
     ss_post_kernel(SsDev g, int seq0, const int* __restrict__ det_off, double* __restrict__ out,
                    int* __restrict__ out_count) {
+  seq_override<TAB>(g, seq0 + (int)blockIdx.x);
   extern __shared__ __align__(16) char ss_lds[];
   const int lane = threadIdx.x, b = blockIdx.x, seq = seq0 + b;
   SsWs w;
@@ -3405,12 +3461,25 @@ __global__ void __launch_bounds__(64) ss_fit_kernel(SsDev g, int seq0) {
   }
 }
 
+// (a thread per sequence: the TAB build reads the sequence's table entry per thread and seeds the
+// adapted state from it when it is set, else from slot S as the plain build always does)
+template <bool TAB>
 __global__ void ss_reset_kernel(SsDev g, int seq0, int nseq) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < nseq) {
     int* q = g.sq + (size_t)(seq0 + k) * SQS;
     for (int i = 0; i < SQS; i++) q[i] = 0;
     q[Q_NEXTID] = 1;
+    if constexpr (TAB) {
+      if (g.seqpar && g.seqpar[seq0 + k].set) {
+        const SsSeqPar p = g.seqpar[seq0 + k];
+        q[Q_MAXAGE] = p.max_age;
+        q[Q_BUDGET] = p.budget;
+        g.sqd[(size_t)(seq0 + k) * 2] = p.max_cos;
+        g.sqd[(size_t)(seq0 + k) * 2 + 1] = p.max_cos;
+        return;
+      }
+    }
     q[Q_MAXAGE] = g.sq[(size_t)g.S * SQS + 0];
     q[Q_BUDGET] = g.sq[(size_t)g.S * SQS + 1];
     g.sqd[(size_t)(seq0 + k) * 2] = g.sqd[(size_t)g.S * 2];
@@ -3500,9 +3569,55 @@ __global__ void __launch_bounds__(64) ss_lsap_op_kernel(const double* C, int R, 
 
 }  // namespace
 
+// The table builds live in a translation unit of their own (bx_strongsort_tab.hip, which includes
+// this file with BX_SS_TAB_UNIT defined and compiles it up to here): this unit's code object then
+// holds the kernels it held before the table builds existed, and an engine without a table runs
+// code whose placement does not depend on them (after 2.23's measurement).
+#ifdef BX_SS_TAB_UNIT
+int bx_ss_tab_lds_attr(size_t lds) {
+  hipError_t rc = bx_lds_attr((const void*)ss_pre_kernel<true>, lds);
+  if (rc == hipSuccess) rc = bx_lds_attr((const void*)ss_match_kernel<true>, lds);
+  if (rc == hipSuccess) rc = bx_lds_attr((const void*)ss_post_kernel<true>, lds);
+  return (int)rc;
+}
+void bx_ss_tab_prep(const void* dev, dim3 grid, hipStream_t st, int seq0, const int* off,
+                    const double* embs, const double* dets) {
+  hipLaunchKernelGGL(ss_prep_kernel<true>, grid, dim3(64), 0, st, *(const SsDev*)dev, seq0, off,
+                     embs, dets);
+}
+void bx_ss_tab_crowd(const void* dev, dim3 grid, size_t lds, hipStream_t st, int seq0) {
+  hipLaunchKernelGGL(ss_crowd_kernel<true>, grid, dim3(256), lds, st, *(const SsDev*)dev, seq0);
+}
+void bx_ss_tab_pre(const void* dev, dim3 grid, size_t lds, hipStream_t st, int seq0,
+                   const double* dets, const int* off, const double* warps) {
+  hipLaunchKernelGGL(ss_pre_kernel<true>, grid, dim3(64), lds, st, *(const SsDev*)dev, seq0, dets,
+                     off, warps);
+}
+void bx_ss_tab_cost(const void* dev, dim3 grid, hipStream_t st, int seq0) {
+  hipLaunchKernelGGL(ss_cost_kernel<true>, grid, dim3(64), 0, st, *(const SsDev*)dev, seq0);
+}
+void bx_ss_tab_match(const void* dev, dim3 grid, size_t lds, hipStream_t st, int seq0) {
+  hipLaunchKernelGGL(ss_match_kernel<true>, grid, dim3(128), lds, st, *(const SsDev*)dev, seq0);
+}
+void bx_ss_tab_post(const void* dev, dim3 grid, size_t lds, hipStream_t st, int seq0,
+                    const int* off, double* out, int* cnt) {
+  hipLaunchKernelGGL(ss_post_kernel<true>, grid, dim3(64), lds, st, *(const SsDev*)dev, seq0, off,
+                     out, cnt);
+}
+void bx_ss_tab_reset(const void* dev, dim3 grid, hipStream_t st, int seq0, int nseq) {
+  hipLaunchKernelGGL(ss_reset_kernel<true>, grid, dim3(256), 0, st, *(const SsDev*)dev, seq0,
+                     nseq);
+}
+#else
+
 struct bx_ss {
   SsDev dev;
   bx_ss_config cfg;
+  // per-sequence parameters (bx_ss_set_seq_params_host): the device table dev.seqpar points to,
+  // allocated by the first set, and its host mirror with the values as they were given
+  SsSeqPar* d_seqpar = nullptr;
+  std::vector<SsSeqPar> h_seqpar;
+  std::vector<bx_ss_seq_params> h_seqgiven;
   void* arena = nullptr;
   // update_host staging (detections as doubles, 10-wide rows); sg.p_sq: the counters row of the
   // last update_host sequence (bx_ss_counters_host answers from it)
@@ -3526,7 +3641,12 @@ static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int
   int rc;
   if (!embs) return bx_record_error(BX_ERR_SHAPE, "StrongSort needs embeddings");
   if ((rc = e->probe.begin(0, st))) return rc;
-  hipLaunchKernelGGL(ss_prep_kernel, dim3(d.D + 1, nseq), dim3(64), 0, st, d, seq0, off, embs,
+  // an engine with a table launches the table builds of the kernels that read a parameter
+  const bool tab = d.seqpar != nullptr;
+  if (tab)
+    bx_ss_tab_prep(&d, dim3(d.D + 1, nseq), st, seq0, off, embs, dets);
+  else
+    hipLaunchKernelGGL(ss_prep_kernel<false>, dim3(d.D + 1, nseq), dim3(64), 0, st, d, seq0, off, embs,
                      dets);
   BX_HIPCHK(hipGetLastError());
   if ((rc = e->probe.end(0, st))) return rc;
@@ -3544,8 +3664,10 @@ static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int
     BX_HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
   }
   if ((rc = e->probe.begin(3, sm))) return rc;
-  if (d.crowd)
-    hipLaunchKernelGGL(ss_crowd_kernel, dim3(crowd_blocks(nseq), nseq), dim3(256),
+  if (tab)  // (a sequence's own crowd_detection decides in the kernel)
+    bx_ss_tab_crowd(&d, dim3(crowd_blocks(nseq), nseq), sizeof(double) * 4 * d.T, sm, seq0);
+  else if (d.crowd)
+    hipLaunchKernelGGL(ss_crowd_kernel<false>, dim3(crowd_blocks(nseq), nseq), dim3(256),
                        sizeof(double) * 4 * d.T, sm, d, seq0);
   hipLaunchKernelGGL(ss_motion_kernel, dim3(d.T, nseq), dim3(64), 0, sm, d, seq0, warps);
   BX_HIPCHK(hipGetLastError());
@@ -3555,7 +3677,10 @@ static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int
     BX_HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
     if ((rc = e->probe.begin(3, e->side))) return rc;
   }
-  hipLaunchKernelGGL(ss_pre_kernel, dim3(nseq), dim3(64), lds, e->side, d, seq0, dets, off,
+  if (tab)
+    bx_ss_tab_pre(&d, dim3(nseq), lds, e->side, seq0, dets, off, warps);
+  else
+    hipLaunchKernelGGL(ss_pre_kernel<false>, dim3(nseq), dim3(64), lds, e->side, d, seq0, dets, off,
                      warps);
   BX_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(ss_sort_kernel, dim3((d.D + 255) / 256, nseq), dim3(256), 0, e->side, d,
@@ -3598,11 +3723,17 @@ static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int
   if ((rc = e->probe.end(2, st))) return rc;
   BX_HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));  // join
   if ((rc = e->probe.begin(4, st))) return rc;
-  hipLaunchKernelGGL(ss_cost_kernel, dim3(d.T, nseq), dim3(64), 0, st, d, seq0);
+  if (tab)
+    bx_ss_tab_cost(&d, dim3(d.T, nseq), st, seq0);
+  else
+    hipLaunchKernelGGL(ss_cost_kernel<false>, dim3(d.T, nseq), dim3(64), 0, st, d, seq0);
   BX_HIPCHK(hipGetLastError());
   if ((rc = e->probe.end(4, st))) return rc;
   if ((rc = e->probe.begin(5, st))) return rc;
-  hipLaunchKernelGGL(ss_match_kernel, dim3(nseq), dim3(128), lds, st, d, seq0);
+  if (tab)
+    bx_ss_tab_match(&d, dim3(nseq), lds, st, seq0);
+  else
+    hipLaunchKernelGGL(ss_match_kernel<false>, dim3(nseq), dim3(128), lds, st, d, seq0);
   BX_HIPCHK(hipGetLastError());
   if ((rc = e->probe.end(5, st))) return rc;
   if ((rc = e->probe.begin(6, st))) return rc;
@@ -3612,7 +3743,10 @@ static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int
   BX_HIPCHK(hipGetLastError());
   if ((rc = e->probe.end(6, st))) return rc;
   if ((rc = e->probe.begin(7, st))) return rc;
-  hipLaunchKernelGGL(ss_post_kernel, dim3(nseq), dim3(64), lds, st, d, seq0, off, out, cnt);
+  if (tab)
+    bx_ss_tab_post(&d, dim3(nseq), lds, st, seq0, off, out, cnt);
+  else
+    hipLaunchKernelGGL(ss_post_kernel<false>, dim3(nseq), dim3(64), lds, st, d, seq0, off, out, cnt);
   BX_HIPCHK(hipGetLastError());
   if ((rc = e->probe.end(7, st))) return rc;
   if ((rc = e->probe.begin(8, st))) return rc;
@@ -3756,6 +3890,7 @@ int bx_ss_create(const bx_ss_config* c, bx_ss** out) {
 #else
     d.dbg = nullptr;
 #endif
+    d.seqpar = nullptr;
     // per-sequence defaults (row S holds them for bx_ss_reset): max_age, budget, threshold
     std::vector<int> q((S + 1) * SQS, 0);
     std::vector<double> qd((S + 1) * 2, c->max_cos_dist);
@@ -3770,9 +3905,10 @@ int bx_ss_create(const bx_ss_config* c, bx_ss** out) {
     BX_HIPCHK(hipMemcpy(d.sqd, qd.data(), qd.size() * sizeof(double), hipMemcpyHostToDevice));
     if (d.ws_lds) {
       const int lds = (int)ss_lds_bytes(d);
-      BX_HIPCHK(bx_lds_attr((const void*)ss_pre_kernel, lds));
-      BX_HIPCHK(bx_lds_attr((const void*)ss_match_kernel, lds));
-      BX_HIPCHK(bx_lds_attr((const void*)ss_post_kernel, lds));
+      BX_HIPCHK(bx_lds_attr((const void*)ss_pre_kernel<false>, lds));
+      BX_HIPCHK(bx_lds_attr((const void*)ss_match_kernel<false>, lds));
+      BX_HIPCHK(bx_lds_attr((const void*)ss_post_kernel<false>, lds));
+      BX_HIPCHK((hipError_t)bx_ss_tab_lds_attr(lds));
     }
     BX_HIPCHK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
     BX_HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
@@ -3823,6 +3959,126 @@ int bx_ss_copy_state(bx_ss* dst, bx_ss* src) {
   return BX_OK;
 }
 
+int bx_ss_set_seq_params_host(bx_ss* e, int seq0, int nseq, const bx_ss_seq_params* params_host,
+                              void* stream) {
+  if (!e || seq0 < 0 || nseq < 0 || seq0 > e->dev.S - nseq)
+    return bx_record_error(BX_ERR_INVALID, "bad sequence range");
+  SsDev& d = e->dev;
+  for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
+    const bx_ss_seq_params& p = params_host[k];
+    if (p.nn_budget <= 0 || p.max_age < 0)  // (bx_ss_create's checks)
+      return bx_record_error(BX_ERR_INVALID, "nn_budget must be positive, max_age not negative");
+    const int crowd_budget = p.nn_budget * 2 < 300 ? p.nn_budget * 2 : 300;
+    const int gb = (p.nn_budget > crowd_budget ? p.nn_budget : crowd_budget) + MAXF;
+    if (gb > GB_MAX)
+      return bx_record_error(BX_ERR_INVALID, "nn_budget too large (gallery > 320 entries)");
+    if (gb > d.GB)  // the galleries are sized by the engine's own nn_budget
+      return bx_record_error(BX_ERR_INVALID,
+                             "nn_budget above the engine's: its galleries hold fewer entries");
+  }
+  // frames in flight on any stream read the table and write the adapted state
+  BX_HIPCHK(hipDeviceSynchronize());
+  if (!nseq) return BX_OK;
+  // max_age, nn_budget and max_cos_dist seed state that crowd mode adapts: only a sequence that
+  // has not run a frame (fresh or just reset) takes new seeds
+  std::vector<int> sq((size_t)nseq * SQS);
+  BX_HIPCHK(hipMemcpy(sq.data(), d.sq + (size_t)seq0 * SQS, sq.size() * sizeof(int),
+                      hipMemcpyDeviceToHost));
+  for (int k = 0; k < nseq; k++)
+    if (sq[(size_t)k * SQS + Q_FRAME] != 0)
+      return bx_record_error(BX_ERR_INVALID,
+                             "per-sequence parameters change only at frame counter 0 "
+                             "(a fresh or just reset sequence)");
+  if (!params_host && !e->d_seqpar) return BX_OK;  // (nothing to clear)
+  hipStream_t st = (hipStream_t)stream;
+  const size_t S = d.S;
+  // the entries as bx_ss_create resolves bx_ss_config, and the seeds of the adapted state (the
+  // engine's own for a cleared sequence), staged beside the mirror
+  std::vector<SsSeqPar> stage(nseq, SsSeqPar{});
+  std::vector<double> thr((size_t)nseq * 2, e->cfg.max_cos_dist);
+  for (int k = 0; k < nseq; k++) {
+    int* q = sq.data() + (size_t)k * SQS;
+    q[Q_MAXAGE] = e->cfg.max_age;
+    q[Q_BUDGET] = e->cfg.nn_budget;
+    if (!params_host) continue;
+    const bx_ss_seq_params& p = params_host[k];
+    SsSeqPar& o = stage[k];
+    o.min_conf = p.min_conf;
+    o.max_iou = p.max_iou_dist;
+    o.mc_lambda = p.mc_lambda;
+    o.ema_alpha = p.ema_alpha;
+    o.thi = p.conf_thresh_high;
+    o.tlo = p.conf_thresh_low;
+    o.idw = p.id_preservation_weight;
+    o.max_cos = p.max_cos_dist;
+    o.n_init = p.n_init;
+    o.crowd = p.crowd_detection != 0;
+    o.born = p.born_confirmed != 0;
+    o.max_age = p.max_age;
+    o.budget = p.nn_budget;
+    o.set = 1;
+    q[Q_MAXAGE] = p.max_age;
+    q[Q_BUDGET] = p.nn_budget;
+    thr[2 * k] = thr[2 * k + 1] = p.max_cos_dist;
+  }
+  SsSeqPar* tbl = e->d_seqpar;
+  const bool first = !tbl;
+  bool ok = true;
+  if (first)
+    ok = hipMalloc(&tbl, S * sizeof(SsSeqPar)) == hipSuccess &&
+         hipMemset(tbl, 0, S * sizeof(SsSeqPar)) == hipSuccess;
+  ok = ok && hipMemcpyAsync(tbl + seq0, stage.data(), nseq * sizeof(SsSeqPar),
+                            hipMemcpyHostToDevice, st) == hipSuccess &&
+       hipStreamSynchronize(st) == hipSuccess;
+  if (!ok) {
+    // nothing was committed: the mirror, SsDev and the launches' builds are as they were; an
+    // existing table gets the mirror's entries back
+    if (first)
+      (void)hipFree(tbl);
+    else
+      (void)hipMemcpy(tbl + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(SsSeqPar),
+                      hipMemcpyHostToDevice);
+    return bx_record_error(BX_ERR_HIP, "allocation or copy of the parameter table failed");
+  }
+  // the sequences' seeds (their rows hold nothing else yet: frame counter 0)
+  BX_HIPCHK(hipMemcpy(d.sq + (size_t)seq0 * SQS, sq.data(), sq.size() * sizeof(int),
+                      hipMemcpyHostToDevice));
+  BX_HIPCHK(hipMemcpy(d.sqd + (size_t)seq0 * 2, thr.data(), thr.size() * sizeof(double),
+                      hipMemcpyHostToDevice));
+  e->cache_seq = -1;
+  // commit: the device holds the entries
+  if (first) {
+    e->d_seqpar = tbl;
+    e->h_seqpar.assign(S, SsSeqPar{});
+    e->h_seqgiven.assign(S, bx_ss_seq_params{});
+  }
+  for (int k = 0; k < nseq; k++) {
+    e->h_seqpar[seq0 + k] = stage[k];
+    if (params_host) e->h_seqgiven[seq0 + k] = params_host[k];
+  }
+  d.seqpar = e->d_seqpar;
+  return BX_OK;
+}
+
+int bx_ss_seq_params_host(bx_ss* e, int seq, bx_ss_seq_params* out_host) {
+  if (!e || seq < 0 || seq >= e->dev.S || !out_host)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ss_seq_params_host");
+  if (!e->h_seqpar.empty() && e->h_seqpar[seq].set) {
+    *out_host = e->h_seqgiven[seq];
+    return BX_OK;
+  }
+  const bx_ss_config& c = e->cfg;
+  bx_ss_seq_params o;
+  o.min_conf = c.min_conf; o.max_cos_dist = c.max_cos_dist; o.max_iou_dist = c.max_iou_dist;
+  o.max_age = c.max_age; o.n_init = c.n_init; o.nn_budget = c.nn_budget;
+  o.mc_lambda = c.mc_lambda; o.ema_alpha = c.ema_alpha;
+  o.conf_thresh_high = c.conf_thresh_high; o.conf_thresh_low = c.conf_thresh_low;
+  o.id_preservation_weight = c.id_preservation_weight;
+  o.crowd_detection = c.crowd_detection; o.born_confirmed = c.born_confirmed;
+  *out_host = o;
+  return BX_OK;
+}
+
 int bx_ss_destroy(bx_ss* e) {
   if (!e) return BX_OK;
   if (e->side) (void)hipStreamDestroy(e->side);
@@ -3830,6 +4086,7 @@ int bx_ss_destroy(bx_ss* e) {
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   e->probe.destroy();
   (void)hipFree(e->arena);
+  (void)hipFree(e->d_seqpar);
   e->sg.free();
   delete e;
   return BX_OK;
@@ -3840,7 +4097,10 @@ int bx_ss_reset(bx_ss* e, int seq0, int nseq, void* stream) {
     return bx_record_error(BX_ERR_INVALID, "bad sequence range");
   if (!nseq) return BX_OK;
   e->cache_seq = -1;
-  hipLaunchKernelGGL(ss_reset_kernel, dim3((nseq + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+  if (e->dev.seqpar)  // a sequence with an entry is seeded from it
+    bx_ss_tab_reset(&e->dev, dim3((nseq + 255) / 256), (hipStream_t)stream, seq0, nseq);
+  else
+    hipLaunchKernelGGL(ss_reset_kernel<false>, dim3((nseq + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      e->dev, seq0, nseq);
   BX_HIPCHK(hipGetLastError());
   return BX_OK;
@@ -4153,3 +4413,5 @@ int bx_ss_probe_read(bx_ss* e, double* total_ms, int* count) {
 }
 
 }  // extern "C"
+
+#endif  // BX_SS_TAB_UNIT

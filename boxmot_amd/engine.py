@@ -1223,13 +1223,15 @@ class SequenceFeeder(_NativeHandle):
     out, out_count)`` with the last five as device addresses."""
 
     _PREFIX = "bx_feed"
+    det_f64, out_cols = False, 8  # the runs' types (SharedSequenceFeeder may choose others)
 
     def __init__(self, dets, embs, tables, emb_dim: int, res_cap=None, guard_rows: int = 0):
         self._build(dets, embs, tables, emb_dim, res_cap, guard_rows, None)
 
-    def _build(self, dets, embs, tables, emb_dim, res_cap, guard_rows, source) -> None:
+    def _build(self, dets, embs, tables, emb_dim, res_cap, guard_rows, source, fmt=None) -> None:
         """Create, upload and read the schedule.  ``source``: None, or SharedSequenceFeeder's
-        map (only a source's rows are read and uploaded)."""
+        map (only a source's rows are read and uploaded).  ``fmt``: None, or SharedSequenceFeeder's
+        (det_f64, out_cols) for bx_feed_create_shared_fmt."""
         S = len(dets)
         self.n_seq, self.emb_dim = S, int(emb_dim)
         src = None if source is None else np.ascontiguousarray(source, np.int32).reshape(S)
@@ -1251,11 +1253,17 @@ class SequenceFeeder(_NativeHandle):
             N.check(self._L.bx_feed_create(S, self.emb_dim, rows.ctypes.data, tab_off.ctypes.data,
                                            start.ctypes.data, cnt.ctypes.data, fid.ctypes.data,
                                            _p(cap), int(guard_rows), C.byref(h)), "bx_feed_create")
-        else:
+        elif fmt is None:
             N.check(self._L.bx_feed_create_shared(
                 S, self.emb_dim, rows.ctypes.data, tab_off.ctypes.data, start.ctypes.data,
                 cnt.ctypes.data, fid.ctypes.data, _p(cap), int(guard_rows), src.ctypes.data,
                 C.byref(h)), "bx_feed_create_shared")
+        else:
+            N.check(self._L.bx_feed_create_shared_fmt(
+                S, self.emb_dim, rows.ctypes.data, tab_off.ctypes.data, start.ctypes.data,
+                cnt.ctypes.data, fid.ctypes.data, _p(cap), int(guard_rows), src.ctypes.data,
+                int(fmt[0]), int(fmt[1]), C.byref(h)), "bx_feed_create_shared_fmt")
+            self.det_f64, self.out_cols = bool(fmt[0]), int(fmt[1])
         self._h = h
         for k in range(S):
             if not rows[k]:
@@ -1333,7 +1341,7 @@ class SequenceFeeder(_NativeHandle):
     def read_run(self, t: int, r: int):
         """Host copies of the gathered (dets, det_off, embs) of run r of frame index t."""
         _, nseq, rows = self.schedule[t][r][:3]
-        d = np.empty((rows, 6), np.float32)
+        d = np.empty((rows, 6), np.float64 if self.det_f64 else np.float32)
         o = np.empty(nseq + 1, np.int32)
         e = np.empty((rows, self.emb_dim), np.float64) if self.emb_dim else None
         N.check(self._L.bx_feed_read_run_host(self._h, int(t), int(r), d.ctypes.data,
@@ -1341,9 +1349,10 @@ class SequenceFeeder(_NativeHandle):
         return d, o, e
 
     def write_run(self, t: int, r: int, out, out_count) -> None:
-        """Set out [rows, 8] / out_count [nseq] of run r of frame index t from host arrays."""
+        """Set out [rows, 8] ([rows, out_cols]) / out_count [nseq] of run r of frame index t from
+        host arrays."""
         _, nseq, rows = self.schedule[t][r][:3]
-        o = np.ascontiguousarray(out, np.float64).reshape(rows, 8)
+        o = np.ascontiguousarray(out, np.float64).reshape(rows, self.out_cols)
         c = np.ascontiguousarray(out_count, np.int32).reshape(nseq)
         N.check(self._L.bx_feed_write_run_host(self._h, int(t), int(r), o.ctypes.data,
                                                c.ctypes.data), "bx_feed_write_run_host")
@@ -1364,12 +1373,23 @@ class SharedSequenceFeeder(SequenceFeeder):
     read and uploaded; the entries of the other sequences may be None.  Tables, runs, gathered
     arrays and results stay per sequence.  ``source=None`` is a plain SequenceFeeder.  (A class
     of its own because SequenceFeeder's constructor signature is pinned by
-    tests/test_engine_api_host.py.)"""
+    tests/test_engine_api_host.py.)
+
+    ``det_f64`` / ``out_cols`` (``bx_feed_create_shared_fmt``; they need a ``source``) choose the
+    runs' types for an engine like StrongSort's: with ``det_f64`` the gathered ``dets`` are float64
+    (the packed rows stay float32; the widening is exact), with ``out_cols=10`` the runs' ``out``
+    rows have 10 columns, of which the append reads the first 8.  The defaults are
+    ``bx_feed_create_shared`` as before."""
 
     def __init__(self, dets, embs, tables, emb_dim: int, res_cap=None, guard_rows: int = 0,
-                 source=None):
+                 source=None, *, det_f64: bool = False, out_cols: int = 8):
         self.source = None if source is None else [int(q) for q in source]
-        self._build(dets, embs, tables, emb_dim, res_cap, guard_rows, source)
+        fmt = None
+        if det_f64 or out_cols != 8:
+            if source is None:
+                raise ValueError("det_f64 / out_cols need a source map (bx_feed_create_shared_fmt)")
+            fmt = (bool(det_f64), int(out_cols))
+        self._build(dets, embs, tables, emb_dim, res_cap, guard_rows, source, fmt)
 
 
 @dataclass
@@ -1748,6 +1768,78 @@ class SsEngine(_NativeEngine):
         N.check(self._L.bx_ss_lsap_stats_host(self._h, seq0, nseq, a), "lsap_stats")
         return dict(zip(["solves", "unique", "unique_up_to_rejected", "ties", "restarts"],
                         [int(x) for x in a]))
+
+
+class SsTableEngine(SsEngine):
+    """An ``SsEngine`` whose sequences may each run on parameters of their own
+    (``bx_ss_set_seq_params_host``, include/bxstrongsort.h): the engine of a StrongSort
+    hyper-parameter sweep, K configs x S sequences as K*S sequences of one handle
+    (boxmot_amd.tune.sweep_strong).  The capacities, ``emb_dim`` and ``vec_cap`` stay the
+    engine's, and an entry's ``nn_budget`` may not exceed the engine's own, which sized the
+    galleries.  ``max_age``, ``nn_budget`` and ``max_cos_dist`` of an entry seed the state crowd
+    mode adapts, so a sequence takes an entry only at frame counter 0 (fresh or just reset).  (A
+    class of its own because SsEngine's method set is pinned by tests/test_engine_api_host.py.)"""
+
+    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
+                 emb_dim: int = 512, vec_cap: int = 32, params: SsParams | None = None):
+        super().__init__(n_seq, track_cap, det_cap, emb_dim, vec_cap, params)
+        self._seq_over = {}  # sequence -> its own SsParams, for grown()
+
+    def grown(self, track_cap: int, det_cap: int) -> "SsTableEngine":
+        """As SsEngine.grown; bx_ss_copy_state carries the tracks and the sequences' adapted
+        state but not the table, which is set on the new engine first: its sequences are at
+        frame counter 0 then, as the call requires."""
+        e = SsTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim, self.vec_cap, self.params)
+        for k, p in sorted(self._seq_over.items()):
+            e.set_seq_params(k, [p])
+        N.check(self._L.bx_ss_copy_state(e._h, self._h), "bx_ss_copy_state")
+        return e
+
+    @staticmethod
+    def _seq_struct(p: SsParams):
+        return N.BxSsSeqParams(
+            min_conf=float(p.min_conf), max_cos_dist=float(p.max_cos_dist),
+            max_iou_dist=float(p.max_iou_dist), max_age=int(p.max_age), n_init=int(p.n_init),
+            nn_budget=int(p.nn_budget), mc_lambda=float(p.mc_lambda),
+            ema_alpha=float(p.ema_alpha), conf_thresh_high=float(p.conf_thresh_high),
+            conf_thresh_low=float(p.conf_thresh_low),
+            id_preservation_weight=float(p.id_preservation_weight),
+            crowd_detection=int(bool(p.crowd_detection)),
+            born_confirmed=int(bool(p.born_confirmed)))
+
+    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
+        """Give sequences [seq0, seq0 + len(params)) parameters of their own
+        (bx_ss_set_seq_params_host): ``params`` is a list of SsParams.  ``None`` clears the
+        override of ``nseq`` sequences from seq0 (default: all from seq0).  ``ValueError`` for a
+        sequence that has run a frame since its last reset, and for an entry ``SsEngine`` would
+        refuse or whose ``nn_budget`` is above the engine's; nothing changes then."""
+        if params is None:
+            n = self.n_seq - seq0 if nseq is None else nseq
+            arr = None
+        else:
+            n = len(params)
+            arr = (N.BxSsSeqParams * max(n, 1))(*[self._seq_struct(p) for p in params])
+        N.check(self._L.bx_ss_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
+                "bx_ss_set_seq_params_host")
+        for k in range(n):
+            if params is None:
+                self._seq_over.pop(seq0 + k, None)
+            else:
+                self._seq_over[seq0 + k] = params[k]
+
+    def seq_params(self, seq: int) -> SsParams:
+        """The parameters sequence ``seq`` runs on (bx_ss_seq_params_host): its own when set,
+        else the engine's; ``max_age``, ``nn_budget`` and ``max_cos_dist`` as seeded, not as crowd
+        mode adapted them."""
+        o = N.BxSsSeqParams()
+        N.check(self._L.bx_ss_seq_params_host(self._h, int(seq), C.byref(o)),
+                "bx_ss_seq_params_host")
+        return SsParams(
+            min_conf=o.min_conf, max_cos_dist=o.max_cos_dist, max_iou_dist=o.max_iou_dist,
+            max_age=o.max_age, n_init=o.n_init, nn_budget=o.nn_budget, mc_lambda=o.mc_lambda,
+            ema_alpha=o.ema_alpha, conf_thresh_high=o.conf_thresh_high,
+            conf_thresh_low=o.conf_thresh_low, id_preservation_weight=o.id_preservation_weight,
+            crowd_detection=bool(o.crowd_detection), born_confirmed=bool(o.born_confirmed))
 
 
 def _ptr(x):

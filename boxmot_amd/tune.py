@@ -13,7 +13,9 @@ the two appearance trackers of its family, DeepOCSort and HybridSort (``sweep_re
 2.20), whose K*S sequences read each sequence's detections and embeddings from ONE copy in device
 memory (``engine.SharedSequenceFeeder``).  ByteTrack and BoT-SORT, which share ``bx_engine``, have
 them too (``sweep_bot``), fed the same way, and so has BoostTrack
-(``sweep_boost``), whose variants differ in constructor flags only.
+(``sweep_boost``), whose variants differ in constructor flags only.  StrongSort
+(``sweep_strong``) completes the set: its feeder gathers float64 detections and
+10-column rows, and its occlusion post-process stays on the host, per sweep.
 """
 from __future__ import annotations
 
@@ -26,6 +28,7 @@ SUPPORTED = ("ocsort",)
 SUPPORTED_REID = ("deepocsort", "hybridsort")  # sweep_reid's trackers
 SUPPORTED_BOT = ("bytetrack", "botsort")       # sweep_bot's trackers
 SUPPORTED_BOOST = ("boosttrack",)              # sweep_boost's tracker
+SUPPORTED_STRONG = ("strongsort",)             # sweep_strong's tracker
 _CAPS = ("track_cap", "det_cap")
 
 
@@ -528,6 +531,197 @@ def sweep_boost(sequences: dict, configs, *, exp_dir=None, gt: dict | None = Non
             feed.close()
         eng.close()
     return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
+
+
+def _strong_occ(cfg: dict) -> bool:
+    """handle_occlusions as run_sequences("strongsort", tracker_kwargs=cfg) resolves it: on, the
+    reference's default, unless cfg switches it off."""
+    return bool(cfg.get("handle_occlusions", True))
+
+
+def _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps) -> list:
+    """The refusals of ``sweep_strong`` that need no engine and no device."""
+    from . import motio
+
+    configs = _check("strongsort", configs, sequences, gt, exp_dir, score, keep_results,
+                     supported=SUPPORTED_STRONG, what="tune.sweep_strong")
+    if len({repr(c.get("vec_cap")) for c in configs}) > 1:
+        raise ValueError("vec_cap sizes the engine's memory: it must be absent from every config "
+                         "or equal in all of them")
+    occ = {_strong_occ(c) for c in configs}
+    if len(occ) > 1:
+        raise ValueError("handle_occlusions is a setting of the sweep, not of a config: it must "
+                         "resolve to the same value in every config")
+    if True in occ and score == "device":
+        raise ValueError('score="device" reads rows appended on the device; with '
+                         "handle_occlusions the rows are edited on the host: use "
+                         'score="host", or handle_occlusions=False in every config')
+    if True in occ and not keep_results:
+        raise ValueError("keep_results=False needs the rows on the device; with "
+                         "handle_occlusions they are formed on the host")
+    if warps is not None:
+        for c in configs:  # (cmc_off / use_ecc=False against warps)
+            motio._check_warp_args("strongsort", c, 0, warps, None, None)
+    return configs
+
+
+def _resolve_strong(F: int, cfg: dict):
+    """(SsParams, track_cap, det_cap, vec_cap, occlusion_threshold or None) of one config,
+    resolved as run_sequences resolves its tracker_kwargs: through ``motio._batched_engine``
+    itself, on a one-sequence engine."""
+    from . import motio
+
+    eng = motio._batched_engine("strongsort", 1, F, cfg)[0]
+    try:
+        return eng.params, eng.track_cap, eng.det_cap, eng.vec_cap, eng.occlusion_threshold
+    finally:
+        eng.close()
+
+
+def sweep_strong(sequences: dict, configs, *, exp_dir=None, gt: dict | None = None,
+                 benchmark: str = "MOT17", seq_lengths: dict | None = None,
+                 frame_ids: dict | None = None, score: str = "host", keep_results: bool = True,
+                 warps=None) -> list:
+    """``sweep`` for StrongSort: every config of ``configs`` over every sequence in one
+    ``engine.SsTableEngine`` of K*S sequences, engine sequence ``k*S + s`` being sequence ``s``
+    under config ``k``.
+
+    Arguments, return value, scoring and ``keep_results`` as in ``sweep``; each config means what
+    ``run_sequences("strongsort", ..., tracker_kwargs=cfg)`` makes of it, and the files under
+    ``exp_dir/<k as 4 digits>/`` are byte-identical to that run's with the same ``warps``.  The
+    sequences are fed by one ``SharedSequenceFeeder`` with ``source[k*S + s] = s`` in its float64 /
+    10-column mode: detections (held as float32, which ``BinSequence``'s values are widened from
+    exactly as ``run_sequences`` widens them) and float64 embeddings are uploaded and held once
+    per sequence, not once per config.  The engine's own ``nn_budget``, which sizes the galleries,
+    is the largest of the configs'.
+
+    ``handle_occlusions`` is a setting of the sweep: it must resolve to the same value in every
+    config.  Off, the rows are appended on the device and ``score="device"`` is available.  On
+    (the reference's default, and what an empty config means) the feeder still gathers and the
+    one engine still steps, but after each frame index the runs' rows come back to the host, an
+    ``OcclusionHandler`` per engine sequence (with its config's ``occlusion_threshold``) edits
+    tracks and rows as in ``run_sequences``, and the host formatter makes the MOT rows;
+    ``score="device"`` and ``keep_results=False`` are refused then.  The handler's ``TypeError``
+    on mutual occlusion propagates.
+
+    ``warps``: what ``run_sequences(warps=...)`` takes; every config's copy of a sequence gets that
+    sequence's warp.
+
+    Raised before any engine is built: ``NotImplementedError`` for ``per_class`` in a config;
+    ``ValueError`` for ``track_cap``, ``det_cap`` or ``vec_cap`` that differ across configs, mixed
+    ``handle_occlusions``, ``warps`` with a config that switches the camera-motion compensation
+    off, sequences whose embedding widths differ or whose detections are not float32 values (the
+    feeder holds float32, ``run_sequences`` feeds StrongSort float64: pack such a sequence from
+    detections rounded to float32, e.g. ``dets.astype(np.float32)``), and the ``score`` / ``gt`` /
+    ``keep_results`` combinations ``sweep`` refuses.
+    """
+    configs = _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps)
+    import dataclasses
+
+    from . import motio
+    from . import engine as E
+
+    names = list(sequences)
+    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
+            for s in sequences.values()]
+    S, K = len(seqs), len(configs)
+    if not S:
+        return [{"config": c, "results": {} if keep_results else None, "summary": None}
+                for c in configs]
+    widths = sorted({int(s.emb_dim) for s in seqs})
+    if len(widths) > 1 or not widths[0]:
+        raise ValueError(f"StrongSort needs embeddings of one width in every sequence (got "
+                         f"{widths}): one engine has one emb_dim")
+    F = widths[0]
+    dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
+    for s, d in zip(seqs, dets):  # (before any engine is built)
+        if not np.array_equal(d.astype(np.float64), np.asarray(s.dets)):
+            raise ValueError(f"{s.path}: detections that are not float32 values cannot be "
+                             "held once as float32 (run_sequences feeds them as float64): "
+                             "pack the sequence from detections rounded to float32")
+    fids, tables = _frame_tables(names, seqs, frame_ids)
+    table = None
+    if warps is not None:  # [T, S, 6] as run_sequences builds it, then every config's copy
+        table = motio._flow_warps(names, seqs, fids, F, warps, None, None).repeat(1, K, 1)
+    resolved = [_resolve_strong(F, c) for c in configs]
+    params = [r[0] for r in resolved]
+    occ_thr = [r[4] for r in resolved]
+    if len({r[1:4] for r in resolved}) > 1 or len({t is None for t in occ_thr}) > 1:
+        raise ValueError("the configs resolve to different capacities or handle_occlusions: "
+                         f"{[r[1:] for r in resolved]}")
+    base = dataclasses.replace(params[0], nn_budget=max(int(p.nn_budget) for p in params))
+    eng = E.SsTableEngine(n_seq=K * S, track_cap=resolved[0][1], det_cap=resolved[0][2],
+                          emb_dim=F, vec_cap=resolved[0][3], params=base)
+    feed = None
+    try:
+        embs = [s.embs for s in seqs]
+        for k in range(K):
+            eng.set_seq_params(k * S, [params[k]] * S)
+        none = [None] * ((K - 1) * S)
+        feed = E.SharedSequenceFeeder(dets + none, embs + none, tables * K, F,
+                                      source=list(range(S)) * K, det_f64=True, out_cols=10)
+
+        def step(t, run, out=None, cnt=None):
+            q0, ns, _, pd, po, pe, pout, pcnt = run
+            eng.step(pd, po, pe, None if table is None else table[t, q0: q0 + ns],
+                     pout if out is None else out, pcnt if cnt is None else cnt,
+                     seq0=q0, nseq=ns)
+
+        if occ_thr[0] is None:
+            rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
+                                     keep_results)
+        else:
+            rows, summaries = _drive_occlusion(eng, feed, step, fids * K,
+                                               [tb[1] for tb in tables] * K,
+                                               [t for t in occ_thr for _ in range(S)]), None
+    finally:
+        if feed is not None:
+            feed.close()
+        eng.close()
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
+
+
+def _drive_occlusion(eng, feed, step, fids, feed_cnt, thresholds) -> list:
+    """``_drive`` for a StrongSort sweep with handle_occlusions: per frame index one gather and
+    the steps of its runs, then the runs' out / out_count back on the host, the occlusion
+    post-process of every stepped sequence (with its update count, as run_sequences calls it)
+    and the host formatter.  ``feed_cnt[q][t]``: detections of engine sequence q at frame index
+    t.  Returns each engine sequence's MOT rows [n, 9]."""
+    import torch
+
+    from . import motio
+    from .occlusion import OcclusionHandler
+
+    occ = [OcclusionHandler(eng, q, thr) for q, thr in enumerate(thresholds)]
+    nupd = [0] * feed.n_seq
+    results = [[] for _ in range(feed.n_seq)]
+    dev = torch.device("cuda")
+    for t in range(feed.n_frames):
+        runs = feed.schedule[t]
+        if not runs:
+            continue
+        feed.gather(t)
+        outs = []
+        for run in runs:  # the rows go to tensors of this frame index, which the host reads
+            out = torch.empty((run[2], 10), dtype=torch.float64, device=dev)
+            cnt = torch.empty(run[1], dtype=torch.int32, device=dev)
+            step(t, run, out, cnt)
+            outs.append((out, cnt))
+        # every run is stepped before a handler edits the engine: a handler touches its own
+        # sequence alone, and the next frame index is stepped after all of them
+        for (q0, ns, *_), (out, cnt) in zip(runs, outs):
+            o, c = out.cpu().numpy(), cnt.cpu().numpy()
+            r0 = 0
+            for q in range(q0, q0 + ns):
+                rows = o[r0: r0 + c[q - q0]]
+                r0 += int(feed_cnt[q][t])  # (the sequence's detections: its det_off step)
+                nupd[q] += 1
+                rows = occ[q](nupd[q], rows)
+                if rows.shape[0]:
+                    results[q].append(motio.convert_to_mot_format(rows, int(fids[q][t])))
+    if eng.status() != 0:
+        raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
+    return [np.vstack(r) if r else np.empty((0, 9)) for r in results]
 
 
 def _score(gt: dict, results: list, benchmark: str, seq_lengths) -> list:

@@ -77,6 +77,22 @@ int bx_feed_create_shared(int n_seq, int emb_dim, const int64_t *seq_rows_host,
                           const int32_t *row_cnt_host, const int32_t *frame_id_host,
                           const int64_t *res_cap_host, int guard_rows, const int32_t *src_host,
                           bx_feed **out);
+/* bx_feed_create_shared with a choice of the steps' types, for an engine whose step takes
+ * float64 detections and writes 10-column rows (bx_ss_step):
+ *   det_f64   0: the runs' dets are float32 [rows][6]; 1: float64 [rows][6].  The packed rows are
+ *             stored and uploaded as float32 either way (bx_feed_upload_host is unchanged); the
+ *             gather writes each value widened to float64, which is exact
+ *   out_cols  8 or 10: columns of the runs' out rows.  With 10 the append reads the first 8
+ *             columns of each row (stride 10) and writes the same 9-column MOT row
+ * (0, 8) is bx_feed_create_shared exactly; any other det_f64 or out_cols is BX_ERR_INVALID.
+ * Run regions stay 256-byte aligned: BX_FEED_ROW_ALIGN rows of 48 or of 80 bytes are multiples of
+ * 256.  bx_feed_run reports, and bx_feed_read_run_host / bx_feed_write_run_host take, dets and out
+ * of the mode's types. */
+int bx_feed_create_shared_fmt(int n_seq, int emb_dim, const int64_t *seq_rows_host,
+                              const int64_t *tab_off_host, const int64_t *row_start_host,
+                              const int32_t *row_cnt_host, const int32_t *frame_id_host,
+                              const int64_t *res_cap_host, int guard_rows,
+                              const int32_t *src_host, int det_f64, int out_cols, bx_feed **out);
 int bx_feed_destroy(bx_feed *f);
 /* Bytes of device memory the feeder allocated at creation (host, no device work). */
 int bx_feed_device_bytes(bx_feed *f, int64_t *bytes);
@@ -89,8 +105,9 @@ int bx_feed_shape(bx_feed *f, int *n_frames, int *max_runs);
 int bx_feed_frame_runs(bx_feed *f, int t, int *n_runs);
 /* Run r of frame index t: its sequences, its detections and the device arrays of its step —
  * dets float32 [rows][6], det_off int32 [nseq + 1], embs float64 [rows][emb_dim] (NULL when
- * emb_dim is 0), out float64 [rows][8] and out_count int32 [nseq].  The arrays are the feeder's
- * and are reused by the next frame index. */
+ * emb_dim is 0), out float64 [rows][8] and out_count int32 [nseq]; dets float64 [rows][6] and out
+ * float64 [rows][out_cols] in the modes of bx_feed_create_shared_fmt.  The arrays are the
+ * feeder's and are reused by the next frame index. */
 int bx_feed_run(bx_feed *f, int t, int r, int *seq0, int *nseq, int *rows, void **dets,
                 void **det_off, void **embs, void **out, void **out_count);
 /* Gather every run of frame index t (one launch; none when the frame has no run). */
@@ -114,8 +131,10 @@ int bx_feed_results_host(bx_feed *f, double *res_host, int64_t *base_host, int64
  * caller orders its reads behind the appends.  Valid until bx_feed_destroy. */
 int bx_feed_results_device(bx_feed *f, void **res, void **base, void **n, int64_t *rows);
 /* Diagnostics (synchronous): read back the gathered inputs of run r of frame index t (after a
- * gather of t), and write out / out_count of that run from host arrays (before an append). */
-int bx_feed_read_run_host(bx_feed *f, int t, int r, float *dets_host, int32_t *det_off_host,
+ * gather of t), and write out / out_count of that run from host arrays (before an append).
+ * dets_host is float32 [rows][6], or float64 [rows][6] for a feeder created with det_f64;
+ * out_host is float64 [rows][out_cols]. */
+int bx_feed_read_run_host(bx_feed *f, int t, int r, void *dets_host, int32_t *det_off_host,
                           double *embs_host);
 int bx_feed_write_run_host(bx_feed *f, int t, int r, const double *out_host,
                            const int32_t *out_count_host);

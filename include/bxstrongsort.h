@@ -89,6 +89,45 @@ int bx_ss_update_host(bx_ss *e, int seq, const double *dets, int n, const double
  * sequence's tracker state of `src` into `dst`, a fresh engine with the same configuration and
  * sequences and track_cap / det_cap at least src's (slot ids stay valid).  Synchronous. */
 int bx_ss_copy_state(bx_ss *dst, bx_ss *src);
+/* Per-sequence parameters (a hyper-parameter sweep: K configs x S sequences as K*S sequences of
+ * one engine; boxmot_amd.tune.sweep_strong).  The names, order and meaning of
+ * bx_ss_config's: every field of it that sizes no memory. */
+typedef struct {
+    double min_conf, max_cos_dist, max_iou_dist;
+    int32_t max_age, n_init, nn_budget;
+    double mc_lambda, ema_alpha, conf_thresh_high, conf_thresh_low, id_preservation_weight;
+    int32_t crowd_detection, born_confirmed;
+} bx_ss_seq_params;
+/* Give sequences [seq0, seq0+nseq) parameters of their own: params_host [nseq], read as
+ * bx_ss_create reads the configuration, the flags as != 0.  NULL clears the range: those
+ * sequences run on the engine's values again.  n_seq, track_cap, det_cap, emb_dim and vec_cap stay
+ * engine-wide.  Every entry is checked before anything is written, by bx_ss_create's checks on the
+ * same fields: nn_budget > 0, max_age >= 0, max(nn_budget, crowd budget min(2 nn_budget, 300))
+ * + 10 <= 320, and no more than the engine's own nn_budget gives, which sized the galleries.  A
+ * failing entry or a bad range is BX_ERR_INVALID and changes nothing.
+ *
+ * Contract with the state crowd mode adapts.  A sequence's live max_age, nn_budget and
+ * metric.matching_threshold are device state that crowd mode saves, scales and restores per
+ * sequence.  An entry's max_age, nn_budget and max_cos_dist are the SEEDS of that state, not live
+ * values: the set writes them into the sequence's state (live value and restore value alike),
+ * bx_ss_reset seeds a sequence from its entry when it has one and from the engine's configuration
+ * otherwise, and crowd mode then works on the sequence's state exactly as without a table, so it
+ * restores to the entry's values.  A set or a clear is therefore accepted only for sequences
+ * whose frame counter (bx_ss_counters_host) is 0, fresh or just reset; otherwise it is
+ * BX_ERR_INVALID and changes nothing.  A clear seeds the engine's values.  The other ten fields
+ * are read by the frame's kernels each frame.
+ *
+ * The entry applies to bx_ss_step and bx_ss_update_host alike.  The first set allocates the
+ * device table; an engine on which none was ever set launches the kernels built without it.
+ * bx_ss_reset keeps the table, bx_ss_copy_state does not copy it (it copies the tracks and the
+ * sequences' adapted state: set the table on the fresh engine first, then copy).  Synchronises the
+ * device before anything is read or written and `stream` after. */
+int bx_ss_set_seq_params_host(bx_ss *e, int seq0, int nseq, const bx_ss_seq_params *params_host,
+                              void *stream);
+/* The parameters sequence `seq` runs on (host mirror, no device work): its own as they were given
+ * when set, else the engine's.  max_age, nn_budget and max_cos_dist are the seeds, not what crowd
+ * mode made of them. */
+int bx_ss_seq_params_host(bx_ss *e, int seq, bx_ss_seq_params *out_host);
 int bx_ss_status(bx_ss *e, int *status);
 /* Per-sequence counters (host): frame count, next id, live tracks, lost-buffer tracks. */
 int bx_ss_counters_host(bx_ss *e, int seq, int *frame_count, int *next_id, int *n_tracks,
