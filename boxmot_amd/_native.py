@@ -327,6 +327,7 @@ EXPORTS = [
     "bx_hybrid_bank_mean",
     "bx_gsi_plan_workspace_bytes", "bx_gsi_interpolate_plan", "bx_gsi_interpolate",
     "bx_gsi_workspace_bytes", "bx_gsi_smooth", "bx_gsi_run_host",
+    "bx_gsi_device_plan", "bx_gsi_device_run", "bx_gsi_device_free",
     "bx_feed_create", "bx_feed_destroy", "bx_feed_upload_host", "bx_feed_shape",
     "bx_feed_frame_runs", "bx_feed_run", "bx_feed_gather", "bx_feed_append", "bx_feed_status",
     "bx_feed_result_rows", "bx_feed_results_host", "bx_feed_results_device",
@@ -527,6 +528,10 @@ _SIGS = {
                        _vp, _vp], C.c_int),
     "bx_gsi_run_host": ([_vp, C.c_int64, C.c_int, C.c_int, C.c_double, _vp, C.c_int64,
                          C.POINTER(C.c_int64), _vp], C.c_int),
+    "bx_gsi_device_plan": ([_vp, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int64),
+                            C.POINTER(C.c_void_p), _vp], C.c_int),
+    "bx_gsi_device_run": ([_vp, C.c_double, C.c_int, _vp, C.c_int64, _vp, _vp, _vp], C.c_int),
+    "bx_gsi_device_free": ([_vp], C.c_int),
     "bx_feed_create": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
                         C.POINTER(C.c_void_p)], C.c_int),
     "bx_feed_create_shared": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp,

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -180,6 +181,75 @@ __global__ void gsi_fill_kernel(const Key* keys, const double* rows, int R, int 
   if (p == R - 1) track_off[t + 1] = pos + 1;
 }
 
+// ---------------------------------------------------------------- result slots in device memory
+// The slot-aware key/pack stage.  One thread per candidate row i of the packed order (slot 0's
+// rows, then slot 1's, ...): its slot is the last q with pre[q] <= i (pre: the exclusive prefix of
+// n, n_seq + 1 entries; empty slots share a prefix value with their successor and are passed
+// over), its row's columns 0..7 go to packed[i] and its key to keys[i].  Only rows inside a slot
+// are addressed.  Threads R..P-1 write the padding keys of gsi_keys_kernel.
+__global__ void gsi_slot_pack_kernel(const double* rows, long long stride, const long long* base,
+                                     const long long* pre, int n_seq, int R, int P,
+                                     double* packed, Key* keys) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  Key k;
+  if (i < R) {
+    int lo = 0, hi = n_seq - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (pre[mid] <= i) lo = mid;
+      else hi = mid - 1;
+    }
+    const double* r = rows + (size_t)(base[lo] + ((long long)i - pre[lo])) * (size_t)stride;
+    double* p = packed + (size_t)i * 8;
+#pragma unroll
+    for (int q = 0; q < 8; q++) p[q] = r[q];
+    k.frame = p[0];
+    k.id = p[1];
+    k.seq = lo;
+    k.idx = i;
+  } else {
+    k.frame = 0.0;
+    k.id = 0.0;
+    k.seq = INT_MAX;
+    k.idx = i;
+  }
+  keys[i] = k;
+}
+
+// The finalise stage, one thread per output row, sequence and tracklet (whichever are more):
+//   * row i: every value truncated toward zero, what "%d" writes and a reader gets back; the
+//     + 0.0 turns the -0.0 of a negative fraction into +0.0 (the library is built without
+//     fast-math, so it stays);
+//   * sequence q: out_base / out_n from the sorted labels oseq, as the lower bounds of q and
+//     q + 1, so a sequence without rows, wherever it lies, gets its successor's base and n = 0;
+//   * tracklet t: the smallest t whose factorisation failed, into *fail (preset above any t).
+__global__ void gsi_finalise_kernel(double* out, const int32_t* oseq, int n_out, int n_seq,
+                                    int truncate, const int32_t* status, int n_tracks,
+                                    long long* out_base, long long* out_n, int* fail) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_out && truncate) {
+    double* o = out + (size_t)i * 9;
+#pragma unroll
+    for (int q = 0; q < 9; q++) o[q] = trunc(o[q]) + 0.0;
+  }
+  if (i < n_seq) {
+    int b[2];
+    for (int e = 0; e < 2; e++) {
+      int lo = 0, hi = n_out;  // first row whose label is >= i + e
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (oseq[mid] < i + e) lo = mid + 1;
+        else hi = mid;
+      }
+      b[e] = lo;
+    }
+    out_base[i] = b[0];
+    out_n[i] = b[1] - b[0];
+  }
+  if (i < n_tracks && status[i] != BX_OK) atomicMin(fail, i);
+}
+
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 int pow2_at_least(int64_t n) {
   int p = 1;
@@ -200,6 +270,38 @@ PlanLayout plan_layout(int64_t R) {
   l.total = l.tidx + align256((size_t)R * 4) + 256;
   return l;
 }
+// the sort of the P keys in the workspace w and the scan of the first R of them
+void sort_scan(const PlanLayout& l, int R, int interval, char* w, int64_t* counts,
+               hipStream_t st) {
+  Key* keys = (Key*)(w + l.keys);
+  const int P = l.P, nblk = (P + 255) / 256;
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) gsi_bitonic_kernel<<<nblk, 256, 0, st>>>(keys, P, k, j);
+  gsi_scan_kernel<<<1, 1024, 0, st>>>(keys, R, interval, (int*)(w + l.cnt), (int*)(w + l.opos),
+                                      (int*)(w + l.tidx), (long long*)counts);
+}
+
+// device allocations that live as long as their owner
+struct DevBufs {
+  std::vector<void*> p;
+  ~DevBufs() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  hipError_t get(void** q, size_t bytes) {
+    const hipError_t e = hipMalloc(q, bytes ? bytes : 1);
+    if (e == hipSuccess) p.push_back(*q);
+    return e;
+  }
+};
+
+// what bx_gsi_device_plan leaves for bx_gsi_device_run
+struct DevicePlan {
+  DevBufs bufs;
+  int64_t R = 0, n_out = 0;
+  int n_seq = 0, n_tracks = 0;
+  double* packed = nullptr;  // [R][8], slot order
+  void* ws = nullptr;        // plan_layout(R)
+};
 
 // ---------------------------------------------------------------------------------- smoothing
 // offset of row i of the packed layout of a tracklet of n rows (rows >= n: right-hand sides)
@@ -493,15 +595,9 @@ int bx_gsi_interpolate_plan(const double* rows, const int32_t* seq, int64_t R, i
   const PlanLayout l = plan_layout(R);
   if (ws_bytes < l.total) return gsi_err(BX_ERR_CAPACITY, "gsi: interpolation workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)ws;
-  Key* keys = (Key*)(w + l.keys);
-  const int P = l.P, nblk = (P + 255) / 256;
-  gsi_keys_kernel<<<nblk, 256, 0, st>>>(rows, seq, (int)R, C, P, keys);
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) gsi_bitonic_kernel<<<nblk, 256, 0, st>>>(keys, P, k, j);
-  gsi_scan_kernel<<<1, 1024, 0, st>>>(keys, (int)R, interval, (int*)(w + l.cnt),
-                                      (int*)(w + l.opos), (int*)(w + l.tidx),
-                                      (long long*)counts);
+  gsi_keys_kernel<<<(l.P + 255) / 256, 256, 0, st>>>(rows, seq, (int)R, C, l.P,
+                                                     (Key*)((char*)ws + l.keys));
+  sort_scan(l, (int)R, interval, (char*)ws, counts, st);
   BX_HIPCHK(hipGetLastError());
   return BX_OK;
 }
@@ -566,17 +662,7 @@ int bx_gsi_run_host(const double* rows_host, int64_t R, int C, int interval, dou
   *n_out = 0;
   if (R == 0) return BX_OK;
   hipStream_t st = (hipStream_t)stream;
-  struct Bufs {
-    std::vector<void*> p;
-    ~Bufs() {
-      for (void* q : p) (void)hipFree(q);
-    }
-    hipError_t get(void** q, size_t bytes) {
-      const hipError_t e = hipMalloc(q, bytes ? bytes : 1);
-      if (e == hipSuccess) p.push_back(*q);
-      return e;
-    }
-  } bufs;
+  DevBufs bufs;
   size_t pbytes = 0;
   if (const int rc = bx_gsi_plan_workspace_bytes(R, &pbytes)) return rc;
   void *d_rows, *d_plan, *d_counts;
@@ -618,6 +704,126 @@ int bx_gsi_run_host(const double* rows_host, int64_t R, int C, int interval, dou
     if (status[k] != BX_OK)
       return gsi_err(BX_ERR_INVALID, "gsi: tracklet " + std::to_string(k) +
                                          ": the kernel matrix is not positive definite");
+  return BX_OK;
+}
+
+int bx_gsi_device_plan(const double* rows, int64_t row_stride, const int64_t* base,
+                       const int64_t* n, int n_seq, int interval, int64_t* counts_host,
+                       void** plan, void* stream) {
+  if (!counts_host || !plan || n_seq < 0 || row_stride < 8 || (n_seq > 0 && (!base || !n)))
+    return gsi_err(BX_ERR_INVALID, "gsi: bad result-slot arguments");
+  *plan = nullptr;
+  counts_host[0] = counts_host[1] = 0;
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int64_t> hb((size_t)n_seq), hn((size_t)n_seq), pre((size_t)n_seq + 1, 0);
+  if (n_seq) {
+    BX_HIPCHK(hipMemcpyAsync(hb.data(), base, (size_t)n_seq * 8, hipMemcpyDeviceToHost, st));
+    BX_HIPCHK(hipMemcpyAsync(hn.data(), n, (size_t)n_seq * 8, hipMemcpyDeviceToHost, st));
+    BX_HIPCHK(hipStreamSynchronize(st));
+  }
+  for (int q = 0; q < n_seq; q++) {
+    if (hb[q] < 0 || hn[q] < 0)
+      return gsi_err(BX_ERR_INVALID, "gsi: slot " + std::to_string(q) + " has a negative base or n");
+    pre[q + 1] = pre[q] + hn[q];
+    if (pre[q + 1] >= INT_MAX / 2)
+      return gsi_err(BX_ERR_INVALID, "gsi: the slots hold too many rows for one call");
+  }
+  const int64_t R = pre[n_seq];
+  if (R > 0 && !rows) return gsi_err(BX_ERR_INVALID, "gsi: null rows");
+  DevicePlan* p = new DevicePlan;
+  struct Guard {  // (released on success)
+    DevicePlan* p;
+    ~Guard() { delete p; }
+  } guard{p};
+  p->R = R;
+  p->n_seq = n_seq;
+  if (R > 0) {
+    const PlanLayout l = plan_layout(R);
+    void *d_pre, *d_counts, *d_packed;
+    BX_HIPCHK(p->bufs.get(&d_pre, pre.size() * 8));
+    BX_HIPCHK(p->bufs.get(&d_counts, 16));
+    BX_HIPCHK(p->bufs.get(&d_packed, (size_t)R * 8 * sizeof(double)));
+    BX_HIPCHK(p->bufs.get(&p->ws, l.total));
+    p->packed = (double*)d_packed;
+    BX_HIPCHK(hipMemcpyAsync(d_pre, pre.data(), pre.size() * 8, hipMemcpyHostToDevice, st));
+    gsi_slot_pack_kernel<<<(l.P + 255) / 256, 256, 0, st>>>(
+        rows, (long long)row_stride, (const long long*)base, (const long long*)d_pre, n_seq,
+        (int)R, l.P, p->packed, (Key*)((char*)p->ws + l.keys));
+    sort_scan(l, (int)R, interval, (char*)p->ws, (int64_t*)d_counts, st);
+    BX_HIPCHK(hipGetLastError());
+    BX_HIPCHK(hipMemcpyAsync(counts_host, d_counts, 16, hipMemcpyDeviceToHost, st));
+    BX_HIPCHK(hipStreamSynchronize(st));
+    if (counts_host[0] >= INT_MAX / 2)
+      return gsi_err(BX_ERR_INVALID, "gsi: the interpolation yields too many rows for one call");
+    p->n_out = counts_host[0];
+    p->n_tracks = (int)counts_host[1];
+  }
+  guard.p = nullptr;
+  *plan = p;
+  return BX_OK;
+}
+
+int bx_gsi_device_run(void* plan, double tau, int truncate, double* out, int64_t cap,
+                      int64_t* out_base, int64_t* out_n, void* stream) {
+  DevicePlan* p = (DevicePlan*)plan;
+  if (!p || cap < 0 || (p->n_seq > 0 && (!out_base || !out_n)))
+    return gsi_err(BX_ERR_INVALID, "gsi: bad result-slot arguments");
+  if (!(tau > 0.0)) return gsi_err(BX_ERR_INVALID, "gsi: tau must be positive");
+  if (p->n_out > cap || (p->n_out > 0 && !out))
+    return gsi_err(BX_ERR_CAPACITY, "gsi: output holds fewer rows than the interpolation yields");
+  hipStream_t st = (hipStream_t)stream;
+  if (p->n_out == 0) {  // no slot has a row
+    if (p->n_seq) {
+      BX_HIPCHK(hipMemsetAsync(out_base, 0, (size_t)p->n_seq * 8, st));
+      BX_HIPCHK(hipMemsetAsync(out_n, 0, (size_t)p->n_seq * 8, st));
+    }
+    BX_HIPCHK(hipStreamSynchronize(st));
+    return BX_OK;
+  }
+  const int nt = p->n_tracks, n_out = (int)p->n_out;
+  void *d_interp, *d_oseq, *d_off, *d_status, *d_fail, *d_ws;
+  BX_HIPCHK(p->bufs.get(&d_interp, (size_t)n_out * 8 * sizeof(double)));
+  BX_HIPCHK(p->bufs.get(&d_oseq, (size_t)n_out * 4));
+  BX_HIPCHK(p->bufs.get(&d_off, ((size_t)nt + 1) * 4));
+  BX_HIPCHK(p->bufs.get(&d_status, (size_t)nt * 4));
+  BX_HIPCHK(p->bufs.get(&d_fail, 4));
+  if (const int rc = bx_gsi_interpolate(p->packed, p->R, 8, p->ws, (double*)d_interp,
+                                        (int32_t*)d_oseq, n_out, (int32_t*)d_off, st))
+    return rc;
+  std::vector<int32_t> off((size_t)nt + 1);
+  BX_HIPCHK(hipMemcpyAsync(off.data(), d_off, off.size() * 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
+  size_t sbytes = 0;
+  if (const int rc = bx_gsi_workspace_bytes(off.data(), nt, 0, &sbytes)) return rc;
+  BX_HIPCHK(p->bufs.get(&d_ws, sbytes));
+  if (const int rc = bx_gsi_smooth((const double*)d_interp, 8, off.data(), nt, tau, 0, d_ws, sbytes,
+                                   out, (int32_t*)d_status, st))
+    return rc;
+  BX_HIPCHK(hipMemsetAsync(d_fail, 0x7f, 4, st));  // above any tracklet index
+  const int threads = n_out > p->n_seq ? n_out : p->n_seq;  // (n_out >= nt)
+  gsi_finalise_kernel<<<(threads + 255) / 256, 256, 0, st>>>(
+      out, (const int32_t*)d_oseq, n_out, p->n_seq, truncate, (const int32_t*)d_status, nt,
+      (long long*)out_base, (long long*)out_n, (int*)d_fail);
+  BX_HIPCHK(hipGetLastError());
+  int fail = 0;
+  BX_HIPCHK(hipMemcpyAsync(&fail, d_fail, 4, hipMemcpyDeviceToHost, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
+  if (fail < nt) {
+    double id = 0.0;
+    BX_HIPCHK(hipMemcpy(&id, (const double*)d_interp + (size_t)off[fail] * 8 + 1, 8,
+                        hipMemcpyDeviceToHost));
+    char ident[32];
+    snprintf(ident, sizeof(ident), "%g", id);
+    return gsi_err(BX_ERR_INVALID, std::string("the kernel matrix of id ") + ident + " (" +
+                                       std::to_string(off[fail + 1] - off[fail]) +
+                                       " rows) is not positive definite: duplicate or "
+                                       "non-finite frames?");
+  }
+  return BX_OK;
+}
+
+int bx_gsi_device_free(void* plan) {
+  delete (DevicePlan*)plan;
   return BX_OK;
 }
 

@@ -145,6 +145,70 @@ def gsi_batch(arrays, interval: int = 20, tau: float = 10) -> list:
     return res
 
 
+def gsi_device(rows, base, n, n_seq: int | None = None, interval: int = 20, tau: float = 10,
+               row_stride: int = 9, truncate: bool = True):
+    """GSI of result slots in device memory (``SequenceFeeder.results_device``) into rows in
+    device memory that ``MotEvaluator.run_device`` takes as they are: sequence ``q`` owns rows
+    ``[base[q], base[q] + n[q])`` of ``rows`` (``[., row_stride]`` float64, ``row_stride >= 8``),
+    and rows outside the slots are never read.  ``rows`` / ``base`` / ``n`` are contiguous CUDA
+    tensors (float64, int64, int64) or raw integer device pointers; ``n_seq`` is needed with raw
+    pointers only (a pointer carries no length) and defaults to ``n.numel()``.
+
+    Returns CUDA tensors ``(out_rows [n_out, 9] float64, out_base [n_seq] int64, out_n [n_seq]
+    int64)``: the sequences consecutively in input order, each holding the bits
+    ``gsi_batch([its rows], interval, tau)[0]`` holds, and with ``truncate`` every value truncated
+    toward zero (a zero is ``+0.0``), which is what ``np.loadtxt`` reads from the file ``gsi``
+    leaves.  Equal ids in different sequences are different tracklets.  No row crosses to the
+    host; the counts, the tracklet offsets and ``base`` / ``n`` do (include/bxgsi.h).
+    ``LinAlgError`` / ``ValueError`` as in the host path."""
+    L, torch, st = _device()
+    dev = torch.device("cuda")
+    S = None if n_seq is None else int(n_seq)
+    ptr = []
+    for name, x, dt in (("rows", rows, torch.float64), ("base", base, torch.int64),
+                        ("n", n, torch.int64)):
+        if isinstance(x, torch.Tensor):
+            if not x.is_cuda or x.dtype != dt or not x.is_contiguous():
+                raise ValueError(f"gsi_device: {name} must be a contiguous CUDA {dt} tensor")
+            if name == "n" and S is None:
+                S = x.numel()
+            if name != "rows" and S is not None and x.numel() < S:
+                raise ValueError(f"gsi_device: {name} needs n_seq = {S} entries")
+            ptr.append(x.data_ptr() if x.numel() else None)
+        else:
+            ptr.append(int(x) or None)
+    if S is None:
+        raise ValueError("gsi_device: raw pointers carry no length: give n_seq")
+    if S < 0 or int(row_stride) < 8:
+        raise ValueError("gsi_device: n_seq must not be negative and row_stride at least 8")
+    if isinstance(rows, torch.Tensor):
+        if rows.numel() % int(row_stride):
+            raise ValueError("gsi_device: rows is not a whole number of row_stride columns")
+        if S and isinstance(base, torch.Tensor) and isinstance(n, torch.Tensor):
+            have = rows.numel() // int(row_stride)
+            b, c = base[:S], n[:S]
+            if bool(((b < 0) | (c < 0) | (b + c > have)).any()):
+                raise ValueError("gsi_device: base / n reach outside the rows tensor")
+    counts = (C.c_int64 * 2)()
+    plan = C.c_void_p()
+    N.check(L.bx_gsi_device_plan(ptr[0], int(row_stride), ptr[1], ptr[2], S, int(interval),
+                                 counts, C.byref(plan), st), "bx_gsi_device_plan")
+    try:
+        out = torch.empty((counts[0], 9), dtype=torch.float64, device=dev)
+        out_base = torch.zeros(S, dtype=torch.int64, device=dev)
+        out_n = torch.zeros(S, dtype=torch.int64, device=dev)
+        rc = L.bx_gsi_device_run(plan, float(tau), int(bool(truncate)),
+                                 out.data_ptr() if counts[0] else None, counts[0],
+                                 out_base.data_ptr() if S else None,
+                                 out_n.data_ptr() if S else None, st)
+        if rc == 1 and b"not positive definite" in L.bx_last_error():
+            raise np.linalg.LinAlgError(L.bx_last_error().decode(errors="replace"))
+        N.check(rc, "bx_gsi_device_run")
+    finally:
+        L.bx_gsi_device_free(plan)
+    return out, out_base, out_n
+
+
 def gsi(mot_results_folder: Path, interval: int = 20, tau: float = 10):
     """gsi.py:115-142: apply GSI in place to every ``MOT*.txt`` of the folder (comma-separated in,
     the reference's space-separated ``%d`` rows out; a file without rows is left untouched)."""

@@ -16,6 +16,9 @@ them too (``sweep_bot``), fed the same way, and so has BoostTrac
 (``sweep_boost``), whose variants differ in constructor flags only.  StrongSort
 (``sweep_strong``) completes the set: its feeder gathers float64 detections and
 10-column rows, and its occlusion post-process stays on the host, per sweep.
+
+``sweep_gsi`` runs any of the five with GSI between tracking and scoring, on the
+feeder's result slots in device memory (``postprocessing.gsi_device``, include/bxgsi.h).
 """
 from __future__ import annotations
 
@@ -122,6 +125,14 @@ def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict
     The detections are uploaded once per (config, sequence): K copies of a few MB for MOT-sized
     inputs.  A nonzero engine or feeder status raises ``RuntimeError``.
     """
+    return _sweep(tracker_type, sequences, configs, None, exp_dir=exp_dir, gt=gt,
+                  benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
+                  frame_sizes=frame_sizes, score=score, keep_results=keep_results)
+
+
+def _sweep(tracker_type, sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths,
+           frame_ids, frame_sizes, score, keep_results) -> list:
+    """``sweep``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
     configs = _check(tracker_type, configs, sequences, gt, exp_dir, score, keep_results)
     from . import motio
     from .engine import OcsortTableEngine, SequenceFeeder
@@ -153,12 +164,12 @@ def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict
             eng.step(pd, po, pout, pcnt, seq0=q0, nseq=ns)
 
         rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                 keep_results)
+                                 keep_results, post)
     finally:
         if feed is not None:
             feed.close()
         eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
 
 
 def _frame_tables(names, seqs, frame_ids) -> tuple:
@@ -177,10 +188,14 @@ def _frame_tables(names, seqs, frame_ids) -> tuple:
     return fids, tables
 
 
-def _drive(eng, feed, step, K: int, gt, benchmark, seq_lengths, score, keep_results) -> tuple:
+def _drive(eng, feed, step, K: int, gt, benchmark, seq_lengths, score, keep_results,
+           post=None) -> tuple:
     """The frame loop both sweeps share: per frame index one gather, ``step(t, run)`` for each of
     its runs and one append; then the status checks, the device-side scores and the one copy of
-    the rows.  Returns (rows per engine sequence or None, summaries per config or None)."""
+    the rows.  Returns (rows per engine sequence or None, summaries per config or None).
+
+    ``post`` (``sweep_gsi``'s (interval, tau)): the feeder's slots go through ``gsi_device`` once;
+    its three tensors are what the device scores and what comes back as the rows."""
     for t in range(feed.n_frames):
         runs = feed.schedule[t]
         if not runs:
@@ -192,17 +207,49 @@ def _drive(eng, feed, step, K: int, gt, benchmark, seq_lengths, score, keep_resu
     if eng.status() != 0:
         raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
     summaries = None
+    if post is not None:
+        from .postprocessing import gsi_device
+
+        if feed.status() != 0:
+            raise RuntimeError(f"feeder status {feed.status()} (result buffer overflow)")
+        res, base, n, _ = feed.results_device
+        post = gsi_device(res, base, n, feed.n_seq, *post)
     if score == "device":
         if feed.status() != 0:
             raise RuntimeError(f"feeder status {feed.status()} (result buffer overflow)")
-        summaries = _score_device(gt, feed, K, benchmark, seq_lengths)
-    return (feed.results() if keep_results else None), summaries
+        summaries = _score_device(gt, feed, K, benchmark, seq_lengths, post)
+    if not keep_results:
+        return None, summaries
+    if post is None:
+        return feed.results(), summaries
+    out, b, c = (x.cpu().numpy() for x in post)
+    return [out[b[q]: b[q] + c[q]] for q in range(feed.n_seq)], summaries
 
 
-def _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths) -> list:
+def _gsi_host_rows(rows: list, post) -> list:
+    """``sweep_gsi``'s post-stage for rows that were formed on the host (a StrongSort sweep with
+    handle_occlusions): every engine sequence's rows as one slot of one ``gsi_device`` call."""
+    import torch
+
+    from .postprocessing import gsi_device
+
+    n = np.array([r.shape[0] for r in rows], np.int64)
+    base = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64)
+    flat = np.ascontiguousarray(np.concatenate([r.reshape(-1, 9) for r in rows]), np.float64)
+    out, b, c = (x.cpu().numpy() for x in gsi_device(
+        torch.from_numpy(flat).cuda(), torch.from_numpy(base).cuda(), torch.from_numpy(n).cuda(),
+        None, *post))
+    return [out[b[q]: b[q] + c[q]] for q in range(len(rows))]
+
+
+def _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths,
+            post=None) -> list:
     """One entry per config from the rows of engine sequences ``k*S + s``: the files under
-    ``exp_dir``, and the host-side scores when the device did not score."""
+    ``exp_dir``, and the host-side scores when the device did not score.  With ``post`` the rows
+    are ``gsi_device``'s and the files are what ``postprocessing.gsi`` leaves: space-separated
+    ``%d`` rows, and an empty file for a sequence without rows."""
     from . import motio
+    from .postprocessing import MOT_FMT
 
     S = len(names)
     out = []
@@ -213,8 +260,12 @@ def _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths
         res = {nm: rows[k * S + q].copy() for q, nm in enumerate(names)}
         if exp_dir is not None:
             for nm, r in res.items():
-                motio.write_mot_results(Path(exp_dir) / f"{k:04d}" / f"{nm}.txt",
-                                        r if r.size else np.empty((0, 0)))
+                p = Path(exp_dir) / f"{k:04d}" / f"{nm}.txt"
+                if post is None or not r.size:
+                    motio.write_mot_results(p, r if r.size else np.empty((0, 0)))
+                else:
+                    p.parent.mkdir(parents=True, exist_ok=True)
+                    np.savetxt(p, r, fmt=MOT_FMT)
         out.append({"config": cfg, "results": res, "summary": None})
     if summaries is not None:
         for o, summary in zip(out, summaries):
@@ -286,6 +337,15 @@ def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
     camera-motion compensation off (``cmc_off`` / ``use_ecc``), sequences whose embedding widths
     differ, and the ``score`` / ``keep_results`` combinations ``sweep`` refuses.
     """
+    return _sweep_reid(tracker_type, sequences, configs, None, exp_dir=exp_dir, gt=gt,
+                       benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
+                       frame_sizes=frame_sizes, score=score, keep_results=keep_results,
+                       warps=warps)
+
+
+def _sweep_reid(tracker_type, sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths,
+                frame_ids, frame_sizes, score, keep_results, warps) -> list:
+    """``sweep_reid``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
     configs = _check_reid(tracker_type, configs, sequences, gt, exp_dir, score, keep_results,
                           warps)
     from . import motio
@@ -332,12 +392,12 @@ def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
                         None if table is None else table[t, q0: q0 + ns])
 
         rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                 keep_results)
+                                 keep_results, post)
     finally:
         if feed is not None:
             feed.close()
         eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
 
 
 def _check_bot(tracker_type: str, configs, sequences, gt, exp_dir, score, keep_results,
@@ -380,6 +440,14 @@ def sweep_bot(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
     configs, ``warps`` with bytetrack, sequences whose embedding widths differ, and the ``score``
     / ``keep_results`` combinations ``sweep`` refuses.
     """
+    return _sweep_bot(tracker_type, sequences, configs, None, exp_dir=exp_dir, gt=gt,
+                      benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
+                      score=score, keep_results=keep_results, warps=warps)
+
+
+def _sweep_bot(tracker_type, sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths,
+               frame_ids, score, keep_results, warps) -> list:
+    """``sweep_bot``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
     configs = _check_bot(tracker_type, configs, sequences, gt, exp_dir, score, keep_results,
                          warps)
     from . import motio
@@ -424,12 +492,12 @@ def sweep_bot(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
                      seq0=q0, nseq=ns)
 
         rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                 keep_results)
+                                 keep_results, post)
     finally:
         if feed is not None:
             feed.close()
         eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
 
 
 def _boost_reid(cfg: dict) -> bool:
@@ -480,6 +548,14 @@ def sweep_boost(sequences: dict, configs, *, exp_dir=None, gt: dict | None = Non
     that switches ``use_ecc`` off, sequences whose embedding widths differ, and the ``score`` /
     ``gt`` / ``keep_results`` combinations ``sweep`` refuses.
     """
+    return _sweep_boost(sequences, configs, None, exp_dir=exp_dir, gt=gt, benchmark=benchmark,
+                        seq_lengths=seq_lengths, frame_ids=frame_ids, score=score,
+                        keep_results=keep_results, warps=warps)
+
+
+def _sweep_boost(sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths, frame_ids,
+                 score, keep_results, warps) -> list:
+    """``sweep_boost``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
     configs = _check_boost(configs, sequences, gt, exp_dir, score, keep_results, warps)
     from . import motio
     from . import engine as E
@@ -525,12 +601,12 @@ def sweep_boost(sequences: dict, configs, *, exp_dir=None, gt: dict | None = Non
                      seq0=q0, nseq=ns)
 
         rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                 keep_results)
+                                 keep_results, post)
     finally:
         if feed is not None:
             feed.close()
         eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
 
 
 def _strong_occ(cfg: dict) -> bool:
@@ -615,6 +691,14 @@ def sweep_strong(sequences: dict, configs, *, exp_dir=None, gt: dict | None = No
     detections rounded to float32, e.g. ``dets.astype(np.float32)``), and the ``score`` / ``gt`` /
     ``keep_results`` combinations ``sweep`` refuses.
     """
+    return _sweep_strong(sequences, configs, None, exp_dir=exp_dir, gt=gt, benchmark=benchmark,
+                         seq_lengths=seq_lengths, frame_ids=frame_ids, score=score,
+                         keep_results=keep_results, warps=warps)
+
+
+def _sweep_strong(sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths, frame_ids,
+                  score, keep_results, warps) -> list:
+    """``sweep_strong``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
     configs = _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps)
     import dataclasses
 
@@ -669,16 +753,18 @@ def sweep_strong(sequences: dict, configs, *, exp_dir=None, gt: dict | None = No
 
         if occ_thr[0] is None:
             rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                     keep_results)
+                                     keep_results, post)
         else:
             rows, summaries = _drive_occlusion(eng, feed, step, fids * K,
                                                [tb[1] for tb in tables] * K,
                                                [t for t in occ_thr for _ in range(S)]), None
+            if post is not None:
+                rows = _gsi_host_rows(rows, post)
     finally:
         if feed is not None:
             feed.close()
         eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths)
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
 
 
 def _drive_occlusion(eng, feed, step, fids, feed_cnt, thresholds) -> list:
@@ -724,6 +810,61 @@ def _drive_occlusion(eng, feed, step, fids, feed_cnt, thresholds) -> list:
     return [np.vstack(r) if r else np.empty((0, 9)) for r in results]
 
 
+GSI_MAX_INTERVAL = 22
+# tracker -> the public sweep sweep_gsi runs for it (its keyword arguments, its implementation)
+GSI_DISPATCH = {"ocsort": "sweep", "deepocsort": "sweep_reid", "hybridsort": "sweep_reid",
+                "bytetrack": "sweep_bot", "botsort": "sweep_bot", "boosttrack": "sweep_boost",
+                "strongsort": "sweep_strong"}
+
+
+def sweep_gsi(tracker_type: str, sequences: dict, configs, *, interval: int = 20,
+              tau: float = 10, **sweep_kwargs) -> list:
+    """The sweep of ``tracker_type`` with GSI (``postprocessing.gsi``: tracklet interpolation and
+    Gaussian smoothing, the reference's ``val.py --gsi``) applied to every config's rows before
+    they are scored, returned or written: the flow track -> GSI -> evaluate, per config, in one
+    engine, one ``gsi_device`` call and one evaluator run.
+
+    ``tracker_type`` chooses the sweep (``GSI_DISPATCH``): ocsort -> ``sweep``; deepocsort,
+    hybridsort -> ``sweep_reid``; bytetrack, botsort -> ``sweep_bot``; boosttrack ->
+    ``sweep_boost``; strongsort -> ``sweep_strong``.  ``sweep_kwargs`` are that sweep's own keyword
+    arguments (``exp_dir``, ``gt``, ``score``, ``keep_results``, ``warps``, ...), with its meaning
+    and its refusals, raised before any engine is built.
+
+    Per config ``k``, ``results[name]`` is ``[n, 9]`` float64 with whole-number values, ids
+    ascending and frames ascending within an id: what ``np.loadtxt`` reads from the file
+    ``postprocessing.gsi`` leaves.  With ``exp_dir``, ``exp_dir/<k as 4 digits>/<name>.txt`` is
+    byte-identical to what the plain sweep writes there followed by ``gsi(exp_dir/<k as 4
+    digits>, interval, tau)``: space-separated ``%d`` rows, and a sequence without rows keeps its
+    empty file.  ``gsi`` globs ``MOT*.txt`` only; ``sweep_gsi`` treats EVERY sequence, whatever
+    its name.  ``score="host"`` evaluates those arrays; ``score="device"`` runs ``gsi_device`` on
+    the feeder's result slots and scores its tensors in one evaluator run of K groups, with
+    ``keep_results=False`` without copying a row to the host; the summaries are bit-identical.
+    A ``LinAlgError`` of the smoothing propagates.
+
+    ``interval`` must not exceed 22 (``ValueError``): the reference computes an inserted row's
+    frame as ``prev + (cur - prev) * (i / (cur - prev))`` in float64, which is a whole number for
+    every gap up to 21 (every ``prev`` in 1..3999 checked) but not from a gap of 22 on (first at
+    i = 15); ``%d`` truncates such a frame to the one before it, the id then stands twice in a
+    frame, and the evaluator refuses the rows.
+    """
+    if tracker_type not in GSI_DISPATCH:
+        raise NotImplementedError(
+            f"tune.sweep_gsi drives {', '.join(GSI_DISPATCH)} (the trackers with a sweep), not "
+            f"{tracker_type}")
+    if int(interval) > GSI_MAX_INTERVAL:
+        raise ValueError(
+            f"interval must not exceed {GSI_MAX_INTERVAL}, got {interval}: from a gap of 22 "
+            "frames on, the reference's prev + (cur - prev) * (i / (cur - prev)) is not a whole "
+            "number for every inserted frame, so after %d an id can stand twice in a frame, "
+            "which the evaluator refuses")
+    name = GSI_DISPATCH[tracker_type]
+    # the public sweep's defaults under the caller's keywords; one it does not have is the
+    # implementation's TypeError
+    kw = {**globals()[name].__kwdefaults__, **sweep_kwargs}
+    head = () if name in ("sweep_boost", "sweep_strong") else (tracker_type,)  # (one tracker)
+    return globals()["_" + name](*head, sequences, configs, (int(interval), float(tau)), **kw)
+
+
 def _score(gt: dict, results: list, benchmark: str, seq_lengths) -> list:
     """mot_summary of every config's results, as ``evaluate_mot(gt, results_k)`` gives it: the
     gt is parsed once, and one evaluator handle runs once per config."""
@@ -749,9 +890,11 @@ def _score(gt: dict, results: list, benchmark: str, seq_lengths) -> list:
     return summaries
 
 
-def _score_device(gt: dict, feed, n_groups: int, benchmark: str, seq_lengths) -> list:
+def _score_device(gt: dict, feed, n_groups: int, benchmark: str, seq_lengths,
+                  post=None) -> list:
     """mot_summary of every config from the feeder's device-resident rows: the gt is bucketed
-    and uploaded once, and ONE evaluator run of ``n_groups`` groups forms every COMBINED."""
+    and uploaded once, and ONE evaluator run of ``n_groups`` groups forms every COMBINED.
+    ``post``: None, or ``gsi_device``'s three tensors, scored in place of the feeder's slots."""
     from . import evaluation as E
 
     if benchmark not in E.BENCHMARKS:
@@ -759,7 +902,7 @@ def _score_device(gt: dict, feed, n_groups: int, benchmark: str, seq_lengths) ->
     if "COMBINED" in gt:
         raise ValueError("a sequence cannot be called COMBINED")
     names, frames, gts, _ = E.prepare_inputs(gt, {}, seq_lengths)
-    res, base, n, _ = feed.results_device
+    res, base, n = feed.results_device[:3] if post is None else post
     ev = E.MotEvaluator()
     try:
         ev.set_gt(frames, gts)

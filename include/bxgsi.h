@@ -6,6 +6,10 @@
  *   bx_gsi_interpolate_plan + bx_gsi_interpolate   linear_interpolation   gsi.py:13-54
  *   bx_gsi_smooth                                  gaussian_smooth        gsi.py:57-93
  *   bx_gsi_run_host                                process_file's two calls  gsi.py:106-109
+ *   bx_gsi_device_plan + bx_gsi_device_run         the same two calls, then process_file's
+ *                                                  np.savetxt(fmt="%d ...") and the evaluator's
+ *                                                  read of that file, for rows that stay in
+ *                                                  device memory
  *
  * Conventions as in bxassoc.h: pointer arguments are DEVICE pointers unless their name ends in
  * _host, calls are asynchronous on `stream` (NULL = the default stream), every function returns
@@ -81,6 +85,40 @@ int bx_gsi_smooth(const double *rows, int C, const int32_t *track_off_host, int 
  * factorisation failed. */
 int bx_gsi_run_host(const double *rows_host, int64_t R, int C, int interval, double tau,
                     double *out_host, int64_t cap, int64_t *n_out, void *stream);
+
+/* GSI from result slots in device memory to evaluator-ready rows in device memory: what
+ * bx_feed_results_device hands out goes in, what bx_eval_run_device takes (row_stride 9) comes
+ * out, and no result row crosses to the host.  Sequence q owns rows [base[q], base[q] + n[q]) of
+ * `rows`; rows outside the slots (slack, guard rows) are never read.  A tracklet is a run of one
+ * (sequence, id): equal ids in different sequences never merge.
+ *
+ * Plan: packs the slots' rows (columns 0..7) densely in slot order, sorts and counts them as
+ * bx_gsi_interpolate_plan does, and synchronises to bring two numbers back.
+ *   rows   [.][row_stride] float64, row_stride >= 8
+ *   base   [n_seq] int64, n [n_seq] int64 (both are read back: 16 * n_seq bytes)
+ *   counts_host [2] int64: rows of the output, tracklets
+ *   plan   receives a handle that owns its device memory; bx_gsi_device_free releases it
+ * BX_ERR_INVALID for a negative base or n, or a total of 2^30 - 1 rows or more (the limit of
+ * bx_gsi_interpolate_plan). */
+int bx_gsi_device_plan(const double *rows, int64_t row_stride, const int64_t *base,
+                       const int64_t *n, int n_seq, int interval, int64_t *counts_host,
+                       void **plan, void *stream);
+/* Run: interpolation, smoothing (bx_gsi_smooth: its paths, its bits, its BX_ERR_CAPACITY for a
+ * tracklet over BX_GSI_MAX_N) and the finalise pass; synchronises for the tracklet offsets and at
+ * the end.
+ *   out      [cap][9] float64, cap >= counts_host[0] (else BX_ERR_CAPACITY): sequences
+ *            consecutively in input order, within a sequence ids ascending and frames ascending
+ *            within an id, the values of bx_gsi_smooth on that sequence's rows alone
+ *   out_base [n_seq] int64 first output row of each sequence; out_n [n_seq] int64 its row count
+ *            (0 for a sequence without rows)
+ *   truncate nonzero: every value is truncated toward zero, as the reference's
+ *            np.savetxt(fmt="%d ...") leaves it in a file, and a zero is +0.0; 0: the float rows
+ * Read back: the tracklet offsets (4 bytes per tracklet) and one int32, the first tracklet whose
+ * factorisation met a non-positive pivot.  That is BX_ERR_INVALID; the message names the
+ * tracklet's id and its row count. */
+int bx_gsi_device_run(void *plan, double tau, int truncate, double *out, int64_t cap,
+                      int64_t *out_base, int64_t *out_n, void *stream);
+int bx_gsi_device_free(void *plan);
 
 #ifdef __cplusplus
 }
