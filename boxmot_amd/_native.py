@@ -42,7 +42,7 @@ HIPCC_FLAGS = [
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
            "bx_strongsort.hip", "bx_deepocsort.hip", "bx_hybridsort.hip", "bx_gsi.hip", "bx_feed.hip",
            "bx_classes.hip", "bx_eval.hip", "bx_cmc.hip", "bx_reid.hip", "bx_sof.hip",
-           "bx_io.cpp", "bx_boost_tab.hip", "bx_strongsort_tab.hip"]
+           "bx_io.cpp", "bx_boost_tab.hip", "bx_strongsort_tab.hip", "bx_strongsort_occ.hip"]
 
 
 class NativeUnavailable(RuntimeError):
@@ -294,6 +294,8 @@ EXPORTS = [
     "bx_boost_copy_state", "bx_ss_copy_state",
     "bx_boost_set_seq_params_host", "bx_boost_seq_params_host",
     "bx_ss_set_seq_params_host", "bx_ss_seq_params_host",
+    "bx_ss_set_occlusion_host", "bx_ss_occlusion_host", "bx_ss_occlusion_buffer_host",
+    "bx_pyset_order_host",
     "bx_nn_cosine_distance", "bx_ocsort_create", "bx_ocsort_destroy", "bx_ocsort_reset", "bx_ocsort_step",
     "bx_ocsort_update_host", "bx_ocsort_status", "bx_ocsort_counters_host",
     "bx_ocsort_set_id_count", "bx_ocsort_set_frame_size", "bx_ocsort_tracks_host", "bx_ocsort_probe", "bx_ocsort_probe_read",
@@ -410,6 +412,10 @@ _SIGS = {
     "bx_ss_copy_state": ([_vp, _vp], C.c_int),
     "bx_ss_set_seq_params_host": ([_vp, C.c_int, C.c_int, C.POINTER(BxSsSeqParams), _vp], C.c_int),
     "bx_ss_seq_params_host": ([_vp, C.c_int, C.POINTER(BxSsSeqParams)], C.c_int),
+    "bx_ss_set_occlusion_host": ([_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
+    "bx_ss_occlusion_host": ([_vp, C.c_int, _ip, _dp, _ip, _ip], C.c_int),
+    "bx_ss_occlusion_buffer_host": ([_vp, C.c_int, C.c_int, _vp, _ip], C.c_int),
+    "bx_pyset_order_host": ([_vp, C.c_int, _vp, _ip], C.c_int),
     "bx_engine_slots_used_host": ([_vp, C.c_int, _ip], C.c_int),
     "bx_lapjv": ([_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp], C.c_int),
     "bx_nn_cosine_distance": ([_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp,

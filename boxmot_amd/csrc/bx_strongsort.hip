@@ -63,6 +63,10 @@ void bx_ss_tab_match(const void* dev, dim3 grid, size_t lds, hipStream_t st, int
 void bx_ss_tab_post(const void* dev, dim3 grid, size_t lds, hipStream_t st, int seq0,
                     const int* off, double* out, int* cnt);
 void bx_ss_tab_reset(const void* dev, dim3 grid, hipStream_t st, int seq0, int nseq);
+// the occlusion pass's entry points (bx_strongsort_occ.hip): `occ` is the engine's SsOcc
+int bx_ss_occ_lds_attr(size_t lds);
+void bx_ss_occ_launch(const void* dev, const void* occ, int nseq, size_t lds, hipStream_t st,
+                      int seq0, const int* off, double* out);
 
 namespace {
 
@@ -160,6 +164,24 @@ struct SsDev {
   unsigned long long* dbg;  // [S][SS_DBG] phase stamps (diagnostic builds only, else null)
   const SsSeqPar* seqpar;   // [S] per-sequence parameters, null until the first set
 };
+// Occlusion handling on the device (bx_ss_set_occlusion_host; ss_occ_kernel in
+// bx_strongsort_occ.hip): per-sequence settings and latch, and per sequence a pool of `cap`
+// buffered tracks (OcclusionStateManager.occlusion_buffer: id -> deque(maxlen=10) of features).
+// Passed to ss_occ_kernel beside SsDev, which no other kernel's arguments change for.
+constexpr int OCC_RING = 10;
+struct SsOcc {
+  int cap;        // pool entries per sequence
+  int setcap;     // slots of one of the two set tables in LDS: bx_pyset_cap(track_cap - 1)
+  int* on;        // [S] handle_occlusions
+  double* thr;    // [S] occlusion_threshold
+  int* mutual;    // [S] update count at which a mutual occlusion latched, 0 = none
+  int* pid;       // [S][cap] track id of the entry, 0 = free
+  int* phead;     // [S][cap] ring position of the oldest vector
+  int* pcnt;      // [S][cap] vectors held (<= OCC_RING)
+  double* pnorm;  // [S][cap][OCC_RING] wave-order norms
+  double* pvec;   // [S][cap][OCC_RING][F]
+};
+
 // Entry of a kernel's table build (TAB; ss_launch picks it only for an engine with a table):
 // sequence s's own values over the kernel's copy of g.  s is workgroup-uniform, the loads come
 // before any store and no kernel writes the table, so these are scalar loads, once per workgroup.
@@ -3608,11 +3630,20 @@ void bx_ss_tab_reset(const void* dev, dim3 grid, hipStream_t st, int seq0, int n
   hipLaunchKernelGGL(ss_reset_kernel<true>, grid, dim3(256), 0, st, *(const SsDev*)dev, seq0,
                      nseq);
 }
-#else
+#elif !defined(BX_SS_OCC_UNIT)  // (bx_strongsort_occ.hip continues from here with its kernel)
+
+#include "bx_pyset.h"
 
 struct bx_ss {
   SsDev dev;
   bx_ss_config cfg;
+  // occlusion handling on the device (bx_ss_set_occlusion_host): the pools' arena, allocated by
+  // the first set (occ.cap stays 0 until then), and the settings' host mirror
+  SsOcc occ{};
+  void* occ_arena = nullptr;
+  size_t occ_bytes = 0;
+  std::vector<int> h_occ_on;
+  std::vector<double> h_occ_thr;
   // per-sequence parameters (bx_ss_set_seq_params_host): the device table dev.seqpar points to,
   // allocated by the first set, and its host mirror with the values as they were given
   SsSeqPar* d_seqpar = nullptr;
@@ -3632,6 +3663,52 @@ struct bx_ss {
 
 static size_t ss_lds_bytes(const SsDev& d) {
   return d.ws_lds == 1 ? (size_t)d.wsd_n * 8 + (size_t)d.wsi_n * 4 : (size_t)ws_lsap_bytes(d.N);
+}
+
+// ss_occ_kernel's dynamic LDS (its carve): 6T + PW_MAXLEAF doubles, then the ints
+static size_t occ_lds_bytes(int T, int cap, int setcap) {
+  return sizeof(double) * ((size_t)6 * T + PW_MAXLEAF) +
+         sizeof(int) * ((size_t)8 * T + 2 * (size_t)setcap + cap + 2 * PW_MAXLEAF + 8);
+}
+
+// The occlusion pools of `cap` entries per sequence, zeroed (all off, threshold 0.3, no entry in
+// use), and the kernel's LDS attribute.  Frees nothing on failure: bx_ss_destroy does.
+static int ss_occ_alloc(bx_ss* e, int cap) {
+  const SsDev& d = e->dev;
+  const size_t S = d.S, F = d.F;
+  BxCarve cb;
+  const size_t o_on = cb(S * sizeof(int));
+  const size_t o_thr = cb(S * sizeof(double));
+  const size_t o_mut = cb(S * sizeof(int));
+  const size_t o_pid = cb(S * cap * sizeof(int));
+  const size_t o_head = cb(S * cap * sizeof(int));
+  const size_t o_cnt = cb(S * cap * sizeof(int));
+  const size_t o_norm = cb(S * cap * OCC_RING * sizeof(double));
+  const size_t o_vec = cb(S * cap * OCC_RING * F * sizeof(double));
+  const int setcap = bx_pyset_cap(d.T - 1);
+  BX_HIPCHK((hipError_t)bx_ss_occ_lds_attr(occ_lds_bytes(d.T, cap, setcap)));
+  void* a = nullptr;
+  if (hipMalloc(&a, cb.off) != hipSuccess)
+    return bx_record_error(BX_ERR_HIP, "hipMalloc of the occlusion pools failed");
+  e->occ_arena = a;
+  e->occ_bytes = cb.off;
+  BX_HIPCHK(hipMemset(a, 0, cb.off));
+  char* base = (char*)a;
+  SsOcc& o = e->occ;
+  o.setcap = setcap;
+  o.on = (int*)(base + o_on);
+  o.thr = (double*)(base + o_thr);
+  o.mutual = (int*)(base + o_mut);
+  o.pid = (int*)(base + o_pid);
+  o.phead = (int*)(base + o_head);
+  o.pcnt = (int*)(base + o_cnt);
+  o.pnorm = (double*)(base + o_norm);
+  o.pvec = (double*)(base + o_vec);
+  e->h_occ_on.assign(S, 0);
+  e->h_occ_thr.assign(S, 0.3);
+  BX_HIPCHK(hipMemcpy(o.thr, e->h_occ_thr.data(), S * sizeof(double), hipMemcpyHostToDevice));
+  o.cap = cap;  // commit: ss_launch runs the pass from now on
+  return BX_OK;
 }
 
 static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int* off,
@@ -3753,6 +3830,11 @@ static int ss_launch(bx_ss* e, int seq0, int nseq, const double* dets, const int
   hipLaunchKernelGGL(ss_fit_kernel, dim3(d.T + LOSTN, nseq), dim3(64), 0, st, d, seq0);
   BX_HIPCHK(hipGetLastError());
   if ((rc = e->probe.end(8, st))) return rc;
+  if (e->occ.cap) {  // occlusion handling was enabled on this engine: the pass closes the frame
+    bx_ss_occ_launch(&d, &e->occ, nseq, occ_lds_bytes(d.T, e->occ.cap, e->occ.setcap), st, seq0,
+                     off, out);
+    BX_HIPCHK(hipGetLastError());
+  }
   return BX_OK;
 }
 
@@ -3954,6 +4036,29 @@ int bx_ss_copy_state(bx_ss* dst, bx_ss* src) {
   BX_HIPCHK(hipMemcpy(b.sqd, a.sqd, (S + 1) * 2 * sizeof(double), hipMemcpyDeviceToDevice));
   BX_HIPCHK(hipMemcpy(b.lost, a.lost, S * LOSTN * sizeof(int), hipMemcpyDeviceToDevice));
   BX_HIPCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
+  // occlusion handling: settings, latches and pools (one layout for equal S, F and occ_cap)
+  if (src->occ.cap) {
+    if (dst->occ.cap && dst->occ.cap != src->occ.cap)
+      return bx_record_error(BX_ERR_INVALID, "bx_ss_copy_state: the engines' occ_cap differ");
+    if (!dst->occ.cap)
+      if (int rc = ss_occ_alloc(dst, src->occ.cap)) {
+        (void)hipFree(dst->occ_arena);  // (as bx_ss_set_occlusion_host: nothing half-made stays)
+        dst->occ_arena = nullptr;
+        dst->occ = SsOcc{};
+        return rc;
+      }
+    BX_HIPCHK(hipMemcpy(dst->occ_arena, src->occ_arena, src->occ_bytes, hipMemcpyDeviceToDevice));
+    dst->h_occ_on = src->h_occ_on;
+    dst->h_occ_thr = src->h_occ_thr;
+  } else if (dst->occ.cap) {
+    // the source never enabled the pass: the destination's pools, latches and settings go (all
+    // off, threshold 0.3, as after its first set)
+    BX_HIPCHK(hipMemset(dst->occ_arena, 0, dst->occ_bytes));
+    dst->h_occ_on.assign(S, 0);
+    dst->h_occ_thr.assign(S, 0.3);
+    BX_HIPCHK(hipMemcpy(dst->occ.thr, dst->h_occ_thr.data(), S * sizeof(double),
+                        hipMemcpyHostToDevice));
+  }
   dst->cache_seq = -1;
   BX_HIPCHK(hipDeviceSynchronize());
   return BX_OK;
@@ -4087,6 +4192,7 @@ int bx_ss_destroy(bx_ss* e) {
   e->probe.destroy();
   (void)hipFree(e->arena);
   (void)hipFree(e->d_seqpar);
+  (void)hipFree(e->occ_arena);
   e->sg.free();
   delete e;
   return BX_OK;
@@ -4103,6 +4209,15 @@ int bx_ss_reset(bx_ss* e, int seq0, int nseq, void* stream) {
     hipLaunchKernelGGL(ss_reset_kernel<false>, dim3((nseq + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      e->dev, seq0, nseq);
   BX_HIPCHK(hipGetLastError());
+  if (e->occ.cap) {  // the sequences' pools and latches go, their settings stay
+    const SsOcc& o = e->occ;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t c = o.cap;
+    BX_HIPCHK(hipMemsetAsync(o.mutual + seq0, 0, nseq * sizeof(int), st));
+    BX_HIPCHK(hipMemsetAsync(o.pid + seq0 * c, 0, nseq * c * sizeof(int), st));
+    BX_HIPCHK(hipMemsetAsync(o.phead + seq0 * c, 0, nseq * c * sizeof(int), st));
+    BX_HIPCHK(hipMemsetAsync(o.pcnt + seq0 * c, 0, nseq * c * sizeof(int), st));
+  }
   return BX_OK;
 }
 
@@ -4327,6 +4442,111 @@ int bx_ss_state_set_host(bx_ss* e, int seq, int n, const int32_t* ids, const dou
     if (cov) memcpy(t.cov, cov + 64 * j, sizeof(t.cov));
     BX_HIPCHK(hipMemcpy(dt, &t, sizeof(SsTrk), hipMemcpyHostToDevice));
   }
+  return BX_OK;
+}
+
+int bx_ss_set_occlusion_host(bx_ss* e, int seq0, int nseq, const int32_t* on,
+                             const double* threshold, int occ_cap, void* stream) {
+  if (!e || seq0 < 0 || nseq < 0 || seq0 > e->dev.S - nseq)
+    return bx_record_error(BX_ERR_INVALID, "bad sequence range");
+  if (!on || !threshold || occ_cap <= 0 || occ_cap > 4096)
+    return bx_record_error(BX_ERR_INVALID, "bx_ss_set_occlusion_host: on and threshold are "
+                                           "required, 1 <= occ_cap <= 4096");
+  if (e->occ.cap && e->occ.cap != occ_cap)
+    return bx_record_error(BX_ERR_INVALID, "occ_cap is fixed by the first call");
+  BX_HIPCHK(hipDeviceSynchronize());  // frames in flight read the settings
+  if (!nseq) return BX_OK;
+  SsDev& d = e->dev;
+  std::vector<int> sq((size_t)nseq * SQS);
+  BX_HIPCHK(hipMemcpy(sq.data(), d.sq + (size_t)seq0 * SQS, sq.size() * sizeof(int),
+                      hipMemcpyDeviceToHost));
+  for (int k = 0; k < nseq; k++)
+    if (sq[(size_t)k * SQS + Q_FRAME] != 0)
+      return bx_record_error(BX_ERR_INVALID,
+                             "occlusion settings change only at frame counter 0 "
+                             "(a fresh or just reset sequence)");
+  if (!e->occ.cap) {
+    if (int rc = ss_occ_alloc(e, occ_cap)) {
+      (void)hipFree(e->occ_arena);
+      e->occ_arena = nullptr;
+      e->occ = SsOcc{};
+      return rc;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int> von(nseq);
+  for (int k = 0; k < nseq; k++) von[k] = on[k] != 0;
+  BX_HIPCHK(hipMemcpyAsync(e->occ.on + seq0, von.data(), nseq * sizeof(int),
+                           hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipMemcpyAsync(e->occ.thr + seq0, threshold, nseq * sizeof(double),
+                           hipMemcpyHostToDevice, st));
+  BX_HIPCHK(hipStreamSynchronize(st));
+  for (int k = 0; k < nseq; k++) {
+    e->h_occ_on[seq0 + k] = von[k];
+    e->h_occ_thr[seq0 + k] = threshold[k];
+  }
+  return BX_OK;
+}
+
+int bx_ss_occlusion_host(bx_ss* e, int seq, int* on, double* threshold, int* mutual_frame,
+                         int* n_buffered) {
+  if (!e || seq < 0 || seq >= e->dev.S)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ss_occlusion_host");
+  int mf = 0, nb = 0;
+  if (e->occ.cap) {
+    BX_HIPCHK(hipDeviceSynchronize());
+    std::vector<int> pid(e->occ.cap);
+    BX_HIPCHK(hipMemcpy(&mf, e->occ.mutual + seq, sizeof(int), hipMemcpyDeviceToHost));
+    BX_HIPCHK(hipMemcpy(pid.data(), e->occ.pid + (size_t)seq * e->occ.cap,
+                        sizeof(int) * pid.size(), hipMemcpyDeviceToHost));
+    for (int v : pid) nb += v != 0;
+  }
+  if (on) *on = e->occ.cap ? e->h_occ_on[seq] : 0;
+  if (threshold) *threshold = e->occ.cap ? e->h_occ_thr[seq] : 0.3;
+  if (mutual_frame) *mutual_frame = mf;
+  if (n_buffered) *n_buffered = nb;
+  return BX_OK;
+}
+
+int bx_ss_occlusion_buffer_host(bx_ss* e, int seq, int id, double* vecs, int* n) {
+  if (!e || seq < 0 || seq >= e->dev.S || id <= 0 || !n)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ss_occlusion_buffer_host");
+  *n = 0;
+  if (!e->occ.cap) return BX_OK;
+  BX_HIPCHK(hipDeviceSynchronize());
+  const SsOcc& o = e->occ;
+  const size_t p0 = (size_t)seq * o.cap, F = e->dev.F;
+  std::vector<int> pid(o.cap);
+  BX_HIPCHK(hipMemcpy(pid.data(), o.pid + p0, sizeof(int) * pid.size(), hipMemcpyDeviceToHost));
+  for (int k = 0; k < o.cap; k++) {
+    if (pid[k] != id) continue;
+    int head = 0, cnt = 0;
+    BX_HIPCHK(hipMemcpy(&head, o.phead + p0 + k, sizeof(int), hipMemcpyDeviceToHost));
+    BX_HIPCHK(hipMemcpy(&cnt, o.pcnt + p0 + k, sizeof(int), hipMemcpyDeviceToHost));
+    if (cnt < 0 || cnt > OCC_RING || head < 0 || head >= OCC_RING)
+      return bx_record_error(BX_ERR_INVALID, "occlusion pool entry out of range");
+    for (int q = 0; q < cnt && vecs; q++)  // oldest first
+      BX_HIPCHK(hipMemcpy(vecs + (size_t)q * F,
+                          o.pvec + ((p0 + k) * OCC_RING + (head + q) % OCC_RING) * F,
+                          sizeof(double) * F, hipMemcpyDeviceToHost));
+    *n = cnt;
+    break;
+  }
+  return BX_OK;
+}
+
+int bx_pyset_order_host(const int64_t* adds, int n, int64_t* out, int* n_out) {
+  if (n < 0 || (n && (!adds || !out)) || !n_out)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_pyset_order_host");
+  for (int k = 0; k < n; k++)
+    if (adds[k] < 0)
+      return bx_record_error(BX_ERR_INVALID, "bx_pyset_order_host: keys are non-negative ints "
+                                             "(hash(i) = i)");
+  const int cap = bx_pyset_cap(n);
+  std::vector<int> ta(cap), tb(cap), ord(n > 0 ? n : 1);
+  const int m = bx_pyset_order<int64_t>(adds, n, ta.data(), tb.data(), ord.data());
+  for (int k = 0; k < m; k++) out[k] = adds[ord[k]];
+  *n_out = m;
   return BX_OK;
 }
 

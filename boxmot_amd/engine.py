@@ -1793,6 +1793,8 @@ class SsTableEngine(SsEngine):
         for k, p in sorted(self._seq_over.items()):
             e.set_seq_params(k, [p])
         N.check(self._L.bx_ss_copy_state(e._h, self._h), "bx_ss_copy_state")
+        if hasattr(self, "occ_cap"):  # (the copy carried pools, latches and settings)
+            e.occ_cap = self.occ_cap
         return e
 
     @staticmethod
@@ -1826,6 +1828,47 @@ class SsTableEngine(SsEngine):
                 self._seq_over.pop(seq0 + k, None)
             else:
                 self._seq_over[seq0 + k] = params[k]
+
+    # ---- occlusion handling on the device (bx_ss_set_occlusion_host).  Here and not on SsEngine
+    # for the reason the class exists: SsEngine's method set is pinned.  An engine on which
+    # neither a table nor occlusion was set launches SsEngine's kernels.
+    def set_occlusion(self, seq0: int, on, threshold, nseq: int | None = None,
+                      occ_cap: int = 32) -> None:
+        """``handle_occlusions`` / ``occlusion_threshold`` of sequences [seq0, seq0 + nseq):
+        ``on`` and ``threshold`` are scalars or one value per sequence (nseq defaults to their
+        length, or to every sequence from seq0 for two scalars).  From the first call on every
+        frame of this engine ends with the occlusion pass (OcclusionHandler's edits, on the
+        device); it allocates ``occ_cap`` buffered tracks per sequence, fixed from then on.
+        ``ValueError`` for a sequence that has run a frame since its last reset, or another
+        ``occ_cap``.  ``grown()`` carries settings, pools and latches over."""
+        on_a, thr_a = np.atleast_1d(np.asarray(on)), np.atleast_1d(np.asarray(threshold))
+        if nseq is None:
+            nseq = max(on_a.size, thr_a.size) if max(on_a.size, thr_a.size) > 1 \
+                else self.n_seq - seq0
+        on_a = np.ascontiguousarray(np.broadcast_to(on_a != 0, (nseq,)), np.int32)
+        thr_a = np.ascontiguousarray(np.broadcast_to(thr_a, (nseq,)), np.float64)
+        N.check(self._L.bx_ss_set_occlusion_host(self._h, int(seq0), int(nseq), on_a.ctypes.data,
+                                                 thr_a.ctypes.data, int(occ_cap), None),
+                "bx_ss_set_occlusion_host")
+        self.occ_cap = int(occ_cap)
+
+    def occlusion(self, seq: int = 0) -> dict:
+        """Sequence ``seq``'s settings, the update count at which a mutual occlusion latched (0:
+        none; the reference raises TypeError there) and the buffered tracks."""
+        on, mf, nb, thr = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        N.check(self._L.bx_ss_occlusion_host(self._h, int(seq), C.byref(on), C.byref(thr),
+                                             C.byref(mf), C.byref(nb)), "bx_ss_occlusion_host")
+        return {"on": bool(on.value), "threshold": thr.value, "mutual_frame": mf.value,
+                "n_buffered": nb.value}
+
+    def occlusion_buffer(self, seq: int, id: int) -> np.ndarray:
+        """The buffered features of track ``id``, oldest first ([n, emb_dim], n <= 10; n = 0
+        without a buffer): OcclusionStateManager.occlusion_buffer[id]."""
+        v = np.zeros((10, self.emb_dim))
+        n = C.c_int()
+        N.check(self._L.bx_ss_occlusion_buffer_host(self._h, int(seq), int(id), v.ctypes.data,
+                                                    C.byref(n)), "bx_ss_occlusion_buffer_host")
+        return v[: n.value].copy()
 
     def seq_params(self, seq: int) -> SsParams:
         """The parameters sequence ``seq`` runs on (bx_ss_seq_params_host): its own when set,

@@ -131,7 +131,7 @@ def write_mot_results(txt_path, mot_results: np.ndarray | None) -> None:
 
 # ------------------------------------------------------------------------------ the runner
 def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs: dict,
-                    n_classes: int = 0):
+                    n_classes: int = 0, occlusion: str = "host"):
     """One engine handle for n_seq sequences, parameterised exactly as the drop-in tracker
     `tracker_type` is by `tracker_kwargs` (create_tracker's YAML defaults when empty).
     n_classes > 0 (deepocsort, hybridsort): the per_class mode, n_classes class sequences per
@@ -195,6 +195,15 @@ def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs:
                            params=tr._params), np.float32, 8
     if tracker_type == "strongsort":
         tc, dc, vc = tr._caps
+        if occlusion == "device" and tr.handle_occlusions:
+            # the occlusion pass closes every frame on the device: no host handler
+            from .engine import SsTableEngine
+
+            eng = SsTableEngine(n_seq=n_seq, track_cap=tc, det_cap=dc, emb_dim=emb_dim,
+                                vec_cap=vc, params=tr._params)
+            eng.set_occlusion(0, True, tr.occlusion_threshold)
+            eng.occlusion_threshold = None
+            return eng, np.float64, 10
         eng = SsEngine(n_seq=n_seq, track_cap=tc, det_cap=dc, emb_dim=emb_dim, vec_cap=vc,
                        params=tr._params)
         # handle_occlusions: the host post-process runs per sequence after each batched step
@@ -260,6 +269,35 @@ def _resident_results(eng, tracker_type: str, seqs, fids, F: int, ddt, warps=Non
         return feed.results()
     finally:
         feed.close()
+
+
+def check_occlusion(tracker_type: str, occlusion) -> None:
+    """The refusals of the ``occlusion=`` argument of run_sequences and the StrongSort sweeps."""
+    if occlusion not in ("host", "device"):
+        raise ValueError(f'occlusion must be "host" or "device", got {occlusion!r}')
+    if occlusion == "device" and tracker_type != "strongsort":
+        raise ValueError(f'occlusion="device" is StrongSort\'s occlusion pass; {tracker_type} has '
+                         "no occlusion handling")
+
+
+def raise_device_occlusion(eng, names) -> None:
+    """After a run with the occlusion pass on the device: the reference's TypeError for the first
+    sequence with a latched mutual occlusion, RuntimeError for a full buffer pool."""
+    if not hasattr(eng, "occ_cap"):  # (handle_occlusions=False: no pass on this engine)
+        return
+    for q in range(eng.n_seq):
+        mf = eng.occlusion(q)["mutual_frame"]
+        if mf:
+            raise TypeError(f"'int' object is not iterable (mutual occlusion in sequence "
+                            f"{names[q % len(names)]}, engine sequence {q}, at its update {mf}: "
+                            "the reference's _resolve_mutual_occlusion)")
+    # status 2 is also what a frame with more detections than det_cap latches: the pool is named
+    # only where a sequence's pool is in fact full
+    if eng.status() == 2 and any(eng.occlusion(q)["n_buffered"] >= eng.occ_cap
+                                 for q in range(eng.n_seq)):
+        raise RuntimeError(f"engine status 2 (capacity): the occlusion buffer pool of a sequence "
+                           f"is full, occ_cap = {eng.occ_cap} tracks with buffered features at "
+                           "once (or a frame's detections exceeded det_cap)")
 
 
 WARP_TRACKERS = ("botsort", "boosttrack", "strongsort", "deepocsort")  # run_sequences(warps=...)
@@ -364,8 +402,8 @@ def _torch():
 def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict | None = None,
                   frame_sizes: dict | None = None, tracker_kwargs: dict | None = None,
                   gsi: bool = False, gsi_interval: int = 20, gsi_tau: float = 10,
-                  resident: bool = False, n_classes: int = 0, warps=None, images: dict | None = None,
-                  cmc=None) -> dict:
+                  resident: bool = False, n_classes: int = 0, occlusion: str = "host", warps=None,
+                  images: dict | None = None, cmc=None) -> dict:
     """process_sequence (val.py:304-354) for every sequence at once.
 
     sequences: name -> packed file (pack_sequence) or BinSequence; frame_ids: name -> the frames
@@ -400,7 +438,17 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
     returns and the drop-ins pass on.  ValueError, before anything is built: a tracker outside
     WARP_TRACKERS, a per_class run, ``images`` without ``cmc`` or with ``warps``, a table or an
     array that does not match the sequences and their iterated frames.
+    occlusion: where StrongSort's ``handle_occlusions`` runs.  ``"host"`` (default): an
+    ``OcclusionHandler`` per sequence after every step, reading tracks back and writing edits.
+    ``"device"`` (strongsort only): the engine's occlusion pass (``SsTableEngine.set_occlusion``)
+    ends every frame on the device and no handler is built; the files are byte-identical.
+    Ignored when the config has ``handle_occlusions=False``.  Where the host handler raises the
+    reference's ``TypeError`` on a mutual occlusion in the middle of the run, the device flow
+    raises it after the run, naming the sequence and its update count; either way before any
+    file is written.  A full buffer pool is a ``RuntimeError`` naming ``occ_cap``.  ``ValueError``,
+    before anything is built, for another tracker or another value.
     """
+    check_occlusion(tracker_type, occlusion)
     if resident and tracker_type not in RESIDENT_TRACKERS:
         raise NotImplementedError(
             f"run_sequences(resident=True) is not available for {tracker_type}: the "
@@ -417,8 +465,12 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
     table = None
     if warps is not None or images is not None:
         table = _flow_warps(names, seqs, fids, F, warps, images, ecc_kw)
-    eng, ddt, ncol = _batched_engine(tracker_type, S, F, tracker_kwargs or {}, n_classes) \
-        if n_classes else _batched_engine(tracker_type, S, F, tracker_kwargs or {})
+    if occlusion == "device":
+        eng, ddt, ncol = _batched_engine(tracker_type, S, F, tracker_kwargs or {}, n_classes,
+                                         occlusion=occlusion)
+    else:
+        eng, ddt, ncol = _batched_engine(tracker_type, S, F, tracker_kwargs or {}, n_classes) \
+            if n_classes else _batched_engine(tracker_type, S, F, tracker_kwargs or {})
     if tracker_type == "ocsort" and frame_sizes:
         for k, nm in enumerate(names):
             if nm in frame_sizes:
@@ -494,6 +546,8 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
                 if rows.shape[0]:
                     results[q].append(convert_to_mot_format(rows, int(fids[q][t])))
             k = k1
+    if occlusion == "device":
+        raise_device_occlusion(eng, names)
     if eng.status() != 0:
         raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
     exp_dir = Path(exp_dir)

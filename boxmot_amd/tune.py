@@ -15,7 +15,8 @@ memory (``engine.SharedSequenceFeeder``).  ByteTrack and BoT-SORT, which share `
 them too (``sweep_bot``), fed the same way, and so has BoostTrack
 (``sweep_boost``), whose variants differ in constructor flags only.  StrongSort
 (``sweep_strong``) completes the set: its feeder gathers float64 detections and
-10-column rows, and its occlusion post-process stays on the host, per sweep.
+10-column rows, and its occlusion post-process stays on the host, per sweep, unless
+``occlusion="device"`` asks for the engine's own pass.
 
 ``sweep_gsi`` runs any of the five with GSI between tracking and scoring, on the
 feeder's result slots in device memory (``postprocessing.gsi_device``, include/bxgsi.h).
@@ -189,13 +190,14 @@ def _frame_tables(names, seqs, frame_ids) -> tuple:
 
 
 def _drive(eng, feed, step, K: int, gt, benchmark, seq_lengths, score, keep_results,
-           post=None) -> tuple:
+           post=None, after=None) -> tuple:
     """The frame loop both sweeps share: per frame index one gather, ``step(t, run)`` for each of
     its runs and one append; then the status checks, the device-side scores and the one copy of
     the rows.  Returns (rows per engine sequence or None, summaries per config or None).
 
     ``post`` (``sweep_gsi``'s (interval, tau)): the feeder's slots go through ``gsi_device`` once;
-    its three tensors are what the device scores and what comes back as the rows."""
+    its three tensors are what the device scores and what comes back as the rows.
+    ``after``: called once after the frame loop, before any check (a flow's own errors)."""
     for t in range(feed.n_frames):
         runs = feed.schedule[t]
         if not runs:
@@ -204,6 +206,8 @@ def _drive(eng, feed, step, K: int, gt, benchmark, seq_lengths, score, keep_resu
         for run in runs:
             step(t, run)
         feed.append(t)
+    if after is not None:
+        after()
     if eng.status() != 0:
         raise RuntimeError(f"engine status {eng.status()} (capacity overflow)")
     summaries = None
@@ -615,16 +619,18 @@ def _strong_occ(cfg: dict) -> bool:
     return bool(cfg.get("handle_occlusions", True))
 
 
-def _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps) -> list:
+def _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps,
+                  occlusion="host") -> list:
     """The refusals of ``sweep_strong`` that need no engine and no device."""
     from . import motio
 
+    motio.check_occlusion("strongsort", occlusion)
     configs = _check("strongsort", configs, sequences, gt, exp_dir, score, keep_results,
                      supported=SUPPORTED_STRONG, what="tune.sweep_strong")
     if len({repr(c.get("vec_cap")) for c in configs}) > 1:
         raise ValueError("vec_cap sizes the engine's memory: it must be absent from every config "
                          "or equal in all of them")
-    occ = {_strong_occ(c) for c in configs}
+    occ = set() if occlusion == "device" else {_strong_occ(c) for c in configs}
     if len(occ) > 1:
         raise ValueError("handle_occlusions is a setting of the sweep, not of a config: it must "
                          "resolve to the same value in every config")
@@ -680,6 +686,9 @@ def sweep_strong(sequences: dict, configs, *, exp_dir=None, gt: dict | None = No
     ``score="device"`` and ``keep_results=False`` are refused then.  The handler's ``TypeError``
     on mutual occlusion propagates.
 
+    ``sweep_strong_device`` is this sweep with the occlusion handling in the engine instead
+    (its signature is this one's plus ``occlusion``; this one's is pinned).
+
     ``warps``: what ``run_sequences(warps=...)`` takes; every config's copy of a sequence gets that
     sequence's warp.
 
@@ -696,10 +705,31 @@ def sweep_strong(sequences: dict, configs, *, exp_dir=None, gt: dict | None = No
                          keep_results=keep_results, warps=warps)
 
 
+def sweep_strong_device(sequences: dict, configs, *, exp_dir=None, gt: dict | None = None,
+                        benchmark: str = "MOT17", seq_lengths: dict | None = None,
+                        frame_ids: dict | None = None, score: str = "host",
+                        keep_results: bool = True, warps=None,
+                        occlusion: str = "device") -> list:
+    """``sweep_strong`` with an ``occlusion`` argument (``sweep_strong`` itself keeps its
+    signature).  ``"host"`` is ``sweep_strong``, refusals included.  ``"device"``: the engine's
+    occlusion pass (``SsTableEngine.set_occlusion``) ends every frame, and no
+    ``OcclusionHandler`` is built; each engine sequence gets its config's ``handle_occlusions``
+    and ``occlusion_threshold``, so configs may differ in ``handle_occlusions``, the rows are
+    appended on the device, ``score="device"`` and ``keep_results=False`` are accepted, and the
+    files are byte-identical to the host flow's.  A mutual occlusion raises the reference's
+    ``TypeError`` after the frame loop, naming the sequence and its update count, before anything
+    is scored or written; a full buffer pool is a ``RuntimeError`` naming ``occ_cap``.
+    ``sweep_gsi("strongsort", ..., occlusion="device")`` passes the argument through."""
+    return _sweep_strong(sequences, configs, None, exp_dir=exp_dir, gt=gt, benchmark=benchmark,
+                         seq_lengths=seq_lengths, frame_ids=frame_ids, score=score,
+                         keep_results=keep_results, warps=warps, occlusion=occlusion)
+
+
 def _sweep_strong(sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths, frame_ids,
-                  score, keep_results, warps) -> list:
+                  score, keep_results, warps, occlusion="host") -> list:
     """``sweep_strong``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
-    configs = _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps)
+    configs = _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps,
+                            occlusion)
     import dataclasses
 
     from . import motio
@@ -730,7 +760,9 @@ def _sweep_strong(sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengt
     resolved = [_resolve_strong(F, c) for c in configs]
     params = [r[0] for r in resolved]
     occ_thr = [r[4] for r in resolved]
-    if len({r[1:4] for r in resolved}) > 1 or len({t is None for t in occ_thr}) > 1:
+    device = occlusion == "device"
+    if len({r[1:4] for r in resolved}) > 1 or (
+            not device and len({t is None for t in occ_thr}) > 1):
         raise ValueError("the configs resolve to different capacities or handle_occlusions: "
                          f"{[r[1:] for r in resolved]}")
     base = dataclasses.replace(params[0], nn_budget=max(int(p.nn_budget) for p in params))
@@ -741,6 +773,12 @@ def _sweep_strong(sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengt
         embs = [s.embs for s in seqs]
         for k in range(K):
             eng.set_seq_params(k * S, [params[k]] * S)
+        after = None
+        if device and any(t is not None for t in occ_thr):
+            for k in range(K):
+                eng.set_occlusion(k * S, occ_thr[k] is not None,
+                                  0.3 if occ_thr[k] is None else occ_thr[k], nseq=S)
+            after = lambda: motio.raise_device_occlusion(eng, names)  # noqa: E731
         none = [None] * ((K - 1) * S)
         feed = E.SharedSequenceFeeder(dets + none, embs + none, tables * K, F,
                                       source=list(range(S)) * K, det_f64=True, out_cols=10)
@@ -751,9 +789,9 @@ def _sweep_strong(sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengt
                      pout if out is None else out, pcnt if cnt is None else cnt,
                      seq0=q0, nseq=ns)
 
-        if occ_thr[0] is None:
+        if device or occ_thr[0] is None:
             rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                     keep_results, post)
+                                     keep_results, post, after)
         else:
             rows, summaries = _drive_occlusion(eng, feed, step, fids * K,
                                                [tb[1] for tb in tables] * K,

@@ -27,7 +27,9 @@
  * The fork needs the minimal patch P6; `born_confirmed` stands for its
  * GITHUB_ACTIONS=true switch (D8).  handle_occlusions=True (OcclusionAwareTracker,
  * utils/occlusion_handler.py:312-439) is a host post-process (boxmot_amd/occlusion.py) over the
- * track-attribute calls below; it raises where the reference crashes on mutual occlusion (D7).
+ * track-attribute calls below, which raises where the reference crashes on mutual occlusion (D7)
+ * and which the single-stream drop-in uses; or, for the many-sequence flows, an eleventh kernel
+ * at the end of the frame (bx_ss_set_occlusion_host) that makes the same edits on the device.
  * Bit-identical to oracle/bxo_strongsort.c (pinned by tests/golden/trk_strongsort_*.npz).
  *
  * Conventions as in bxassoc.h: device pointers unless a name ends in _host, asynchronous on
@@ -74,8 +76,9 @@ int bx_ss_reset(bx_ss *e, int seq0, int nseq, void *stream);
  *   det_off [nseq+1] int32 prefix offsets
  *   embs    [sum N][emb_dim] float64
  *   warps   [nseq][6] float64 2x3 camera-motion affine per sequence, NULL = identity
- *   out     [sum N][10] float64 rows [x1,y1,x2,y2,id,conf,cls,det_ind,quality,occlusion(=0)]
- *           in track-list order, sequence k from row det_off[k]
+ *   out     [sum N][10] float64 rows [x1,y1,x2,y2,id,conf,cls,det_ind,quality,occlusion]
+ *           in track-list order, sequence k from row det_off[k]; occlusion is 0 unless the
+ *           sequence runs the occlusion pass (bx_ss_set_occlusion_host), which writes the level
  *   out_count [nseq] int32 */
 int bx_ss_step(bx_ss *e, int seq0, int nseq, const double *dets, const int32_t *det_off,
                const double *embs, const double *warps, double *out, int32_t *out_count,
@@ -158,6 +161,54 @@ int bx_ss_track_attrs_set_host(bx_ss *e, int seq, int n, const int32_t *ids, con
 int bx_ss_last_feature_host(bx_ss *e, int seq, int n, const int32_t *ids, double *feats);
 int bx_ss_last_feature_set_host(bx_ss *e, int seq, int n, const int32_t *ids, const double *feats,
                                 int normalize);
+/* Occlusion handling on the device: OcclusionAwareTracker.update_with_occlusion_handling
+ * (utils/occlusion_handler.py:312-439) as the last kernel of a frame, one workgroup per stepped
+ * sequence, bit for bit what boxmot_amd/occlusion.py's OcclusionHandler does through the host
+ * calls above: the O(T^2) overlap analysis over the track list's tlwh rows (read as corner
+ * boxes, as the reference reads them), _max_age doubled (held at 2^30) and quality_score floored
+ * at 0.6 for a level above 0.3, features[-1] buffered, the mean replaced by the occluders' mean
+ * centre (summed in the iteration order of the reference's Python set; covariance[:4,:4] x 1.5)
+ * above 0.8, an emerging track's conf + 0.1 and features[-1] blended with its strongest buffered
+ * vector, and the sequence's output rows written again (moved boxes, conf, quality, column 9 the
+ * level).  The reference's occlusion_stats events are not kept.
+ *
+ * bx_ss_set_occlusion_host: on [nseq] (!= 0 enables) and threshold [nseq] (occlusion_threshold)
+ * of sequences [seq0, seq0+nseq).  The first call allocates, per sequence, a pool of occ_cap
+ * buffered tracks (each an id and a ring of the 10 newest vectors, deque(maxlen=10)); occ_cap is
+ * fixed from then on, another value is BX_ERR_INVALID.  Accepted only for sequences whose frame
+ * counter is 0, as the parameter table.  An engine on which it was never called launches exactly
+ * the kernels it launched before; afterwards every frame ends with the pass, which returns at
+ * once for a sequence that is off.  Synchronises the device and `stream`.
+ *
+ * A pool entry is released when its track emerges (the reference deletes the buffer) and when
+ * its id is in neither the track list nor the lost buffer: such an id cannot come back (ID
+ * recovery revives ids from the lost buffer only), while the reference keeps the dead buffer for
+ * ever.  A full pool latches BX_ERR_CAPACITY (bx_ss_status) and skips that append; nothing else
+ * of the frame changes.  Entries of tracks that emerge in a frame become free at the end of that
+ * frame, while the host deletes and appends in list order: a pool that is exactly full can
+ * therefore skip an append for which the host order had room.  The error is on the safe side;
+ * size occ_cap with one frame's emergences to spare.  The pass is outside bx_ss_probe's stages.
+ *
+ * A mutual occlusion (size ratio in [0.8, 1.2] above the threshold) is where the reference raises
+ * TypeError (D7): the sequence makes no edit in that frame, its update count (the frame counter)
+ * is latched and the pass skips the sequence from then on.
+ *
+ * bx_ss_occlusion_host: the settings, the latched update count (0: none) and the pool entries in
+ * use (any pointer may be NULL).  bx_ss_occlusion_buffer_host: the buffer of track `id`, oldest
+ * first, vecs [10][emb_dim] (may be NULL), n = 0 without one.  bx_ss_reset clears a sequence's
+ * pool and latch and keeps its settings; bx_ss_copy_state copies pools, latches and settings
+ * (allocating the destination's pools with the source's occ_cap when it has none; a source that
+ * never enabled the pass clears the destination's pools, latches and settings). */
+int bx_ss_set_occlusion_host(bx_ss *e, int seq0, int nseq, const int32_t *on,
+                             const double *threshold, int occ_cap, void *stream);
+int bx_ss_occlusion_host(bx_ss *e, int seq, int *on, double *threshold, int *mutual_frame,
+                         int *n_buffered);
+int bx_ss_occlusion_buffer_host(bx_ss *e, int seq, int id, double *vecs, int *n);
+/* Iteration order of a CPython set of non-negative ints after adding adds[0..n) in order
+ * (hash(i) = i, 9 linear probes then perturb >>= 5, growth to the first power of two above
+ * 4 * fill when fill * 5 >= mask * 3, iteration in table order; csrc/bx_pyset.h, the function the
+ * occlusion kernel runs in LDS): out [n] gets the distinct keys, n_out their number.  Host only. */
+int bx_pyset_order_host(const int64_t *adds, int n, int64_t *out, int *n_out);
 /* Last-frame statistics over sequences [seq0, seq0+nseq) (host): sums[7] = {detections kept,
  * tracks entering the frame, confirmed tracks queried next frame, gallery sample rows compared,
  * output rows, max frame counter, matches} — bench.py's unit counts. */
