@@ -12,11 +12,13 @@ many consecutive frames of a camera per call, for the many-sequence file flow
 (``motio.run_sequences(images=..., cmc=...)``).
 ``tune.grid`` / ``tune.sweep`` run a hyper-parameter sweep (K configs x S sequences) as one batched OCSort engine; ``tune.sweep_reid`` does it for DeepOCSort / HybridSort, ``tune.sweep_bot`` for ByteTrack / BoT-SORT, ``tune.sweep_boost`` for BoostTrack and ``tune.sweep_strong`` for StrongSort; ``tune.sweep_gsi`` runs any of them with GSI applied before the rows are scored or written.
 ``ReidFrontEnd`` / ``crop_batch`` / ``normalize_features`` are the ReID front end around the caller's network.
+``DetFrontEnd`` / ``letterbox`` / ``postprocess`` are the detector front end around the caller's network: letterbox in, score filter, batched NMS and rescale out.
 """
 from .cmc import (MOTION_AFFINE, MOTION_EUCLIDEAN, MOTION_HOMOGRAPHY, MOTION_TRANSLATION, ECC,
                   EccBatch, EccChain, SOF, SofBatch, SofChain, get_cmc_method, sof_warp_table,
                   warp_table)
 from . import tune
+from .det import DetFrontEnd, letterbox, postprocess
 from .evaluation import evaluate_mot, evaluate_mot_device, mot_summary
 from .postprocessing import gaussian_smooth, gsi, gsi_device, linear_interpolation
 from .reid import ReidFrontEnd, crop_batch, normalize_features
@@ -32,4 +34,5 @@ __all__ = ["create_tracker", "get_tracker_config", "ByteTrack", "BotSort", "OcSo
            "mot_summary", "ECC", "EccBatch", "EccChain", "warp_table", "SOF", "SofBatch", "SofChain",
            "sof_warp_table", "get_cmc_method", "MOTION_TRANSLATION",
            "MOTION_EUCLIDEAN", "MOTION_AFFINE", "MOTION_HOMOGRAPHY", "ReidFrontEnd",
-           "crop_batch", "normalize_features", "tune", "__version__"]
+           "crop_batch", "normalize_features", "DetFrontEnd", "letterbox", "postprocess", "tune",
+           "__version__"]

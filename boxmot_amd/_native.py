@@ -30,6 +30,7 @@ HEADER_EVAL = REPO / "include" / "bxeval.h"
 HEADER_CMC = REPO / "include" / "bxcmc.h"
 HEADER_REID = REPO / "include" / "bxreid.h"
 HEADER_SOF = REPO / "include" / "bxsof.h"
+HEADER_DET = REPO / "include" / "bxdet.h"
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -42,7 +43,8 @@ HIPCC_FLAGS = [
 SOURCES = ["bx_engine.hip", "bx_ops.hip", "bx_ocsort.hip", "bx_nn.hip", "bx_boost.hip",
            "bx_strongsort.hip", "bx_deepocsort.hip", "bx_hybridsort.hip", "bx_gsi.hip", "bx_feed.hip",
            "bx_classes.hip", "bx_eval.hip", "bx_cmc.hip", "bx_reid.hip", "bx_sof.hip",
-           "bx_io.cpp", "bx_boost_tab.hip", "bx_strongsort_tab.hip", "bx_strongsort_occ.hip"]
+           "bx_io.cpp", "bx_boost_tab.hip", "bx_strongsort_tab.hip", "bx_strongsort_occ.hip",
+           "bx_det.hip"]
 
 
 class NativeUnavailable(RuntimeError):
@@ -352,6 +354,7 @@ EXPORTS = [
     "bx_sof_apply_host", "bx_sof_status", "bx_sof_pyramid_bytes", "bx_sof_state_host",
     "bx_sof_points_host",
     "bx_sof_chain_reserve", "bx_sof_apply_chain", "bx_sof_apply_chain_host",
+    "bx_det_letterbox", "bx_det_scratch_bytes", "bx_det_postprocess",
 ]
 
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -629,6 +632,10 @@ _SIGS = {
                             C.POINTER(BxSofParams), _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "bx_sof_apply_chain_host": ([_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp,
                                  C.POINTER(BxSofParams), _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_det_letterbox": ([_vp] + [C.c_int] * 7 + [C.c_double] * 6 + [C.c_int, _vp, _vp], C.c_int),
+    "bx_det_scratch_bytes": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
+    "bx_det_postprocess": ([_vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_float,
+                            C.c_float, _vp, _vp, C.c_int, C.c_int, C.c_int] + [_vp] * 7, C.c_int),
 }
 
 _lib = None
