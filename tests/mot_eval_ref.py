@@ -1,12 +1,14 @@
 """numpy / scipy restatement of the MOT evaluation contract: HOTA, CLEAR and
 Identity with the MOT16/17/20 pedestrian preprocessing, written from that contract and the
 published metric definitions with plain loops and scipy's linear_sum_assignment.  It is the oracle
-of tests/test_eval_gpu.py and is itself pinned by the hand-worked cases of tests/test_eval_host.py.
+of tests/test_eval_gpu.py and tests/test_eval_cases_gpu.py and is itself pinned by the hand-worked
+cases of tests/test_eval_host.py and tests/test_eval_cases_host.py.
 
 evaluate_ref takes what boxmot_amd.evaluation.prepare_inputs returns and gives the dictionary
 evaluate_mot gives.  With ``gaps`` (a list) it also records, for every preprocessing, HOTA and
 CLEAR assignment, by how much the optimum falls when one of its value-carrying pairs is
-forbidden: a positive gap for every pair means those pairs are the same in every optimum.
+forbidden (for a pair that stands alone in its row and column, a lower bound of that, without a
+second solve): a positive gap for every pair means those pairs are the same in every optimum.
 """
 import numpy as np
 from scipy.optimize import linear_sum_assignment
@@ -18,23 +20,25 @@ DISTRACTORS = {"MOT16": (2, 7, 8, 12), "MOT17": (2, 7, 8, 12), "MOT20": (2, 7, 8
 
 
 def iou_xywh(g, t):
-    """[a, 4] x [b, 4] xywh boxes -> [a, b] IoU (areas from the corner form)."""
+    """[a, 4] x [b, 4] xywh boxes -> [a, b] IoU (areas from the corner form).  One gt box at a
+    time against all tracker boxes: the same operations in the same order for every pair."""
+    g, t = np.asarray(g, np.float64), np.asarray(t, np.float64)
     out = np.zeros((len(g), len(t)))
+    if len(g) == 0 or len(t) == 0:
+        return out
+    bx0, by0 = t[:, 0], t[:, 1]
+    bx1, by1 = t[:, 0] + t[:, 2], t[:, 1] + t[:, 3]
+    ab = (bx1 - bx0) * (by1 - by0)
     for i in range(len(g)):
         ax0, ay0 = g[i, 0], g[i, 1]
         ax1, ay1 = g[i, 0] + g[i, 2], g[i, 1] + g[i, 3]
         aa = (ax1 - ax0) * (ay1 - ay0)
-        for j in range(len(t)):
-            bx0, by0 = t[j, 0], t[j, 1]
-            bx1, by1 = t[j, 0] + t[j, 2], t[j, 1] + t[j, 3]
-            ab = (bx1 - bx0) * (by1 - by0)
-            inter = max(min(ax1, bx1) - max(ax0, bx0), 0.0) * max(min(ay1, by1) - max(ay0, by0), 0.0)
-            union = aa + ab - inter
-            if aa <= EPS or ab <= EPS:
-                inter = 0.0
-            if union <= EPS:
-                inter, union = 0.0, 1.0
-            out[i, j] = inter / union
+        inter = np.maximum(np.minimum(ax1, bx1) - np.maximum(ax0, bx0), 0.0) * \
+            np.maximum(np.minimum(ay1, by1) - np.maximum(ay0, by0), 0.0)
+        union = aa + ab - inter
+        inter = np.where((aa <= EPS) | (ab <= EPS), 0.0, inter)
+        empty = union <= EPS
+        out[i] = np.where(empty, 0.0, inter) / np.where(empty, 1.0, union)
     return out
 
 
@@ -44,8 +48,15 @@ def _solve(score, gaps, floor=EPS):
     r, c = linear_sum_assignment(-score)
     if gaps is not None:
         best = score[r, c].sum()
+        alone = (score > 0).sum(1)[:, None] + (score > 0).sum(0)[None, :] == 2
+        alone &= score.min() >= 0
         for i, j in zip(r, c):
-            if score[i, j] > floor:
+            if score[i, j] > floor and alone[i, j]:
+                # the only positive entry of its row and its column, no negative one anywhere:
+                # an assignment without it gains nothing from row i and column j and at most the
+                # optimum of the rest from the rest, so the loss is at least score[i, j]
+                gaps.append(score[i, j])
+            elif score[i, j] > floor:
                 alt = score.copy()
                 alt[i, j] = -1e6
                 r2, c2 = linear_sum_assignment(-alt)

@@ -11,22 +11,11 @@ import pytest
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
+import eval_cases as EC  # noqa: E402
 import mot_eval_ref as R  # noqa: E402
 from boxmot_amd import _native as N  # noqa: E402
 from boxmot_amd import evaluate_mot, evaluation, mot_summary  # noqa: E402
-
-
-def box(k, t=0):
-    """Object k's 10 x 20 box, 100 px from its neighbours, drifting 1 px per frame."""
-    return [100.0 * k + t, 50.0, 10.0, 20.0]
-
-
-def gt_row(t, i, k, zm=1, cls=1):
-    return [t, i, *box(k, t), zm, cls, 1.0]
-
-
-def tr_row(t, i, k):
-    return [t, i, *box(k, t), 0.9, -1, -1]
+from eval_cases import gt_row, tr_row  # noqa: E402
 
 
 def ref(gt, tr, T=None, benchmark="MOT17"):
@@ -37,8 +26,7 @@ def ref(gt, tr, T=None, benchmark="MOT17"):
 
 
 def test_perfect_tracker():
-    gt = [gt_row(t, i, i) for t in range(1, 6) for i in (1, 2)]
-    tr = [tr_row(t, 10 + i, i) for t in range(1, 6) for i in (1, 2)]
+    gt, tr = EC.perfect_tracker()
     res = ref(gt, tr)
     for r in (res["S"], res["COMBINED"]):
         assert r["HOTA"]["HOTA"] == 1.0 and r["CLEAR"]["MOTA"] == 1.0 and r["Identity"]["IDF1"] == 1.0
@@ -51,8 +39,7 @@ def test_perfect_tracker():
 
 def test_id_swap_midway():
     """Two gt tracks, 10 frames; the tracker's two ids swap after frame 5.  Every box is exact."""
-    gt = [gt_row(t, i, i) for t in range(1, 11) for i in (1, 2)]
-    tr = [tr_row(t, (i if t <= 5 else 3 - i), i) for t in range(1, 11) for i in (1, 2)]
+    gt, tr = EC.id_swap_midway()
     r = ref(gt, tr)["S"]
     c = r["CLEAR"]
     assert (c["CLR_TP"], c["CLR_FN"], c["CLR_FP"], c["IDSW"], c["Frag"]) == (20, 0, 0, 2, 0)
@@ -73,14 +60,12 @@ def test_id_swap_midway():
 
 
 def test_track_dropped_for_three_frames():
-    gt = [gt_row(t, i, i) for t in range(1, 11) for i in (1, 2)]
-    tr = [tr_row(t, i, i) for t in range(1, 11) for i in (1, 2) if not (i == 2 and 4 <= t <= 6)]
+    gt, tr = EC.track_dropped_for_three_frames()
     c = ref(gt, tr)["S"]["CLEAR"]
     assert (c["CLR_TP"], c["CLR_FN"], c["CLR_FP"], c["IDSW"], c["Frag"]) == (17, 3, 0, 0, 1)
     assert c["MOTA"] == 17 / 20 and (c["MT"], c["PT"], c["ML"]) == (1, 1, 0)  # 7 / 10 <= 0.8
     # the same with the whole frame empty (prev_t is cleared on a frame without tracker boxes)
-    gt1 = [gt_row(t, 1, 1) for t in range(1, 11)]
-    tr1 = [tr_row(t, 1, 1) for t in range(1, 11) if not 4 <= t <= 6]
+    gt1, tr1 = EC.whole_frames_dropped()
     c = ref(gt1, tr1)["S"]["CLEAR"]
     assert (c["CLR_TP"], c["CLR_FN"], c["Frag"], c["IDSW"]) == (7, 3, 1, 0)
 
@@ -88,9 +73,7 @@ def test_track_dropped_for_three_frames():
 def test_distractor_and_zero_marked_rows():
     """Object 1 is a pedestrian, object 2 a class-8 distractor, object 3 a class-1 row with
     zero_marked = 0; the tracker reports all three."""
-    gt = [r for t in range(1, 5) for r in (gt_row(t, 1, 1), gt_row(t, 2, 2, zm=0, cls=8),
-                                           gt_row(t, 3, 3, zm=0, cls=1))]
-    tr = [tr_row(t, i, i) for t in range(1, 5) for i in (1, 2, 3)]
+    gt, tr = EC.distractor_and_zero_marked_rows()
     r = ref(gt, tr)["S"]
     # the box on the distractor is removed; the one on the unmarked pedestrian stays as an FP
     assert r["Count"] == {"Dets": 8, "GT_Dets": 4, "IDs": 2, "GT_IDs": 1}
@@ -99,8 +82,7 @@ def test_distractor_and_zero_marked_rows():
     assert (r["Identity"]["IDTP"], r["Identity"]["IDFN"], r["Identity"]["IDFP"]) == (4, 0, 4)
     assert r["HOTA"]["DetA"] == 0.5 and r["HOTA"]["AssA"] == 1.0
     # class 6 is a distractor for MOT20 only
-    gt6 = [r for t in range(1, 5) for r in (gt_row(t, 1, 1), gt_row(t, 2, 2, zm=0, cls=6))]
-    tr6 = [tr_row(t, i, i) for t in range(1, 5) for i in (1, 2)]
+    gt6, tr6 = EC.class6_rows()
     assert ref(gt6, tr6, benchmark="MOT17")["S"]["Count"]["Dets"] == 8
     assert ref(gt6, tr6, benchmark="MOT20")["S"]["Count"]["Dets"] == 4
 
@@ -120,7 +102,8 @@ def test_empty_results_and_gt_free_frames(tmp_path):
     names, frames, gts, trs2 = evaluation.prepare_inputs({"S": np.asarray(gt)}, tmp_path / "none")
     assert trs2[0].shape == (0, 6)
     # frames 4 and 5 have tracker boxes and no gt: two FPs, state untouched
-    tr = [tr_row(t, 1, 1) for t in range(1, 6)] + [tr_row(t, 2, 2) for t in range(1, 4)]
+    gt_again, tr = EC.gt_free_frames()
+    assert gt_again == gt
     r = ref(gt, tr, T=5)["S"]
     assert (r["CLEAR"]["CLR_TP"], r["CLEAR"]["CLR_FP"], r["CLEAR"]["CLR_FN"]) == (6, 2, 0)
     assert r["CLEAR"]["MOTA"] == (6 - 2) / 6 and r["CLEAR"]["CLR_Frames"] == 5
