@@ -1141,9 +1141,7 @@ struct bx_boost {
   BxProbe probe;  // stages: 0 embcost, 1 frame, 2 feature
   // per-sequence parameters (bx_boost_set_seq_params_host): the device table dev.seqpar points
   // to, allocated by the first set, and its host mirror with the values as they were given
-  BstSeqPar* d_seqpar = nullptr;
-  std::vector<BstSeqPar> h_seqpar;
-  std::vector<bx_boost_seq_params> h_seqgiven;
+  BxSeqTable<BstSeqPar, bx_boost_seq_params> seqtab;
   double* d_tab = nullptr;  // get_confidence's table once an entry's max_age outgrew the arena's
   double* d_eg = nullptr;   // the DLO numerators' spill when only a table entry needs it
   bool need_g = false;      // D * T entries do not fit cost_lds (the HBM workspace layout)
@@ -1330,7 +1328,7 @@ int bx_boost_copy_state(bx_boost* dst, bx_boost* src) {
 
 int bx_boost_set_seq_params_host(bx_boost* e, int seq0, int nseq,
                                  const bx_boost_seq_params* params_host, void* stream) {
-  if (!e || seq0 < 0 || nseq < 0 || seq0 > e->dev.S - nseq)
+  if (!e || e->seqtab.bad_range(seq0, nseq, e->dev.S))
     return bx_record_error(BX_ERR_INVALID, "bad sequence range");
   int top_age = 0;
   bool want_eg = false;
@@ -1344,8 +1342,7 @@ int bx_boost_set_seq_params_host(bx_boost* e, int seq0, int nseq,
   }
   // frames in flight on any stream read the table, get_confidence's table and BstDev by value
   BX_HIPCHK(hipDeviceSynchronize());
-  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
-  hipStream_t st = (hipStream_t)stream;
+  if (!nseq || (!params_host && !e->seqtab.allocated())) return BX_OK;  // (nothing to clear)
   BstDev& d = e->dev;
   const size_t S = d.S;
   // everything that can fail before anything becomes visible
@@ -1399,37 +1396,14 @@ int bx_boost_set_seq_params_host(bx_boost* e, int seq0, int nseq,
     q.use_vt = p.use_vt != 0;
     q.set = 1;
   }
-  BstSeqPar* tbl = e->d_seqpar;
-  const bool first = !tbl;
-  bool ok = true;
-  if (first)
-    ok = hipMalloc(&tbl, S * sizeof(BstSeqPar)) == hipSuccess &&
-         hipMemset(tbl, 0, S * sizeof(BstSeqPar)) == hipSuccess;
-  ok = ok && hipMemcpyAsync(tbl + seq0, stage.data(), nseq * sizeof(BstSeqPar),
-                            hipMemcpyHostToDevice, st) == hipSuccess &&
-       hipStreamSynchronize(st) == hipSuccess;
-  if (!ok) {
-    // nothing was committed: the mirror, BstDev and the launches' build are as they were; an
-    // existing table gets the mirror's entries back
-    if (first)
-      (void)hipFree(tbl);
-    else
-      (void)hipMemcpy(tbl + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(BstSeqPar),
-                      hipMemcpyHostToDevice);
+  if (int rc = e->seqtab.put(seq0, stage, S, (hipStream_t)stream,
+                             "allocation or copy of the parameter table failed", params_host)) {
+    // nothing was committed: the mirror, BstDev and the launches' build are as they were
     (void)hipFree(eg_new);
     (void)hipFree(tab_new);
-    return bx_record_error(BX_ERR_HIP, "allocation or copy of the parameter table failed");
+    return rc;
   }
   // commit: the device holds the entries
-  if (first) {
-    e->d_seqpar = tbl;
-    e->h_seqpar.assign(S, BstSeqPar{});
-    e->h_seqgiven.assign(S, bx_boost_seq_params{});
-  }
-  for (int k = 0; k < nseq; k++) {
-    e->h_seqpar[seq0 + k] = stage[k];
-    if (params_host) e->h_seqgiven[seq0 + k] = params_host[k];
-  }
   if (tab_new) {
     (void)hipFree(e->d_tab);  // (the device is idle)
     e->d_tab = tab_new;
@@ -1440,15 +1414,15 @@ int bx_boost_set_seq_params_host(bx_boost* e, int seq0, int nseq,
     e->d_eg = eg_new;
     d.e_g = eg_new;
   }
-  d.seqpar = e->d_seqpar;
+  d.seqpar = e->seqtab.dev;
   return BX_OK;
 }
 
 int bx_boost_seq_params_host(bx_boost* e, int seq, bx_boost_seq_params* out_host) {
   if (!e || seq < 0 || seq >= e->dev.S || !out_host)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_boost_seq_params_host");
-  if (!e->h_seqpar.empty() && e->h_seqpar[seq].set) {
-    *out_host = e->h_seqgiven[seq];
+  if (e->seqtab.set_entry(seq)) {
+    *out_host = e->seqtab.given[seq];
     return BX_OK;
   }
   const bx_boost_config& c = e->cfg;
@@ -1474,7 +1448,7 @@ int bx_boost_destroy(bx_boost* e) {
   (void)hipFree(e->h_ccnt);
   (void)hipFree(e->h_hold);
   (void)hipFree(e->h_cwarp);
-  (void)hipFree(e->d_seqpar);
+  e->seqtab.free();
   (void)hipFree(e->d_tab);
   (void)hipFree(e->d_eg);
   delete e;

@@ -410,8 +410,7 @@ struct bx_deepoc : OcsHost {
   BxProbe probe;  // stages: 0 embcost, 1 frame, 2 feature
   // per-sequence parameters (bx_deepoc_set_seq_params_host): the device table dev.seqpar points
   // to, allocated by the first set, and its host mirror
-  DocSeqPar* d_seqpar = nullptr;
-  std::vector<DocSeqPar> h_seqpar;
+  BxSeqTable<DocSeqPar> seqtab;
 };
 
 // the field checks bx_deepoc_create and bx_deepoc_set_seq_params_host share
@@ -569,7 +568,7 @@ int bx_deepoc_destroy(bx_deepoc* e) {
   if (!e) return BX_OK;
   e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->d_seqpar);
+  e->seqtab.free();
   e->sg.free();
   cls_glue_free(e->pc);
   (void)hipFree(e->h_cwarp);
@@ -707,7 +706,7 @@ int bx_deepoc_set_frame_size(bx_deepoc* e, int seq, double w, double h, void* st
 
 int bx_deepoc_set_seq_params_host(bx_deepoc* e, int seq0, int nseq,
                                   const bx_deepoc_seq_params* params_host, void* stream) {
-  if (!e || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.o.S)
+  if (!e || e->seqtab.bad_range(seq0, nseq, e->dev.o.S))
     return bx_record_error(BX_ERR_INVALID, "bad sequence range");
   for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
     if (bad_delta_t(params_host[k].delta_t))
@@ -715,23 +714,11 @@ int bx_deepoc_set_seq_params_host(bx_deepoc* e, int seq0, int nseq,
     if (bad_asso_kind(params_host[k].asso_kind))
       return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
   }
-  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
-  hipStream_t st = (hipStream_t)stream;
-  const size_t S = e->dev.o.S;
-  if (!e->d_seqpar) {
-    if (hipMalloc(&e->d_seqpar, S * sizeof(DocSeqPar)) != hipSuccess) {
-      e->d_seqpar = nullptr;
-      return bx_record_error(BX_ERR_HIP, "hipMalloc of the DeepOCSort parameter table failed");
-    }
-    BX_HIPCHK(hipMemset(e->d_seqpar, 0, S * sizeof(DocSeqPar)));
-    e->h_seqpar.assign(S, DocSeqPar{});
-    e->dev.seqpar = e->d_seqpar;
-  }
-  for (int k = 0; k < nseq; k++) {
-    DocSeqPar& d = e->h_seqpar[seq0 + k];
-    d = DocSeqPar{};
-    if (!params_host) continue;
+  if (!nseq || (!params_host && !e->seqtab.allocated())) return BX_OK;  // (nothing to clear)
+  std::vector<DocSeqPar> stage(nseq, DocSeqPar{});
+  for (int k = 0; params_host && k < nseq; k++) {
     const bx_deepoc_seq_params& p = params_host[k];
+    DocSeqPar& d = stage[k];
     d.o.min_conf = 0.0;
     d.o.det_thresh = p.det_thresh;
     d.o.asso_threshold = p.iou_threshold;
@@ -749,9 +736,10 @@ int bx_deepoc_set_seq_params_host(bx_deepoc* e, int seq0, int nseq,
     d.aw_param = p.aw_param;
     d.aw_off = p.aw_off != 0;
   }
-  BX_HIPCHK(hipMemcpyAsync(e->d_seqpar + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(DocSeqPar),
-                           hipMemcpyHostToDevice, st));
-  BX_HIPCHK(hipStreamSynchronize(st));
+  if (int rc = e->seqtab.put(seq0, stage, e->dev.o.S, (hipStream_t)stream,
+                             "allocation or copy of the DeepOCSort parameter table failed"))
+    return rc;
+  e->dev.seqpar = e->seqtab.dev;
   return BX_OK;
 }
 
@@ -762,12 +750,10 @@ int bx_deepoc_seq_params_host(bx_deepoc* e, int seq, bx_deepoc_seq_params* out_h
   bx_deepoc_seq_params o = {c.det_thresh, c.iou_threshold, c.inertia, c.q_xy_scaling,
                             c.q_s_scaling, c.w_association_emb, c.alpha_fixed_emb, c.aw_param,
                             c.max_age, c.min_hits, c.delta_t, c.aw_off != 0, c.asso_kind};
-  if (!e->h_seqpar.empty() && e->h_seqpar[seq].o.set) {
-    const DocSeqPar& d = e->h_seqpar[seq];
-    o = {d.o.det_thresh, d.o.asso_threshold, d.o.inertia, d.o.q_xy, d.o.q_s, d.w_emb,
-         d.alpha_fixed, d.aw_param, d.o.max_age, d.o.min_hits, d.o.delta_t, d.aw_off,
-         d.o.asso_kind};
-  }
+  if (const DocSeqPar* d = e->seqtab.set_entry(seq))
+    o = {d->o.det_thresh, d->o.asso_threshold, d->o.inertia, d->o.q_xy, d->o.q_s, d->w_emb,
+         d->alpha_fixed, d->aw_param, d->o.max_age, d->o.min_hits, d->o.delta_t, d->aw_off,
+         d->o.asso_kind};
   *out_host = o;
   return BX_OK;
 }

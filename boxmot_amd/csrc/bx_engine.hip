@@ -2023,9 +2023,7 @@ struct bx_engine {
   double* h_cwarp = nullptr;  // [C][6] the class calls' warps
   // per-sequence parameters (bx_engine_set_seq_params_host): the device table dev.seqpar points
   // to, allocated by the first set, and its host mirror with the values as they were given
-  SeqPar* d_seqpar = nullptr;
-  std::vector<SeqPar> h_seqpar;
-  std::vector<bx_engine_seq_params> h_seqgiven;
+  BxSeqTable<SeqPar, bx_engine_seq_params> seqtab;
 };
 
 namespace {
@@ -2431,7 +2429,7 @@ int bx_engine_destroy(bx_engine* e) {
   (void)hipFree(e->h_coff);
   (void)hipFree(e->h_ccnt);
   (void)hipFree(e->h_cwarp);
-  (void)hipFree(e->d_seqpar);
+  e->seqtab.free();
   delete e;
   return BX_OK;
 }
@@ -2924,7 +2922,7 @@ int bx_engine_embdist_host(bx_engine* e, int seq, int cap, uint32_t* pairs_out, 
 
 int bx_engine_set_seq_params_host(bx_engine* e, int seq0, int nseq,
                                   const bx_engine_seq_params* params_host, void* stream) {
-  if (!e || seq0 < 0 || nseq < 0 || seq0 > e->dev.S - nseq)
+  if (!e || e->seqtab.bad_range(seq0, nseq, e->dev.S))
     return set_err(BX_ERR_INVALID, "bad sequence range");
   for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
     if (params_host[k].track_buffer < 0)
@@ -2935,26 +2933,12 @@ int bx_engine_set_seq_params_host(bx_engine* e, int seq0, int nseq,
   if (int rc = settle(e)) return rc;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (e->k1s) BX_HIPCHK(hipStreamSynchronize(e->k1s));
-  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
-  hipStream_t st = (hipStream_t)stream;
-  const size_t S = e->dev.S;
-  if (!e->d_seqpar) {
-    if (hipMalloc(&e->d_seqpar, S * sizeof(SeqPar)) != hipSuccess) {
-      e->d_seqpar = nullptr;
-      return set_err(BX_ERR_HIP, "hipMalloc of the engine's parameter table failed");
-    }
-    BX_HIPCHK(hipMemset(e->d_seqpar, 0, S * sizeof(SeqPar)));
-    e->h_seqpar.assign(S, SeqPar{});
-    e->h_seqgiven.assign(S, bx_engine_seq_params{});
-    e->dev.seqpar = e->d_seqpar;
-  }
+  if (!nseq || (!params_host && !e->seqtab.allocated())) return BX_OK;  // (nothing to clear)
   const bool byte = e->dev.kind == BX_BYTETRACK;
-  for (int k = 0; k < nseq; k++) {
-    SeqPar& d = e->h_seqpar[seq0 + k];
-    d = SeqPar{};
-    if (!params_host) continue;
+  std::vector<SeqPar> stage(nseq, SeqPar{});
+  for (int k = 0; params_host && k < nseq; k++) {
     const bx_engine_seq_params& p = params_host[k];
-    e->h_seqgiven[seq0 + k] = p;
+    SeqPar& d = stage[k];
     // as bx_engine_create resolves bx_config
     d.match_thresh = p.match_thresh;
     d.max_time_lost = (int)(p.frame_rate / 30.0 * p.track_buffer);
@@ -2969,9 +2953,11 @@ int bx_engine_set_seq_params_host(bx_engine* e, int seq0, int nseq,
     d.fuse_first = p.fuse_first_associate;
     d.set = 1;
   }
-  BX_HIPCHK(hipMemcpyAsync(e->d_seqpar + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(SeqPar),
-                           hipMemcpyHostToDevice, st));
-  BX_HIPCHK(hipStreamSynchronize(st));
+  if (int rc = e->seqtab.put(seq0, stage, e->dev.S, (hipStream_t)stream,
+                             "allocation or copy of the engine's parameter table failed",
+                             params_host))
+    return rc;
+  e->dev.seqpar = e->seqtab.dev;
   return BX_OK;
 }
 
@@ -2979,8 +2965,8 @@ int bx_engine_seq_params_host(bx_engine* e, int seq, bx_engine_seq_params* out_h
   if (!e || seq < 0 || seq >= e->dev.S || !out_host)
     return set_err(BX_ERR_INVALID, "bad arguments to bx_engine_seq_params_host");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (!e->h_seqpar.empty() && e->h_seqpar[seq].set) {
-    *out_host = e->h_seqgiven[seq];
+  if (e->seqtab.set_entry(seq)) {
+    *out_host = e->seqtab.given[seq];
     return BX_OK;
   }
   const bx_config& c = e->cfg;

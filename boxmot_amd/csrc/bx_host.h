@@ -1,5 +1,6 @@
 // bx_host.h — the host layer every translation unit of the library shares: the HIP error check,
-// the stage timing probe, the update_host staging buffers and the arena carve.  Host code only
+// the stage timing probe, the update_host staging buffers, the arena carve and the per-sequence
+// parameter table.  Host code only
 // (nothing __device__ or __global__): including it leaves a file's device code as it was.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -87,6 +88,77 @@ struct BxProbe {
     }
     BX_HIPCHK(hipEventRecord(ev[used].first, st));
     return BX_OK;
+  }
+};
+
+// An entry's `set` flag: its own, or that of the OcsSeqPar it wraps (DeepOCSort, HybridSort).
+template <class E> auto bx_entry_set(const E& e) -> decltype(e.set) { return e.set; }
+template <class E> auto bx_entry_set(const E& e) -> decltype(e.o.set) { return e.o.set; }
+
+struct BxNoGiven {};
+
+// The per-sequence parameter table of an engine (*_set_seq_params_host): a zeroed [S] device table
+// allocated on first use, its host mirror and, for an engine that echoes the caller's struct back,
+// the structs as given.  An engine validates and resolves its entries into a staged range; put()
+// is the one place that allocates, uploads and rolls back.
+template <class Entry, class Given = BxNoGiven>
+struct BxSeqTable {
+  Entry* dev = nullptr;       // [S], what the engine's dev.seqpar points to after a put
+  std::vector<Entry> mirror;  // [S] once allocated
+  std::vector<Given> given;   // [S] once allocated
+
+  static bool bad_range(int seq0, int nseq, int S) {
+    return seq0 < 0 || nseq < 0 || seq0 > S - nseq;
+  }
+  bool allocated() const { return dev != nullptr; }
+  // sequence `seq`'s entry when it has one of its own, else null
+  const Entry* set_entry(int seq) const {
+    return allocated() && bx_entry_set(mirror[seq]) ? &mirror[seq] : nullptr;
+  }
+
+  // Entries [seq0, seq0 + stage.size()) := stage (a default Entry clears one), on `st`, which is
+  // synchronised.  Nothing is committed before the device holds the range: on a failure a table
+  // allocated by this call is freed, an older one gets the mirror's entries back, and pointer,
+  // mirror and `given` are as they were.  given_in: the caller's structs of the range, or null.
+  int put(int seq0, const std::vector<Entry>& stage, size_t S, hipStream_t st, const char* what,
+          const Given* given_in = nullptr) {
+    const size_t n = stage.size();
+    Entry* tbl = dev;
+    const bool first = !tbl;
+    bool ok = true;
+    if (first) {
+      if (hipMalloc(&tbl, S * sizeof(Entry)) != hipSuccess) tbl = nullptr, ok = false;
+      ok = ok && hipMemset(tbl, 0, S * sizeof(Entry)) == hipSuccess;
+    }
+    ok = ok && hipMemcpyAsync(tbl + seq0, stage.data(), n * sizeof(Entry), hipMemcpyHostToDevice,
+                              st) == hipSuccess &&
+         hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) {
+      if (first)
+        (void)hipFree(tbl);
+      else
+        (void)hipMemcpy(tbl + seq0, mirror.data() + seq0, n * sizeof(Entry),
+                        hipMemcpyHostToDevice);
+      return bx_record_error(BX_ERR_HIP, what);
+    }
+    if (first) {
+      dev = tbl;
+      mirror.assign(S, Entry{});
+      given.assign(S, Given{});
+    }
+    for (size_t k = 0; k < n; k++) {
+      mirror[seq0 + k] = stage[k];
+      if (given_in) given[seq0 + k] = given_in[k];
+    }
+    return BX_OK;
+  }
+
+  // safe on a table that was never allocated, and twice
+  void free() {
+    (void)hipFree(dev);
+    dev = nullptr;
+    mirror.clear();
+    given.clear();
   }
 };
 

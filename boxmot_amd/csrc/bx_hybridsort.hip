@@ -803,8 +803,7 @@ struct bx_hybrid : OcsHost {
   BxProbe probe;  // stages: 0 distances, 1 frame, 2 feature
   // per-sequence parameters (bx_hybrid_set_seq_params_host): the device table dev.seqpar points
   // to, allocated by the first set, and its host mirror
-  HybSeqPar* d_seqpar = nullptr;
-  std::vector<HybSeqPar> h_seqpar;
+  BxSeqTable<HybSeqPar> seqtab;
 };
 
 // the field checks bx_hybrid_create and bx_hybrid_set_seq_params_host share
@@ -978,7 +977,7 @@ int bx_hybrid_destroy(bx_hybrid* e) {
   if (!e) return BX_OK;
   e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->d_seqpar);
+  e->seqtab.free();
   e->sg.free();
   cls_glue_free(e->pc);
   delete e;
@@ -1026,7 +1025,7 @@ int bx_hybrid_update_host(bx_hybrid* e, int seq, const float* dets, int n, const
 
 int bx_hybrid_set_seq_params_host(bx_hybrid* e, int seq0, int nseq,
                                   const bx_hybrid_seq_params* params_host, void* stream) {
-  if (!e || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.o.S)
+  if (!e || e->seqtab.bad_range(seq0, nseq, e->dev.o.S))
     return bx_record_error(BX_ERR_INVALID, "bad sequence range");
   for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
     if (bad_delta_t(params_host[k].delta_t))
@@ -1036,23 +1035,11 @@ int bx_hybrid_set_seq_params_host(bx_hybrid* e, int seq0, int nseq,
     if (bad_asso_kind(params_host[k].asso_kind))
       return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
   }
-  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
-  hipStream_t st = (hipStream_t)stream;
-  const size_t S = e->dev.o.S;
-  if (!e->d_seqpar) {
-    if (hipMalloc(&e->d_seqpar, S * sizeof(HybSeqPar)) != hipSuccess) {
-      e->d_seqpar = nullptr;
-      return bx_record_error(BX_ERR_HIP, "hipMalloc of the HybridSort parameter table failed");
-    }
-    BX_HIPCHK(hipMemset(e->d_seqpar, 0, S * sizeof(HybSeqPar)));
-    e->h_seqpar.assign(S, HybSeqPar{});
-    e->dev.seqpar = e->d_seqpar;
-  }
-  for (int k = 0; k < nseq; k++) {
-    HybSeqPar& d = e->h_seqpar[seq0 + k];
-    d = HybSeqPar{};
-    if (!params_host) continue;
+  if (!nseq || (!params_host && !e->seqtab.allocated())) return BX_OK;  // (nothing to clear)
+  std::vector<HybSeqPar> stage(nseq, HybSeqPar{});
+  for (int k = 0; params_host && k < nseq; k++) {
     const bx_hybrid_seq_params& p = params_host[k];
+    HybSeqPar& d = stage[k];
     d.o.det_thresh = p.det_thresh;
     d.o.asso_threshold = p.iou_threshold;
     d.o.inertia = p.inertia;
@@ -1064,9 +1051,10 @@ int bx_hybrid_set_seq_params_host(bx_hybrid* e, int seq0, int nseq,
     d.tcm_w = p.tcm_first_step_weight;
     d.lt_w = p.longterm_reid_weight;
   }
-  BX_HIPCHK(hipMemcpyAsync(e->d_seqpar + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(HybSeqPar),
-                           hipMemcpyHostToDevice, st));
-  BX_HIPCHK(hipStreamSynchronize(st));
+  if (int rc = e->seqtab.put(seq0, stage, e->dev.o.S, (hipStream_t)stream,
+                             "allocation or copy of the HybridSort parameter table failed"))
+    return rc;
+  e->dev.seqpar = e->seqtab.dev;
   return BX_OK;
 }
 
@@ -1077,11 +1065,9 @@ int bx_hybrid_seq_params_host(bx_hybrid* e, int seq, bx_hybrid_seq_params* out_h
   bx_hybrid_seq_params o = {c.det_thresh, c.iou_threshold, c.inertia, c.longterm_reid_weight,
                             c.tcm_first_step_weight, c.max_age, c.min_hits, c.delta_t,
                             c.asso_kind};
-  if (!e->h_seqpar.empty() && e->h_seqpar[seq].o.set) {
-    const HybSeqPar& d = e->h_seqpar[seq];
-    o = {d.o.det_thresh, d.o.asso_threshold, d.o.inertia, d.lt_w, d.tcm_w, d.o.max_age,
-         d.o.min_hits, d.o.delta_t, d.o.asso_kind};
-  }
+  if (const HybSeqPar* d = e->seqtab.set_entry(seq))
+    o = {d->o.det_thresh, d->o.asso_threshold, d->o.inertia, d->lt_w, d->tcm_w, d->o.max_age,
+         d->o.min_hits, d->o.delta_t, d->o.asso_kind};
   *out_host = o;
   return BX_OK;
 }

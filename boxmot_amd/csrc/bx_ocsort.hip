@@ -199,8 +199,7 @@ struct bx_ocsort : OcsHost {
   BxProbe probe;  // the frame kernel is stage 0
   // per-sequence parameters (bx_ocsort_set_seq_params_host): the device table dev.seqpar points
   // to, allocated by the first set, and its host mirror
-  OcsSeqPar* d_seqpar = nullptr;
-  std::vector<OcsSeqPar> h_seqpar;
+  BxSeqTable<OcsSeqPar> seqtab;
 };
 
 // the field checks bx_ocsort_create and bx_ocsort_set_seq_params_host share
@@ -327,7 +326,7 @@ int bx_ocsort_destroy(bx_ocsort* e) {
   if (!e) return BX_OK;
   e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->d_seqpar);
+  e->seqtab.free();
   e->sg.free();
   (void)hipFree(e->h_coff);
   (void)hipFree(e->h_ccnt);
@@ -490,7 +489,7 @@ int bx_ocsort_set_frame_size(bx_ocsort* e, int seq, double w, double h, void* st
 
 int bx_ocsort_set_seq_params_host(bx_ocsort* e, int seq0, int nseq,
                                   const bx_ocsort_seq_params* params_host, void* stream) {
-  if (!e || seq0 < 0 || nseq < 0 || seq0 + nseq > e->dev.S)
+  if (!e || e->seqtab.bad_range(seq0, nseq, e->dev.S))
     return bx_record_error(BX_ERR_INVALID, "bad sequence range");
   for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
     if (bad_delta_t(params_host[k].delta_t))
@@ -498,23 +497,11 @@ int bx_ocsort_set_seq_params_host(bx_ocsort* e, int seq0, int nseq,
     if (bad_asso_kind(params_host[k].asso_kind))
       return bx_record_error(BX_ERR_INVALID, "unknown asso_kind");
   }
-  if (!nseq || (!params_host && !e->d_seqpar)) return BX_OK;  // (nothing to clear)
-  hipStream_t st = (hipStream_t)stream;
-  const size_t S = e->dev.S;
-  if (!e->d_seqpar) {
-    if (hipMalloc(&e->d_seqpar, S * sizeof(OcsSeqPar)) != hipSuccess) {
-      e->d_seqpar = nullptr;
-      return bx_record_error(BX_ERR_HIP, "hipMalloc of the OCSort parameter table failed");
-    }
-    BX_HIPCHK(hipMemset(e->d_seqpar, 0, S * sizeof(OcsSeqPar)));
-    e->h_seqpar.assign(S, OcsSeqPar{});
-    e->dev.seqpar = e->d_seqpar;
-  }
-  for (int k = 0; k < nseq; k++) {
-    OcsSeqPar& d = e->h_seqpar[seq0 + k];
-    d = OcsSeqPar{};
-    if (!params_host) continue;
+  if (!nseq || (!params_host && !e->seqtab.allocated())) return BX_OK;  // (nothing to clear)
+  std::vector<OcsSeqPar> stage(nseq, OcsSeqPar{});
+  for (int k = 0; params_host && k < nseq; k++) {
     const bx_ocsort_seq_params& p = params_host[k];
+    OcsSeqPar& d = stage[k];
     d.min_conf = p.min_conf;
     d.det_thresh = p.det_thresh;
     d.asso_threshold = p.asso_threshold;
@@ -528,9 +515,10 @@ int bx_ocsort_set_seq_params_host(bx_ocsort* e, int seq0, int nseq,
     d.asso_kind = p.asso_kind;
     d.set = 1;
   }
-  BX_HIPCHK(hipMemcpyAsync(e->d_seqpar + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(OcsSeqPar),
-                           hipMemcpyHostToDevice, st));
-  BX_HIPCHK(hipStreamSynchronize(st));
+  if (int rc = e->seqtab.put(seq0, stage, e->dev.S, (hipStream_t)stream,
+                             "allocation or copy of the OCSort parameter table failed"))
+    return rc;
+  e->dev.seqpar = e->seqtab.dev;
   return BX_OK;
 }
 
@@ -541,11 +529,9 @@ int bx_ocsort_seq_params_host(bx_ocsort* e, int seq, bx_ocsort_seq_params* out_h
   bx_ocsort_seq_params o = {c.min_conf, c.det_thresh, c.asso_threshold, c.inertia, c.q_xy_scaling,
                             c.q_s_scaling, c.max_age, c.min_hits, c.delta_t, c.use_byte,
                             c.asso_kind};
-  if (!e->h_seqpar.empty() && e->h_seqpar[seq].set) {
-    const OcsSeqPar& d = e->h_seqpar[seq];
-    o = {d.min_conf, d.det_thresh, d.asso_threshold, d.inertia, d.q_xy, d.q_s, d.max_age,
-         d.min_hits, d.delta_t, d.use_byte, d.asso_kind};
-  }
+  if (const OcsSeqPar* d = e->seqtab.set_entry(seq))
+    o = {d->min_conf, d->det_thresh, d->asso_threshold, d->inertia, d->q_xy, d->q_s, d->max_age,
+         d->min_hits, d->delta_t, d->use_byte, d->asso_kind};
   *out_host = o;
   return BX_OK;
 }

@@ -3646,9 +3646,7 @@ struct bx_ss {
   std::vector<double> h_occ_thr;
   // per-sequence parameters (bx_ss_set_seq_params_host): the device table dev.seqpar points to,
   // allocated by the first set, and its host mirror with the values as they were given
-  SsSeqPar* d_seqpar = nullptr;
-  std::vector<SsSeqPar> h_seqpar;
-  std::vector<bx_ss_seq_params> h_seqgiven;
+  BxSeqTable<SsSeqPar, bx_ss_seq_params> seqtab;
   void* arena = nullptr;
   // update_host staging (detections as doubles, 10-wide rows); sg.p_sq: the counters row of the
   // last update_host sequence (bx_ss_counters_host answers from it)
@@ -4066,7 +4064,7 @@ int bx_ss_copy_state(bx_ss* dst, bx_ss* src) {
 
 int bx_ss_set_seq_params_host(bx_ss* e, int seq0, int nseq, const bx_ss_seq_params* params_host,
                               void* stream) {
-  if (!e || seq0 < 0 || nseq < 0 || seq0 > e->dev.S - nseq)
+  if (!e || e->seqtab.bad_range(seq0, nseq, e->dev.S))
     return bx_record_error(BX_ERR_INVALID, "bad sequence range");
   SsDev& d = e->dev;
   for (int k = 0; params_host && k < nseq; k++) {  // every entry first: a bad one changes nothing
@@ -4094,9 +4092,7 @@ int bx_ss_set_seq_params_host(bx_ss* e, int seq0, int nseq, const bx_ss_seq_para
       return bx_record_error(BX_ERR_INVALID,
                              "per-sequence parameters change only at frame counter 0 "
                              "(a fresh or just reset sequence)");
-  if (!params_host && !e->d_seqpar) return BX_OK;  // (nothing to clear)
-  hipStream_t st = (hipStream_t)stream;
-  const size_t S = d.S;
+  if (!params_host && !e->seqtab.allocated()) return BX_OK;  // (nothing to clear)
   // the entries as bx_ss_create resolves bx_ss_config, and the seeds of the adapted state (the
   // engine's own for a cleared sequence), staged beside the mirror
   std::vector<SsSeqPar> stage(nseq, SsSeqPar{});
@@ -4126,50 +4122,24 @@ int bx_ss_set_seq_params_host(bx_ss* e, int seq0, int nseq, const bx_ss_seq_para
     q[Q_BUDGET] = p.nn_budget;
     thr[2 * k] = thr[2 * k + 1] = p.max_cos_dist;
   }
-  SsSeqPar* tbl = e->d_seqpar;
-  const bool first = !tbl;
-  bool ok = true;
-  if (first)
-    ok = hipMalloc(&tbl, S * sizeof(SsSeqPar)) == hipSuccess &&
-         hipMemset(tbl, 0, S * sizeof(SsSeqPar)) == hipSuccess;
-  ok = ok && hipMemcpyAsync(tbl + seq0, stage.data(), nseq * sizeof(SsSeqPar),
-                            hipMemcpyHostToDevice, st) == hipSuccess &&
-       hipStreamSynchronize(st) == hipSuccess;
-  if (!ok) {
-    // nothing was committed: the mirror, SsDev and the launches' builds are as they were; an
-    // existing table gets the mirror's entries back
-    if (first)
-      (void)hipFree(tbl);
-    else
-      (void)hipMemcpy(tbl + seq0, e->h_seqpar.data() + seq0, nseq * sizeof(SsSeqPar),
-                      hipMemcpyHostToDevice);
-    return bx_record_error(BX_ERR_HIP, "allocation or copy of the parameter table failed");
-  }
+  if (int rc = e->seqtab.put(seq0, stage, d.S, (hipStream_t)stream,
+                             "allocation or copy of the parameter table failed", params_host))
+    return rc;  // (nothing was committed: SsDev and the launches' builds are as they were)
+  d.seqpar = e->seqtab.dev;
   // the sequences' seeds (their rows hold nothing else yet: frame counter 0)
   BX_HIPCHK(hipMemcpy(d.sq + (size_t)seq0 * SQS, sq.data(), sq.size() * sizeof(int),
                       hipMemcpyHostToDevice));
   BX_HIPCHK(hipMemcpy(d.sqd + (size_t)seq0 * 2, thr.data(), thr.size() * sizeof(double),
                       hipMemcpyHostToDevice));
   e->cache_seq = -1;
-  // commit: the device holds the entries
-  if (first) {
-    e->d_seqpar = tbl;
-    e->h_seqpar.assign(S, SsSeqPar{});
-    e->h_seqgiven.assign(S, bx_ss_seq_params{});
-  }
-  for (int k = 0; k < nseq; k++) {
-    e->h_seqpar[seq0 + k] = stage[k];
-    if (params_host) e->h_seqgiven[seq0 + k] = params_host[k];
-  }
-  d.seqpar = e->d_seqpar;
   return BX_OK;
 }
 
 int bx_ss_seq_params_host(bx_ss* e, int seq, bx_ss_seq_params* out_host) {
   if (!e || seq < 0 || seq >= e->dev.S || !out_host)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_ss_seq_params_host");
-  if (!e->h_seqpar.empty() && e->h_seqpar[seq].set) {
-    *out_host = e->h_seqgiven[seq];
+  if (e->seqtab.set_entry(seq)) {
+    *out_host = e->seqtab.given[seq];
     return BX_OK;
   }
   const bx_ss_config& c = e->cfg;
@@ -4191,7 +4161,7 @@ int bx_ss_destroy(bx_ss* e) {
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   e->probe.destroy();
   (void)hipFree(e->arena);
-  (void)hipFree(e->d_seqpar);
+  e->seqtab.free();
   (void)hipFree(e->occ_arena);
   e->sg.free();
   delete e;

@@ -7,6 +7,7 @@ out); ``update_host`` is the single-sequence numpy path the drop-in tracker clas
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass
 
 import numpy as np
@@ -131,6 +132,57 @@ class _OcsFamilyEngine(_TrackListEngine):
         return dict(zip(["tracks", "outputs", "frame"], [int(x) for x in a]))
 
 
+class _SeqTable:
+    """Mixin of the six table engines: an engine whose sequences may each run on parameters of
+    their own (``<prefix>_set_seq_params_host`` / ``<prefix>_seq_params_host``), the engine of a
+    hyper-parameter sweep, K configs x S sequences as K*S sequences of one handle (boxmot_amd.tune).
+
+    The family names ``_SEQ_STRUCT``, the ctypes struct of one entry, and supplies
+    ``_seq_struct(p)``, the struct of its parameter dataclass (``ValueError`` for an entry that
+    differs from the engine in a field that stays engine-wide), and ``_seq_params_of(o)``, the
+    dataclass of a struct, with the engine-wide fields from ``self.params``.  The three stand on
+    the plain engine class, beside its mapping of the dataclass to the C config: ``seq_params``
+    also serves a plain engine (``TableEngine.seq_params(engine, seq)``), whose handle answers
+    the getter without a table."""
+
+    @functools.cached_property
+    def _seq_over(self) -> dict:
+        """sequence -> its own parameters as they were given, for ``_retable``."""
+        return {}
+
+    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
+        """Give sequences [seq0, seq0 + len(params)) parameters of their own: ``params`` is a list
+        of the engine's parameter dataclass.  ``None`` clears the override of ``nseq`` sequences
+        from seq0 (default: all from seq0).  For use between sequences, at frame 0.  An entry the
+        class or the library refuses changes nothing."""
+        if params is None:
+            n = self.n_seq - seq0 if nseq is None else nseq
+            arr = None
+        else:
+            n = len(params)
+            arr = (self._SEQ_STRUCT * max(n, 1))(*[self._seq_struct(p) for p in params])
+        N.check(self._fn("set_seq_params_host")(self._h, int(seq0), int(n), arr, None),
+                f"{self._PREFIX}_set_seq_params_host")
+        for k in range(n):
+            if params is None:
+                self._seq_over.pop(seq0 + k, None)
+            else:
+                self._seq_over[seq0 + k] = params[k]
+
+    def seq_params(self, seq: int):
+        """The parameters sequence ``seq`` runs on: its own when set, else the engine's."""
+        o = self._SEQ_STRUCT()
+        N.check(self._fn("seq_params_host")(self._h, int(seq), C.byref(o)),
+                f"{self._PREFIX}_seq_params_host")
+        return self._seq_params_of(o)
+
+    def _retable(self, e):
+        """``grown()``'s tail: copy_state carries no table, so it is set again on ``e``."""
+        for k, p in sorted(self._seq_over.items()):
+            e.set_seq_params(k, [p])
+        return e
+
+
 class Engine(_NativeEngine):
     _PREFIX = "bx_engine"
 
@@ -183,6 +235,30 @@ class Engine(_NativeEngine):
         u = C.c_int(0)
         N.check(self._L.bx_engine_slots_used_host(self._h, seq, C.byref(u)), "slots_used")
         return u.value
+
+    # ---- one entry of the per-sequence parameter table (_SeqTable)
+    _SEQ_STRUCT = N.BxEngineSeqParams
+
+    def _seq_struct(self, p: EngineParams):
+        tb = p.track_buffer
+        if tb is None:  # the tracker's own default, as Engine.__init__ resolves it
+            tb = 25 if self.kind == "bytetrack" else 30
+        return N.BxEngineSeqParams(
+            min_conf=p.min_conf, track_thresh=p.track_thresh,
+            track_high_thresh=p.track_high_thresh, track_low_thresh=p.track_low_thresh,
+            new_track_thresh=p.new_track_thresh, proximity_thresh=p.proximity_thresh,
+            appearance_thresh=p.appearance_thresh,
+            fuse_first_associate=int(bool(p.fuse_first_associate)),
+            match_thresh=p.match_thresh, track_buffer=int(tb), frame_rate=int(p.frame_rate))
+
+    def _seq_params_of(self, o) -> EngineParams:
+        return EngineParams(
+            min_conf=o.min_conf, track_thresh=o.track_thresh, match_thresh=o.match_thresh,
+            track_buffer=o.track_buffer, frame_rate=o.frame_rate,
+            track_high_thresh=o.track_high_thresh, track_low_thresh=o.track_low_thresh,
+            new_track_thresh=o.new_track_thresh, proximity_thresh=o.proximity_thresh,
+            appearance_thresh=o.appearance_thresh,
+            fuse_first_associate=bool(o.fuse_first_associate), with_reid=self.params.with_reid)
 
     def grown(self, track_cap: int, det_cap: int) -> "Engine":
         """A new engine with larger capacities holding this one's tracker state
@@ -380,74 +456,19 @@ class Engine(_NativeEngine):
 
 
 
-class TableEngine(Engine):
-    """An ``Engine`` whose sequences may each run on parameters of their own
-    (``bx_engine_set_seq_params_host``, include/bxassoc.h): the engine of a ByteTrack / BoT-SORT
-    hyper-parameter sweep, K configs x S sequences as K*S sequences of one handle
-    (boxmot_amd.tune.sweep_bot).  ``with_reid``, the capacities and the embedding width stay the
-    engine's."""
-
-    def __init__(self, kind: str, n_seq: int = 1, track_cap: int = 1024, det_cap: int = 384,
-                 emb_dim: int = 0, emb_f64: bool = False, params: EngineParams | None = None):
-        super().__init__(kind, n_seq, track_cap, det_cap, emb_dim, emb_f64, params)
-        self._seq_over = {}  # sequence -> its own EngineParams, for grown()
+class TableEngine(_SeqTable, Engine):
+    """An ``Engine`` with per-sequence ``EngineParams`` (``_SeqTable``; include/bxassoc.h,
+    boxmot_amd.tune.sweep_bot).  ``with_reid``, which is not part of the table, the capacities and
+    the embedding width stay the engine's."""
 
     def grown(self, track_cap: int, det_cap: int) -> "TableEngine":
-        """As Engine.grown; bx_engine_copy_state carries tracks only, so the table is set again
-        on the new engine."""
+        """As Engine.grown, with the table."""
         e = TableEngine(self.kind, self.n_seq, track_cap, det_cap, self.emb_dim, self.emb_f64,
                         self.params)
         N.check(self._L.bx_engine_copy_state(e._h, self._h), "bx_engine_copy_state")
         if self._overlap:
             e.set_overlap(True)
-        for k, p in sorted(self._seq_over.items()):
-            e.set_seq_params(k, [p])
-        return e
-
-    def _seq_struct(self, p: EngineParams):
-        tb = p.track_buffer
-        if tb is None:  # the tracker's own default, as Engine.__init__ resolves it
-            tb = 25 if self.kind == "bytetrack" else 30
-        return N.BxEngineSeqParams(
-            min_conf=p.min_conf, track_thresh=p.track_thresh,
-            track_high_thresh=p.track_high_thresh, track_low_thresh=p.track_low_thresh,
-            new_track_thresh=p.new_track_thresh, proximity_thresh=p.proximity_thresh,
-            appearance_thresh=p.appearance_thresh,
-            fuse_first_associate=int(bool(p.fuse_first_associate)),
-            match_thresh=p.match_thresh, track_buffer=int(tb), frame_rate=int(p.frame_rate))
-
-    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
-        """Give sequences [seq0, seq0 + len(params)) parameters of their own
-        (bx_engine_set_seq_params_host): ``params`` is a list of EngineParams, whose ``with_reid``
-        is not part of the table.  ``None`` clears the override of ``nseq`` sequences from seq0
-        (default: all from seq0).  For use between sequences, at frame 0."""
-        if params is None:
-            n = self.n_seq - seq0 if nseq is None else nseq
-            arr = None
-        else:
-            n = len(params)
-            arr = (N.BxEngineSeqParams * max(n, 1))(*[self._seq_struct(p) for p in params])
-        N.check(self._L.bx_engine_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
-                "bx_engine_set_seq_params_host")
-        for k in range(n):
-            if params is None:
-                self._seq_over.pop(seq0 + k, None)
-            else:
-                self._seq_over[seq0 + k] = params[k]
-
-    def seq_params(self, seq: int) -> EngineParams:
-        """The parameters sequence ``seq`` runs on (bx_engine_seq_params_host): its own when set,
-        else the engine's; ``with_reid`` is the engine's."""
-        o = N.BxEngineSeqParams()
-        N.check(self._L.bx_engine_seq_params_host(self._h, int(seq), C.byref(o)),
-                "bx_engine_seq_params_host")
-        return EngineParams(
-            min_conf=o.min_conf, track_thresh=o.track_thresh, match_thresh=o.match_thresh,
-            track_buffer=o.track_buffer, frame_rate=o.frame_rate,
-            track_high_thresh=o.track_high_thresh, track_low_thresh=o.track_low_thresh,
-            new_track_thresh=o.new_track_thresh, proximity_thresh=o.proximity_thresh,
-            appearance_thresh=o.appearance_thresh,
-            fuse_first_associate=bool(o.fuse_first_associate), with_reid=self.params.with_reid)
+        return self._retable(e)
 
 
 def _class_warps(warp, n_classes: int):
@@ -479,6 +500,12 @@ def _asso_kind(name: str) -> int:
     if name not in KINDS:
         raise ValueError(f"Invalid association mode: {name}. Choose from {list(KINDS)}")
     return KINDS[name]
+
+
+def _asso_name(kind: int) -> str:
+    from .iou import KINDS
+
+    return {v: k for k, v in KINDS.items()}[kind]
 
 
 @dataclass
@@ -517,6 +544,24 @@ class OcsortEngine(_OcsFamilyEngine):
             min_hits=int(p.min_hits), delta_t=int(p.delta_t), use_byte=int(bool(p.use_byte)),
             asso_kind=_asso_kind(p.asso_func), frame_w=float(p.frame_w), frame_h=float(p.frame_h))
         self._create(cfg)
+
+    # ---- one entry of the per-sequence parameter table (_SeqTable)
+    _SEQ_STRUCT = N.BxOcsortSeqParams
+
+    def _seq_struct(self, p: OcsortParams):
+        return N.BxOcsortSeqParams(
+            min_conf=p.min_conf, det_thresh=p.det_thresh, asso_threshold=p.asso_threshold,
+            inertia=p.inertia, q_xy_scaling=p.Q_xy_scaling, q_s_scaling=p.Q_s_scaling,
+            max_age=int(p.max_age), min_hits=int(p.min_hits), delta_t=int(p.delta_t),
+            use_byte=int(bool(p.use_byte)), asso_kind=_asso_kind(p.asso_func))
+
+    def _seq_params_of(self, o) -> OcsortParams:
+        return OcsortParams(min_conf=o.min_conf, det_thresh=o.det_thresh, max_age=o.max_age,
+                            min_hits=o.min_hits, asso_threshold=o.asso_threshold,
+                            delta_t=o.delta_t, inertia=o.inertia, use_byte=bool(o.use_byte),
+                            Q_xy_scaling=o.q_xy_scaling, Q_s_scaling=o.q_s_scaling,
+                            asso_func=_asso_name(o.asso_kind), frame_w=self.params.frame_w,
+                            frame_h=self.params.frame_h)
 
     def grown(self, track_cap: int, det_cap: int) -> "OcsortEngine":
         """A new engine with larger capacities holding this one's state (bx_ocsort_copy_state)."""
@@ -575,64 +620,16 @@ class OcsortEngine(_OcsFamilyEngine):
         N.check(self._L.bx_ocsort_probe(self._h, int(bool(on))), "bx_ocsort_probe")
 
 
-class OcsortTableEngine(OcsortEngine):
-    """An ``OcsortEngine`` whose sequences may each run on parameters of their own
-    (``bx_ocsort_set_seq_params_host``, include/bxocsort.h): the engine of a hyper-parameter
-    sweep, K configs x S sequences as K*S sequences of one handle (boxmot_amd.tune)."""
-
-    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
-                 params: OcsortParams | None = None):
-        super().__init__(n_seq, track_cap, det_cap, params)
-        self._seq_over = {}  # sequence -> its own OcsortParams, for grown()
+class OcsortTableEngine(_SeqTable, OcsortEngine):
+    """An ``OcsortEngine`` with per-sequence ``OcsortParams`` (``_SeqTable``; include/bxocsort.h,
+    boxmot_amd.tune.sweep).  frame_w / frame_h, which are not part of the table, stay the
+    engine's."""
 
     def grown(self, track_cap: int, det_cap: int) -> "OcsortTableEngine":
-        """As OcsortEngine.grown; bx_ocsort_copy_state carries tracks only, so the table is set
-        again on the new engine."""
+        """As OcsortEngine.grown, with the table."""
         e = OcsortTableEngine(self.n_seq, track_cap, det_cap, self.params)
         N.check(self._L.bx_ocsort_copy_state(e._h, self._h), "bx_ocsort_copy_state")
-        for k, p in sorted(self._seq_over.items()):
-            e.set_seq_params(k, [p])
-        return e
-
-    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
-        """Give sequences [seq0, seq0 + len(params)) parameters of their own
-        (bx_ocsort_set_seq_params_host): ``params`` is a list of OcsortParams, whose frame_w /
-        frame_h are not part of the table.  ``None`` clears the override of ``nseq`` sequences
-        from seq0 (default: all from seq0).  For use between sequences, at frame 0."""
-        if params is None:
-            n = self.n_seq - seq0 if nseq is None else nseq
-            arr = None
-        else:
-            n = len(params)
-            arr = (N.BxOcsortSeqParams * max(n, 1))(*[N.BxOcsortSeqParams(
-                min_conf=p.min_conf, det_thresh=p.det_thresh, asso_threshold=p.asso_threshold,
-                inertia=p.inertia, q_xy_scaling=p.Q_xy_scaling, q_s_scaling=p.Q_s_scaling,
-                max_age=int(p.max_age), min_hits=int(p.min_hits), delta_t=int(p.delta_t),
-                use_byte=int(bool(p.use_byte)), asso_kind=_asso_kind(p.asso_func))
-                for p in params])
-        N.check(self._L.bx_ocsort_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
-                "bx_ocsort_set_seq_params_host")
-        for k in range(n):
-            if params is None:
-                self._seq_over.pop(seq0 + k, None)
-            else:
-                self._seq_over[seq0 + k] = params[k]
-
-    def seq_params(self, seq: int) -> OcsortParams:
-        """The parameters sequence ``seq`` runs on (bx_ocsort_seq_params_host): its own when set,
-        else the engine's; frame_w / frame_h are the engine's."""
-        from .iou import KINDS
-
-        o = N.BxOcsortSeqParams()
-        N.check(self._L.bx_ocsort_seq_params_host(self._h, int(seq), C.byref(o)),
-                "bx_ocsort_seq_params_host")
-        name = {v: k for k, v in KINDS.items()}[o.asso_kind]
-        return OcsortParams(min_conf=o.min_conf, det_thresh=o.det_thresh, max_age=o.max_age,
-                            min_hits=o.min_hits, asso_threshold=o.asso_threshold,
-                            delta_t=o.delta_t, inertia=o.inertia, use_byte=bool(o.use_byte),
-                            Q_xy_scaling=o.q_xy_scaling, Q_s_scaling=o.q_s_scaling,
-                            asso_func=name, frame_w=self.params.frame_w,
-                            frame_h=self.params.frame_h)
+        return self._retable(e)
 
 
 @dataclass
@@ -682,6 +679,30 @@ class DeepOcsortEngine(_OcsFamilyEngine):
             embedding_off=int(bool(p.embedding_off)), aw_off=int(bool(p.aw_off)),
             asso_kind=_asso_kind(p.asso_func), frame_w=float(p.frame_w), frame_h=float(p.frame_h))
         self._create(cfg)
+
+    # ---- one entry of the per-sequence parameter table (_SeqTable)
+    _SEQ_STRUCT = N.BxDeepocSeqParams
+
+    def _seq_struct(self, p: DeepOcsortParams):
+        if bool(p.embedding_off) != bool(self.params.embedding_off):
+            raise ValueError("embedding_off is engine-wide: a sequence cannot have its own")
+        return N.BxDeepocSeqParams(
+            det_thresh=float(p.det_thresh), iou_threshold=float(p.iou_threshold),
+            inertia=float(p.inertia), q_xy_scaling=float(p.Q_xy_scaling),
+            q_s_scaling=float(p.Q_s_scaling), w_association_emb=float(p.w_association_emb),
+            alpha_fixed_emb=float(p.alpha_fixed_emb), aw_param=float(p.aw_param),
+            max_age=int(p.max_age), min_hits=int(p.min_hits), delta_t=int(p.delta_t),
+            aw_off=int(bool(p.aw_off)), asso_kind=_asso_kind(p.asso_func))
+
+    def _seq_params_of(self, o) -> DeepOcsortParams:
+        return DeepOcsortParams(
+            det_thresh=o.det_thresh, max_age=o.max_age, min_hits=o.min_hits,
+            iou_threshold=o.iou_threshold, delta_t=o.delta_t, asso_func=_asso_name(o.asso_kind),
+            inertia=o.inertia,
+            w_association_emb=o.w_association_emb, alpha_fixed_emb=o.alpha_fixed_emb,
+            aw_param=o.aw_param, embedding_off=self.params.embedding_off, aw_off=bool(o.aw_off),
+            Q_xy_scaling=o.q_xy_scaling, Q_s_scaling=o.q_s_scaling,
+            frame_w=self.params.frame_w, frame_h=self.params.frame_h)
 
     def grown(self, track_cap: int, det_cap: int, map_cap: int | None = None) -> "DeepOcsortEngine":
         """A new engine with larger capacities holding this one's state (bx_deepoc_copy_state);
@@ -797,76 +818,20 @@ class DeepOcsortEngine(_OcsFamilyEngine):
                                                  _p(e)), "state_set")
 
 
-class DeepOcsortTableEngine(DeepOcsortEngine):
-    """A ``DeepOcsortEngine`` whose sequences may each run on parameters of their own
-    (``bx_deepoc_set_seq_params_host``, include/bxdeepocsort.h): the engine of a hyper-parameter
-    sweep, K configs x S sequences as K*S sequences of one handle (boxmot_amd.tune.sweep_reid).
-    ``embedding_off`` stays the engine's: it decides the embedding width and two of the three
-    launches."""
-
-    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
-                 emb_dim: int = 512, params: DeepOcsortParams | None = None):
-        super().__init__(n_seq, track_cap, det_cap, emb_dim, params)
-        self._seq_over = {}  # sequence -> its own DeepOcsortParams, for grown()
+class DeepOcsortTableEngine(_SeqTable, DeepOcsortEngine):
+    """A ``DeepOcsortEngine`` with per-sequence ``DeepOcsortParams`` (``_SeqTable``;
+    include/bxdeepocsort.h, boxmot_amd.tune.sweep_reid).  ``embedding_off`` stays the engine's (it
+    decides the embedding width and two of the three launches: an entry's must be the engine's,
+    ``ValueError``), and so do frame_w / frame_h, which are not part of the table."""
 
     def grown(self, track_cap: int, det_cap: int,
               map_cap: int | None = None) -> "DeepOcsortTableEngine":
-        """As DeepOcsortEngine.grown; bx_deepoc_copy_state carries tracks only, so the table is
-        set again on the new engine."""
+        """As DeepOcsortEngine.grown, with the table."""
         e = DeepOcsortTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim or 1, self.params)
         if map_cap is not None:
             e.classes_config(self.classes().n_classes, map_cap)
         N.check(self._L.bx_deepoc_copy_state(e._h, self._h), "bx_deepoc_copy_state")
-        for k, p in sorted(self._seq_over.items()):
-            e.set_seq_params(k, [p])
-        return e
-
-    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
-        """Give sequences [seq0, seq0 + len(params)) parameters of their own
-        (bx_deepoc_set_seq_params_host): ``params`` is a list of DeepOcsortParams, whose
-        embedding_off must be the engine's and whose frame_w / frame_h are not part of the table.
-        ``None`` clears the override of ``nseq`` sequences from seq0 (default: all from seq0).
-        For use between sequences, at frame 0."""
-        if params is None:
-            n = self.n_seq - seq0 if nseq is None else nseq
-            arr = None
-        else:
-            n = len(params)
-            for p in params:
-                if bool(p.embedding_off) != bool(self.params.embedding_off):
-                    raise ValueError("embedding_off is engine-wide: a sequence cannot have its own")
-            arr = (N.BxDeepocSeqParams * max(n, 1))(*[N.BxDeepocSeqParams(
-                det_thresh=float(p.det_thresh), iou_threshold=float(p.iou_threshold),
-                inertia=float(p.inertia), q_xy_scaling=float(p.Q_xy_scaling),
-                q_s_scaling=float(p.Q_s_scaling), w_association_emb=float(p.w_association_emb),
-                alpha_fixed_emb=float(p.alpha_fixed_emb), aw_param=float(p.aw_param),
-                max_age=int(p.max_age), min_hits=int(p.min_hits), delta_t=int(p.delta_t),
-                aw_off=int(bool(p.aw_off)), asso_kind=_asso_kind(p.asso_func))
-                for p in params])
-        N.check(self._L.bx_deepoc_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
-                "bx_deepoc_set_seq_params_host")
-        for k in range(n):
-            if params is None:
-                self._seq_over.pop(seq0 + k, None)
-            else:
-                self._seq_over[seq0 + k] = params[k]
-
-    def seq_params(self, seq: int) -> DeepOcsortParams:
-        """The parameters sequence ``seq`` runs on (bx_deepoc_seq_params_host): its own when set,
-        else the engine's; embedding_off, frame_w and frame_h are the engine's."""
-        from .iou import KINDS
-
-        o = N.BxDeepocSeqParams()
-        N.check(self._L.bx_deepoc_seq_params_host(self._h, int(seq), C.byref(o)),
-                "bx_deepoc_seq_params_host")
-        name = {v: k for k, v in KINDS.items()}[o.asso_kind]
-        return DeepOcsortParams(
-            det_thresh=o.det_thresh, max_age=o.max_age, min_hits=o.min_hits,
-            iou_threshold=o.iou_threshold, delta_t=o.delta_t, asso_func=name, inertia=o.inertia,
-            w_association_emb=o.w_association_emb, alpha_fixed_emb=o.alpha_fixed_emb,
-            aw_param=o.aw_param, embedding_off=self.params.embedding_off, aw_off=bool(o.aw_off),
-            Q_xy_scaling=o.q_xy_scaling, Q_s_scaling=o.q_s_scaling,
-            frame_w=self.params.frame_w, frame_h=self.params.frame_h)
+        return self._retable(e)
 
 
 def deepoc_embcost(dets_embs, trk_embs, out, stream=None) -> None:
@@ -920,6 +885,25 @@ class HybridsortEngine(_OcsFamilyEngine):
             min_hits=int(p.min_hits), delta_t=int(p.delta_t), asso_kind=_asso_kind(p.asso_func),
             frame_w=float(p.frame_w), frame_h=float(p.frame_h))
         self._create(cfg)
+
+    # ---- one entry of the per-sequence parameter table (_SeqTable)
+    _SEQ_STRUCT = N.BxHybridSeqParams
+
+    def _seq_struct(self, p: HybridsortParams):
+        return N.BxHybridSeqParams(
+            det_thresh=float(p.det_thresh), iou_threshold=float(p.iou_threshold),
+            inertia=float(p.inertia), longterm_reid_weight=float(p.longterm_reid_weight),
+            tcm_first_step_weight=float(p.TCM_first_step_weight), max_age=int(p.max_age),
+            min_hits=int(p.min_hits), delta_t=int(p.delta_t), asso_kind=_asso_kind(p.asso_func))
+
+    def _seq_params_of(self, o) -> HybridsortParams:
+        return HybridsortParams(
+            det_thresh=o.det_thresh, max_age=o.max_age, min_hits=o.min_hits,
+            iou_threshold=o.iou_threshold, delta_t=o.delta_t, asso_func=_asso_name(o.asso_kind),
+            inertia=o.inertia,
+            longterm_reid_weight=o.longterm_reid_weight,
+            TCM_first_step_weight=o.tcm_first_step_weight, frame_w=self.params.frame_w,
+            frame_h=self.params.frame_h)
 
     def grown(self, track_cap: int, det_cap: int, map_cap: int | None = None) -> "HybridsortEngine":
         """A new engine with larger capacities holding this one's state (bx_hybrid_copy_state);
@@ -1070,67 +1054,19 @@ def hybrid_bank_mean(bank, pushed, out, stream=None) -> None:
                                          stream), "bx_hybrid_bank_mean")
 
 
-class HybridsortTableEngine(HybridsortEngine):
-    """A ``HybridsortEngine`` whose sequences may each run on parameters of their own
-    (``bx_hybrid_set_seq_params_host``, include/bxhybridsort.h): the engine of a hyper-parameter
-    sweep, K configs x S sequences as K*S sequences of one handle (boxmot_amd.tune.sweep_reid)."""
-
-    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
-                 emb_dim: int = 512, params: HybridsortParams | None = None):
-        super().__init__(n_seq, track_cap, det_cap, emb_dim, params)
-        self._seq_over = {}  # sequence -> its own HybridsortParams, for grown()
+class HybridsortTableEngine(_SeqTable, HybridsortEngine):
+    """A ``HybridsortEngine`` with per-sequence ``HybridsortParams`` (``_SeqTable``;
+    include/bxhybridsort.h, boxmot_amd.tune.sweep_reid).  frame_w / frame_h, which are not part of
+    the table, stay the engine's."""
 
     def grown(self, track_cap: int, det_cap: int,
               map_cap: int | None = None) -> "HybridsortTableEngine":
-        """As HybridsortEngine.grown; bx_hybrid_copy_state carries tracks only, so the table is
-        set again on the new engine."""
+        """As HybridsortEngine.grown, with the table."""
         e = HybridsortTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim, self.params)
         if map_cap is not None:
             e.classes_config(self.classes().n_classes, map_cap)
         N.check(self._L.bx_hybrid_copy_state(e._h, self._h), "bx_hybrid_copy_state")
-        for k, p in sorted(self._seq_over.items()):
-            e.set_seq_params(k, [p])
-        return e
-
-    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
-        """Give sequences [seq0, seq0 + len(params)) parameters of their own
-        (bx_hybrid_set_seq_params_host): ``params`` is a list of HybridsortParams, whose frame_w /
-        frame_h are not part of the table.  ``None`` clears the override of ``nseq`` sequences
-        from seq0 (default: all from seq0).  For use between sequences, at frame 0."""
-        if params is None:
-            n = self.n_seq - seq0 if nseq is None else nseq
-            arr = None
-        else:
-            n = len(params)
-            arr = (N.BxHybridSeqParams * max(n, 1))(*[N.BxHybridSeqParams(
-                det_thresh=float(p.det_thresh), iou_threshold=float(p.iou_threshold),
-                inertia=float(p.inertia), longterm_reid_weight=float(p.longterm_reid_weight),
-                tcm_first_step_weight=float(p.TCM_first_step_weight), max_age=int(p.max_age),
-                min_hits=int(p.min_hits), delta_t=int(p.delta_t),
-                asso_kind=_asso_kind(p.asso_func)) for p in params])
-        N.check(self._L.bx_hybrid_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
-                "bx_hybrid_set_seq_params_host")
-        for k in range(n):
-            if params is None:
-                self._seq_over.pop(seq0 + k, None)
-            else:
-                self._seq_over[seq0 + k] = params[k]
-
-    def seq_params(self, seq: int) -> HybridsortParams:
-        """The parameters sequence ``seq`` runs on (bx_hybrid_seq_params_host): its own when set,
-        else the engine's; frame_w / frame_h are the engine's."""
-        from .iou import KINDS
-
-        o = N.BxHybridSeqParams()
-        N.check(self._L.bx_hybrid_seq_params_host(self._h, int(seq), C.byref(o)),
-                "bx_hybrid_seq_params_host")
-        name = {v: k for k, v in KINDS.items()}[o.asso_kind]
-        return HybridsortParams(
-            det_thresh=o.det_thresh, max_age=o.max_age, min_hits=o.min_hits,
-            iou_threshold=o.iou_threshold, delta_t=o.delta_t, asso_func=name, inertia=o.inertia,
-            longterm_reid_weight=o.longterm_reid_weight,
-            TCM_first_step_weight=o.tcm_first_step_weight, frame_w=self.params.frame_w,
-            frame_h=self.params.frame_h)
+        return self._retable(e)
 
 
 class ClassSplit(_NativeHandle):
@@ -1443,6 +1379,33 @@ class BoostEngine(_TrackListEngine):
             with_reid=int(bool(p.with_reid)))
         self._create(cfg)
 
+    # ---- one entry of the per-sequence parameter table (_SeqTable)
+    _SEQ_STRUCT = N.BxBoostSeqParams
+
+    def _seq_struct(self, p: BoostParams):
+        if bool(p.with_reid) != bool(self.params.with_reid):
+            raise ValueError("with_reid is engine-wide: a sequence cannot have its own")
+        return N.BxBoostSeqParams(
+            max_age=int(p.max_age), min_hits=int(p.min_hits), det_thresh=float(p.det_thresh),
+            iou_threshold=float(p.iou_threshold), min_box_area=float(p.min_box_area),
+            aspect_ratio_thresh=float(p.aspect_ratio_thresh), lambda_iou=float(p.lambda_iou),
+            lambda_mhd=float(p.lambda_mhd), lambda_shape=float(p.lambda_shape),
+            dlo_boost_coef=float(p.dlo_boost_coef), use_ecc=int(bool(p.use_ecc)),
+            use_dlo_boost=int(bool(p.use_dlo_boost)), use_duo_boost=int(bool(p.use_duo_boost)),
+            s_sim_corr=int(bool(p.s_sim_corr)), use_rich_s=int(bool(p.use_rich_s)),
+            use_sb=int(bool(p.use_sb)), use_vt=int(bool(p.use_vt)))
+
+    def _seq_params_of(self, o) -> BoostParams:
+        return BoostParams(
+            max_age=o.max_age, min_hits=o.min_hits, det_thresh=o.det_thresh,
+            iou_threshold=o.iou_threshold, use_ecc=bool(o.use_ecc), min_box_area=o.min_box_area,
+            aspect_ratio_thresh=o.aspect_ratio_thresh, lambda_iou=o.lambda_iou,
+            lambda_mhd=o.lambda_mhd, lambda_shape=o.lambda_shape,
+            use_dlo_boost=bool(o.use_dlo_boost), use_duo_boost=bool(o.use_duo_boost),
+            dlo_boost_coef=o.dlo_boost_coef, s_sim_corr=bool(o.s_sim_corr),
+            use_rich_s=bool(o.use_rich_s), use_sb=bool(o.use_sb), use_vt=bool(o.use_vt),
+            with_reid=bool(self.params.with_reid))
+
     def grown(self, track_cap: int, det_cap: int) -> "BoostEngine":
         """A new engine with larger capacities holding this one's state (bx_boost_copy_state)."""
         e = BoostEngine(self.n_seq, track_cap, det_cap, self.emb_dim or 0, self.params)
@@ -1533,75 +1496,18 @@ class BoostEngine(_TrackListEngine):
     STAGES = ["embcost", "frame", "feature"]
 
 
-class BoostTableEngine(BoostEngine):
-    """A ``BoostEngine`` whose sequences may each run on parameters of their own
-    (``bx_boost_set_seq_params_host``, include/bxboost.h): the engine of a BoostTrack
-    hyper-parameter sweep, K configs x S sequences as K*S sequences of one handle
-    (boxmot_amd.tune.sweep_boost), or of cameras with thresholds and track lifetimes of their
-    own.  ``with_reid``, the capacities and the embedding width stay the engine's.  (A class of
-    its own because BoostEngine's method set is pinned by tests/test_engine_api_host.py.)"""
-
-    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
-                 emb_dim: int = 0, params: BoostParams | None = None):
-        super().__init__(n_seq, track_cap, det_cap, emb_dim, params)
-        self._seq_over = {}  # sequence -> its own BoostParams, for grown()
+class BoostTableEngine(_SeqTable, BoostEngine):
+    """A ``BoostEngine`` with per-sequence ``BoostParams`` (``_SeqTable``; include/bxboost.h,
+    boxmot_amd.tune.sweep_boost), also for cameras with thresholds and track lifetimes of their
+    own.  ``with_reid`` (an entry's must be the engine's, ``ValueError``), the capacities and the
+    embedding width stay the engine's.  (A class of its own because BoostEngine's method set is
+    pinned by tests/test_engine_api_host.py.)"""
 
     def grown(self, track_cap: int, det_cap: int) -> "BoostTableEngine":
-        """As BoostEngine.grown; bx_boost_copy_state carries tracks only, so the table is set
-        again on the new engine."""
+        """As BoostEngine.grown, with the table."""
         e = BoostTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim or 0, self.params)
         N.check(self._L.bx_boost_copy_state(e._h, self._h), "bx_boost_copy_state")
-        for k, p in sorted(self._seq_over.items()):
-            e.set_seq_params(k, [p])
-        return e
-
-    def _seq_struct(self, p: BoostParams):
-        if bool(p.with_reid) != bool(self.params.with_reid):
-            raise ValueError("with_reid is engine-wide: a sequence cannot have its own")
-        return N.BxBoostSeqParams(
-            max_age=int(p.max_age), min_hits=int(p.min_hits), det_thresh=float(p.det_thresh),
-            iou_threshold=float(p.iou_threshold), min_box_area=float(p.min_box_area),
-            aspect_ratio_thresh=float(p.aspect_ratio_thresh), lambda_iou=float(p.lambda_iou),
-            lambda_mhd=float(p.lambda_mhd), lambda_shape=float(p.lambda_shape),
-            dlo_boost_coef=float(p.dlo_boost_coef), use_ecc=int(bool(p.use_ecc)),
-            use_dlo_boost=int(bool(p.use_dlo_boost)), use_duo_boost=int(bool(p.use_duo_boost)),
-            s_sim_corr=int(bool(p.s_sim_corr)), use_rich_s=int(bool(p.use_rich_s)),
-            use_sb=int(bool(p.use_sb)), use_vt=int(bool(p.use_vt)))
-
-    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
-        """Give sequences [seq0, seq0 + len(params)) parameters of their own
-        (bx_boost_set_seq_params_host): ``params`` is a list of BoostParams, whose ``with_reid``
-        must be the engine's (``ValueError``).  ``None`` clears the override of ``nseq`` sequences
-        from seq0 (default: all from seq0).  For use between sequences, at frame 0."""
-        if params is None:
-            n = self.n_seq - seq0 if nseq is None else nseq
-            arr = None
-        else:
-            n = len(params)
-            arr = (N.BxBoostSeqParams * max(n, 1))(*[self._seq_struct(p) for p in params])
-        N.check(self._L.bx_boost_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
-                "bx_boost_set_seq_params_host")
-        for k in range(n):
-            if params is None:
-                self._seq_over.pop(seq0 + k, None)
-            else:
-                self._seq_over[seq0 + k] = params[k]
-
-    def seq_params(self, seq: int) -> BoostParams:
-        """The parameters sequence ``seq`` runs on (bx_boost_seq_params_host): its own when set,
-        else the engine's; ``with_reid`` is the engine's."""
-        o = N.BxBoostSeqParams()
-        N.check(self._L.bx_boost_seq_params_host(self._h, int(seq), C.byref(o)),
-                "bx_boost_seq_params_host")
-        return BoostParams(
-            max_age=o.max_age, min_hits=o.min_hits, det_thresh=o.det_thresh,
-            iou_threshold=o.iou_threshold, use_ecc=bool(o.use_ecc), min_box_area=o.min_box_area,
-            aspect_ratio_thresh=o.aspect_ratio_thresh, lambda_iou=o.lambda_iou,
-            lambda_mhd=o.lambda_mhd, lambda_shape=o.lambda_shape,
-            use_dlo_boost=bool(o.use_dlo_boost), use_duo_boost=bool(o.use_duo_boost),
-            dlo_boost_coef=o.dlo_boost_coef, s_sim_corr=bool(o.s_sim_corr),
-            use_rich_s=bool(o.use_rich_s), use_sb=bool(o.use_sb), use_vt=bool(o.use_vt),
-            with_reid=bool(self.params.with_reid))
+        return self._retable(e)
 
 
 @dataclass
@@ -1654,6 +1560,30 @@ class SsEngine(_NativeEngine):
         """Listed tracks plus the lost buffer's (their galleries keep their slots)."""
         c = self.counters(seq)
         return c["n_tracks"] + c["n_lost"]
+
+    # ---- one entry of the per-sequence parameter table (_SeqTable)
+    _SEQ_STRUCT = N.BxSsSeqParams
+
+    @staticmethod
+    def _seq_struct(p: SsParams):
+        return N.BxSsSeqParams(
+            min_conf=float(p.min_conf), max_cos_dist=float(p.max_cos_dist),
+            max_iou_dist=float(p.max_iou_dist), max_age=int(p.max_age), n_init=int(p.n_init),
+            nn_budget=int(p.nn_budget), mc_lambda=float(p.mc_lambda),
+            ema_alpha=float(p.ema_alpha), conf_thresh_high=float(p.conf_thresh_high),
+            conf_thresh_low=float(p.conf_thresh_low),
+            id_preservation_weight=float(p.id_preservation_weight),
+            crowd_detection=int(bool(p.crowd_detection)),
+            born_confirmed=int(bool(p.born_confirmed)))
+
+    @staticmethod
+    def _seq_params_of(o) -> SsParams:
+        return SsParams(
+            min_conf=o.min_conf, max_cos_dist=o.max_cos_dist, max_iou_dist=o.max_iou_dist,
+            max_age=o.max_age, n_init=o.n_init, nn_budget=o.nn_budget, mc_lambda=o.mc_lambda,
+            ema_alpha=o.ema_alpha, conf_thresh_high=o.conf_thresh_high,
+            conf_thresh_low=o.conf_thresh_low, id_preservation_weight=o.id_preservation_weight,
+            crowd_detection=bool(o.crowd_detection), born_confirmed=bool(o.born_confirmed))
 
     def grown(self, track_cap: int, det_cap: int) -> "SsEngine":
         """A new engine with larger capacities holding this one's state (bx_ss_copy_state)."""
@@ -1770,64 +1700,27 @@ class SsEngine(_NativeEngine):
                         [int(x) for x in a]))
 
 
-class SsTableEngine(SsEngine):
-    """An ``SsEngine`` whose sequences may each run on parameters of their own
-    (``bx_ss_set_seq_params_host``, include/bxstrongsort.h): the engine of a StrongSort
-    hyper-parameter sweep, K configs x S sequences as K*S sequences of one handle
-    (boxmot_amd.tune.sweep_strong).  The capacities, ``emb_dim`` and ``vec_cap`` stay the
+class SsTableEngine(_SeqTable, SsEngine):
+    """An ``SsEngine`` with per-sequence ``SsParams`` (``_SeqTable``; include/bxstrongsort.h,
+    boxmot_amd.tune.sweep_strong).  The capacities, ``emb_dim`` and ``vec_cap`` stay the
     engine's, and an entry's ``nn_budget`` may not exceed the engine's own, which sized the
     galleries.  ``max_age``, ``nn_budget`` and ``max_cos_dist`` of an entry seed the state crowd
-    mode adapts, so a sequence takes an entry only at frame counter 0 (fresh or just reset).  (A
-    class of its own because SsEngine's method set is pinned by tests/test_engine_api_host.py.)"""
-
-    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
-                 emb_dim: int = 512, vec_cap: int = 32, params: SsParams | None = None):
-        super().__init__(n_seq, track_cap, det_cap, emb_dim, vec_cap, params)
-        self._seq_over = {}  # sequence -> its own SsParams, for grown()
+    mode adapts, so a sequence takes an entry only at frame counter 0 (fresh or just reset):
+    ``set_seq_params`` raises ``ValueError`` for a sequence that has run a frame since its last
+    reset, and for an entry ``SsEngine`` would refuse; ``seq_params`` gives the three as seeded,
+    not as crowd mode adapted them.  (A class of its own because SsEngine's method set is pinned
+    by tests/test_engine_api_host.py.)"""
 
     def grown(self, track_cap: int, det_cap: int) -> "SsTableEngine":
         """As SsEngine.grown; bx_ss_copy_state carries the tracks and the sequences' adapted
         state but not the table, which is set on the new engine first: its sequences are at
         frame counter 0 then, as the call requires."""
-        e = SsTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim, self.vec_cap, self.params)
-        for k, p in sorted(self._seq_over.items()):
-            e.set_seq_params(k, [p])
+        e = self._retable(SsTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim,
+                                        self.vec_cap, self.params))
         N.check(self._L.bx_ss_copy_state(e._h, self._h), "bx_ss_copy_state")
         if hasattr(self, "occ_cap"):  # (the copy carried pools, latches and settings)
             e.occ_cap = self.occ_cap
         return e
-
-    @staticmethod
-    def _seq_struct(p: SsParams):
-        return N.BxSsSeqParams(
-            min_conf=float(p.min_conf), max_cos_dist=float(p.max_cos_dist),
-            max_iou_dist=float(p.max_iou_dist), max_age=int(p.max_age), n_init=int(p.n_init),
-            nn_budget=int(p.nn_budget), mc_lambda=float(p.mc_lambda),
-            ema_alpha=float(p.ema_alpha), conf_thresh_high=float(p.conf_thresh_high),
-            conf_thresh_low=float(p.conf_thresh_low),
-            id_preservation_weight=float(p.id_preservation_weight),
-            crowd_detection=int(bool(p.crowd_detection)),
-            born_confirmed=int(bool(p.born_confirmed)))
-
-    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
-        """Give sequences [seq0, seq0 + len(params)) parameters of their own
-        (bx_ss_set_seq_params_host): ``params`` is a list of SsParams.  ``None`` clears the
-        override of ``nseq`` sequences from seq0 (default: all from seq0).  ``ValueError`` for a
-        sequence that has run a frame since its last reset, and for an entry ``SsEngine`` would
-        refuse or whose ``nn_budget`` is above the engine's; nothing changes then."""
-        if params is None:
-            n = self.n_seq - seq0 if nseq is None else nseq
-            arr = None
-        else:
-            n = len(params)
-            arr = (N.BxSsSeqParams * max(n, 1))(*[self._seq_struct(p) for p in params])
-        N.check(self._L.bx_ss_set_seq_params_host(self._h, int(seq0), int(n), arr, None),
-                "bx_ss_set_seq_params_host")
-        for k in range(n):
-            if params is None:
-                self._seq_over.pop(seq0 + k, None)
-            else:
-                self._seq_over[seq0 + k] = params[k]
 
     # ---- occlusion handling on the device (bx_ss_set_occlusion_host).  Here and not on SsEngine
     # for the reason the class exists: SsEngine's method set is pinned.  An engine on which
@@ -1869,20 +1762,6 @@ class SsTableEngine(SsEngine):
         N.check(self._L.bx_ss_occlusion_buffer_host(self._h, int(seq), int(id), v.ctypes.data,
                                                     C.byref(n)), "bx_ss_occlusion_buffer_host")
         return v[: n.value].copy()
-
-    def seq_params(self, seq: int) -> SsParams:
-        """The parameters sequence ``seq`` runs on (bx_ss_seq_params_host): its own when set,
-        else the engine's; ``max_age``, ``nn_budget`` and ``max_cos_dist`` as seeded, not as crowd
-        mode adapted them."""
-        o = N.BxSsSeqParams()
-        N.check(self._L.bx_ss_seq_params_host(self._h, int(seq), C.byref(o)),
-                "bx_ss_seq_params_host")
-        return SsParams(
-            min_conf=o.min_conf, max_cos_dist=o.max_cos_dist, max_iou_dist=o.max_iou_dist,
-            max_age=o.max_age, n_init=o.n_init, nn_budget=o.nn_budget, mc_lambda=o.mc_lambda,
-            ema_alpha=o.ema_alpha, conf_thresh_high=o.conf_thresh_high,
-            conf_thresh_low=o.conf_thresh_low, id_preservation_weight=o.id_preservation_weight,
-            crowd_detection=bool(o.crowd_detection), born_confirmed=bool(o.born_confirmed))
 
 
 def _ptr(x):

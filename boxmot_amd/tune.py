@@ -2,27 +2,31 @@
 
 Reference stage replaced (``boxmot/engine/evolve.py``): its objective function runs the tracker
 over all sequences with one configuration and evaluates, once per trial.  Here the K
-configurations of a sweep run together: an ``OcsortTableEngine`` of K*S sequences is built, engine
-sequence ``k*S + s`` is sequence ``s`` under configuration ``k`` (``set_seq_params``,
-include/bxocsort.h), and every frame index is one K*S-wide launch fed from device memory
-(``engine.SequenceFeeder``, include/bxfeed.h).  The search strategy (which configurations to try)
-stays with the caller; ``grid`` builds the cartesian product of a search space.
+configurations of a sweep run together: a table engine (``engine._SeqTable``) of K*S sequences is
+built, engine sequence ``k*S + s`` is sequence ``s`` under configuration ``k``
+(``set_seq_params``), and every frame index is one K*S-wide launch fed from device memory, the K*S
+sequences reading each sequence's detections and embeddings from ONE copy
+(``engine.SharedSequenceFeeder``, include/bxfeed.h).  The search strategy (which configurations
+to try) stays with the caller; ``grid`` builds the cartesian product of a search space.
 
-Three engines have per-sequence parameters: OCSort (``sweep``; DESIGN.md 2.18 is the contract) and
-the two appearance trackers of its family, DeepOCSort and HybridSort (``sweep_reid``; DESIGN.md
-2.20), whose K*S sequences read each sequence's detections and embeddings from ONE copy in device
-memory (``engine.SharedSequenceFeeder``).  ByteTrack and BoT-SORT, which share ``bx_engine``, have
-them too (``sweep_bot``), fed the same way, and so has BoostTrack
-(``sweep_boost``), whose variants differ in constructor flags only.  StrongSort
-(``sweep_strong``) completes the set: its feeder gathers float64 detections and
-10-column rows, and its occlusion post-process stays on the host, per sweep, unless
-``occlusion="device"`` asks for the engine's own pass.
+One driver, ``_run_sweep``, runs every sweep: the refusals that need no engine, the sequences and
+their frame tables, every config resolved as ``run_sequences`` resolves it, the engine, the
+feeder, the frame loop (``_drive``) and the report (``_report``).  What a tracker family adds is a
+``_Spec`` in ``_SPECS``: its trackers, its own refusals, how its engine is built and stepped,
+whether embeddings, frame sizes and warps apply, and the feeder's format.  The public sweeps are
+signatures and documentation over it: ``sweep`` (OCSort; DESIGN.md 2.18 is the contract),
+``sweep_reid`` (DeepOCSort, HybridSort; 2.20), ``sweep_bot`` (ByteTrack, BoT-SORT; 2.22),
+``sweep_boost`` (BoostTrack, whose variants differ in constructor flags only; 2.23) and
+``sweep_strong`` (StrongSort; 2.24), whose spec carries hooks of its own: float64 detections and
+10-column rows from the feeder, and an occlusion post-process that stays on the host, per sweep,
+unless ``occlusion="device"`` asks for the engine's own pass (2.26).
 
 ``sweep_gsi`` runs any of the five with GSI between tracking and scoring, on the
 feeder's result slots in device memory (``postprocessing.gsi_device``, include/bxgsi.h).
 """
 from __future__ import annotations
 
+import dataclasses
 import itertools
 from pathlib import Path
 
@@ -82,16 +86,117 @@ def _check(tracker_type: str, configs, sequences=None, gt=None, exp_dir=None, sc
     return configs
 
 
-def _resolve(cfg: dict):
-    """(OcsortParams, track_cap, det_cap) of one config, resolved as run_sequences resolves its
-    tracker_kwargs: through ``motio._batched_engine`` itself, on a one-sequence engine."""
+def _resolve_reid(tracker_type: str, F: int, cfg: dict, more=()):
+    """(params, track_cap, det_cap, and the attributes ``more`` names) of one config, resolved as
+    run_sequences resolves its tracker_kwargs: through ``motio._batched_engine`` itself, on a
+    one-sequence engine."""
     from . import motio
 
-    eng = motio._batched_engine("ocsort", 1, 0, cfg)[0]
+    eng = motio._batched_engine(tracker_type, 1, F, cfg)[0]
     try:
-        return eng.params, eng.track_cap, eng.det_cap
+        return (eng.params, eng.track_cap, eng.det_cap, *[getattr(eng, a) for a in more])
     finally:
         eng.close()
+
+
+def _resolve(cfg: dict):
+    """``_resolve_reid`` for OCSort: (OcsortParams, track_cap, det_cap)."""
+    return _resolve_reid("ocsort", 0, cfg)
+
+
+@dataclasses.dataclass(frozen=True)
+class _Spec:
+    """What one public sweep adds to ``_run_sweep``.  ``extra`` names the keyword arguments beyond
+    the driver's own; they reach ``check``, ``engine`` and ``drive``, which hold their defaults."""
+
+    name: str                  # the public sweep, as _check names it in its refusals
+    supported: tuple           # its trackers
+    engine: object             # (E, tracker_type, n_seq, F, resolved, **extra) -> (engine, feed_emb):
+    #                            the table engine, E the engine module, and the embedding width fed
+    step: object               # (eng, tracker_type, feed_emb, run, warp): one run of a frame index
+    check: object = None       # its own refusals: (tracker_type, configs, warps, score,
+    #                            keep_results, **extra)
+    embeddings: bool = True    # the sequences' embedding width F matters (else F = 0)
+    frame_sizes: bool = False  # the public sweep takes frame_sizes
+    warps: bool = True         # ... and warps
+    feeder_kw: dict = dataclasses.field(default_factory=dict)  # SharedSequenceFeeder's format
+    resolve_more: tuple = ()   # further attributes of the resolved one-sequence engine
+    seq_check: object = None   # refusals that need the sequences: (seqs, widths, dets)
+    drive: object = None       # in _drive's place: (eng, feed, step, tail, resolved, names, fids,
+    #                            tables, **extra) -> (rows, summaries), tail = _drive's arguments
+    extra: tuple = ()          # the names of those keyword arguments
+
+    @property
+    def keywords(self) -> set:
+        """The keyword arguments the sweep accepts: the public sweep's, and ``extra``."""
+        return {"exp_dir", "gt", "benchmark", "seq_lengths", "frame_ids", "score", "keep_results",
+                *(["frame_sizes"] if self.frame_sizes else []),
+                *(["warps"] if self.warps else []), *self.extra}
+
+
+def _run_sweep(spec: _Spec, tracker_type, sequences, configs, post=None, *, exp_dir, gt, benchmark,
+               seq_lengths, frame_ids, score, keep_results, frame_sizes=None, warps=None,
+               **extra) -> list:
+    """Every public sweep; ``post``: None, or ``sweep_gsi``'s (interval, tau).  The refusals come
+    in this order: ``_check`` and the family's own, the return for no sequences, the sequences'
+    embedding widths, the configs as they resolve, and then the engine is built."""
+    configs = _check(tracker_type, configs, sequences, gt, exp_dir, score, keep_results,
+                     supported=spec.supported, what=f"tune.{spec.name}")
+    if spec.check is not None:
+        spec.check(tracker_type, configs, warps, score, keep_results, **extra)
+    from . import engine as E  # (looked up when the sweep runs: tests replace its classes)
+    from . import motio
+
+    names = list(sequences)
+    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
+            for s in sequences.values()]
+    S, K = len(seqs), len(configs)
+    if not S:
+        return [{"config": c, "results": {} if keep_results else None, "summary": None}
+                for c in configs]
+    widths = sorted({int(s.emb_dim) for s in seqs}) if spec.embeddings else [0]
+    dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
+    if spec.seq_check is not None:
+        spec.seq_check(seqs, widths, dets)
+    if len(widths) > 1:
+        raise ValueError(f"the sequences' embedding widths differ ({widths}): one engine has one "
+                         "emb_dim")
+    F = widths[0]
+    fids, tables = _frame_tables(names, seqs, frame_ids)
+    table = None
+    if warps is not None:  # [T, S, 6] as run_sequences builds it, then every config's copy
+        table = motio._flow_warps(names, seqs, fids, F, warps, None, None).repeat(1, K, 1)
+    more = {"more": spec.resolve_more} if spec.resolve_more else {}
+    resolved = [_resolve_reid(tracker_type, F, c, **more) for c in configs]
+    eng, feed_emb = spec.engine(E, tracker_type, K * S, F, resolved, **extra)
+    feed = None
+    try:
+        for k in range(K):
+            eng.set_seq_params(k * S, [resolved[k][0]] * S)
+            for q, nm in enumerate(names):
+                if frame_sizes and nm in frame_sizes:
+                    eng.set_frame_size(k * S + q, *frame_sizes[nm])
+        none = [None] * ((K - 1) * S)
+        feed = E.SharedSequenceFeeder(dets + none, [s.embs if feed_emb else None for s in seqs]
+                                      + none, tables * K, feed_emb, source=list(range(S)) * K,
+                                      **spec.feeder_kw)
+
+        def step(t, run):
+            q0, ns = run[:2]
+            spec.step(eng, tracker_type, feed_emb, run,
+                      None if table is None else table[t, q0: q0 + ns])
+
+        tail = (K, gt, benchmark, seq_lengths, score, keep_results, post)
+        if spec.drive is None:
+            rows, summaries = _drive(eng, feed, step, *tail)
+        else:
+            rows, summaries = spec.drive(eng, feed, step, tail, resolved, names, fids, tables,
+                                         **extra)
+    finally:
+        if feed is not None:
+            feed.close()
+        eng.close()
+    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
 
 
 def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict | None = None,
@@ -123,54 +228,22 @@ def sweep(tracker_type: str, sequences: dict, configs, *, exp_dir=None, gt: dict
     ``"results"`` is None.  Combinations that cannot work raise ``ValueError`` before any engine
     is built.
 
-    The detections are uploaded once per (config, sequence): K copies of a few MB for MOT-sized
-    inputs.  A nonzero engine or feeder status raises ``RuntimeError``.
+    The detections are uploaded and held once per sequence, not once per config.  A nonzero
+    engine or feeder status raises ``RuntimeError``.
     """
-    return _sweep(tracker_type, sequences, configs, None, exp_dir=exp_dir, gt=gt,
-                  benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
-                  frame_sizes=frame_sizes, score=score, keep_results=keep_results)
+    return _run_sweep(_SPECS["sweep"], tracker_type, sequences, configs, exp_dir=exp_dir, gt=gt,
+                      benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
+                      frame_sizes=frame_sizes, score=score, keep_results=keep_results)
 
 
-def _sweep(tracker_type, sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths,
-           frame_ids, frame_sizes, score, keep_results) -> list:
-    """``sweep``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
-    configs = _check(tracker_type, configs, sequences, gt, exp_dir, score, keep_results)
-    from . import motio
-    from .engine import OcsortTableEngine, SequenceFeeder
+def _ocsort_engine(E, tracker_type, n_seq, F, resolved):
+    p, tc, dc = resolved[0]
+    return E.OcsortTableEngine(n_seq=n_seq, track_cap=tc, det_cap=dc, params=p), 0
 
-    names = list(sequences)
-    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
-            for s in sequences.values()]
-    S, K = len(seqs), len(configs)
-    if not S:
-        return [{"config": c, "results": {} if keep_results else None, "summary": None}
-                for c in configs]
-    resolved = [_resolve(c) for c in configs]
-    params = [r[0] for r in resolved]
-    eng = OcsortTableEngine(n_seq=K * S, track_cap=resolved[0][1], det_cap=resolved[0][2],
-                       params=params[0])
-    feed = None
-    try:
-        fids, tables = _frame_tables(names, seqs, frame_ids)
-        dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
-        for k in range(K):
-            eng.set_seq_params(k * S, [params[k]] * S)
-            for q, nm in enumerate(names):
-                if frame_sizes and nm in frame_sizes:
-                    eng.set_frame_size(k * S + q, *frame_sizes[nm])
-        feed = SequenceFeeder(dets * K, [None] * (K * S), tables * K, 0)
 
-        def step(t, run):
-            q0, ns, _, pd, po, _, pout, pcnt = run
-            eng.step(pd, po, pout, pcnt, seq0=q0, nseq=ns)
-
-        rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                 keep_results, post)
-    finally:
-        if feed is not None:
-            feed.close()
-        eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
+def _ocsort_step(eng, tracker_type, feed_emb, run, warp):
+    q0, ns, _, pd, po, _, pout, pcnt = run
+    eng.step(pd, po, pout, pcnt, seq0=q0, nseq=ns)
 
 
 def _frame_tables(names, seqs, frame_ids) -> tuple:
@@ -281,13 +354,10 @@ def _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths
     return out
 
 
-def _check_reid(tracker_type: str, configs, sequences, gt, exp_dir, score, keep_results,
-                warps) -> list:
-    """The refusals of ``sweep_reid`` that need no engine and no device."""
+def _check_reid(tracker_type: str, configs, warps, score, keep_results) -> None:
+    """The refusals of ``sweep_reid`` beyond ``_check``'s that need no engine and no device."""
     from . import motio
 
-    configs = _check(tracker_type, configs, sequences, gt, exp_dir, score, keep_results,
-                     supported=SUPPORTED_REID, what="tune.sweep_reid")
     if len({bool(c.get("embedding_off", False)) for c in configs}) > 1:
         raise ValueError("embedding_off decides the engine's embedding width and launches: it "
                          "must be the same in every config")
@@ -299,19 +369,6 @@ def _check_reid(tracker_type: str, configs, sequences, gt, exp_dir, score, keep_
                 "behaviour")
         if warps is not None:  # (hybridsort, cmc_off / use_ecc against warps)
             motio._check_warp_args(tracker_type, c, 0, warps, None, None)
-    return configs
-
-
-def _resolve_reid(tracker_type: str, F: int, cfg: dict):
-    """(params, track_cap, det_cap) of one config, resolved as run_sequences resolves its
-    tracker_kwargs: through ``motio._batched_engine`` itself, on a one-sequence engine."""
-    from . import motio
-
-    eng = motio._batched_engine(tracker_type, 1, F, cfg)[0]
-    try:
-        return eng.params, eng.track_cap, eng.det_cap
-    finally:
-        eng.close()
 
 
 def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
@@ -341,83 +398,43 @@ def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
     camera-motion compensation off (``cmc_off`` / ``use_ecc``), sequences whose embedding widths
     differ, and the ``score`` / ``keep_results`` combinations ``sweep`` refuses.
     """
-    return _sweep_reid(tracker_type, sequences, configs, None, exp_dir=exp_dir, gt=gt,
-                       benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
-                       frame_sizes=frame_sizes, score=score, keep_results=keep_results,
-                       warps=warps)
+    return _run_sweep(_SPECS["sweep_reid"], tracker_type, sequences, configs, exp_dir=exp_dir,
+                      gt=gt, benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
+                      frame_sizes=frame_sizes, score=score, keep_results=keep_results,
+                      warps=warps)
 
 
-def _sweep_reid(tracker_type, sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths,
-                frame_ids, frame_sizes, score, keep_results, warps) -> list:
-    """``sweep_reid``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
-    configs = _check_reid(tracker_type, configs, sequences, gt, exp_dir, score, keep_results,
-                          warps)
-    from . import motio
-    from . import engine as E
-
-    names = list(sequences)
-    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
-            for s in sequences.values()]
-    S, K = len(seqs), len(configs)
-    if not S:
-        return [{"config": c, "results": {} if keep_results else None, "summary": None}
-                for c in configs]
-    widths = sorted({int(s.emb_dim) for s in seqs})
-    if len(widths) > 1:
-        raise ValueError(f"the sequences' embedding widths differ ({widths}): one engine has one "
-                         "emb_dim")
-    F = widths[0]
-    fids, tables = _frame_tables(names, seqs, frame_ids)
-    table = None
-    if warps is not None:  # [T, S, 6] as run_sequences builds it, then every config's copy
-        table = motio._flow_warps(names, seqs, fids, F, warps, None, None).repeat(1, K, 1)
-    resolved = [_resolve_reid(tracker_type, F, c) for c in configs]
-    params = [r[0] for r in resolved]
+def _reid_engine(E, tracker_type, n_seq, F, resolved):
+    p, tc, dc = resolved[0]
     cls = E.DeepOcsortTableEngine if tracker_type == "deepocsort" else E.HybridsortTableEngine
-    eng = cls(n_seq=K * S, track_cap=resolved[0][1], det_cap=resolved[0][2], emb_dim=F or 1,
-              params=params[0])
-    feed = None
-    try:
-        feed_emb = F if eng.emb_dim else 0
-        dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
-        embs = [s.embs if feed_emb else None for s in seqs]
-        for k in range(K):
-            eng.set_seq_params(k * S, [params[k]] * S)
-            for q, nm in enumerate(names):
-                if frame_sizes and nm in frame_sizes:
-                    eng.set_frame_size(k * S + q, *frame_sizes[nm])
-        none = [None] * ((K - 1) * S)
-        feed = E.SharedSequenceFeeder(dets + none, embs + none, tables * K, feed_emb,
-                                      source=list(range(S)) * K)
-
-        def step(t, run):
-            q0, ns, _, pd, po, pe, pout, pcnt = run
-            motio._step(eng, tracker_type, pd, po, pe, pout, pcnt, q0, ns,
-                        None if table is None else table[t, q0: q0 + ns])
-
-        rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                 keep_results, post)
-    finally:
-        if feed is not None:
-            feed.close()
-        eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
+    eng = cls(n_seq=n_seq, track_cap=tc, det_cap=dc, emb_dim=F or 1, params=p)
+    return eng, F if eng.emb_dim else 0
 
 
-def _check_bot(tracker_type: str, configs, sequences, gt, exp_dir, score, keep_results,
-               warps) -> list:
-    """The refusals of ``sweep_bot`` that need no engine and no device."""
+def _reid_step(eng, tracker_type, feed_emb, run, warp):
     from . import motio
 
-    configs = _check(tracker_type, configs, sequences, gt, exp_dir, score, keep_results,
-                     supported=SUPPORTED_BOT, what="tune.sweep_bot")
+    q0, ns, _, pd, po, pe, pout, pcnt = run
+    motio._step(eng, tracker_type, pd, po, pe, pout, pcnt, q0, ns, warp)
+
+
+def _emb_step(eng, tracker_type, feed_emb, run, warp):
+    """The step of the engines that take (embeddings or None, warps or None): bx_engine's,
+    BoostTrack's and StrongSort's."""
+    q0, ns, _, pd, po, pe, pout, pcnt = run
+    eng.step(pd, po, pe if feed_emb else None, warp, pout, pcnt, seq0=q0, nseq=ns)
+
+
+def _check_bot(tracker_type: str, configs, warps, score, keep_results) -> None:
+    """The refusals of ``sweep_bot`` beyond ``_check``'s that need no engine and no device."""
+    from . import motio
+
     if len({bool(c.get("with_reid", True)) for c in configs}) > 1:
         raise ValueError("with_reid decides the engine's embedding width and launches: it must "
                          "be absent from every config or equal in all of them")
     if warps is not None:
         for c in configs:  # (bytetrack against warps)
             motio._check_warp_args(tracker_type, c, 0, warps, None, None)
-    return configs
 
 
 def sweep_bot(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
@@ -444,64 +461,16 @@ def sweep_bot(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
     configs, ``warps`` with bytetrack, sequences whose embedding widths differ, and the ``score``
     / ``keep_results`` combinations ``sweep`` refuses.
     """
-    return _sweep_bot(tracker_type, sequences, configs, None, exp_dir=exp_dir, gt=gt,
-                      benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
+    return _run_sweep(_SPECS["sweep_bot"], tracker_type, sequences, configs, exp_dir=exp_dir,
+                      gt=gt, benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
                       score=score, keep_results=keep_results, warps=warps)
 
 
-def _sweep_bot(tracker_type, sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths,
-               frame_ids, score, keep_results, warps) -> list:
-    """``sweep_bot``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
-    configs = _check_bot(tracker_type, configs, sequences, gt, exp_dir, score, keep_results,
-                         warps)
-    from . import motio
-    from . import engine as E
-
-    names = list(sequences)
-    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
-            for s in sequences.values()]
-    S, K = len(seqs), len(configs)
-    if not S:
-        return [{"config": c, "results": {} if keep_results else None, "summary": None}
-                for c in configs]
-    widths = sorted({int(s.emb_dim) for s in seqs})
-    if len(widths) > 1:
-        raise ValueError(f"the sequences' embedding widths differ ({widths}): one engine has one "
-                         "emb_dim")
-    F = widths[0]
-    fids, tables = _frame_tables(names, seqs, frame_ids)
-    table = None
-    if warps is not None:  # [T, S, 6] as run_sequences builds it, then every config's copy
-        table = motio._flow_warps(names, seqs, fids, F, warps, None, None).repeat(1, K, 1)
-    resolved = [_resolve_reid(tracker_type, F, c) for c in configs]
-    params = [r[0] for r in resolved]
-    reid = tracker_type == "botsort" and bool(params[0].with_reid)
-    feed_emb = F if reid else 0
-    eng = E.TableEngine(tracker_type, n_seq=K * S, track_cap=resolved[0][1],
-                        det_cap=resolved[0][2], emb_dim=feed_emb, emb_f64=True, params=params[0])
-    feed = None
-    try:
-        dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
-        embs = [s.embs if feed_emb else None for s in seqs]
-        for k in range(K):
-            eng.set_seq_params(k * S, [params[k]] * S)
-        none = [None] * ((K - 1) * S)
-        feed = E.SharedSequenceFeeder(dets + none, embs + none, tables * K, feed_emb,
-                                      source=list(range(S)) * K)
-
-        def step(t, run):
-            q0, ns, _, pd, po, pe, pout, pcnt = run
-            eng.step(pd, po, pe if feed_emb else None,
-                     None if table is None else table[t, q0: q0 + ns], pout, pcnt,
-                     seq0=q0, nseq=ns)
-
-        rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                 keep_results, post)
-    finally:
-        if feed is not None:
-            feed.close()
-        eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
+def _bot_engine(E, tracker_type, n_seq, F, resolved):
+    p, tc, dc = resolved[0]
+    feed_emb = F if tracker_type == "botsort" and p.with_reid else 0
+    return E.TableEngine(tracker_type, n_seq=n_seq, track_cap=tc, det_cap=dc, emb_dim=feed_emb,
+                         emb_f64=True, params=p), feed_emb
 
 
 def _boost_reid(cfg: dict) -> bool:
@@ -510,19 +479,16 @@ def _boost_reid(cfg: dict) -> bool:
     return bool(cfg.get("with_reid", False)) if cfg else True
 
 
-def _check_boost(configs, sequences, gt, exp_dir, score, keep_results, warps) -> list:
-    """The refusals of ``sweep_boost`` that need no engine and no device."""
+def _check_boost(tracker_type: str, configs, warps, score, keep_results) -> None:
+    """The refusals of ``sweep_boost`` beyond ``_check``'s that need no engine and no device."""
     from . import motio
 
-    configs = _check("boosttrack", configs, sequences, gt, exp_dir, score, keep_results,
-                     supported=SUPPORTED_BOOST, what="tune.sweep_boost")
     if len({_boost_reid(c) for c in configs}) > 1:
         raise ValueError("with_reid decides the engine's embedding width and launches: it must "
                          "resolve to the same value in every config")
     if warps is not None:
         for c in configs:  # (use_ecc=False against warps)
-            motio._check_warp_args("boosttrack", c, 0, warps, None, None)
-    return configs
+            motio._check_warp_args(tracker_type, c, 0, warps, None, None)
 
 
 def sweep_boost(sequences: dict, configs, *, exp_dir=None, gt: dict | None = None,
@@ -552,65 +518,19 @@ def sweep_boost(sequences: dict, configs, *, exp_dir=None, gt: dict | None = Non
     that switches ``use_ecc`` off, sequences whose embedding widths differ, and the ``score`` /
     ``gt`` / ``keep_results`` combinations ``sweep`` refuses.
     """
-    return _sweep_boost(sequences, configs, None, exp_dir=exp_dir, gt=gt, benchmark=benchmark,
-                        seq_lengths=seq_lengths, frame_ids=frame_ids, score=score,
-                        keep_results=keep_results, warps=warps)
+    return _run_sweep(_SPECS["sweep_boost"], "boosttrack", sequences, configs, exp_dir=exp_dir,
+                      gt=gt, benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
+                      score=score, keep_results=keep_results, warps=warps)
 
 
-def _sweep_boost(sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths, frame_ids,
-                 score, keep_results, warps) -> list:
-    """``sweep_boost``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
-    configs = _check_boost(configs, sequences, gt, exp_dir, score, keep_results, warps)
-    from . import motio
-    from . import engine as E
-
-    names = list(sequences)
-    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
-            for s in sequences.values()]
-    S, K = len(seqs), len(configs)
-    if not S:
-        return [{"config": c, "results": {} if keep_results else None, "summary": None}
-                for c in configs]
-    widths = sorted({int(s.emb_dim) for s in seqs})
-    if len(widths) > 1:
-        raise ValueError(f"the sequences' embedding widths differ ({widths}): one engine has one "
-                         "emb_dim")
-    F = widths[0]
-    fids, tables = _frame_tables(names, seqs, frame_ids)
-    table = None
-    if warps is not None:  # [T, S, 6] as run_sequences builds it, then every config's copy
-        table = motio._flow_warps(names, seqs, fids, F, warps, None, None).repeat(1, K, 1)
-    resolved = [_resolve_reid("boosttrack", F, c) for c in configs]
+def _boost_engine(E, tracker_type, n_seq, F, resolved):
     params = [r[0] for r in resolved]
     if len({bool(p.with_reid) for p in params}) > 1:  # (what _check_boost's reading missed)
         raise ValueError("with_reid resolves differently across the configs: "
                          f"{[bool(p.with_reid) for p in params]}")
     feed_emb = F if params[0].with_reid else 0
-    eng = E.BoostTableEngine(n_seq=K * S, track_cap=resolved[0][1], det_cap=resolved[0][2],
-                             emb_dim=feed_emb, params=params[0])
-    feed = None
-    try:
-        dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
-        embs = [s.embs if feed_emb else None for s in seqs]
-        for k in range(K):
-            eng.set_seq_params(k * S, [params[k]] * S)
-        none = [None] * ((K - 1) * S)
-        feed = E.SharedSequenceFeeder(dets + none, embs + none, tables * K, feed_emb,
-                                      source=list(range(S)) * K)
-
-        def step(t, run):
-            q0, ns, _, pd, po, pe, pout, pcnt = run
-            eng.step(pd, po, pe if feed_emb else None,
-                     None if table is None else table[t, q0: q0 + ns], pout, pcnt,
-                     seq0=q0, nseq=ns)
-
-        rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                 keep_results, post)
-    finally:
-        if feed is not None:
-            feed.close()
-        eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
+    return E.BoostTableEngine(n_seq=n_seq, track_cap=resolved[0][1], det_cap=resolved[0][2],
+                              emb_dim=feed_emb, params=params[0]), feed_emb
 
 
 def _strong_occ(cfg: dict) -> bool:
@@ -619,14 +539,12 @@ def _strong_occ(cfg: dict) -> bool:
     return bool(cfg.get("handle_occlusions", True))
 
 
-def _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps,
-                  occlusion="host") -> list:
-    """The refusals of ``sweep_strong`` that need no engine and no device."""
+def _check_strong(tracker_type: str, configs, warps, score, keep_results,
+                  occlusion="host") -> None:
+    """The refusals of ``sweep_strong`` beyond ``_check``'s that need no engine and no device."""
     from . import motio
 
-    motio.check_occlusion("strongsort", occlusion)
-    configs = _check("strongsort", configs, sequences, gt, exp_dir, score, keep_results,
-                     supported=SUPPORTED_STRONG, what="tune.sweep_strong")
+    motio.check_occlusion(tracker_type, occlusion)
     if len({repr(c.get("vec_cap")) for c in configs}) > 1:
         raise ValueError("vec_cap sizes the engine's memory: it must be absent from every config "
                          "or equal in all of them")
@@ -643,21 +561,7 @@ def _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps,
                          "handle_occlusions they are formed on the host")
     if warps is not None:
         for c in configs:  # (cmc_off / use_ecc=False against warps)
-            motio._check_warp_args("strongsort", c, 0, warps, None, None)
-    return configs
-
-
-def _resolve_strong(F: int, cfg: dict):
-    """(SsParams, track_cap, det_cap, vec_cap, occlusion_threshold or None) of one config,
-    resolved as run_sequences resolves its tracker_kwargs: through ``motio._batched_engine``
-    itself, on a one-sequence engine."""
-    from . import motio
-
-    eng = motio._batched_engine("strongsort", 1, F, cfg)[0]
-    try:
-        return eng.params, eng.track_cap, eng.det_cap, eng.vec_cap, eng.occlusion_threshold
-    finally:
-        eng.close()
+            motio._check_warp_args(tracker_type, c, 0, warps, None, None)
 
 
 def sweep_strong(sequences: dict, configs, *, exp_dir=None, gt: dict | None = None,
@@ -700,9 +604,9 @@ def sweep_strong(sequences: dict, configs, *, exp_dir=None, gt: dict | None = No
     detections rounded to float32, e.g. ``dets.astype(np.float32)``), and the ``score`` / ``gt`` /
     ``keep_results`` combinations ``sweep`` refuses.
     """
-    return _sweep_strong(sequences, configs, None, exp_dir=exp_dir, gt=gt, benchmark=benchmark,
-                         seq_lengths=seq_lengths, frame_ids=frame_ids, score=score,
-                         keep_results=keep_results, warps=warps)
+    return _run_sweep(_SPECS["sweep_strong"], "strongsort", sequences, configs, exp_dir=exp_dir,
+                      gt=gt, benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
+                      score=score, keep_results=keep_results, warps=warps)
 
 
 def sweep_strong_device(sequences: dict, configs, *, exp_dir=None, gt: dict | None = None,
@@ -720,89 +624,54 @@ def sweep_strong_device(sequences: dict, configs, *, exp_dir=None, gt: dict | No
     ``TypeError`` after the frame loop, naming the sequence and its update count, before anything
     is scored or written; a full buffer pool is a ``RuntimeError`` naming ``occ_cap``.
     ``sweep_gsi("strongsort", ..., occlusion="device")`` passes the argument through."""
-    return _sweep_strong(sequences, configs, None, exp_dir=exp_dir, gt=gt, benchmark=benchmark,
-                         seq_lengths=seq_lengths, frame_ids=frame_ids, score=score,
-                         keep_results=keep_results, warps=warps, occlusion=occlusion)
+    return _run_sweep(_SPECS["sweep_strong"], "strongsort", sequences, configs, exp_dir=exp_dir,
+                      gt=gt, benchmark=benchmark, seq_lengths=seq_lengths, frame_ids=frame_ids,
+                      score=score, keep_results=keep_results, warps=warps, occlusion=occlusion)
 
 
-def _sweep_strong(sequences, configs, post, *, exp_dir, gt, benchmark, seq_lengths, frame_ids,
-                  score, keep_results, warps, occlusion="host") -> list:
-    """``sweep_strong``; ``post``: None, or ``sweep_gsi``'s (interval, tau)."""
-    configs = _check_strong(configs, sequences, gt, exp_dir, score, keep_results, warps,
-                            occlusion)
-    import dataclasses
-
-    from . import motio
-    from . import engine as E
-
-    names = list(sequences)
-    seqs = [s if isinstance(s, motio.BinSequence) else motio.BinSequence(s)
-            for s in sequences.values()]
-    S, K = len(seqs), len(configs)
-    if not S:
-        return [{"config": c, "results": {} if keep_results else None, "summary": None}
-                for c in configs]
-    widths = sorted({int(s.emb_dim) for s in seqs})
+def _strong_seq_check(seqs, widths, dets) -> None:
     if len(widths) > 1 or not widths[0]:
         raise ValueError(f"StrongSort needs embeddings of one width in every sequence (got "
                          f"{widths}): one engine has one emb_dim")
-    F = widths[0]
-    dets = [np.asarray(s.dets).astype(np.float32) for s in seqs]
-    for s, d in zip(seqs, dets):  # (before any engine is built)
+    for s, d in zip(seqs, dets):
         if not np.array_equal(d.astype(np.float64), np.asarray(s.dets)):
             raise ValueError(f"{s.path}: detections that are not float32 values cannot be "
                              "held once as float32 (run_sequences feeds them as float64): "
                              "pack the sequence from detections rounded to float32")
-    fids, tables = _frame_tables(names, seqs, frame_ids)
-    table = None
-    if warps is not None:  # [T, S, 6] as run_sequences builds it, then every config's copy
-        table = motio._flow_warps(names, seqs, fids, F, warps, None, None).repeat(1, K, 1)
-    resolved = [_resolve_strong(F, c) for c in configs]
+
+
+def _strong_engine(E, tracker_type, n_seq, F, resolved, occlusion="host"):
+    """``resolved``: per config (SsParams, track_cap, det_cap, vec_cap, occlusion_threshold or
+    None).  The engine's own nn_budget, which sizes the galleries, is the configs' largest."""
     params = [r[0] for r in resolved]
-    occ_thr = [r[4] for r in resolved]
-    device = occlusion == "device"
     if len({r[1:4] for r in resolved}) > 1 or (
-            not device and len({t is None for t in occ_thr}) > 1):
+            occlusion != "device" and len({r[4] is None for r in resolved}) > 1):
         raise ValueError("the configs resolve to different capacities or handle_occlusions: "
                          f"{[r[1:] for r in resolved]}")
     base = dataclasses.replace(params[0], nn_budget=max(int(p.nn_budget) for p in params))
-    eng = E.SsTableEngine(n_seq=K * S, track_cap=resolved[0][1], det_cap=resolved[0][2],
-                          emb_dim=F, vec_cap=resolved[0][3], params=base)
-    feed = None
-    try:
-        embs = [s.embs for s in seqs]
+    return E.SsTableEngine(n_seq=n_seq, track_cap=resolved[0][1], det_cap=resolved[0][2],
+                           emb_dim=F, vec_cap=resolved[0][3], params=base), F
+
+
+def _strong_drive(eng, feed, step, tail, resolved, names, fids, tables, occlusion="host"):
+    """StrongSort's frame loop.  Without handle_occlusions, or with the engine's own occlusion
+    pass (each engine sequence with its config's settings), ``_drive``; else ``_drive_occlusion``
+    with each config's threshold, and ``sweep_gsi``'s post-stage on its host rows."""
+    from . import motio
+
+    S, K, post = len(names), tail[0], tail[-1]
+    occ_thr = [r[4] for r in resolved]
+    after = None
+    if occlusion == "device" and any(t is not None for t in occ_thr):
         for k in range(K):
-            eng.set_seq_params(k * S, [params[k]] * S)
-        after = None
-        if device and any(t is not None for t in occ_thr):
-            for k in range(K):
-                eng.set_occlusion(k * S, occ_thr[k] is not None,
-                                  0.3 if occ_thr[k] is None else occ_thr[k], nseq=S)
-            after = lambda: motio.raise_device_occlusion(eng, names)  # noqa: E731
-        none = [None] * ((K - 1) * S)
-        feed = E.SharedSequenceFeeder(dets + none, embs + none, tables * K, F,
-                                      source=list(range(S)) * K, det_f64=True, out_cols=10)
-
-        def step(t, run, out=None, cnt=None):
-            q0, ns, _, pd, po, pe, pout, pcnt = run
-            eng.step(pd, po, pe, None if table is None else table[t, q0: q0 + ns],
-                     pout if out is None else out, pcnt if cnt is None else cnt,
-                     seq0=q0, nseq=ns)
-
-        if device or occ_thr[0] is None:
-            rows, summaries = _drive(eng, feed, step, K, gt, benchmark, seq_lengths, score,
-                                     keep_results, post, after)
-        else:
-            rows, summaries = _drive_occlusion(eng, feed, step, fids * K,
-                                               [tb[1] for tb in tables] * K,
-                                               [t for t in occ_thr for _ in range(S)]), None
-            if post is not None:
-                rows = _gsi_host_rows(rows, post)
-    finally:
-        if feed is not None:
-            feed.close()
-        eng.close()
-    return _report(configs, names, rows, summaries, exp_dir, gt, benchmark, seq_lengths, post)
+            eng.set_occlusion(k * S, occ_thr[k] is not None,
+                              0.3 if occ_thr[k] is None else occ_thr[k], nseq=S)
+        after = lambda: motio.raise_device_occlusion(eng, names)  # noqa: E731
+    if occlusion == "device" or occ_thr[0] is None:
+        return _drive(eng, feed, step, *tail, after)
+    rows = _drive_occlusion(eng, feed, step, fids * K, [tb[1] for tb in tables] * K,
+                            [t for t in occ_thr for _ in range(S)])
+    return (rows if post is None else _gsi_host_rows(rows, post)), None
 
 
 def _drive_occlusion(eng, feed, step, fids, feed_cnt, thresholds) -> list:
@@ -829,7 +698,7 @@ def _drive_occlusion(eng, feed, step, fids, feed_cnt, thresholds) -> list:
         for run in runs:  # the rows go to tensors of this frame index, which the host reads
             out = torch.empty((run[2], 10), dtype=torch.float64, device=dev)
             cnt = torch.empty(run[1], dtype=torch.int32, device=dev)
-            step(t, run, out, cnt)
+            step(t, (*run[:6], out, cnt))
             outs.append((out, cnt))
         # every run is stepped before a handler edits the engine: a handler touches its own
         # sequence alone, and the next frame index is stepped after all of them
@@ -895,12 +764,28 @@ def sweep_gsi(tracker_type: str, sequences: dict, configs, *, interval: int = 20
             "frames on, the reference's prev + (cur - prev) * (i / (cur - prev)) is not a whole "
             "number for every inserted frame, so after %d an id can stand twice in a frame, "
             "which the evaluator refuses")
-    name = GSI_DISPATCH[tracker_type]
-    # the public sweep's defaults under the caller's keywords; one it does not have is the
-    # implementation's TypeError
-    kw = {**globals()[name].__kwdefaults__, **sweep_kwargs}
-    head = () if name in ("sweep_boost", "sweep_strong") else (tracker_type,)  # (one tracker)
-    return globals()["_" + name](*head, sequences, configs, (int(interval), float(tau)), **kw)
+    spec = _SPECS[GSI_DISPATCH[tracker_type]]
+    for k in sweep_kwargs:
+        if k not in spec.keywords:
+            raise TypeError(f"tune.{spec.name}() got an unexpected keyword argument {k!r}")
+    # the public sweep's defaults under the caller's keywords
+    return _run_sweep(spec, tracker_type, sequences, configs, (int(interval), float(tau)),
+                      **{**_PUBLIC[spec.name].__kwdefaults__, **sweep_kwargs})
+
+
+_SPECS = {s.name: s for s in (
+    _Spec("sweep", SUPPORTED, _ocsort_engine, _ocsort_step, embeddings=False, frame_sizes=True,
+          warps=False),
+    _Spec("sweep_reid", SUPPORTED_REID, _reid_engine, _reid_step, _check_reid, frame_sizes=True),
+    _Spec("sweep_bot", SUPPORTED_BOT, _bot_engine, _emb_step, _check_bot),
+    _Spec("sweep_boost", SUPPORTED_BOOST, _boost_engine, _emb_step, _check_boost),
+    _Spec("sweep_strong", SUPPORTED_STRONG, _strong_engine, _emb_step, _check_strong,
+          feeder_kw=dict(det_f64=True, out_cols=10),
+          resolve_more=("vec_cap", "occlusion_threshold"), seq_check=_strong_seq_check,
+          drive=_strong_drive, extra=("occlusion",)),
+)}
+_PUBLIC = {"sweep": sweep, "sweep_reid": sweep_reid, "sweep_bot": sweep_bot,
+           "sweep_boost": sweep_boost, "sweep_strong": sweep_strong}
 
 
 def _score(gt: dict, results: list, benchmark: str, seq_lengths) -> list:

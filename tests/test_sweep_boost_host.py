@@ -188,13 +188,26 @@ def test_setter_refuses_a_null_engine():
 
 
 def test_table_engine_adds_three_methods():
-    from boxmot_amd.engine import BoostEngine, BoostTableEngine
+    """Over its base engine a table class adds set_seq_params and seq_params, both inherited from
+    the one _SeqTable, and overrides grown; all six table classes do."""
+    from boxmot_amd import engine as E
 
     def methods(cls):
-        return {k for k, v in vars(cls).items() if callable(v) and not k.startswith("_")}
+        return {k for k in dir(cls) if callable(getattr(cls, k)) and not k.startswith("_")}
 
-    assert issubclass(BoostTableEngine, BoostEngine)
-    assert methods(BoostTableEngine) == {"grown", "set_seq_params", "seq_params"}
+    assert issubclass(E.BoostTableEngine, E.BoostEngine)
+    for table, base in ((E.BoostTableEngine, E.BoostEngine), (E.TableEngine, E.Engine),
+                        (E.OcsortTableEngine, E.OcsortEngine), (E.SsTableEngine, E.SsEngine),
+                        (E.DeepOcsortTableEngine, E.DeepOcsortEngine),
+                        (E.HybridsortTableEngine, E.HybridsortEngine)):
+        # (the occlusion pass lives on StrongSort's table class, DESIGN.md 2.26)
+        occ = {"set_occlusion", "occlusion", "occlusion_buffer"} if table is E.SsTableEngine \
+            else set()
+        assert methods(table) - methods(base) == {"set_seq_params", "seq_params"} | occ, table
+        own = {k for k, v in vars(table).items() if callable(v) and not k.startswith("_")}
+        assert own == {"grown"} | occ and table.grown is not base.grown
+        for m in ("set_seq_params", "seq_params"):
+            assert m not in vars(table) and getattr(table, m) is getattr(E._SeqTable, m)
 
 
 def test_with_reid_of_an_entry_must_be_the_engines():

@@ -148,13 +148,19 @@ def test_setter_refuses_a_null_engine():
 
 
 def test_table_engine_adds_three_methods():
-    from boxmot_amd.engine import Engine, TableEngine
+    """Over Engine, TableEngine adds set_seq_params and seq_params, both inherited from the one
+    _SeqTable (tests/test_sweep_boost_host.py checks all six table classes), and overrides grown."""
+    from boxmot_amd.engine import Engine, TableEngine, _SeqTable
 
     def methods(cls):
-        return {k for k, v in vars(cls).items() if callable(v) and not k.startswith("_")}
+        return {k for k in dir(cls) if callable(getattr(cls, k)) and not k.startswith("_")}
 
     assert issubclass(TableEngine, Engine)
-    assert methods(TableEngine) == {"grown", "set_seq_params", "seq_params"}
+    assert methods(TableEngine) - methods(Engine) == {"set_seq_params", "seq_params"}
+    own = {k for k, v in vars(TableEngine).items() if callable(v) and not k.startswith("_")}
+    assert own == {"grown"} and TableEngine.grown is not Engine.grown
+    for m in ("set_seq_params", "seq_params"):
+        assert m not in vars(TableEngine) and getattr(TableEngine, m) is getattr(_SeqTable, m)
 
 
 def test_configs_resolve_as_run_sequences_resolves_them():
