@@ -344,6 +344,9 @@ EXPORTS = [
     "bx_deepoc_update_classes_host", "bx_hybrid_step_classes", "bx_hybrid_classes_config",
     "bx_hybrid_classes", "bx_hybrid_update_classes_host", "bx_hybrid_probe",
     "bx_hybrid_probe_read",
+    "bx_hybrid_set_ecc_host", "bx_hybrid_ecc_host", "bx_hybrid_step_cmc",
+    "bx_hybrid_update_host_cmc", "bx_hybrid_step_classes_cmc",
+    "bx_hybrid_update_classes_host_cmc",
     "bx_eval_create", "bx_eval_destroy", "bx_eval_capacity", "bx_eval_run_host",
     "bx_eval_set_gt_host", "bx_eval_run_device",
     "bx_ecc_create", "bx_ecc_destroy", "bx_ecc_reset", "bx_ecc_work_size", "bx_ecc_apply",
@@ -590,6 +593,15 @@ _SIGS = {
     "bx_hybrid_classes": ([_vp, C.POINTER(C.c_void_p)], C.c_int),
     "bx_hybrid_update_classes_host": ([_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _ip, _vp, _ip,
                                        _vp], C.c_int),
+    "bx_hybrid_set_ecc_host": ([_vp, C.c_int, C.c_int, _vp], C.c_int),
+    "bx_hybrid_ecc_host": ([_vp, C.c_int, _ip, _ip], C.c_int),
+    "bx_hybrid_step_cmc": ([_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "bx_hybrid_update_host_cmc": ([_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _ip, _vp],
+                                  C.c_int),
+    "bx_hybrid_step_classes_cmc": ([_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp], C.c_int),
+    "bx_hybrid_update_classes_host_cmc": ([_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _ip,
+                                           _vp, _ip, _vp], C.c_int),
     "bx_eval_create": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "bx_eval_destroy": ([_vp], C.c_int),
     "bx_eval_capacity": ([_vp, _ip, _ip, _ip, _ip], C.c_int),

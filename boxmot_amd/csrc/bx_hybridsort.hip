@@ -7,7 +7,10 @@
 // (motion/kalman_filters/aabb/xysr_kf.py:137-291), associate_4_points_with_score_with_reid
 // (hybridsort/association.py:537-644), cost_vel (:328-349), embedding_distance (:734-751) and
 // linear_assignment (:312-325), with the patches H1-H3 of tests/golden/make_golden_hybridsort.py
-// (H1: the ORU replay of a 5-vector measurement).  use_byte is not built.
+// (H1: the ORU replay of a 5-vector measurement).  use_byte is not built.  The
+// ECC switch (KalmanBoxTracker.camera_update, :237-249, :448-451) is hyb_camera_kernel, a phase
+// ahead of the frame kernel that only an engine on which bx_hybrid_set_ecc_host has switched a
+// sequence on launches.
 //
 // Per frame, three launches on the caller's stream:
 //   hyb_dist_kernel     max(0, 1 - u.v / (|u||v|)) of every detection against every pre-frame
@@ -521,6 +524,58 @@ __global__ void __launch_bounds__(64)
   bank_mean(bank + (size_t)t * BANK * F, cnt[t], F, threadIdx.x, out + (size_t)t * F);
 }
 
+// KalmanBoxTracker.camera_update (hybridsort.py:237-249) of one track, by one lane: state ->
+// corner box -> the two warped corners -> convert_bbox_to_z, all float64; only x[0], x[1], x[2]
+// and x[4] are written (the score passes through).  numpy's `warp @ [x, y, 1]` of a 2x3 is BLAS's
+// gemv, whose row sum is fma(m0, x, m1 * y) + m2 (pinned by tests/golden/hybcmc_*.npz): the
+// fma is the one fused operation of the phase, spelled out; nothing else contracts.  A state
+// score of exactly 0 is where the reference raises (convert_bbox_to_z returns 4 rows): the track
+// is left as it was and counted; returns whether it was.
+__device__ __forceinline__ bool hyb_camera_update(HybTrk& t, const double* w) {
+  if (t.x[3] == 0.0) return true;
+  double b[4];
+  x9_to_bbox(t.x, b);
+  const double x1 = fma(w[0], b[0], w[1] * b[1]) + w[2], y1 = fma(w[3], b[0], w[4] * b[1]) + w[5];
+  const double x2 = fma(w[0], b[2], w[1] * b[3]) + w[2], y2 = fma(w[3], b[2], w[4] * b[3]) + w[5];
+  const double bw = x2 - x1, bh = y2 - y1;
+  t.x[0] = x1 + bw / 2.0;
+  t.x[1] = y1 + bh / 2.0;
+  t.x[2] = bw * bh;
+  t.x[4] = bw / (bh + 1e-6);
+  return false;
+}
+
+// The camera-update phase of the frame (hybridsort.py:448-451), ahead of hyb_frame_kernel on the
+// same stream and launched only by an engine that has ECC switches: one wave per sequence of the
+// call, a lane per live track, for the sequences whose switch is on - under the identity (a null
+// table) too.  sw: [S][2] per engine sequence, the switch and the tracks skipped for a score of
+// 0; warps: [nseq][6] of the call, or null.  A phase of its own launch and not a second
+// instantiation of the frame kernel: see DESIGN.md 2.28.
+__global__ void __launch_bounds__(OW)
+    hyb_camera_kernel(HybDev gd, int seq0, int* __restrict__ sw, const double* __restrict__ warps) {
+  const int b = blockIdx.x, seq = seq0 + b;
+  if (!sw[2 * seq]) return;  // workgroup-uniform
+  const int T = gd.o.T, lane = threadIdx.x;
+  int nt = gd.o.seqst[(size_t)seq * SQO + SO_NTR];
+  if (nt > T) nt = T;
+  const int* order = gd.o.order + (size_t)seq * T;
+  HybTrk* trk = gd.trk + (size_t)seq * T;
+  double w[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+  if (warps)
+    for (int q = 0; q < 6; q++) w[q] = warps[(size_t)b * 6 + q];
+  int skipped = 0;
+  for (int c = 0; c < nt; c += OW) {
+    const int p = c + lane;
+    bool sk = false;
+    if (p < nt) {
+      const int slot = order[p];
+      if (slot >= 0 && slot < T) sk = hyb_camera_update(trk[slot], w);
+    }
+    skipped += __popcll(__ballot(sk));
+  }
+  if (skipped && lane == 0) sw[2 * seq + 1] += skipped;
+}
+
 __global__ void __launch_bounds__(OW)
     hyb_frame_kernel(HybDev gd, int seq0, const float* __restrict__ dets,
                      const int* __restrict__ det_off, double* __restrict__ out,
@@ -804,6 +859,13 @@ struct bx_hybrid : OcsHost {
   // per-sequence parameters (bx_hybrid_set_seq_params_host): the device table dev.seqpar points
   // to, allocated by the first set, and its host mirror
   BxSeqTable<HybSeqPar> seqtab;
+  // the ECC switch (bx_hybrid_set_ecc_host): [S][2] on the device (switch, score-zero skips),
+  // allocated by the first call that switches a sequence on; null until then, and no camera
+  // kernel is launched.  ecc_on: the switches' host mirror
+  int* ecc = nullptr;
+  std::vector<int> ecc_on;
+  // the update_host forms' warps: device buffer and pinned mirror, [S][6], on first use
+  double *h_warp = nullptr, *p_warp = nullptr;
 };
 
 // the field checks bx_hybrid_create and bx_hybrid_set_seq_params_host share
@@ -811,7 +873,8 @@ static bool bad_delta_t(int delta_t) { return delta_t < 1 || delta_t > OBS_KEEP 
 static bool bad_asso_kind(int k) { return k < ASSO_IOU || k > ASSO_CENTROID; }
 
 static int launch(bx_hybrid* e, int seq0, int nseq, const float* dets, const int* off,
-                  const double* embs, double* out, int* cnt, hipStream_t st) {
+                  const double* embs, const double* warps, double* out, int* cnt,
+                  hipStream_t st) {
   const HybDev& d = e->dev;
   int rc;
   if (!embs) return bx_record_error(BX_ERR_SHAPE, "HybridSort needs embeddings");
@@ -821,6 +884,10 @@ static int launch(bx_hybrid* e, int seq0, int nseq, const float* dets, const int
   BX_HIPCHK(hipGetLastError());
   if ((rc = e->probe.end(0, st))) return rc;
   if ((rc = e->probe.begin(1, st))) return rc;
+  if (e->ecc) {  // (null until a sequence is switched on: the frame's launches as they always were)
+    hipLaunchKernelGGL(hyb_camera_kernel, dim3(nseq), dim3(OW), 0, st, d, seq0, e->ecc, warps);
+    BX_HIPCHK(hipGetLastError());
+  }
   hipLaunchKernelGGL(hyb_frame_kernel, dim3(nseq), dim3(OW), e->lds, st, d, seq0, dets, off, out,
                      cnt);
   BX_HIPCHK(hipGetLastError());
@@ -830,6 +897,38 @@ static int launch(bx_hybrid* e, int seq0, int nseq, const float* dets, const int
                      off, embs);
   BX_HIPCHK(hipGetLastError());
   if ((rc = e->probe.end(2, st))) return rc;
+  return BX_OK;
+}
+
+// a host warp table [n][6] through the pinned mirror to the device buffer on `st` (null: none)
+static int put_warps(bx_hybrid* e, const double* warps_host, int n, hipStream_t st,
+                     const double** dev) {
+  *dev = nullptr;
+  if (!warps_host) return BX_OK;
+  if (!e->h_warp) {
+    const size_t bytes = sizeof(double) * 6 * e->dev.o.S;
+    BX_HIPCHK(hipMalloc(&e->h_warp, bytes));
+    BX_HIPCHK(hipHostMalloc(&e->p_warp, bytes));
+  }
+  memcpy(e->p_warp, warps_host, sizeof(double) * 6 * n);
+  BX_HIPCHK(hipMemcpyAsync(e->h_warp, e->p_warp, sizeof(double) * 6 * n, hipMemcpyHostToDevice, st));
+  *dev = e->h_warp;
+  return BX_OK;
+}
+
+// the switch table on first use: zeroed, every sequence off
+static int ecc_alloc(bx_hybrid* e) {
+  if (e->ecc) return BX_OK;
+  const size_t S = e->dev.o.S;
+  int* p = nullptr;
+  if (hipMalloc(&p, S * 2 * sizeof(int)) != hipSuccess)
+    return bx_record_error(BX_ERR_HIP, "allocation of the HybridSort ECC switches failed");
+  if (hipMemset(p, 0, S * 2 * sizeof(int)) != hipSuccess) {
+    (void)hipFree(p);
+    return bx_record_error(BX_ERR_HIP, "allocation of the HybridSort ECC switches failed");
+  }
+  e->ecc = p;
+  e->ecc_on.assign(S, 0);
   return BX_OK;
 }
 
@@ -970,6 +1069,15 @@ int bx_hybrid_copy_state(bx_hybrid* dst, bx_hybrid* src) {
   BX_HIPCHK(hipMemcpy(b.status, a.status, 4 * sizeof(int), hipMemcpyDeviceToDevice));
   dst->cache_seq = -1;
   BX_HIPCHK(hipDeviceSynchronize());
+  // the ECC switches and skip counts: the source's, or all off for a source that never set one
+  if (src->ecc) {
+    if (int rc = ecc_alloc(dst)) return rc;
+    BX_HIPCHK(hipMemcpy(dst->ecc, src->ecc, S * 2 * sizeof(int), hipMemcpyDeviceToDevice));
+    dst->ecc_on = src->ecc_on;
+  } else if (dst->ecc) {
+    BX_HIPCHK(hipMemset(dst->ecc, 0, S * 2 * sizeof(int)));
+    dst->ecc_on.assign(S, 0);
+  }
   return cls_glue_copy(dst->pc, src->pc, b.S, b.D, dst->dev.F, 1);
 }
 
@@ -977,6 +1085,9 @@ int bx_hybrid_destroy(bx_hybrid* e) {
   if (!e) return BX_OK;
   e->probe.destroy();
   (void)hipFree(e->arena);
+  (void)hipFree(e->ecc);
+  (void)hipFree(e->h_warp);
+  (void)hipHostFree(e->p_warp);
   e->seqtab.free();
   e->sg.free();
   cls_glue_free(e->pc);
@@ -992,19 +1103,31 @@ int bx_hybrid_reset(bx_hybrid* e, int seq0, int nseq, void* stream) {
   hipLaunchKernelGGL(hyb_reset_kernel, dim3((nseq * SQO + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, e->dev, seq0, nseq);
   BX_HIPCHK(hipGetLastError());
+  if (e->ecc) {  // the range's switches go off, its skip counts to 0
+    BX_HIPCHK(hipMemsetAsync(e->ecc + 2 * (size_t)seq0, 0, sizeof(int) * 2 * nseq,
+                             (hipStream_t)stream));
+    for (int k = 0; k < nseq; k++) e->ecc_on[seq0 + k] = 0;
+  }
   return cls_glue_reset(e->pc, seq0, nseq, stream);
+}
+
+int bx_hybrid_step_cmc(bx_hybrid* e, int seq0, int nseq, const float* dets,
+                       const int32_t* det_off, const double* embs, const double* warps,
+                       double* out, int32_t* out_count, void* stream) {
+  if (!e || seq0 < 0 || nseq <= 0 || seq0 + nseq > e->dev.o.S || !det_off || !out || !out_count)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_step");
+  e->cache_seq = -1;
+  return launch(e, seq0, nseq, dets, det_off, embs, warps, out, out_count, (hipStream_t)stream);
 }
 
 int bx_hybrid_step(bx_hybrid* e, int seq0, int nseq, const float* dets, const int32_t* det_off,
                    const double* embs, double* out, int32_t* out_count, void* stream) {
-  if (!e || seq0 < 0 || nseq <= 0 || seq0 + nseq > e->dev.o.S || !det_off || !out || !out_count)
-    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_step");
-  e->cache_seq = -1;
-  return launch(e, seq0, nseq, dets, det_off, embs, out, out_count, (hipStream_t)stream);
+  return bx_hybrid_step_cmc(e, seq0, nseq, dets, det_off, embs, nullptr, out, out_count, stream);
 }
 
-int bx_hybrid_update_host(bx_hybrid* e, int seq, const float* dets, int n, const double* embs,
-                          double* out, int* n_out, void* stream) {
+int bx_hybrid_update_host_cmc(bx_hybrid* e, int seq, const float* dets, int n,
+                              const double* embs, const double* warp_host, double* out,
+                              int* n_out, void* stream) {
   if (!e || seq < 0 || seq >= e->dev.o.S || n < 0 || (n && (!dets || !out)) || !n_out)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_update_host");
   if (n > e->dev.o.D) return bx_record_error(BX_ERR_CAPACITY, "detections exceed det_cap");
@@ -1014,13 +1137,53 @@ int bx_hybrid_update_host(bx_hybrid* e, int seq, const float* dets, int n, const
   BxStaging& sg = e->sg;
   int rc;
   if (n && (rc = sg.put(sg.h_embs, sg.p_embs, embs, sizeof(double) * F * n, st))) return rc;
+  const double* warp = nullptr;
+  if ((rc = put_warps(e, warp_host, 1, st, &warp))) return rc;
   return ocs_update_host_roundtrip(
       *e, seq, dets, n, out, n_out, st, true,
       [&] {
-        return launch(e, seq, 1, (float*)sg.h_dets, sg.h_off, (double*)sg.h_embs, sg.h_out,
+        return launch(e, seq, 1, (float*)sg.h_dets, sg.h_off, (double*)sg.h_embs, warp, sg.h_out,
                       sg.h_cnt, st);
       },
       OcsStreamSync{st});
+}
+
+int bx_hybrid_update_host(bx_hybrid* e, int seq, const float* dets, int n, const double* embs,
+                          double* out, int* n_out, void* stream) {
+  return bx_hybrid_update_host_cmc(e, seq, dets, n, embs, nullptr, out, n_out, stream);
+}
+
+int bx_hybrid_set_ecc_host(bx_hybrid* e, int seq0, int nseq, const int32_t* on) {
+  if (!e || seq0 < 0 || nseq < 0 || seq0 > e->dev.o.S - nseq)
+    return bx_record_error(BX_ERR_INVALID, "bad sequence range");
+  if (nseq && !on) return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_set_ecc_host");
+  bool any = false;
+  for (int k = 0; k < nseq; k++) any = any || on[k] != 0;
+  if (!nseq || (!any && !e->ecc)) return BX_OK;  // (nothing to switch off)
+  BX_HIPCHK(hipDeviceSynchronize());  // a reset's clear of the range may still be queued
+  if (int rc = ecc_alloc(e)) return rc;
+  // one strided copy: the switches are the first int of each [2] entry, the counts stay
+  std::vector<int> v(nseq);
+  for (int k = 0; k < nseq; k++) v[k] = on[k] != 0;
+  BX_HIPCHK(hipMemcpy2D(e->ecc + 2 * (size_t)seq0, 2 * sizeof(int), v.data(), sizeof(int),
+                        sizeof(int), nseq, hipMemcpyHostToDevice));
+  for (int k = 0; k < nseq; k++) e->ecc_on[seq0 + k] = v[k];
+  return BX_OK;
+}
+
+int bx_hybrid_ecc_host(bx_hybrid* e, int seq, int* on, int* score_zero_skips) {
+  if (!e || seq < 0 || seq >= e->dev.o.S)
+    return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_ecc_host");
+  if (on) *on = e->ecc ? e->ecc_on[seq] : 0;
+  if (score_zero_skips) {
+    *score_zero_skips = 0;
+    if (e->ecc) {
+      BX_HIPCHK(hipDeviceSynchronize());
+      BX_HIPCHK(hipMemcpy(score_zero_skips, e->ecc + 2 * (size_t)seq + 1, sizeof(int),
+                          hipMemcpyDeviceToHost));
+    }
+  }
+  return BX_OK;
 }
 
 int bx_hybrid_set_seq_params_host(bx_hybrid* e, int seq0, int nseq,
@@ -1085,9 +1248,10 @@ int bx_hybrid_probe_read(bx_hybrid* e, double* total_ms, int* count) {
 
 // per_class=True (include/bxclasses.h): class c of sequence s is engine sequence s * C + c; the
 // frame is split -> the three launches over the class sequences -> merge, all on `stream`.
-int bx_hybrid_step_classes(bx_hybrid* e, int seq0, int nseq, int n_classes, const float* dets,
-                           const int32_t* det_off, const double* embs, double* out,
-                           int32_t* out_count, void* stream) {
+int bx_hybrid_step_classes_cmc(bx_hybrid* e, int seq0, int nseq, int n_classes,
+                               const float* dets, const int32_t* det_off, const double* embs,
+                               const double* warps, double* out, int32_t* out_count,
+                               void* stream) {
   if (!e) return bx_record_error(BX_ERR_INVALID, "null engine");
   if (!embs) return bx_record_error(BX_ERR_SHAPE, "HybridSort needs embeddings");
   e->cache_seq = -1;
@@ -1096,8 +1260,15 @@ int bx_hybrid_step_classes(bx_hybrid* e, int seq0, int nseq, int n_classes, cons
                        seq0, nseq, n_classes, dets, det_off, embs, out, out_count, st,
                        [&](int q0, int nq, const float* d, const int* off, const double* em,
                            double* o, int* cnt) {
-                         return launch(e, q0, nq, d, off, em, o, cnt, st);
+                         return launch(e, q0, nq, d, off, em, warps, o, cnt, st);
                        });
+}
+
+int bx_hybrid_step_classes(bx_hybrid* e, int seq0, int nseq, int n_classes, const float* dets,
+                           const int32_t* det_off, const double* embs, double* out,
+                           int32_t* out_count, void* stream) {
+  return bx_hybrid_step_classes_cmc(e, seq0, nseq, n_classes, dets, det_off, embs, nullptr, out,
+                                    out_count, stream);
 }
 
 int bx_hybrid_classes_config(bx_hybrid* e, int n_classes, int map_cap) {
@@ -1113,9 +1284,9 @@ int bx_hybrid_classes(bx_hybrid* e, bx_classes** out) {
   return BX_OK;
 }
 
-int bx_hybrid_update_classes_host(bx_hybrid* e, int seq, int n_classes, const float* dets, int n,
-                                  const double* embs, int* id_count, double* out, int* n_out,
-                                  void* stream) {
+int bx_hybrid_update_classes_host_cmc(bx_hybrid* e, int seq, int n_classes, const float* dets,
+                                      int n, const double* embs, const double* warps_host,
+                                      int* id_count, double* out, int* n_out, void* stream) {
   if (!e || seq < 0 || n < 0 || (n && (!dets || !out)) || !n_out || !id_count)
     return bx_record_error(BX_ERR_INVALID, "bad arguments to bx_hybrid_update_classes_host");
   if (n > e->dev.o.D) return bx_record_error(BX_ERR_CAPACITY, "detections exceed det_cap");
@@ -1127,14 +1298,23 @@ int bx_hybrid_update_classes_host(bx_hybrid* e, int seq, int n_classes, const fl
   hipStream_t st = (hipStream_t)stream;
   BxStaging& sg = e->sg;
   if (n && (rc = sg.put(sg.h_embs, sg.p_embs, embs, sizeof(double) * F * n, st))) return rc;
+  const double* warps = nullptr;
+  if ((rc = put_warps(e, warps_host, n_classes, st, &warps))) return rc;
   return ocs_update_host_roundtrip(
       *e, -1, dets, n, out, n_out, st, true,
       [&] {
         if (int r = cls_glue_put_ids(e->pc, seq, *id_count, st)) return r;
-        return bx_hybrid_step_classes(e, seq, 1, n_classes, (float*)sg.h_dets, sg.h_off,
-                                      (double*)sg.h_embs, sg.h_out, sg.h_cnt, st);
+        return bx_hybrid_step_classes_cmc(e, seq, 1, n_classes, (float*)sg.h_dets, sg.h_off,
+                                          (double*)sg.h_embs, warps, sg.h_out, sg.h_cnt, st);
       },
       [&](int* cstatus) { return cls_glue_take_ids(e->pc, seq, id_count, cstatus, st); });
+}
+
+int bx_hybrid_update_classes_host(bx_hybrid* e, int seq, int n_classes, const float* dets, int n,
+                                  const double* embs, int* id_count, double* out, int* n_out,
+                                  void* stream) {
+  return bx_hybrid_update_classes_host_cmc(e, seq, n_classes, dets, n, embs, nullptr, id_count,
+                                           out, n_out, stream);
 }
 
 int bx_hybrid_status(bx_hybrid* e, int* status) {

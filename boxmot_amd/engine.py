@@ -7,6 +7,7 @@ out); ``update_host`` is the single-sequence numpy path the drop-in tracker clas
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import functools
 from dataclasses import dataclass
 
@@ -1054,6 +1055,142 @@ def hybrid_bank_mean(bank, pushed, out, stream=None) -> None:
                                          stream), "bx_hybrid_bank_mean")
 
 
+@dataclass
+class HybridsortCmcParams(HybridsortParams):
+    """HybridsortParams and the reference's ``ECC`` attribute (hybridsort.py:417), which is no
+    constructor argument there: the parameters of a HybridsortCmcEngine whose sequences start
+    with their camera update switched on, and an entry of HybridsortCmcTableEngine's table."""
+
+    ECC: bool = False
+
+
+def _ecc_off(p):
+    """``p`` with its ECC (if it has one) off: grown() copies the switches, it does not set them."""
+    return dataclasses.replace(p, ECC=False) if getattr(p, "ECC", False) else p
+
+
+class HybridsortCmcEngine(HybridsortEngine):
+    """A ``HybridsortEngine`` with the reference's ``ECC`` switch per sequence and the
+    camera-motion warps of ``KalmanBoxTracker.camera_update`` (hybridsort.py:237-249, 448-451;
+    include/bxhybridsort.h): ``set_ecc`` / ``ecc``, and ``warps`` on ``step``,
+    ``update_host`` and their per-class forms.  ``params.ECC`` (HybridsortCmcParams) switches
+    every sequence on at construction.  An engine on which no sequence was ever switched on launches
+    ``HybridsortEngine``'s kernels and nothing else.  (A class of its own because
+    HybridsortEngine's method set is pinned by tests/test_engine_api_host.py.)"""
+
+    def __init__(self, n_seq: int = 1, track_cap: int = 256, det_cap: int = 256,
+                 emb_dim: int = 512, params: HybridsortParams | None = None):
+        super().__init__(n_seq, track_cap, det_cap, emb_dim, params)
+        if getattr(self.params, "ECC", False):
+            self.set_ecc(0, True)
+
+    def set_ecc(self, seq0: int, flags, nseq: int | None = None) -> None:
+        """The ``ECC`` attribute of sequences [seq0, seq0 + nseq) (bx_hybrid_set_ecc_host):
+        ``flags`` is one value per sequence, or a scalar for ``nseq`` sequences (default: all from
+        seq0).  A sequence whose switch is on starts every frame with ``camera_update`` of its
+        live tracks under its row of ``warps`` (the identity without one), whatever the warp.
+        Off after ``reset``; ``grown()`` carries it.  Synchronous."""
+        f = np.atleast_1d(np.asarray(flags))
+        if nseq is None:
+            nseq = f.size if np.ndim(flags) else self.n_seq - seq0
+        on = np.ascontiguousarray(np.broadcast_to(f != 0, (nseq,)), np.int32)
+        N.check(self._L.bx_hybrid_set_ecc_host(self._h, int(seq0), int(nseq), on.ctypes.data),
+                "bx_hybrid_set_ecc_host")
+
+    def ecc(self, seq: int = 0) -> dict:
+        """Sequence ``seq``'s switch and the number of tracks its camera updates left as they
+        were for a state score of exactly 0 (where the reference raises) since the last reset.
+        Synchronises the device (the count is read back); ``ecc_on`` does not."""
+        on, sk = C.c_int(), C.c_int()
+        N.check(self._L.bx_hybrid_ecc_host(self._h, int(seq), C.byref(on), C.byref(sk)),
+                "bx_hybrid_ecc_host")
+        return {"on": bool(on.value), "score_zero_skips": sk.value}
+
+    def ecc_on(self, seq: int = 0) -> bool:
+        """Sequence ``seq``'s switch from the library's host mirror: no device work."""
+        on = C.c_int()
+        N.check(self._L.bx_hybrid_ecc_host(self._h, int(seq), C.byref(on), None),
+                "bx_hybrid_ecc_host")
+        return bool(on.value)
+
+    def grown(self, track_cap: int, det_cap: int,
+              map_cap: int | None = None) -> "HybridsortCmcEngine":
+        """As HybridsortEngine.grown; bx_hybrid_copy_state carries the switches."""
+        e = HybridsortCmcEngine(self.n_seq, track_cap, det_cap, self.emb_dim, _ecc_off(self.params))
+        e.params = self.params
+        if map_cap is not None:
+            e.classes_config(self.classes().n_classes, map_cap)
+        N.check(self._L.bx_hybrid_copy_state(e._h, self._h), "bx_hybrid_copy_state")
+        return e
+
+    def step(self, dets, det_off, embs, out, out_count, seq0: int = 0, nseq: int | None = None,
+             stream=None, warps=None):
+        """HybridsortEngine.step with warps: float64 [nseq, 6] device tensor, one row-major 2x3
+        affine per sequence of the call, or None (the identity); read by the sequences whose
+        switch is on (bx_hybrid_step_cmc).  ``ValueError`` for another shape."""
+        nseq, stream = self._range(seq0, nseq, stream)
+        if warps is not None and tuple(warps.shape) not in ((nseq, 6), (nseq, 2, 3)):
+            raise ValueError(f"warps of shape {tuple(warps.shape)} for {nseq} sequences: one "
+                             f"2x3 affine per sequence is [{nseq}, 6]")
+        N.check(self._L.bx_hybrid_step_cmc(self._h, seq0, nseq, _ptr(dets), _ptr(det_off),
+                                           _ptr(embs), _ptr(warps), _ptr(out), _ptr(out_count),
+                                           stream), "bx_hybrid_step")
+
+    def _host_frame(self, dets, embs):
+        d = np.ascontiguousarray(dets, dtype=np.float32).reshape(-1, 6)
+        n = d.shape[0]
+        e = None
+        if n:
+            if embs is None:
+                raise ValueError("HybridSort needs embeddings")
+            e = np.ascontiguousarray(embs, dtype=np.float64).reshape(n, -1)
+            if e.shape[1] != self.emb_dim:
+                raise ValueError(f"embedding dim {e.shape[1]} != engine emb_dim {self.emb_dim}")
+        return d, n, e
+
+    def update_host(self, seq: int, dets: np.ndarray, embs: np.ndarray | None = None,
+                    warp: np.ndarray | None = None) -> np.ndarray:
+        """HybridsortEngine.update_host with warp: a 2x3 (or [6]) host array, or None."""
+        d, n, e = self._host_frame(dets, embs)
+        w = None if warp is None else np.ascontiguousarray(warp, np.float64).reshape(6)
+        out = np.empty((max(n, 1), 8), np.float64)
+        m = C.c_int(0)
+        N.check(self._L.bx_hybrid_update_host_cmc(
+            self._h, seq, d.ctypes.data if n else None, n, _p(e), _p(w), out.ctypes.data,
+            C.byref(m), None), "bx_hybrid_update_host")
+        return out[: m.value].copy()
+
+    def step_classes(self, dets, det_off, embs, out, out_count, n_classes: int, seq0: int = 0,
+                     nseq: int | None = None, stream=None, warps=None):
+        """HybridsortEngine.step_classes with warps [nseq * n_classes, 6] or None, one per class
+        sequence.  ``ValueError`` for another shape."""
+        nseq = self.n_seq // int(n_classes) - seq0 if nseq is None else nseq
+        if stream is None:
+            stream = _current_stream()
+        rows = nseq * int(n_classes)
+        if warps is not None and tuple(warps.shape) not in ((rows, 6), (rows, 2, 3)):
+            raise ValueError(f"warps of shape {tuple(warps.shape)} for {nseq} sequences of "
+                             f"{n_classes} classes: one 2x3 affine per class sequence is "
+                             f"[{rows}, 6]")
+        N.check(self._L.bx_hybrid_step_classes_cmc(
+            self._h, seq0, nseq, int(n_classes), _ptr(dets), _ptr(det_off), _ptr(embs),
+            _ptr(warps), _ptr(out), _ptr(out_count), stream), "bx_hybrid_step_classes")
+
+    def update_classes_host(self, seq: int, n_classes: int, dets: np.ndarray,
+                            embs: np.ndarray | None, id_count: int,
+                            warps: np.ndarray | None = None):
+        """HybridsortEngine.update_classes_host with warps: [n_classes, 2, 3] or None."""
+        d, n, e = self._host_frame(dets, embs)
+        w = None if warps is None else np.ascontiguousarray(warps, np.float64).reshape(
+            int(n_classes) * 6)
+        out = np.empty((max(n, 1), 8), np.float64)
+        m, g = C.c_int(0), C.c_int(int(id_count))
+        N.check(self._L.bx_hybrid_update_classes_host_cmc(
+            self._h, seq, int(n_classes), d.ctypes.data if n else None, n, _p(e), _p(w),
+            C.byref(g), out.ctypes.data, C.byref(m), None), "bx_hybrid_update_classes_host")
+        return out[: m.value].copy(), g.value
+
+
 class HybridsortTableEngine(_SeqTable, HybridsortEngine):
     """A ``HybridsortEngine`` with per-sequence ``HybridsortParams`` (``_SeqTable``;
     include/bxhybridsort.h, boxmot_amd.tune.sweep_reid).  frame_w / frame_h, which are not part of
@@ -1063,6 +1200,36 @@ class HybridsortTableEngine(_SeqTable, HybridsortEngine):
               map_cap: int | None = None) -> "HybridsortTableEngine":
         """As HybridsortEngine.grown, with the table."""
         e = HybridsortTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim, self.params)
+        if map_cap is not None:
+            e.classes_config(self.classes().n_classes, map_cap)
+        N.check(self._L.bx_hybrid_copy_state(e._h, self._h), "bx_hybrid_copy_state")
+        return self._retable(e)
+
+
+class HybridsortCmcTableEngine(_SeqTable, HybridsortCmcEngine):
+    """A ``HybridsortCmcEngine`` with per-sequence ``HybridsortParams``: the engine of a
+    ``tune.sweep_reid`` in which a config sets ``ECC``.  An entry's ``ECC`` is the sequence's
+    camera-update switch: ``set_seq_params`` sets it with the entry and ``seq_params`` reads it
+    back, so the configs of one sweep may mix it.  (Beside HybridsortTableEngine, whose method
+    set is pinned by tests/test_sweep_reid_host.py.)"""
+
+    def set_seq_params(self, seq0: int, params, nseq: int | None = None) -> None:
+        super().set_seq_params(seq0, params, nseq)
+        if params is None:
+            self.set_ecc(seq0, False, self.n_seq - seq0 if nseq is None else nseq)
+        elif len(params):
+            self.set_ecc(seq0, [bool(getattr(p, "ECC", False)) for p in params])
+
+    def seq_params(self, seq: int):
+        return HybridsortCmcParams(**dataclasses.asdict(super().seq_params(seq)),
+                                   ECC=self.ecc_on(seq))
+
+    def grown(self, track_cap: int, det_cap: int,
+              map_cap: int | None = None) -> "HybridsortCmcTableEngine":
+        """As HybridsortCmcEngine.grown, with the table."""
+        e = HybridsortCmcTableEngine(self.n_seq, track_cap, det_cap, self.emb_dim,
+                                     _ecc_off(self.params))
+        e.params = self.params
         if map_cap is not None:
             e.classes_config(self.classes().n_classes, map_cap)
         N.check(self._L.bx_hybrid_copy_state(e._h, self._h), "bx_hybrid_copy_state")

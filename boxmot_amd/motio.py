@@ -159,16 +159,26 @@ def _batched_engine(tracker_type: str, n_seq: int, emb_dim: int, tracker_kwargs:
     if tracker_type == "hybridsort":
         # as deepocsort; det_thresh has no default in the reference's constructor: the drop-in's
         # engine parameters' 0.3 stands in when tracker_kwargs leaves it out
-        from .engine import HybridsortEngine, HybridsortParams
+        import dataclasses
+
+        from .engine import (HybridsortCmcEngine, HybridsortCmcParams, HybridsortEngine,
+                             HybridsortParams)
         from .trackers.hybridsort import HybridSort, HybridSortPerClass
 
         kw = dict(reid_weights=None, device=None, half=False,
                   det_thresh=HybridsortParams().det_thresh)
         kw.update(tracker_kwargs)
+        # ECC is an attribute of the drop-in, not a constructor argument (as in the reference):
+        # in tracker_kwargs it asks for the engine that takes warps, every sequence's switch on
+        ecc = bool(kw.pop("ECC", False))
         tr = HybridSortPerClass(nr_classes=n_classes, **kw) if n_classes else HybridSort(**kw)
         tc, dc = tr._caps
-        eng = HybridsortEngine(n_seq=n_seq * (tr.nr_classes if tr.per_class else 1), track_cap=tc,
-                               det_cap=dc, emb_dim=emb_dim, params=tr._params)
+        cls, par = HybridsortEngine, tr._params
+        if ecc:
+            cls = HybridsortCmcEngine
+            par = HybridsortCmcParams(**dataclasses.asdict(par), ECC=True)
+        eng = cls(n_seq=n_seq * (tr.nr_classes if tr.per_class else 1), track_cap=tc, det_cap=dc,
+                  emb_dim=emb_dim, params=par)
         eng.n_classes = tr.nr_classes if tr.per_class else 0
         return eng, np.float32, 8
     from .engine import BoostEngine, Engine, OcsortEngine, SsEngine
@@ -218,14 +228,16 @@ RESIDENT_TRACKERS = ("deepocsort", "hybridsort")  # trackers run_sequences(resid
 def _step(eng, tracker_type: str, dets, det_off, embs, out, out_count, seq0: int, nseq: int,
           warps=None):
     """One frame of sequences [seq0, seq0 + nseq) on a DeepOcsortEngine / HybridsortEngine:
-    ``step``, or ``step_classes`` on a per_class engine (HybridsortEngine.step takes no warps).
-    warps: the run's [nseq, 6] block of a warp table (DeepOcsortEngine.step only)."""
+    ``step``, or ``step_classes`` on a per_class engine.  warps: the run's [nseq, 6] block of a
+    warp table (never with a per_class engine).  The two families differ in where ``step`` takes
+    its warps: DeepOCSort's as the fourth argument, HybridSort's as a keyword."""
     C = getattr(eng, "n_classes", 0)
     if tracker_type == "hybridsort":
         if C:
             eng.step_classes(dets, det_off, embs, out, out_count, C, seq0=seq0, nseq=nseq)
         else:
-            eng.step(dets, det_off, embs, out, out_count, seq0=seq0, nseq=nseq)
+            kw = {} if warps is None else {"warps": warps}  # (a plain engine takes none)
+            eng.step(dets, det_off, embs, out, out_count, seq0=seq0, nseq=nseq, **kw)
     elif C:
         eng.step_classes(dets, det_off, embs, None, out, out_count, C, seq0=seq0, nseq=nseq)
     else:
@@ -313,7 +325,10 @@ def _check_warp_args(tracker_type: str, tracker_kwargs: dict, n_classes: int, wa
         if cmc is not None:
             raise ValueError("cmc names how warps are computed from images: give images too")
         return None
-    if tracker_type not in WARP_TRACKERS:
+    # hybridsort applies warps iff its ECC switch is on (the reference's attribute, False by
+    # default): a condition of its own, WARP_TRACKERS names the trackers that always take them
+    if tracker_type not in WARP_TRACKERS and not (
+            tracker_type == "hybridsort" and tracker_kwargs.get("ECC")):
         raise ValueError(
             f"{tracker_type} takes no camera-motion warp (its engine has none and the "
             f"reference's tracker runs no CMC): warps / images are for {', '.join(WARP_TRACKERS)}")
@@ -420,8 +435,9 @@ def run_sequences(tracker_type: str, sequences: dict, exp_dir, frame_ids: dict |
     tracker_kwargs raises for these two, as their plain constructors do), with the class split and
     the id merge on the device, resident or not.
     Camera-motion compensation (the reference's ``tracker.update(dets, img, embs)`` runs its CMC
-    on every stepped frame), for the trackers in WARP_TRACKERS, resident or not; left out, no
-    warp is applied, as before:
+    on every stepped frame), for the trackers in WARP_TRACKERS and for hybridsort with
+    ``ECC=True`` in tracker_kwargs (the reference's switch; without it hybridsort is refused as
+    before), resident or not; left out, no warp is applied, as before:
     warps: a ``cmc.WarpTable`` over these sequences (in their order) and their iterated frames,
     or a mapping name -> ``[n_frames, 6]`` (or ``[n_frames, 2, 3]``) array of the warp at every
     iterated frame of that sequence (rows of frames that are not stepped are not read), e.g.

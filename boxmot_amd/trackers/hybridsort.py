@@ -15,6 +15,15 @@ output rows is a confidence, not a detection index: HybridSort reads ``cls`` and
 the unfiltered frame at an index into the kept detections, ``det_ind`` from its score column
 (hybridsort.py:458,467,604).
 
+Camera-motion compensation is the reference's ``ECC`` attribute (hybridsort.py:417, 448-451;
+like there it is no constructor argument, ``tracker.ECC = True`` switches it on, and
+``HybridSortPerClass`` alone takes it as a keyword): while it is true every frame starts with ``self.cmc.apply(img,
+dets)`` (``boxmot_amd.ECC()`` unless another estimator is assigned; built on the first frame
+that needs it), the warp is rounded to float32, the type the reference's estimator returns, and
+every live track's ``camera_update`` runs under it on the device before the predict, under an
+identity warp too.  Where the reference raises on a state score of exactly 0
+the track is left as it was (``engine.ecc(0)["score_zero_skips"]`` counts them).
+
 Out of scope: the ReID embeddings are an input (``embs``; the reference would run its ReID
 backend) and ``use_byte=True`` (the reference's BYTE round cannot run).  Embeddings are float64
 on the engine: ``embs`` is converted with ``np.asarray(embs, np.float64)``.
@@ -29,7 +38,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..engine import HybridsortEngine, HybridsortParams
+from ..engine import HybridsortCmcEngine, HybridsortEngine, HybridsortParams
 from ..iou import KINDS
 from .basetracker import BaseTracker, CapacityGuard, ClassMapGuard, model_embs
 
@@ -67,6 +76,8 @@ class HybridSort(BaseTracker):
         self.use_byte = use_byte
         self.longterm_reid_weight = longterm_reid_weight
         self.TCM_first_step_weight = TCM_first_step_weight
+        self.ECC = False  # a plain attribute, as in the reference: read at every update
+        self._cmc = None  # the estimator, built by the first read of `cmc`
         HybridSort._id_count = 1
         # an unknown asso_func never reaches the engine: setup_decorator raises ValueError for it
         # on the first update (basetracker.py:140-147), as DeepOcSort's; "iou" only fills the field
@@ -86,9 +97,47 @@ class HybridSort(BaseTracker):
         self.engine = None
         self._empty_before_engine = 0
 
+    @property
+    def cmc(self):
+        """The camera-motion estimator (``apply(img, dets)`` -> a 2x3 affine): ``boxmot_amd.ECC()``,
+        the reference's ``get_cmc_method("ecc")()``, built on first use; assignable."""
+        if self._cmc is None:
+            from ..cmc import ECC
+
+            self._cmc = ECC()
+        return self._cmc
+
+    @cmc.setter
+    def cmc(self, value):
+        self._cmc = value
+
     def _make_engine(self, emb_dim: int) -> HybridsortEngine:
-        return HybridsortEngine(n_seq=self.nr_classes if self.per_class else 1, track_cap=self._caps[0], det_cap=self._caps[1],
-                                emb_dim=emb_dim, params=self._params)
+        # (with ECC on: the engine that takes warps; its switches are set in _sync_ecc)
+        cls = HybridsortCmcEngine if self.ECC else HybridsortEngine
+        return cls(n_seq=self.nr_classes if self.per_class else 1, track_cap=self._caps[0],
+                   det_cap=self._caps[1], emb_dim=emb_dim, params=self._params)
+
+    def _warp(self, img, dets):
+        """One class call's ``self.cmc.apply(img, dets)`` (hybridsort.py:448-451), rounded to
+        float32 as the reference's estimator returns it."""
+        w = self.cmc.apply(img, dets)
+        return np.asarray(w, np.float64).reshape(2, 3).astype(np.float32).astype(np.float64)
+
+    def _sync_ecc(self) -> bool:
+        """The engine's switches follow the attribute; returns it.  The first frame with ECC on
+        moves a plain engine's state into one that takes warps."""
+        on = bool(self.ECC)
+        if not isinstance(self.engine, HybridsortCmcEngine):
+            if not on:
+                return False
+            old = self.engine
+            has_cls = self.per_class and old.classes() is not None
+            self.engine = HybridsortCmcEngine.grown(old, old.track_cap, old.det_cap,
+                                                    self._map.cap if has_cls else None)
+            old.close()
+        if self.engine.ecc_on(0) != on:  # (the host mirror: nothing waits on the device)
+            self.engine.set_ecc(0, on)
+        return on
 
     @BaseTracker.setup_decorator
     @BaseTracker.per_class_decorator
@@ -106,6 +155,9 @@ class HybridSort(BaseTracker):
                 # tracker only advances the frame counter; replayed below
                 self.frame_count += 1
                 self._empty_before_engine += 1
+                if self.ECC:  # (the estimator keeps state: it sees every frame)
+                    for _ in range(self.nr_classes if self.per_class else 1):
+                        self.cmc.apply(img, dets)
                 return np.empty((0, 8))
             self.engine = self._make_engine(e.shape[1])
             for _ in range(self._empty_before_engine):
@@ -127,13 +179,20 @@ class HybridSort(BaseTracker):
             C = self.nr_classes
             self.engine = self._cap.fit(self.engine, ClassMapGuard.class_counts(dets, C), n)
             self.engine = self._map.fit(self.engine, C, n)
+            warps = None
+            if self._sync_ecc():
+                # one CMC call per class call, on that class's rows (basetracker.py:175-189 ->
+                # hybridsort.py:448-449), as DeepOcSortPerClass
+                d = np.asarray(dets, np.float32).reshape(-1, 6)
+                warps = np.stack([self._warp(img, d[d[:, 5] == c]) for c in range(C)])
             out, HybridSort._id_count = self.engine.update_classes_host(
-                0, C, dets, e, HybridSort._id_count)
+                0, C, dets, e, HybridSort._id_count, *([warps] if warps is not None else []))
             return out if out.shape[0] else np.empty((0, 8))
         self.engine = self._cap.fit(self.engine, {0: n}, n)
+        warp = self._warp(img, dets) if self._sync_ecc() else None
         if self._engine_ids != HybridSort._id_count:
             self.engine.set_id_count(0, HybridSort._id_count)
-        out = self.engine.update_host(0, dets, e)
+        out = self.engine.update_host(0, dets, e, *([warp] if warp is not None else []))
         self._engine_ids = HybridSort._id_count = self.engine.counters(0)["id_count"]
         return out if out.shape[0] else np.empty((0, 8))
 
@@ -169,5 +228,7 @@ class HybridSortPerClass(HybridSort):
 
     def __init__(self, reid_weights, device, half, det_thresh, nr_classes: int = 80, **kwargs):
         kwargs.pop("per_class", None)
+        ecc = bool(kwargs.pop("ECC", False))
         self._nr_classes = int(nr_classes)
         super().__init__(reid_weights, device, half, det_thresh, per_class=True, **kwargs)
+        self.ECC = ecc

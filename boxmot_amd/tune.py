@@ -367,8 +367,12 @@ def _check_reid(tracker_type: str, configs, warps, score, keep_results) -> None:
                 f"config {k}: HybridSort(use_byte=True) is not built: the reference's BYTE round "
                 "calls KalmanBoxTracker.update with the wrong arguments, so it defines no "
                 "behaviour")
-        if warps is not None:  # (hybridsort, cmc_off / use_ecc against warps)
-            motio._check_warp_args(tracker_type, c, 0, warps, None, None)
+        if warps is not None:  # (cmc_off / use_ecc against warps)
+            # hybridsort: one config with ECC=True takes the warps; the others run uncompensated
+            # in the same engine (their switches are off).  None: run_sequences' refusal
+            hyb = tracker_type == "hybridsort" and any(x.get("ECC") for x in configs)
+            motio._check_warp_args(tracker_type, dict(c, ECC=True) if hyb else c, 0, warps, None,
+                                   None)
 
 
 def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
@@ -385,7 +389,9 @@ def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
     fed by one ``SharedSequenceFeeder`` with ``source[k*S + s] = s``: detections and embeddings
     are uploaded and held once per sequence, not once per config.
 
-    ``warps`` (deepocsort only): what ``run_sequences(warps=...)`` takes, a ``cmc.WarpTable`` over
+    ``warps`` (deepocsort, and hybridsort when at least one config sets ``ECC=True``: configs
+    without it run uncompensated in the same engine): what ``run_sequences(warps=...)`` takes, a
+    ``cmc.WarpTable`` over
     these sequences or a mapping name -> ``[n_frames, 6]``; rounded to float32 as there, and every
     config's copy of a sequence gets that sequence's warp (the ``[T, K*S, 6]`` table is built once
     on the device).  ``cmc.sof_warp_table(images, stepped, sof=SOF(...))`` returns such a table:
@@ -394,7 +400,8 @@ def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
 
     Raised before any engine is built: ``NotImplementedError`` for another tracker, ``per_class``
     in a config or HybridSort's ``use_byte=True``; ``ValueError`` for caps or ``embedding_off``
-    that differ across configs, ``warps`` with hybridsort or with a config that switches the
+    that differ across configs, ``warps`` with hybridsort when no config sets ``ECC=True`` or with
+    a config that switches the
     camera-motion compensation off (``cmc_off`` / ``use_ecc``), sequences whose embedding widths
     differ, and the ``score`` / ``keep_results`` combinations ``sweep`` refuses.
     """
@@ -407,6 +414,8 @@ def sweep_reid(tracker_type: str, sequences: dict, configs, *, exp_dir=None,
 def _reid_engine(E, tracker_type, n_seq, F, resolved):
     p, tc, dc = resolved[0]
     cls = E.DeepOcsortTableEngine if tracker_type == "deepocsort" else E.HybridsortTableEngine
+    if tracker_type == "hybridsort" and any(getattr(r[0], "ECC", False) for r in resolved):
+        cls = E.HybridsortCmcTableEngine  # (a config switches the camera update on)
     eng = cls(n_seq=n_seq, track_cap=tc, det_cap=dc, emb_dim=F or 1, params=p)
     return eng, F if eng.emb_dim else 0
 

@@ -23,7 +23,8 @@
  *   bx_hybrid_cosdist                  embedding_distance  hybridsort/association.py:734-751
  * The reference does not run as published; parity is defined against it with the patches H1-H3
  * listed in tests/golden/make_golden_hybridsort.py.  use_byte is not built.
- * ECC is False in the reference, so no camera-motion warp crosses this ABI.
+ * The reference's ECC switch (False by default) is per sequence here: bx_hybrid_set_ecc_host and
+ * the *_cmc entry points below carry the camera-motion warp.
  *
  * Conventions as in bxassoc.h: device pointers unless a name ends in _host, asynchronous on
  * `stream`, every function returns a bx_status (bx_last_error explains failures).
@@ -144,6 +145,55 @@ int bx_hybrid_copy_state(bx_hybrid *dst, bx_hybrid *src);
 int bx_hybrid_set_seq_params_host(bx_hybrid *e, int seq0, int nseq,
                                   const bx_hybrid_seq_params *params_host, void *stream);
 int bx_hybrid_seq_params_host(bx_hybrid *e, int seq, bx_hybrid_seq_params *out_host);
+/* Camera-motion compensation: the reference's `ECC` attribute (hybridsort.py:417, 448-451;
+ * KalmanBoxTracker.camera_update :237-249), DESIGN.md 2.28.
+ *
+ * bx_hybrid_set_ecc_host: on [nseq] (!= 0 switches on) for sequences [seq0, seq0+nseq).  Every
+ * switch is off after create and after a reset of its sequence; bx_hybrid_copy_state carries the
+ * switches and the skip counts (the state blob of bx_hybrid_state_save_host does not).  A range
+ * outside [0, n_seq) or a null `on` is BX_ERR_INVALID and changes nothing.  Host, synchronous
+ * (it synchronises the device first).  The first call that switches a sequence on allocates the
+ * switches; from then on every frame of the engine has a fourth launch, the camera-update
+ * kernel ahead of the frame kernel (one wave per sequence of the call; a sequence whose switch
+ * is off leaves it after one uniform load).  Until then - and a call that only switches off on
+ * such an engine changes nothing - a frame is the three launches it always was, of unchanged
+ * kernels.  bx_hybrid_probe's stage 1 times the camera-update launch with the frame's.
+ *
+ * A sequence whose switch is on starts every frame with camera_update of every live track under
+ * its warp, before the predict: state -> corner box (w = sqrt(x2 x4), h = x2 / w) -> the two
+ * warped corners -> convert_bbox_to_z, in float64; x[0], x[1], x[2], x[4] are rewritten, the score
+ * x[3], the covariance, the observations, the corner velocities and the features are not.  The
+ * phase runs whenever the switch is on, under the identity too (the round trip is not the
+ * identity in floating point).  A track whose state score is exactly 0 - where the reference
+ * raises - is left as it was and counted.  A negative x2 x4 gives NaN, as numpy's does.
+ *
+ * The *_cmc entry points are bx_hybrid_step / update_host / step_classes / update_classes_host
+ * plus the warps, which those call with NULL:
+ *   warps      [nseq][6] float64 device, the row-major 2x3 affine per sequence of the call
+ *              (step_classes: [nseq * n_classes][6], one per class sequence); NULL = identity
+ *   warp_host  [6] host (update_host_cmc), warps_host [n_classes][6] host
+ *              (update_classes_host_cmc); NULL = identity
+ * Warps are read by sequences whose switch is on and ignored by the others.
+ *
+ * bx_hybrid_ecc_host: a sequence's switch and the number of tracks its camera updates left out
+ * for a score of exactly 0 since the last reset (either pointer may be NULL).  Host; the switch
+ * comes from the host mirror, and only a non-NULL count synchronises the device. */
+int bx_hybrid_set_ecc_host(bx_hybrid *e, int seq0, int nseq, const int32_t *on);
+int bx_hybrid_ecc_host(bx_hybrid *e, int seq, int *on, int *score_zero_skips);
+int bx_hybrid_step_cmc(bx_hybrid *e, int seq0, int nseq, const float *dets,
+                       const int32_t *det_off, const double *embs, const double *warps,
+                       double *out, int32_t *out_count, void *stream);
+int bx_hybrid_update_host_cmc(bx_hybrid *e, int seq, const float *dets, int n,
+                              const double *embs, const double *warp_host, double *out,
+                              int *n_out, void *stream);
+int bx_hybrid_step_classes_cmc(bx_hybrid *e, int seq0, int nseq, int n_classes,
+                               const float *dets, const int32_t *det_off, const double *embs,
+                               const double *warps, double *out, int32_t *out_count,
+                               void *stream);
+int bx_hybrid_update_classes_host_cmc(bx_hybrid *e, int seq, int n_classes,
+                                      const float *dets_host, int n, const double *embs_host,
+                                      const double *warps_host, int *id_count_host,
+                                      double *out_host, int *n_out, void *stream);
 /* Latched device status (BX_OK, BX_ERR_TRACK_OVERFLOW or BX_ERR_CAPACITY). */
 int bx_hybrid_status(bx_hybrid *e, int *status);
 int bx_hybrid_counters_host(bx_hybrid *e, int seq, int *frame_count, int *id_count,
