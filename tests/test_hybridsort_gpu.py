@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from boxmot_amd import HybridSort
+from tests.emb_ref import cosdist_bound
 from tests.golden_util import compare_outputs
 from tests.scenes import scene_of
 
@@ -118,21 +119,6 @@ def cosdist_ref(T, D):
     nt = np.sqrt((T * T).sum(1))
     nd = np.sqrt((D * D).sum(1))
     return np.maximum(0.0, 1.0 - (D @ T.T) / (nd[:, None] * nt[None, :]))
-
-
-def cosdist_bound(T, D):
-    """|got - ref| for two float64 evaluations of 1 - d.t / (|d||t|) in any summation order.
-    The dot product: the bound DeepOCSort's contraction test uses, F * 2^-53 * (|D| @ |T|.T), once
-    for each side, divided by the norms.  Each norm is the square root of such a sum of F
-    non-negative terms (relative error F * 2^-53 / 2, plus one rounding), for two norms and two
-    sides; the product of the norms, the division and the subtraction round once each, per side."""
-    F = T.shape[1]
-    nt = np.sqrt((T * T).sum(1))
-    nd = np.sqrt((D * D).sum(1))
-    nn = nd[:, None] * nt[None, :]
-    dot = 2 * F * U * (np.abs(D) @ np.abs(T).T) / nn
-    cos = np.abs(D @ T.T) / nn
-    return dot + cos * (2 * (F + 2) * U + 4 * U) + 2 * U
 
 
 @pytest.mark.parametrize("nt,nd,F", [(1, 1, 1), (3, 5, 20), (65, 33, 64), (64, 64, 130)])
